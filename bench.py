@@ -9,11 +9,18 @@ One "step" = one full render of the workload.  N > 1 (one process per GPU, torch
 global sample index and the film accumulators are sum-reduced to rank 0 by trhip_film_reduce (RCCL inside libtracehip.so).
 `--scaling strong` (default for N > 1): the `spp` samples of ONE frame are split over the ranks — what BASELINE configs[4] asks
 (`--workload mesh_10m --res 4096 --spp 1024 --depth 16`) and the only mode in which "x N" is not true by construction; `weak`:
-every rank renders `spp` samples per pixel (per-GPU work fixed).  For N > 1 the line also carries the other mode, measured right
+every rank renders `spp` samples per pixel (per-GPU work fixed).  For N > 1 the line also carries the other mode (with `--full`), measured right
 after, as `"weak_scaling"` / `"strong_scaling"`, the number of ranks the library's RCCL communicator has (`rccl_ranks`: an N-rank
 line cannot be produced without it — a failed trhip_comm_init ends the run with a non-zero exit) and the film reduce's time.
 `--workload mesh_10m --res 4096 --spp 128 --depth 16` on ONE GPU is one rank's share of BASELINE configs[4].
 Inputs (scene, BVH) are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the `--steps` steps and prints the line: `value`, `ms_per_step` and the configuration, nothing
+else.  `--full` adds every other measurement and check the line can carry: the roofline (an instrumented pass, rocprofv3 --pmc child
+runs, the `hbm_resident` child run on the 10.5 M-triangle scene), the CPU baseline, the traversal micro-benchmark, the `bvh_modes` /
+full-size witness comparisons and, for N > 1, the other scaling mode; the `--no-*` options switch single legs of `--full` off.
+`--dump-outputs DIR`: what the last timed step handed its caller (the film, or the SPPM image, and the step's ray counts) as
+DIR/<name>.npy — same arguments, same inputs, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -32,6 +39,26 @@ TRAVERSAL_KERNEL = {1: "k_trace_closest", 2: "k_trace2", 3: "k_trace3", 4: "k_tr
 BVH_MODE = {0: "library-sah", 1: "reference", 2: "hybrid", 3: "library-sah + itself four-wide as accelerator"}  # trhip_scene_bvh_mode: which tree(s) the scene holds (include/tracehip.h)
 L2_PLUS_MALL_BYTES = (32 + 256) << 20  # 8 x 4 MiB L2 + 256 MiB Infinity Cache (MI355X_MICROARCH.md): a scene below this is served from cache, not HBM
 TRAVERSAL_KERNEL_ANY = {1: "k_trace_any", 2: "k_trace2", 3: "k_trace3", 4: "k_trace8", 5: "k_trace_leaf", 6: "k_trace4", 7: "k_trace3"}
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_SEED = 0x5EED0003  # the fixed sample of an output too large for its share
+
+
+def dump_outputs(out_dir: str, outputs) -> None:
+    """--dump-outputs: every output as out_dir/<name>.npy, float32 kept, anything else as float64.  An output larger than its share of DUMP_BYTES is written as a
+    fixed, seeded sample of its rows (all axes but the last flattened: the pixels of a film) in ascending order, their row numbers beside it as <name>_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(outputs))
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+        if a.nbytes > share:
+            rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+            k = share // (rows.shape[1] * rows.itemsize + 8)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], k, replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = rows[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def build_workload(T, name: str, res: int):
@@ -96,7 +123,7 @@ def pmc_child_runs(args, kernel_prefix: str, want_any: bool, passes):
         cmd = [exe, "--pmc"] + list(counters) + ["--output-format", "csv", "-d", out, "--", sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "1", "--warmup", "0",
                "--workload", args.workload, "--res", str(args.res), "--spp", str(args.spp), "--depth", str(args.depth), "--seed", str(args.seed), "--traversal", str(args.traversal),
                "--iterations", str(args.iterations), "--radius", str(args.radius),
-               "--no-cpu-baseline", "--no-traffic", "--no-micro", "--no-visits", "--no-modes"] + [a for kv in args.opt for a in ("--opt", kv)]
+               "--full", "--no-cpu-baseline", "--no-traffic", "--no-micro", "--no-visits", "--no-modes"] + [a for kv in args.opt for a in ("--opt", kv)]
         try:
             res = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=900)
             if res.returncode != 0:
@@ -238,7 +265,7 @@ def run_sppm(args, T, ctx, graft, rank, world, comm_ok):
     rays, replicated, ms, launches = 0, 0, {k: 0.0 for k in KERNEL_CLASSES}, {}
     sub_ms, sub_launches = [0.0] * 4, [0] * 4
     for _ in range(args.steps):
-        integ.render(scene, ctx)
+        image = integ.render(scene, ctx)
         st = integ.stats
         rays += st.closest_rays + st.shadow_rays
         replicated += st.replicated_rays
@@ -260,69 +287,72 @@ def run_sppm(args, T, ctx, graft, rank, world, comm_ok):
     elapsed, rays = float(tmax.item()), float(cnt.item()) + float(replicated)
     if rank != 0:
         return None
-    ctx.set_option("count_visits", 1)
-    if world == 1:
-        integ.render(scene, ctx)
-    sv = integ.stats
-    ctx.set_option("count_visits", 0)
-    # the per-class HIP events the roofline needs are ~12 records per iteration on the launching stream: what the same frames take without them (not `value`: the timed
-    # region above is the one the roofline's launch durations come from)
-    untimed = None
-    if world == 1 and not any(kv.replace(" ", "").startswith("timing=") for kv in args.opt):
-        ctx.set_option("timing", 0)
-        try:
+    if args.dump_outputs:  # the image the last timed step returned, and its ray counts
+        dump_outputs(args.dump_outputs, {"image": image, "ray_counts": [st.camera_samples, st.closest_rays, st.shadow_rays]})
+    sv, roofline, untimed = integ.stats, None, None
+    if args.full:
+        ctx.set_option("count_visits", 1)
+        if world == 1:
             integ.render(scene, ctx)
-            sync()
-            t_u = time.perf_counter()
-            n_u = max(1, min(3, args.steps))
-            for _ in range(n_u):
+        sv = integ.stats
+        ctx.set_option("count_visits", 0)
+        # the per-class HIP events the roofline needs are ~12 records per iteration on the launching stream: what the same frames take without them (not `value`: the timed
+        # region above is the one the roofline's launch durations come from)
+        if world == 1 and not any(kv.replace(" ", "").startswith("timing=") for kv in args.opt):
+            ctx.set_option("timing", 0)
+            try:
                 integ.render(scene, ctx)
-            sync()
-            untimed = {"ms_per_step": round((time.perf_counter() - t_u) / n_u * 1e3, 3), "steps": n_u, "note": "option timing = 0: the library records no per-class events (the default for a caller that passes no stats)"}
-        finally:
-            ctx.set_option("timing", 1)
-    kb = kernel_bytes(sv, 0)
-    per_step = {"raygen+photon_gen": ms["raygen"] / args.steps, "trace_closest": ms["trace_closest"] / args.steps, "photon_gather": sub_ms[0] / args.steps,
-                "camera+photon_shading": sub_ms[1] / args.steps, "grid+bin+scan": sub_ms[2] / args.steps, "fold+pixel_update": sub_ms[3] / args.steps,
-                "trace_any": ms["trace_any"] / args.steps, "image": ms["film"] / args.steps}
-    dominant = max((k for k in per_step if k != "trace_any"), key=lambda k: per_step[k])
-    n_px = args.res * args.res
-    if dominant == "photon_gather":
-        # k_sppm_gather + k_sppm_gather_hot of one iteration = one "launch" (DESIGN.md §10).  Algorithmic bytes: per pixel with a visible point 16 B position +
-        # 4 B radius + 16 B beta + 80 B frame (wo, ng, ns, ss, ts) read, 16 B (phi, M) written; 8 B of bucket bounds per cell visited;
-        # 16 B per candidate distance-tested (sorted photon position + record index); 32 B per accepted pair (photon direction + beta)
-        c = sv.count_sub
-        it = max(1, args.iterations)
-        dom_bytes = ((c[3] * 132 + c[0] * 16 + c[1] * 32) / it) if c[0] else 0
-        dom_ms = sub_ms[0] / max(1, sub_launches[0])
-        dom_launches = sub_launches[0]
-        kname, kprefix = "k_sppm_gather + k_sppm_gather_hot", "k_sppm_gather"
-        extra = {"per_iteration": {"visible_points": int(c[3] / it), "candidates": int(c[0] / it), "accepted_pairs": int(c[1] / it)} if c[0] else None}
-    else:
-        dom_bytes = kb["trace_closest"] * (args.steps if world == 1 else 0) / max(1, launches["trace_closest"])
-        dom_ms = ms["trace_closest"] / max(1, launches["trace_closest"])
-        dom_launches = launches["trace_closest"]
-        kprefix = flat.closest_kernel_name()  # (the library's own launch decision for this scene: a one-leaf accelerator runs k_trace_leaf_c, wide4 = 0 k_trace3c)
-        kname = kprefix + "<closest>"
-        extra = {}
-    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-    roofline = {"bound": "hbm", "kernel": kname, "dominant_class": dominant, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None,
-                "avg_launch_ms": round(dom_ms, 4), "launches": dom_launches, "algorithmic_bytes_per_launch": int(dom_bytes),
-                "visits_per_ray": {"closest_nodes": round(sv.nodes_visited / max(1, sv.closest_rays), 2), "closest_prims": round(sv.prims_tested / max(1, sv.closest_rays), 2),
-                                   "node_bytes": int(sv.node_bytes)},
-                "kernel_ms_per_step": {k: round(v, 3) for k, v in per_step.items()}}
-    roofline.update(extra)
-    if world == 1 and not args.no_traffic:
-        traffic, valu = measure_counters(args, kprefix, False)
-        if traffic:
-            n_k = 2 if dominant == "photon_gather" else 1  # two kernels per "launch" of the gather class
-            roofline["traffic"] = traffic["bytes"] * n_k
-            roofline["traffic_detail"] = traffic
-            roofline["achieved_counters"] = round(roofline["traffic"] / (dom_ms * 1e-3) / 1e9, 2)
-            roofline["frac_counters"] = round(roofline["achieved_counters"] / HBM_PEAK_GBS, 5)
-        if valu:
-            roofline["valu"] = valu
-    roofline["bound"] = classify_bound(roofline)
+                sync()
+                t_u = time.perf_counter()
+                n_u = max(1, min(3, args.steps))
+                for _ in range(n_u):
+                    integ.render(scene, ctx)
+                sync()
+                untimed = {"ms_per_step": round((time.perf_counter() - t_u) / n_u * 1e3, 3), "steps": n_u, "note": "option timing = 0: the library records no per-class events (the default for a caller that passes no stats)"}
+            finally:
+                ctx.set_option("timing", 1)
+        kb = kernel_bytes(sv, 0)
+        per_step = {"raygen+photon_gen": ms["raygen"] / args.steps, "trace_closest": ms["trace_closest"] / args.steps, "photon_gather": sub_ms[0] / args.steps,
+                    "camera+photon_shading": sub_ms[1] / args.steps, "grid+bin+scan": sub_ms[2] / args.steps, "fold+pixel_update": sub_ms[3] / args.steps,
+                    "trace_any": ms["trace_any"] / args.steps, "image": ms["film"] / args.steps}
+        dominant = max((k for k in per_step if k != "trace_any"), key=lambda k: per_step[k])
+        n_px = args.res * args.res
+        if dominant == "photon_gather":
+            # k_sppm_gather + k_sppm_gather_hot of one iteration = one "launch" (DESIGN.md §10).  Algorithmic bytes: per pixel with a visible point 16 B position +
+            # 4 B radius + 16 B beta + 80 B frame (wo, ng, ns, ss, ts) read, 16 B (phi, M) written; 8 B of bucket bounds per cell visited;
+            # 16 B per candidate distance-tested (sorted photon position + record index); 32 B per accepted pair (photon direction + beta)
+            c = sv.count_sub
+            it = max(1, args.iterations)
+            dom_bytes = ((c[3] * 132 + c[0] * 16 + c[1] * 32) / it) if c[0] else 0
+            dom_ms = sub_ms[0] / max(1, sub_launches[0])
+            dom_launches = sub_launches[0]
+            kname, kprefix = "k_sppm_gather + k_sppm_gather_hot", "k_sppm_gather"
+            extra = {"per_iteration": {"visible_points": int(c[3] / it), "candidates": int(c[0] / it), "accepted_pairs": int(c[1] / it)} if c[0] else None}
+        else:
+            dom_bytes = kb["trace_closest"] * (args.steps if world == 1 else 0) / max(1, launches["trace_closest"])
+            dom_ms = ms["trace_closest"] / max(1, launches["trace_closest"])
+            dom_launches = launches["trace_closest"]
+            kprefix = flat.closest_kernel_name()  # (the library's own launch decision for this scene: a one-leaf accelerator runs k_trace_leaf_c, wide4 = 0 k_trace3c)
+            kname = kprefix + "<closest>"
+            extra = {}
+        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+        roofline = {"bound": "hbm", "kernel": kname, "dominant_class": dominant, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None,
+                    "avg_launch_ms": round(dom_ms, 4), "launches": dom_launches, "algorithmic_bytes_per_launch": int(dom_bytes),
+                    "visits_per_ray": {"closest_nodes": round(sv.nodes_visited / max(1, sv.closest_rays), 2), "closest_prims": round(sv.prims_tested / max(1, sv.closest_rays), 2),
+                                       "node_bytes": int(sv.node_bytes)},
+                    "kernel_ms_per_step": {k: round(v, 3) for k, v in per_step.items()}}
+        roofline.update(extra)
+        if world == 1 and not args.no_traffic:
+            traffic, valu = measure_counters(args, kprefix, False)
+            if traffic:
+                n_k = 2 if dominant == "photon_gather" else 1  # two kernels per "launch" of the gather class
+                roofline["traffic"] = traffic["bytes"] * n_k
+                roofline["traffic_detail"] = traffic
+                roofline["achieved_counters"] = round(roofline["traffic"] / (dom_ms * 1e-3) / 1e9, 2)
+                roofline["frac_counters"] = round(roofline["achieved_counters"] / HBM_PEAK_GBS, 5)
+            if valu:
+                roofline["valu"] = valu
+        roofline["bound"] = classify_bound(roofline)
     cpu = None
     if world == 1 and not args.no_cpu_baseline:  # the oracle with its photon loop threaded like sppm.jl:334, on a bounded number of iterations
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -408,7 +438,7 @@ def hbm_resident_record(args):
     (request rate and counter rate against the HBM peak, lanes per VALU instruction, VALU busy) or {"error": ...}."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", "mesh_10m", "--steps", "2", "--warmup", "1", "--res", str(args.res), "--spp", str(args.spp), "--depth", str(args.depth),
-           "--seed", str(args.seed), "--no-cpu-baseline", "--no-micro", "--no-modes", "--no-hbm-resident"] + [a for kv in args.opt for a in ("--opt", kv)]
+           "--seed", str(args.seed), "--full", "--no-cpu-baseline", "--no-micro", "--no-modes", "--no-hbm-resident"] + [a for kv in args.opt for a in ("--opt", kv)]
     t0 = time.perf_counter()
     try:
         res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
@@ -450,7 +480,14 @@ def main():
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="library option (trhip_set_option) set before the scene is committed; repeatable")
     ap.add_argument("--no-hbm-resident", action="store_true", help="skip the short child run on the 10.5 M-triangle scene (`hbm_resident`: the one workload whose nodes + primitives exceed L2 + MALL)")
     ap.add_argument("--no-modes", action="store_true", help="skip the two short comparison runs on the library's tree alone and on the reference's tree alone (`bvh_modes`)")
+    ap.add_argument("--full", action="store_true", help="every measurement and check beyond the headline figure (the legs the --no-* options name, the other scaling mode for N > 1); "
+                                                        "a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: nothing but the headline figure
+        args.no_cpu_baseline = args.no_traffic = args.no_micro = args.no_visits = args.no_modes = args.no_hbm_resident = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -552,8 +589,11 @@ def main():
         return float(tmax.item()), float(counts[0].item()), float(counts[1].item()), agg, integ
 
     elapsed, total_rays, total_samples, agg, integ = timed(args.scaling, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:  # the last timed step's film on the device (N > 1: the reduced frame) and its ray counts, before anything renders again
+        st = integ.stats
+        dump_outputs(args.dump_outputs, {"film": film.cpu().numpy(), "ray_counts": [st.camera_samples, st.closest_rays, st.shadow_rays]})
     other = None
-    if world > 1:  # the other scaling mode, right after (fewer steps): both values in one line
+    if world > 1 and args.full:  # the other scaling mode, right after (fewer steps): both values in one line
         omode = "strong" if args.scaling == "weak" else "weak"
         osteps = max(1, min(args.steps, 5))
         oe, orays, osamples, oagg, _ = timed(omode, osteps, 1)

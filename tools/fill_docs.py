@@ -54,7 +54,7 @@ def main():
              f"| S-caustic SPPM (`caustic-glass.ply`, 100 iterations; `configs[3]`) | **{s['ms_per_step']:.1f} ms** | {s['value']:.0f} | — | closest-hit {sk['trace_closest']:.1f}, photon gather {sk['photon_gather']:.1f},"
              f" camera + photon shading {sk['camera+photon_shading']:.1f}, grid {sk['grid+bin+scan']:.1f}, any-hit {sk['trace_any']:.1f} | | {s['cpu_baseline']['value']:.2f} |\n"
              f"| C5 share per GPU (10.5 M triangles, 4096², 128 spp, depth 16) | **{c5['ms_per_step'] / 1e3:.2f} s** | {c5['value']:.0f} | — | closest-hit {c5['roofline']['kernel_ms_per_step']['trace_closest']:.0f} | | |\n\n"
-             f"`hbm_resident` (inside the default command; child run on S-mesh-10M): {hr.get('ms_per_step')} ms per frame, `{hr.get('kernel')}` {hr.get('avg_launch_ms')} ms per launch, {hr.get('frac_requests')} by requests,"
+             f"`hbm_resident` (a `--full` leg; child run on S-mesh-10M): {hr.get('ms_per_step')} ms per frame, `{hr.get('kernel')}` {hr.get('avg_launch_ms')} ms per launch, {hr.get('frac_requests')} by requests,"
              f" **{hr.get('frac_counters')} by counters** ({hr.get('achieved_counters_GBps')} GB/s left L2), {(hr.get('valu') or {}).get('lanes_per_valu_inst')} of 64 lanes at VALU busy"
              f" {(hr.get('valu') or {}).get('valu_busy')}: `valu_frac` {hr.get('valu_frac')} — VALU issue bounds the walk on the scene that does not fit the caches as well.")
     readme = (f"S-mesh (1 M triangles) **{m['value']:.0f} Mray/s** ({frame:.1f} ms per frame; the library's tree alone, not exact: {m['bvh_modes']['library_tree_alone']['ms_per_step']:.1f} ms; the reference's tree alone:"

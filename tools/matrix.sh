@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/matrix.sh <outdir> — frame-level A/B of traversal kernels / BVH topologies (bench.py lines without the CPU / PMC legs)
 OUT=$1; mkdir -p $OUT
-run() { tag=$1; shift; timeout 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-micro --no-traffic "$@" > $OUT/$tag.json 2>$OUT/$tag.err; python - "$OUT/$tag.json" "$tag" <<'PY'
+run() { tag=$1; shift; timeout 300 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-micro --no-traffic "$@" > $OUT/$tag.json 2>$OUT/$tag.err; python - "$OUT/$tag.json" "$tag" <<'PY'
 import json,sys
 try:
     d=json.load(open(sys.argv[1])); r=d['roofline']
