@@ -96,6 +96,14 @@ int trhip_scene_add_spot_light(trhip_scene* scene, const float light2world_m[16]
 int trhip_scene_add_spot_light_fields(trhip_scene* scene, const float light2world_m[16], const float light2world_inv_m[16], const float I[3],
                                       float cos_total_width, float cos_falloff_start);
 
+/* DirectionalLight(light_to_world, I, direction)  lights/directional.jl:6-33, from the fields the light holds at render time:
+ * direction_world = normalize(light_to_world(direction)) (:29, a vector: translation ignored) and world_radius (0 after the
+ * constructor, the scene's bounding sphere after preprocess!(light, scene) :35-37; Scene never calls it, Trace.jl:184).  The
+ * library does not preprocess: what the caller's light holds is what renders.  sample_li (:39-47): Li = I, wi = direction, pdf 1,
+ * shadow ray spawn_ray(p, p .+ direction .* (2 * world_radius)) — with world_radius 0 a zero-direction ray.  SPPM refuses a call
+ * whose photon pass could pick the light (the reference has no sample_le for it, sppm.jl:361): see trhip_render_sppm. */
+int trhip_scene_add_directional_light(trhip_scene* scene, const float I[3], const float direction_world[3], float world_radius);
+
 /* BVHAccel(primitives, max_node_primitives)  accel/bvh.jl:55-79.  Builds a binned-SAH BVH2 on the host (results of
  * traversal do not depend on the topology except where two primitives are accepted at (nearly) the same t), flattens it
  * in the reference's depth-first layout (first child = i+1, bvh.jl:187-206) and uploads everything to HBM.  Option "bvh_builder" = 2
@@ -229,7 +237,13 @@ int trhip_last_sample_radiance(trhip_ctx* ctx, float* out_rgb, uint64_t n_floats
  * photons_per_iteration <= 0: area(crop_bounds) like sppm.jl:121-124.  The film's crop must start at pixel (1, 1).
  * The camera pass of iteration k draws from the seeded stream (seed, pixel, sample k-1).  Photon contributions are added
  * with Float32 atomics as in the reference (sppm.jl:398-399): M, radius, N, Ld and the visible points are reproducible
- * bit for bit, τ (and the image) up to the summation order of ϕ. */
+ * bit for bit, τ (and the image) up to the summation order of ϕ.
+ * A DirectionalLight has no sample_le in the reference (a photon that picks one ends the reference run at sppm.jl:361): the call
+ * returns TRHIP_ERR_UNSUPPORTED, before any launch, when sample_discrete over the light power (sampling.jl:3-41) could pick one for
+ * a photon of Halton indices 0 .. n_iterations * photons_per_iteration - 1 — its CDF interval has nonzero width (power (I·π)·r² > 0,
+ * directional.jl:54-56; or every light's power is 0 and the uniform CDF gives it an interval), or it is the last light and some
+ * index of the range has radical_inverse(0, index) == 1.0f (index ≡ 2^25 - 1 mod 2^25, the first at 2^25 - 1).  Otherwise the light
+ * renders through the camera pass's direct term alone. */
 int trhip_render_sppm(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, float initial_search_radius, int max_depth, uint32_t n_iterations,
                       int64_t photons_per_iteration, uint64_t seed, float* out_xyzw, trhip_stats* stats);
 /* … with the reference's periodic image (integrators/sppm.jl:166-171: `iteration % write_frequency == 0 || iteration == n_iterations` -> _sppm_to_image,

@@ -324,13 +324,145 @@ class SpotLight:  # lights/spot.jl:10-19
     falloff_start: float
 
 
+class DirectionalLight:  # lights/directional.jl:6-33 (mutable: preprocess! rewrites world_center / world_radius)
+    def __init__(self, light_to_world: Transformation, l: RGBSpectrum, direction):
+        self.light_to_world = light_to_world
+        self.world_to_light = light_to_world.inv()
+        self.i = l
+        self.direction = _normalize(light_to_world.vector(direction))  # normalize(light_to_world(direction)) :29, a vector: no translation
+        self.world_radius = f32(0.0)  # "To be computed in preprocessing stage" (:30): Scene never does (Trace.jl:184)
+        self.world_center = np.zeros(3, dtype=np.float32)
+
+
+# ---- bounds (bounds.jl) -------------------------------------------------------------------------------------------------------
+# Julia's min / max on Float32: NaN wins, and -0 < +0 (so a union does not depend on the order of its operands).
+def _jl_min(a, b):
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    take_b = (b < a) | ((b == a) & np.signbit(b) & ~np.signbit(a)) | np.isnan(b)
+    return np.where(take_b & ~np.isnan(a), b, a).astype(np.float32)
+
+
+def _jl_max(a, b):
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    take_b = (b > a) | ((b == a) & np.signbit(a) & ~np.signbit(b)) | np.isnan(b)
+    return np.where(take_b & ~np.isnan(a), b, a).astype(np.float32)
+
+
+def _jl_clamp(x, lo, hi):  # Base.clamp: ifelse(x > hi, hi, ifelse(x < lo, lo, x))
+    return hi if x > hi else (lo if x < lo else x)
+
+
+def _empty_bounds() -> np.ndarray:  # Bounds3() = Bounds3(Point3f(Inf32), Point3f(-Inf32))  bounds.jl:13
+    return np.array([np.inf] * 3 + [-np.inf] * 3, dtype=np.float32)
+
+
+def _union_points(b: np.ndarray, pts: np.ndarray) -> np.ndarray:
+    """b ∪ Bounds3(p) for every row p of pts (bounds.jl:59-61); min / max are exact, so the order is free."""
+    pts = np.asarray(pts, np.float32).reshape(-1, 3)
+    lo, hi = b[:3], b[3:]
+    for p in pts:
+        lo, hi = _jl_min(lo, p), _jl_max(hi, p)
+    return np.concatenate([lo, hi]).astype(np.float32)
+
+
+def _union_points_bulk(b: np.ndarray, pts: np.ndarray) -> np.ndarray:
+    """The same for many points at once (a million-triangle mesh): column extrema, with Julia's NaN and signed-zero rules."""
+    pts = np.asarray(pts, np.float32).reshape(-1, 3)
+    if pts.shape[0] == 0:
+        return b
+    lo, hi = b[:3].copy(), b[3:].copy()
+    for a in range(3):
+        col = pts[:, a]
+        if np.isnan(col).any():
+            lo[a] = hi[a] = np.float32(np.nan)
+            continue
+        mn, mx = col.min(), col.max()
+        zs = np.signbit(col[col == 0])
+        if mn == 0:
+            mn = np.float32(-0.0) if zs.any() else np.float32(0.0)
+        if mx == 0:
+            mx = np.float32(0.0) if (~zs).any() else np.float32(-0.0)
+        lo[a] = _jl_min(lo[a], mn)
+        hi[a] = _jl_max(hi[a], mx)
+    return np.concatenate([lo, hi]).astype(np.float32)
+
+
+def _sphere_world_bound(s: "Sphere") -> np.ndarray:
+    """world_bound(s) = object_to_world(object_bound(s)) (Shape.jl:17-19, sphere.jl:32-37): the 8 corners of the box over the CLAMPED
+    z range of the constructor (sphere.jl:17-18), each through (t::Transformation)(p) (transformations.jl:141-143)."""
+    r = s.radius
+    z0 = _jl_clamp(min(s.z_min, s.z_max), -r, r)
+    z1 = _jl_clamp(max(s.z_min, s.z_max), -r, r)
+    lo, hi = (-r, -r, z0), (r, r, z1)
+    corners = np.array([[(lo, hi)[c & 1][0], (lo, hi)[1 if c & 2 else 0][1], (lo, hi)[1 if c & 4 else 0][2]] for c in range(8)], dtype=np.float32)
+    return _union_points(_empty_bounds(), np.stack([s.core.object_to_world.point(c) for c in corners]))
+
+
+def _primitives_bound(prims) -> np.ndarray:
+    b = _empty_bounds()
+    for p in prims:
+        if isinstance(p, BVHAccel):  # world_bound(bvh): its root box = the union of its primitives', Bounds3() when it has none (accel/bvh.jl:208-210)
+            inner = _primitives_bound(p.primitives)
+            b = np.concatenate([_jl_min(b[:3], inner[:3]), _jl_max(b[3:], inner[3:])]).astype(np.float32)
+        elif isinstance(p, MeshPrimitives):
+            m = p.mesh
+            b = _union_points_bulk(b, m.vertices[m.indices.reshape(-1).astype(np.int64) - 1])  # 1-based indices (triangle_mesh.jl)
+        elif isinstance(p.shape, Triangle):  # world_bound(t) = reduce(∪, Bounds3.(vertices(t)))  triangle_mesh.jl:97
+            m, k = p.shape.mesh, p.shape.k
+            b = _union_points(b, m.vertices[m.indices[3 * k:3 * k + 3].astype(np.int64) - 1])
+        elif isinstance(p.shape, Sphere):
+            sb = _sphere_world_bound(p.shape)
+            b = np.concatenate([_jl_min(b[:3], sb[:3]), _jl_max(b[3:], sb[3:])]).astype(np.float32)
+        else:
+            raise TraceHipError(f"unsupported shape {type(p.shape).__name__}")
+    return b
+
+
+def _inside(b, p) -> bool:  # bounds.jl:71-73
+    return bool(np.all(p >= b[:3]) and np.all(p <= b[3:]))
+
+
+def bounding_sphere(b):
+    """bounds.jl:145-149: (center, radius), center = (p_min + p_max) / 2f0, radius = distance(center, p_max) when the center is
+    inside b, else 0f0.  ``b``: 6 floats (p_min, p_max), as Scene.bound returns."""
+    b = np.asarray(b, np.float32).reshape(6)
+    with np.errstate(invalid="ignore"):  # Bounds3(): Inf + -Inf = NaN, not inside
+        center = ((b[:3] + b[3:]) / f32(2.0)).astype(np.float32)
+    radius = _norm3(center - b[3:]) if _inside(b, center) else f32(0.0)  # distance(p1, p2) = norm(p1 - p2)  bounds.jl:127
+    return center, f32(radius)
+
+
+def preprocess(light, scene: "Scene") -> None:
+    """preprocess!(light, scene): a DirectionalLight takes the scene's bounding sphere (directional.jl:35-37); Scene itself never
+    calls it (Trace.jl:184), so an un-preprocessed light keeps world_radius = 0.  Other lights have nothing to preprocess."""
+    if isinstance(light, DirectionalLight):
+        light.world_center, light.world_radius = bounding_sphere(scene.bound)
+        scene._flat = None  # the flattened scene holds the light's fields
+
+
+def _light_key(l):
+    return (id(l), bytes(np.asarray(l.direction, np.float32).tobytes()), float(l.world_radius), bytes(np.asarray(l.i.c, np.float32).tobytes())) if isinstance(l, DirectionalLight) else id(l)
+
+
 class Scene:  # Trace.jl:176-187
     def __init__(self, lights, aggregate: BVHAccel):
         self.lights = list(lights)
         self.aggregate = aggregate
         self._flat = None
+        self._bound = None
+
+    @property
+    def bound(self) -> np.ndarray:
+        """scene.bound = world_bound(aggregate) (Trace.jl:183, accel/bvh.jl:208-210), as 6 Float32s p_min, p_max: the root box of the reference's BVH, i.e.
+        the union of every primitive's world_bound (nested BVHs through their own root boxes), Bounds3() = (Inf, -Inf) without primitives."""
+        if self._bound is None:
+            self._bound = _primitives_bound(self.aggregate.primitives)
+        return self._bound.copy()
 
     def flatten(self, ctx: Optional[_ffi.Context] = None) -> "FlatScene":
+        # a light's fields may have changed since (preprocess, or a caller writing world_radius like Julia's mutable struct): the flat scene holds them
+        if self._flat is not None and self._flat.light_keys != [_light_key(l) for l in self.lights]:
+            self._flat = None
         if self._flat is None or (ctx is not None and self._flat.ctx is not ctx):
             self._flat = FlatScene(self, ctx or _ffi.default_context())
         return self._flat
@@ -580,6 +712,7 @@ class FlatScene:
                 i = j
             else:
                 raise TraceHipError(f"unsupported shape {type(p.shape).__name__}")
+        self.light_keys = [_light_key(l) for l in scene.lights]
         for l in scene.lights:
             m, im = _ffi.f32(l.light_to_world.m), _ffi.f32(l.light_to_world.inv_m)
             I = _ffi.f32(l.i.c)
@@ -587,6 +720,8 @@ class FlatScene:
                 ctx.check(L.trhip_scene_add_point_light(self._h, _ffi.fptr(m), _ffi.fptr(im), _ffi.fptr(I)))
             elif isinstance(l, SpotLight):
                 ctx.check(L.trhip_scene_add_spot_light(self._h, _ffi.fptr(m), _ffi.fptr(im), _ffi.fptr(I), float(l.total_width), float(l.falloff_start)))
+            elif isinstance(l, DirectionalLight):  # the fields as the light holds them now (preprocessed or not)
+                ctx.check(L.trhip_scene_add_directional_light(self._h, _ffi.fptr(I), _ffi.fptr(_ffi.f32(l.direction)), float(f32(l.world_radius))))
             else:
                 raise TraceHipError(f"unsupported light {type(l).__name__}")
         ctx.check(L.trhip_scene_commit(self._h, scene.aggregate.max_node_primitives))
@@ -761,6 +896,71 @@ class PathIntegrator(_SamplerIntegrator):
     """Not in the reference; defined in DESIGN.md from integrators/sppm.jl:208-266, 503-554."""
     _entry = "trhip_render_path"
     _entry_device = "trhip_render_path_device"
+
+
+# ---- SPPM and the DirectionalLight -------------------------------------------------------------------------------------------------
+def _to_Y(c) -> np.float32:  # spectrum.jl:64-66
+    c = np.asarray(c, np.float32)
+    return f32(f32(f32(0.212671) * c[0]) + f32(f32(0.715160) * c[1])) + f32(f32(0.072169) * c[2])
+
+
+def light_power_y(light) -> np.float32:
+    """to_Y(power(light)) as the library's SPPM host code forms it (point.jl:74-76, spot.jl:42-44, directional.jl:54-56); a SpotLight's cosines through
+    the library's deterministic cosine, as its constructor (spot.jl:17)."""
+    I = np.asarray(light.i.c, np.float32)
+    if isinstance(light, PointLight):
+        return _to_Y(f32(f32(4.0) * _PI32) * I)
+    if isinstance(light, SpotLight):
+        ct, cf = _ffi.detmath(1, [_deg2rad(light.total_width), _deg2rad(light.falloff_start)])
+        return _to_Y(((I * f32(2.0)) * _PI32) * f32(f32(1.0) - f32(f32(0.5) * f32(cf + ct))))
+    if isinstance(light, DirectionalLight):
+        r = f32(f32(0.5) * f32(f32(2.0) * f32(light.world_radius)))
+        return _to_Y((I * _PI32) * f32(r * r))
+    raise TraceHipError(f"unsupported light {type(light).__name__}")
+
+
+def _light_cdf(func) -> np.ndarray:
+    """Distribution1D(func).cdf (sampling.jl:8-29) in Float32; a zero integral falls back to cdf[i] = i / n (1-based)."""
+    n = len(func)
+    cdf = np.zeros(n + 1, np.float32)
+    for i in range(1, n + 1):
+        cdf[i] = f32(cdf[i - 1] + f32(f32(func[i - 1]) / f32(n)))
+    func_int = cdf[n]
+    for i in range(1, n + 1):
+        cdf[i] = f32((i + 1) / n) if func_int == 0 else f32(cdf[i] / func_int)
+    return cdf
+
+
+def radical_inverse_is_one(lo: int, hi: int) -> bool:
+    """Is radical_inverse(0, i) == 1f0 (sampling.jl:45: reverse_bits(i) * 2^-64 in Float64, then Float32) for some Halton index lo <= i < hi?  It is
+    exactly when the reversed index is >= 2^64 - 2^39 - 2^10 (the Float64 and Float32 roundings to nearest even), i.e. when the low 25 bits of i are all
+    ones, or the low 24 are, bit 24 is not and bits 25..53 are."""
+    for m, v in ((25, (1 << 25) - 1), (54, ((1 << 24) - 1) | (((1 << 54) - 1) ^ ((1 << 25) - 1)))):
+        i = lo + ((v - lo) % (1 << m))  # the first i >= lo with i mod 2^m == v
+        if i < hi:
+            return True
+    return False
+
+
+def sppm_directional_pick(lights, n_photons: int, first_index: int = 0) -> int:
+    """The light (0-based) of ``lights`` that is a DirectionalLight and that sample_discrete over the light power (sampling.jl:32-41) could pick for a
+    photon of Halton index first_index .. first_index + n_photons - 1, or -1.  The reference has no sample_le for the light (sppm.jl:361), so the
+    library's SPPMIntegrator refuses exactly such a call (csrc/tu_sppm.hip, sppm_directional_pick; the range there is 0 .. n_iterations * photons - 1):
+    a light's interval [cdf[k], cdf[k+1]) of nonzero width counts as pickable; the last light, taken for u >= cdf[n], with cdf[n] == 1 only when some
+    index of the range has radical_inverse(0, index) == 1f0."""
+    if not lights:
+        return -1
+    cdf = _light_cdf([light_power_y(l) for l in lights])
+    n = len(lights)
+    for k, l in enumerate(lights):
+        if not isinstance(l, DirectionalLight):
+            continue
+        if k + 1 < n:
+            if not (cdf[k + 1] <= cdf[k]):
+                return k
+        elif not (cdf[k] >= 1) or (cdf[k] == 1 and radical_inverse_is_one(first_index, first_index + n_photons)):
+            return k
+    return -1
 
 
 class SPPMIntegrator:  # integrators/sppm.jl:108-130

@@ -819,15 +819,24 @@ TH_D BsdfSample lambert_bsdf_sample_f(const Lobe& l, const Shading& s, f3 wo_w, 
     return r;
 }
 
-// ---- lights (lights/point.jl:50-58, lights/spot.jl:22-40) -----------------------------------------------------------------
+// ---- lights (lights/point.jl:50-58, lights/spot.jl:22-40, lights/directional.jl:39-47) --------------------------------------
 struct LightSample {
     f3 radiance;
     f3 wi;
     float pdf;
 };
+// DIRL: the scene holds a directional light.  Without one the kind-2 branches are not compiled: the shading kernels of every other scene
+// keep their register allocation (profiles/r7/directional_resources.txt).
+template <bool DIRL>
 TH_D LightSample sample_li(const LightRec& l, f3 p) {
     LightSample s;
     const f3 lp = mk3(l.position[0], l.position[1], l.position[2]);
+    if (DIRL && l.kind == 2) {  // directional: Li = I, wi = direction, pdf = 1; the sample u is not read
+        s.wi = lp;
+        s.pdf = 1.0f;
+        s.radiance = mk3(l.I[0], l.I[1], l.I[2]);
+        return s;
+    }
     s.wi = normalize(lp - p);
     s.pdf = 1.0f;
     const f3 I = mk3(l.I[0], l.I[1], l.I[2]);
@@ -850,6 +859,15 @@ TH_D LightSample sample_li(const LightRec& l, f3 p) {
         s.radiance = I * fall / d2;
     }
     return s;
+}
+// The point the VisibilityTester of sample_li aims at: the light's position, or for a directional light
+// outside_point = ref.p .+ direction .* (2 * world_radius) (directional.jl:42), in that order of operations.  The shadow ray is
+// spawn_ray(p, p1): d = p1 - p, o = p + 1e-6 * d (Trace.jl:196-202), so with world_radius = 0 (no preprocess!) d is exactly +0.
+template <bool DIRL>
+TH_D f3 light_target(const LightRec& l, f3 p) {
+    const f3 lp = mk3(l.position[0], l.position[1], l.position[2]);
+    if (DIRL && l.kind == 2) return p + lp * l.pad;
+    return lp;
 }
 
 }  // namespace th

@@ -185,6 +185,13 @@ struct trhip_scene {
     CertScene cert{};
 };
 
+// some light is a DirectionalLight (kind 2): the shading kernels run their DIRL variants (th_device.h, sample_li)
+inline bool has_directional_light(const trhip_scene* s) {
+    for (const LightRec& l : s->lights)
+        if (l.kind == 2) return true;
+    return false;
+}
+
 inline int fail(trhip_ctx* ctx, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;

@@ -561,7 +561,7 @@ struct ShadeOut {  // what one vertex emits: a shadow ray and / or the continuat
 };
 // One PathIntegrator vertex for queue entry i (a real hit).  FAST: the caller has established that the hit is a triangle whose
 // material is a single LambertianReflection lobe; the sphere path and the general BSDF code are then not even compiled in.
-template <bool STREAM, bool FAST, bool TAN = true>
+template <bool STREAM, bool FAST, bool TAN = true, bool DIRL = false>
 TH_D void shade_vertex(const DeviceScene& sc, const PathQueue& qin, const float4* __restrict__ hits, float4* __restrict__ L, uint32_t i, int depth_fixed, int max_depth,
                        uint32_t hits_have_bary, const ShadeStream& ss, ShadeOut& out) {
     const float4 h4 = hits[i];
@@ -603,7 +603,7 @@ TH_D void shade_vertex(const DeviceScene& sc, const PathQueue& qin, const float4
         const float light_pdf = 1.0f / (float)nl;
         // one light (every scene of the reference): its record comes through scalar loads, off the vector-memory queue
         const LightRec light = nl == 1 ? uniform_load(sc.lights, 0u) : sc.lights[ln - 1];
-        const LightSample ls = sample_li(light, sh.p);
+        const LightSample ls = sample_li<DIRL>(light, sh.p);
         if (ls.pdf > 0.0f && !is_black(ls.radiance)) {
             const f3 f = (lambert ? lambert_bsdf_f(lam, sh, sh.wo, ls.wi) : bsdf_f(bsdf, sh, sh.wo, ls.wi, BSDF_ALL & ~BSDF_SPECULAR)) * fabs_(dot(ls.wi, sh.ns));
             if (!is_black(f)) {
@@ -612,7 +612,7 @@ TH_D void shade_vertex(const DeviceScene& sc, const PathQueue& qin, const float4
                 const f3 Ld1 = splat3(0.0f) + (ls.pdf == 1.0f ? fl : fl / ls.pdf);
                 const f3 Ld = light_pdf == 1.0f ? Ld1 : Ld1 / light_pdf;
                 const f3 c = beta * Ld;
-                const f3 lp = mk3(light.position[0], light.position[1], light.position[2]);
+                const f3 lp = light_target<DIRL>(light, sh.p);
                 const f3 dir = lp - sh.p;  // spawn_ray(p0, p1) Trace.jl:196-202
                 const f3 org = sh.p + 1e-6f * dir;
                 const f3 cd = check_direction(dir);
@@ -671,7 +671,7 @@ TH_D void shade_vertex(const DeviceScene& sc, const PathQueue& qin, const float4
 // more than the 144 bytes of scratch the FAST code gets rid of.)
 // (Round 5 built the two-launch form again — the matte entries alone, restructured to 88 VGPRs without scratch at 5 waves per SIMD, then the rest from index lists: 2 ms per
 // 64 spp SLOWER on S-mesh and S-cornell at 4, 5 and 6 waves alike; the matte path is bound neither by occupancy nor by scratch: profiles/r5/r5_shade_split_experiment.txt.)
-template <bool STREAM, bool TAN = true>
+template <bool STREAM, bool TAN = true, bool DIRL = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE_WAVES))) void k_shade_path(DeviceScene sc, const DeviceSensor* __restrict__ sep, PathQueue qin, PathQueue qout, ShadowQueue sq, uint32_t cap,
                                                        const float4* __restrict__ hits, float4* __restrict__ L, Counters* ctr, int row, int depth_fixed, int max_depth, uint32_t hits_have_bary,
                                                        ShadeStream ss) {
@@ -718,7 +718,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE
         ShadeOut e;
         e.want_shadow = e.want_next = false;
         e.next_depth = 0;
-        if (cls == 1) shade_vertex<STREAM, true, TAN>(sc, qin, hits, L, i, depth_fixed, max_depth, hits_have_bary, ss, e);
+        if (cls == 1) shade_vertex<STREAM, true, TAN, DIRL>(sc, qin, hits, L, i, depth_fixed, max_depth, hits_have_bary, ss, e);
         emit(e);
         // park the others
         const unsigned long long m2 = __ballot(cls == 2);
@@ -731,7 +731,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE
                 ShadeOut g;
                 g.want_shadow = g.want_next = false;
                 g.next_depth = 0;
-                shade_vertex<STREAM, false, TAN>(sc, qin, hits, L, j, depth_fixed, max_depth, hits_have_bary, ss, g);
+                shade_vertex<STREAM, false, TAN, DIRL>(sc, qin, hits, L, j, depth_fixed, max_depth, hits_have_bary, ss, g);
                 emit(g);
                 ring_head = (ring_head + 64u) & 127u;
                 ring_cnt -= 64u;
@@ -743,7 +743,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE
         ShadeOut g;
         g.want_shadow = g.want_next = false;
         g.next_depth = 0;
-        if (lane < ring_cnt) shade_vertex<STREAM, false, TAN>(sc, qin, hits, L, s_ring[wv][(ring_head + lane) & 127u], depth_fixed, max_depth, hits_have_bary, ss, g);
+        if (lane < ring_cnt) shade_vertex<STREAM, false, TAN, DIRL>(sc, qin, hits, L, s_ring[wv][(ring_head + lane) & 127u], depth_fixed, max_depth, hits_have_bary, ss, g);
         emit(g);
     }
 }

@@ -61,15 +61,16 @@ struct MaterialRec {
     LobeSet set[2];  // [allow_multiple_lobes]
 };
 
-struct LightRec {  // lights/point.jl:1-24, lights/spot.jl:1-19
-    int32_t kind;  // 0 point, 1 spot
-    float position[3];
+struct LightRec {  // lights/point.jl:1-24, lights/spot.jl:1-19, lights/directional.jl:6-33
+    int32_t kind;  // 0 point, 1 spot, 2 directional
+    float position[3];  // directional: the world-space `direction` (already normalised, directional.jl:29)
     float I[3];
     float cos_total_width, cos_falloff_start;
     float w2l[9];  // world_to_light.m[1:3,1:3] (= light_to_world.inv_m), row-major, for falloff (spot.jl:32-34)
     float l2w[9];  // light_to_world.m[1:3,1:3], row-major, for sample_le (spot.jl:49)
-    float pad;
+    float pad;     // directional: 2 * world_radius (directional.jl:42; exact in Float32 unless it overflows); 0 otherwise
 };
+static_assert(sizeof(LightRec) == 112, "LightRec: the single-light path loads it through scalar loads (th_kernels.h)");
 
 struct DeviceScene {
     const float4* nodes;

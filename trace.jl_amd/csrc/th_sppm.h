@@ -179,7 +179,7 @@ TH_D void add_nan_where(float4* L, uint32_t slot, uint32_t poison) {  // L += β
 #ifndef TH_SHADE_SPPM_WAVES
 #define TH_SHADE_SPPM_WAVES 3  // 180 VGPRs unconstrained (2 waves per SIMD); capped at 3: C4 shading section 162.9 -> 159.3 ms, at 4 (spills) 162.2
 #endif
-template <bool TAN = true>
+template <bool TAN = true, bool DIRL = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE_SPPM_WAVES))) void k_shade_sppm(DeviceScene sc, PathQueue qin, PathQueue qout, ShadowQueue sq, uint32_t cap, const float4* __restrict__ hits, VisiblePoints vp,
                                                        float4* __restrict__ Ld, Counters* ctr, int depth, int max_depth, uint64_t seed, uint32_t it0, uint32_t n_pix, uint32_t width) {
     __shared__ SegView sv;
@@ -227,12 +227,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE
                         if (ln < 1) ln = 1;
                         const float light_pdf = 1.0f / (float)nl;
                         const LightRec& light = sc.lights[ln - 1];
-                        const LightSample ls = sample_li(light, sh.p);
+                        const LightSample ls = sample_li<DIRL>(light, sh.p);
                         if (ls.pdf > 0.0f && !is_black(ls.radiance)) {
                             const f3 f = bsdf_f(bsdf, sh, sh.wo, ls.wi, BSDF_ALL & ~BSDF_SPECULAR) * fabs_(dot(ls.wi, sh.ns));
                             if (!is_black(f)) {
                                 const f3 c = (splat3(0.0f) + f * ls.radiance / ls.pdf) / light_pdf;
-                                const f3 lp = mk3(light.position[0], light.position[1], light.position[2]);
+                                const f3 lp = light_target<DIRL>(light, sh.p);
                                 const f3 dir = lp - sh.p;
                                 const f3 org = sh.p + 1e-6f * dir;
                                 const f3 cd = check_direction(dir);

@@ -24,7 +24,7 @@ struct WhittedFlags {
 };
 
 // One tree level: interaction, BSDF (allow_multiple_lobes = false), per-light shadow rays, ≤ 2 specular children.
-template <int TH_ONE_COPY = 0> __global__ __launch_bounds__(kBlock) void k_shade_whitted(DeviceScene sc, PathQueue qin, PathQueue qout, ShadowQueue sq, uint32_t cap, uint32_t cap_shadow, const float4* __restrict__ hits,
+template <int TH_ONE_COPY = 0, bool DIRL = false> __global__ __launch_bounds__(kBlock) void k_shade_whitted(DeviceScene sc, PathQueue qin, PathQueue qout, ShadowQueue sq, uint32_t cap, uint32_t cap_shadow, const float4* __restrict__ hits,
                                                           WhittedPool pool, uint32_t base_in, uint32_t base_out, Counters* ctr, WhittedFlags* flags, int depth, int max_depth) {
     __shared__ SegView sv;
     const SegQueue qv{ctr->n_queue[depth - 1], cap, 0u};
@@ -60,12 +60,12 @@ template <int TH_ONE_COPY = 0> __global__ __launch_bounds__(kBlock) void k_shade
             float4 so4, sd4, sc4;
             if (have) {
                 const LightRec& light = sc.lights[l];
-                const LightSample ls = sample_li(light, sh.p);
+                const LightSample ls = sample_li<DIRL>(light, sh.p);
                 if (!(is_black(ls.radiance) || ls.pdf == 0.0f)) {
                     const f3 f = bsdf_f(*bsdf, sh, sh.wo, ls.wi, BSDF_ALL);
                     if (!is_black(f)) {
                         const f3 c = f * ls.radiance * fabs_(dot(ls.wi, sh.ns)) / ls.pdf;
-                        const f3 lp = mk3(light.position[0], light.position[1], light.position[2]);
+                        const f3 lp = light_target<DIRL>(light, sh.p);
                         const f3 dir = lp - sh.p;
                         const f3 org = sh.p + 1e-6f * dir;
                         const f3 cd = check_direction(dir);

@@ -583,6 +583,7 @@ int upload_scene(trhip_scene* s) {
             double w = 0.0;
             for (const LightRec& l : s->lights) {
                 const float* lp = l.position;
+                if (l.kind == 2) continue;  // a directional light has no position: it orders nothing (any order gives the same boolean)
                 if (p.kind == 1) {
                     const HostAABB& b = s->sphere_bounds[p.sphere_id];
                     double c[3], r = 0.0, d2 = 0.0;
@@ -656,7 +657,8 @@ int upload_scene(trhip_scene* s) {
             if (!s->lights.empty()) {
                 for (auto& b : big) {
                     double w = 0.0;
-                    for (const LightRec& l : s->lights) w += solid_angle(b.second, l.position);
+                    for (const LightRec& l : s->lights)
+                        if (l.kind != 2) w += solid_angle(b.second, l.position);  // a directional light has no position
                     b.first = w;
                 }
                 std::stable_sort(big.begin(), big.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
@@ -862,6 +864,7 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
                 double w = 0.0;
                 for (const LightRec& l : s->lights) {
                     const float* lp = l.position;
+                    if (l.kind == 2) continue;  // a directional light has no position: it orders nothing
                     if (p.kind == 1) {
                         const HostAABB& b = s->sphere_bounds[p.sphere_id];
                         double c[3], r = 0.0, d2 = 0.0;
@@ -1423,6 +1426,20 @@ int trhip_scene_add_spot_light(trhip_scene* s, const float* l2w, const float* l2
 
 int trhip_scene_add_spot_light_fields(trhip_scene* s, const float* l2w, const float* l2w_inv, const float* I, float cos_total, float cos_falloff) {
     return add_light(s, 1, l2w, l2w_inv, I, cos_total, cos_falloff, true);
+}
+
+// DirectionalLight from the fields it holds at render time (lights/directional.jl:6-33): the library does not run preprocess! (:35-37)
+int trhip_scene_add_directional_light(trhip_scene* s, const float* I, const float* direction_world, float world_radius) {
+    if (!s || !I || !direction_world) return fail(s ? s->ctx : nullptr, TRHIP_ERR_INVALID, "null argument");
+    LightRec l;
+    std::memset(&l, 0, sizeof l);
+    l.kind = 2;
+    std::memcpy(l.position, direction_world, 3 * sizeof(float));
+    std::memcpy(l.I, I, 3 * sizeof(float));
+    l.pad = 2.0f * world_radius;  // `2 * d.world_radius` (directional.jl:42): Int * Float32 is a Float32 product
+    s->lights.push_back(l);
+    s->committed = false;
+    return 0;
 }
 
 // world_bound of every primitive in caller order (triangle_mesh.jl:97, Shape.jl:17-19)

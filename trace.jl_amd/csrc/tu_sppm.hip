@@ -3,6 +3,25 @@
 #include "th_sppm.h"
 
 namespace {
+// Could the photon pass of Halton indices 0 .. n_photons - 1 pick a DirectionalLight (kind 2)?  The reference has no sample_le for
+// it (sppm.jl:361), so such a run ends in a MethodError there.  sample_discrete (sampling.jl:32-41) picks light k (0-based) for
+// cdf[k] <= u < cdf[k + 1], the last one for cdf[n - 1] <= u, u = radical_inverse(0, index) in [0, 1].  A light whose interval has
+// nonzero width counts as pickable; the last light with cdf[n - 1] == 1 (zero power, or a zero-power CDF's uniform fallback) only
+// for u == 1.0f.  u == 1.0f rounds from Float64 when the reversed index is >= 2^64 - 2^39 - 2^10: the low 25 bits of the index are
+// all ones (or the low 24 are, bit 24 is not and bits 25..53 are) — the smallest such index is 2^25 - 1.  Returns the light's
+// 0-based index, or -1.  Pure: the mirror sppm_refuses_directional (api.py) answers the same.
+int sppm_directional_pick(const LightRec* lights, const float* cdf, uint32_t n_lights, uint64_t n_photons) {
+    for (uint32_t k = 0; k < n_lights; ++k) {
+        if (lights[k].kind != 2) continue;
+        if (k + 1 < n_lights) {
+            if (!(cdf[k + 1] <= cdf[k])) return (int)k;  // a NaN CDF counts as pickable
+        } else if (!(cdf[k] >= 1.0f) || (cdf[k] == 1.0f && n_photons >= (1ull << 25))) {
+            return (int)k;
+        }
+    }
+    return -1;
+}
+
 // SPPMIntegrator (integrators/sppm.jl:132-173): n_iterations x {camera pass, grid, photon pass, pixel update}, then
 // _sppm_to_image + set_image!.  Everything runs on one stream; queue sizes stay in HBM, the host only enqueues.
 int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, float initial_radius, int max_depth, uint32_t n_iterations, int64_t photons_per_iteration,
@@ -33,13 +52,19 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         for (uint32_t l = 0; l < n_lights; ++l) {
             const LightRec& lr = scene->lights[l];
             const f3 I = mk3(lr.I[0], lr.I[1], lr.I[2]);
-            const f3 power = lr.kind == 0 ? 4.0f * kPi * I : I * 2.0f * kPi * (1.0f - 0.5f * (lr.cos_falloff_start + lr.cos_total_width));  // point.jl:74-76, spot.jl:42-44
+            // point.jl:74-76, spot.jl:42-44, directional.jl:54-56 (I * π * world_radius^2 = (I·π)·r², r = pad / 2 exactly)
+            const float r = 0.5f * lr.pad;
+            const f3 power = lr.kind == 0 ? 4.0f * kPi * I : lr.kind == 2 ? I * kPi * (r * r) : I * 2.0f * kPi * (1.0f - 0.5f * (lr.cos_falloff_start + lr.cos_total_width));
             func[l] = to_Y(power);
         }
         cdf[0] = 0.0f;
         for (uint32_t i = 1; i <= n_lights; ++i) cdf[i] = cdf[i - 1] + func[i - 1] / (float)n_lights;
         func_int = cdf[n_lights];
         for (uint32_t i = 1; i <= n_lights; ++i) cdf[i] = func_int == 0.0f ? (float)((double)(i + 1) / (double)n_lights) : cdf[i] / func_int;
+        const int dl = sppm_directional_pick(scene->lights.data(), cdf.data(), n_lights, (uint64_t)n_iterations * (uint64_t)P);
+        if (dl >= 0)
+            return fail(ctx, TRHIP_ERR_UNSUPPORTED,
+                        "SPPM: the photon pass could pick light %d, a DirectionalLight, which has no sample_le in the reference (sppm.jl:361 would raise a MethodError)", dl + 1);
         ld_host = func;
         ld_host.insert(ld_host.end(), cdf.begin(), cdf.end());
         if (int rc = upload(ctx, ctx->sp_ldist, ld_host.data(), ld_host.size() * sizeof(float))) return rc;
@@ -190,7 +215,11 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
                          TraceOut{hits, nullptr, nullptr, nullptr, 0u, depth == 1 && far_camera(scene, sensor) ? 1u : 0u}, ctr->work_closest[depth - 1], ctr, pp.overflow[0].p);
             tm.end(1, st);
             tm.begin(2, st);
-            if (scene->dev.tri_tan)
+            if (has_directional_light(scene) && scene->dev.tri_tan)
+                hipLaunchKernelGGL((k_shade_sppm<true, true>), g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, hits, vp_all, terms, ctr, depth, max_depth, seed, it0, n, W);
+            else if (has_directional_light(scene))
+                hipLaunchKernelGGL((k_shade_sppm<false, true>), g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, hits, vp_all, terms, ctr, depth, max_depth, seed, it0, n, W);
+            else if (scene->dev.tri_tan)
                 hipLaunchKernelGGL(k_shade_sppm<true>, g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, hits, vp_all, terms, ctr, depth, max_depth, seed, it0, n, W);
             else
                 hipLaunchKernelGGL(k_shade_sppm<false>, g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, hits, vp_all, terms, ctr, depth, max_depth, seed, it0, n, W);

@@ -77,7 +77,10 @@ int render_whitted_impl(trhip_ctx* ctx, const trhip_scene* scene, const DeviceSe
                          TraceOut{hits, nullptr, nullptr, nullptr, 0u, depth == 1 && far_camera(scene, sensor) ? 1u : 0u}, ctr->work_closest[depth - 1], ctr);
             tm.end(1, st);
             tm.begin(2, st);
-            hipLaunchKernelGGL(k_shade_whitted, dim3(g_shade), blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, cap_shadow, hits, pool, base_in, base_out, ctr, flags, depth, max_depth);
+            if (has_directional_light(scene))
+                hipLaunchKernelGGL((k_shade_whitted<0, true>), dim3(g_shade), blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, cap_shadow, hits, pool, base_in, base_out, ctr, flags, depth, max_depth);
+            else
+                hipLaunchKernelGGL(k_shade_whitted, dim3(g_shade), blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, cap_shadow, hits, pool, base_in, base_out, ctr, flags, depth, max_depth);
             tm.end(2, st);
             tm.begin(3, st);
             launch_trace(ctx, st, scene, true, SegQueue{ctr->n_shadow[depth - 1], cap_shadow, 0u}, sq.o, sq.d, nullptr, TraceOut{nullptr, nullptr, nullptr, (uint8_t*)ctx->occl.p},
