@@ -243,7 +243,14 @@ int trhip_last_sample_radiance(trhip_ctx* ctx, float* out_rgb, uint64_t n_floats
  * a photon of Halton indices 0 .. n_iterations * photons_per_iteration - 1 — its CDF interval has nonzero width (power (I·π)·r² > 0,
  * directional.jl:54-56; or every light's power is 0 and the uniform CDF gives it an interval), or it is the last light and some
  * index of the range has radical_inverse(0, index) == 1.0f (index ≡ 2^25 - 1 mod 2^25, the first at 2^25 - 1).  Otherwise the light
- * renders through the camera pass's direct term alone. */
+ * renders through the camera pass's direct term alone.
+ * A GeometricPrimitive without a material (primitive.jl:1-9, material = nothing) is crossed as the reference crosses it
+ * (sppm.jl:218-222, 380-410): the ray goes on from p + 1e-6 d along d at the same depth, with the same β and sampler dimensions;
+ * a photon deposits at such a hit when its depth is > 1, as at any other hit.  Such a primitive still blocks shadow rays.  The
+ * reference follows crossings without end; this call follows at most TRHIP_SPPM_MAX_CROSSINGS of them per camera path or photon,
+ * and a call in which any path meets more returns TRHIP_ERR_UNSUPPORTED (the message names the cap and the number of paths over
+ * it) and no image.  With such primitives in the scene max_depth may be at most 63 - TRHIP_SPPM_MAX_CROSSINGS. */
+#define TRHIP_SPPM_MAX_CROSSINGS 8
 int trhip_render_sppm(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, float initial_search_radius, int max_depth, uint32_t n_iterations,
                       int64_t photons_per_iteration, uint64_t seed, float* out_xyzw, trhip_stats* stats);
 /* … with the reference's periodic image (integrators/sppm.jl:166-171: `iteration % write_frequency == 0 || iteration == n_iterations` -> _sppm_to_image,

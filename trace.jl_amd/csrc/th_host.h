@@ -154,7 +154,7 @@ struct trhip_scene {
     // the two optional mesh arrays (shapes/triangle_mesh.jl:11-14), beside the primitives and only when some mesh carries them (no scene of the reference does):
     // prim_tan[9 i ..] = primitive i's vertex tangents (PRIM_HAS_TANGENTS), prim_uv[7 i ..] = its corner (u, v)s and a "has" flag; empty = none
     std::vector<float> prim_tan, prim_uv;
-    bool has_materialless_prim = false;  // set at commit: some GeometricPrimitive has no material (the integrators refuse such a scene; the trace entry points accept it)
+    bool has_materialless_prim = false;  // set at commit: some GeometricPrimitive has no material (path and Whitted refuse such a scene; SPPM crosses it, th_sppm.h XING; the trace entry points accept it)
     std::vector<SphereRec> spheres;
     std::vector<HostAABB> sphere_bounds;
     std::vector<LightRec> lights;

@@ -51,6 +51,8 @@ struct Counters {  // device-resident
     unsigned long long fallback_why[4]; // … by reason, counted under "count_visits" (th_trace7.h)
     // hybrid mode under "count_visits": the visit counters split between the certified walk and the fallback walks (k_hybrid_count_mark, th_trace3c.h)
     unsigned long long nodes_seen, prims_seen, nodes_fallback, prims_fallback;
+    // SPPM in a scene with material-less primitives (th_sppm.h): camera paths [0] and photons [1] that met more than TRHIP_SPPM_MAX_CROSSINGS of them
+    unsigned long long sppm_over_cap[2];
 };
 // How a kernel sees a queue: kSeg segments of `cap` physical entries with fill counts in HBM, or (counts == nullptr) one
 // dense array of n_dense entries (kernel-level API entry points).

@@ -13,10 +13,23 @@
 //     the cells the visible point registers in (the same pairs the reference's bucket walk finds, k_sppm_gather), and the
 //     Float64 pixel update (:438-459).
 // M, radius, N, Ld and the visible points are bit-exact against the oracle; ϕ/τ are sums of the same terms in another order.
+//
+// Material-less primitives (GeometricPrimitive(shape) with material = nothing; XING = the scene holds one, scenes without keep the
+// XING = 0 kernels and launch sequence).  A hit on one is no vertex: the reference re-spawns the ray at p + 1e-6 d along d and goes
+// on at the SAME depth with the same β, specular_bounce and sampler dimensions (sppm.jl:218-222); a photon deposits there first when
+// its depth is > 1 (:380-410).  Here such a path re-enters the queue of the next launch of the host loop, so the loop index (`step`)
+// and the path's depth part: an entry carries its crossings so far in β's .w lane (bits 0-7; photons: bits 8-15 = those made at
+// depth 1) and depth = step - crossings.  Everything indexed by depth (Ld term slots, sampler and Halton dimensions, the max_depth
+// tests) reads the entry's depth; the queue and shadow counters are per step.  A photon's deposits get record slot
+// step - 2 - (crossings at depth 1): distinct per deposit, below max_depth - 1 + kMaxCrossings.  The reference follows crossings
+// without end; a path's crossing number kMaxCrossings + 1 is counted in Counters::sppm_over_cap instead and the call fails.
 #pragma once
+#include "../../include/tracehip.h"
 #include "th_kernels.h"
 
 namespace th {
+
+constexpr uint32_t kMaxCrossings = TRHIP_SPPM_MAX_CROSSINGS;
 
 // primes.jl: the first primes, 2 omitted.  Dimension k >= 1 of radical_inverse uses kOddPrimes[k - 1].
 __constant__ int kOddPrimes[256] = {
@@ -179,11 +192,11 @@ TH_D void add_nan_where(float4* L, uint32_t slot, uint32_t poison) {  // L += β
 #ifndef TH_SHADE_SPPM_WAVES
 #define TH_SHADE_SPPM_WAVES 3  // 180 VGPRs unconstrained (2 waves per SIMD); capped at 3: C4 shading section 162.9 -> 159.3 ms, at 4 (spills) 162.2
 #endif
-template <bool TAN = true, bool DIRL = false>
+template <bool TAN = true, bool DIRL = false, bool XING = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE_SPPM_WAVES))) void k_shade_sppm(DeviceScene sc, PathQueue qin, PathQueue qout, ShadowQueue sq, uint32_t cap, const float4* __restrict__ hits, VisiblePoints vp,
-                                                       float4* __restrict__ Ld, Counters* ctr, int depth, int max_depth, uint64_t seed, uint32_t it0, uint32_t n_pix, uint32_t width) {
+                                                       float4* __restrict__ Ld, Counters* ctr, int step, int max_depth, uint64_t seed, uint32_t it0, uint32_t n_pix, uint32_t width) {
     __shared__ SegView sv;
-    const SegQueue qv{ctr->n_queue[depth - 1], cap, 0u};
+    const SegQueue qv{ctr->n_queue[step - 1], cap, 0u};
     seg_load(qv, sv);
     const uint32_t total = sv.prefix[kSeg];
     uint32_t seg_in = 0;  // (carried over the iterations: seg_locate_from)
@@ -202,6 +215,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE
             const float4 o4 = qin.o[i], d4 = qin.d[i], b4 = qin.beta[i];
             const uint32_t slot = __float_as_uint(o4.w);
             const uint32_t it_local = slot / n_pix, pix = slot - it_local * n_pix;
+            const uint32_t xing = XING ? __float_as_uint(b4.w) : 0u;  // material-less surfaces crossed so far (header)
+            const int depth = step - (int)xing;
             const uint32_t term = (it_local * (uint32_t)max_depth + (uint32_t)(depth - 1)) * n_pix + pix;
             f3 beta = mk3(b4.x, b4.y, b4.z);
             const uint32_t poison = ((isnan_(beta.x) || isinf_(beta.x)) ? 1u : 0u) | ((isnan_(beta.y) || isinf_(beta.y)) ? 2u : 0u) | ((isnan_(beta.z) || isinf_(beta.z)) ? 4u : 0u);
@@ -212,7 +227,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE
                 const bool specular_bounce = __float_as_uint(d4.w) != 0u;
                 Shading sh;
                 uint32_t material;
-                if (rebuild_shading<false, TAN>(sc, prim, o, d, sh, material) && material != PRIM_NO_MATERIAL) {
+                const bool hit = rebuild_shading<false, TAN>(sc, prim, o, d, sh, material);
+                if (hit && material != PRIM_NO_MATERIAL) {
                     const LobeSet& bsdf = sc.materials[material].set[1];
                     const int py = 1 + (int)(pix / width), px = 1 + (int)(pix - (pix / width) * width);
                     const uint64_t key = ts_stream_key(seed, px, py, it0 + it_local - 1u);
@@ -272,21 +288,31 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE
                                 const f3 nd = check_direction(bs.wi);
                                 no4 = make_float4(org.x, org.y, org.z, __uint_as_float(slot));
                                 nd4 = make_float4(nd.x, nd.y, nd.z, __uint_as_float((bs.sampled_type & BSDF_SPECULAR) != 0 ? 1u : 0u));
-                                nb4 = make_float4(beta.x, beta.y, beta.z, 0.0f);
+                                nb4 = make_float4(beta.x, beta.y, beta.z, XING ? b4.w : 0.0f);
                                 want_next = true;
                             }
                         }
                     }
+                } else if constexpr (XING) {  // material-less: spawn_ray(si, ray.d) at the same depth, nothing else (:218-222)
+                    if (hit && xing >= kMaxCrossings) {
+                        atomicAdd(&ctr->sppm_over_cap[0], 1ull);
+                    } else if (hit) {
+                        const f3 org = sh.p + 1e-6f * d;
+                        no4 = make_float4(org.x, org.y, org.z, o4.w);
+                        nd4 = d4;
+                        nb4 = make_float4(b4.x, b4.y, b4.z, __uint_as_float(xing + 1u));
+                        want_next = true;
+                    }
                 }
             }
         }
-        const uint32_t si = seg_out * cap + wave_compact(want_shadow, &ctr->n_shadow[depth - 1][seg_out * kCtrStride]);
+        const uint32_t si = seg_out * cap + wave_compact(want_shadow, &ctr->n_shadow[step - 1][seg_out * kCtrStride]);
         if (want_shadow) {
             sq.o[si] = so4;
             sq.d[si] = sd4;
             sq.c[si] = sc4;
         }
-        const uint32_t ni = seg_out * cap + wave_compact(want_next, &ctr->n_queue[depth][seg_out * kCtrStride]);
+        const uint32_t ni = seg_out * cap + wave_compact(want_next, &ctr->n_queue[step][seg_out * kCtrStride]);
         if (want_next) {
             qout.o[ni] = no4;
             qout.d[ni] = nd4;
@@ -580,12 +606,12 @@ constexpr int kPhotonRings = 4;
 #ifndef TH_SHADE_PHOTON_WAVES
 #define TH_SHADE_PHOTON_WAVES 4
 #endif
-template <bool TAN = true>
+template <bool TAN = true, bool XING = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE_PHOTON_WAVES))) void k_shade_photon(DeviceScene sc, PathQueue qin, PathQueue qout, uint32_t cap, const float4* __restrict__ hits, PhotonRecords rec,
-                                                         uint32_t n_batch_photons, Counters* ctr, int depth, int max_depth, uint64_t halton_base) {
+                                                         uint32_t n_batch_photons, Counters* ctr, int step, int max_depth, uint64_t halton_base) {
     __shared__ SegView sv;
     __shared__ uint32_t s_ring[kBlock / 64][kPhotonRings][128];
-    const SegQueue qv{ctr->n_queue[depth - 1], cap, 0u};
+    const SegQueue qv{ctr->n_queue[step - 1], cap, 0u};
     seg_load(qv, sv);
     const uint32_t total = sv.prefix[kSeg];
     const uint32_t lane = lane_id(), wv = threadIdx.x >> 6;
@@ -606,10 +632,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE
             const f3 beta = mk3(b4.x, b4.y, b4.z);
             Shading sh;
             uint32_t material;
-            if (rebuild_shading<false, TAN>(sc, prim, o, d, sh, material) && material != PRIM_NO_MATERIAL) {
+            const bool hit = rebuild_shading<false, TAN>(sc, prim, o, d, sh, material);
+            // (after the line above: the lambda's captures keep the order, hence the closure layout and the code, of the kernel before XING)
+            const uint32_t xw = XING ? __float_as_uint(b4.w) : 0u, xing = xw & 0xffu, xing1 = xw >> 8;  // crossings so far, those at depth 1 (header)
+            const int depth = step - (int)xing;
+            const int rec_slot = XING ? step - 2 - (int)xing1 : depth - 2;  // (a deposit's slot, read only at depth > 1)
+            if (hit && material != PRIM_NO_MATERIAL) {
                 const f3 wi_photon = -d;
                 if (depth > 1) {
-                    const size_t r = (size_t)(depth - 2) * n_batch_photons + photon;
+                    const size_t r = (size_t)rec_slot * n_batch_photons + photon;
                     rec.p[r] = make_float4(sh.p.x, sh.p.y, sh.p.z, 0.0f);
                     rec.wi[r] = make_float4(wi_photon.x, wi_photon.y, wi_photon.z, 0.0f);
                     rec.beta[r] = b4;
@@ -632,9 +663,26 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE
                         want_next = true;
                     }
                 }
+            } else if constexpr (XING) {  // material-less: deposit as at any hit, then spawn_ray(si, ray.d) at the same depth and Halton dimension (:380-410)
+                if (hit && xing >= kMaxCrossings) {
+                    atomicAdd(&ctr->sppm_over_cap[1], 1ull);
+                } else if (hit) {
+                    if (depth > 1) {
+                        const size_t r = (size_t)rec_slot * n_batch_photons + photon;
+                        rec.p[r] = make_float4(sh.p.x, sh.p.y, sh.p.z, 0.0f);
+                        rec.wi[r] = make_float4(-d.x, -d.y, -d.z, 0.0f);
+                        rec.beta[r] = b4;
+                        rec.valid[r] = 1;
+                    }
+                    const f3 org = sh.p + 1e-6f * d;
+                    no4 = make_float4(org.x, org.y, org.z, o4.w);
+                    nd4 = d4;
+                    nb4 = make_float4(b4.x, b4.y, b4.z, __uint_as_float(xw + (depth == 1 ? 0x101u : 1u)));
+                    want_next = true;
+                }
             }
         }
-        const uint32_t ni = seg_out * cap + wave_compact(want_next, &ctr->n_queue[depth][seg_out * kCtrStride]);
+        const uint32_t ni = seg_out * cap + wave_compact(want_next, &ctr->n_queue[step][seg_out * kCtrStride]);
         if (want_next) {
             qout.o[ni] = no4;
             qout.d[ni] = nd4;

@@ -36,7 +36,13 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     if (ds.film_w <= 0 || ds.film_h <= 0) return fail(ctx, TRHIP_ERR_INVALID, "empty film");
     if (ds.crop_min[0] != 1.0f || ds.crop_min[1] != 1.0f)
         return fail(ctx, TRHIP_ERR_UNSUPPORTED, "SPPM needs a film whose crop starts at pixel (1, 1): sppm.jl:203 indexes pixels[y, x] with raster coordinates");
-    if (scene->has_materialless_prim) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "SPPM: primitives without a material are not supported on the device");
+    // material-less primitives (th_sppm.h, XING): a crossing re-enters the queue of the next step at its old depth, so the step loops below run up to
+    // kMaxCrossings more launches than max_depth; the queue counters have rows for kMaxDepth + 2 steps.  Scenes without such primitives keep their launch sequence.
+    const bool xing = scene->has_materialless_prim;
+    const int n_steps = max_depth + (xing ? (int)kMaxCrossings : 0);
+    if (xing && n_steps > kMaxDepth + 1)
+        return fail(ctx, TRHIP_ERR_UNSUPPORTED, "SPPM: with material-less primitives max_depth must be at most %d (%d steps of the wavefront are kept for crossings)", kMaxDepth + 1 - (int)kMaxCrossings,
+                    (int)kMaxCrossings);
     const uint32_t W = (uint32_t)ds.film_w, H = (uint32_t)ds.film_h;
     const uint64_t n64 = (uint64_t)W * H;
     if (n64 >= (1ull << 26)) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "SPPM: more than 2^26 film pixels");
@@ -74,7 +80,9 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     // independent of the pixel statistics, so B iterations share every traversal / shading launch (B x the rays per
     // launch, 1/B the launches and traversal tails); only grid -> deposit -> update runs once per iteration, in order.
     const uint64_t Qit = std::max<uint64_t>(n, (uint64_t)P);
-    const int ndep = std::max(1, max_depth - 1);
+    // photon deposits per photon: one per depth 2 .. max_depth, and one per crossing of a material-less surface at depth > 1 (th_sppm.h)
+    const int rec_depths = max_depth - 1 + (xing ? (int)kMaxCrossings : 0);
+    const int ndep = std::max(1, rec_depths);
     const double per_iter = (double)n * (7 * 16.0 + max_depth * 16.0) + (double)P * ndep * 49.0 + (double)Qit * 10 * 16.0;
     uint64_t B = ctx->sppm_batch;
     if (B == 0) {
@@ -85,7 +93,8 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     }
     B = std::min<uint64_t>(B, n_iterations);
     while (B > 1 && (B * Qit >= (1ull << 31) || B * (uint64_t)max_depth * n >= (1ull << 32) || B * (uint64_t)P * ndep >= (1ull << 32))) B = (B + 1) / 2;
-    if ((uint64_t)P * ndep >= (1ull << 32)) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "SPPM: photons_per_iteration x (max_depth - 1) must stay below 2^32");
+    if ((uint64_t)P * ndep >= (1ull << 32))
+        return fail(ctx, TRHIP_ERR_UNSUPPORTED, "SPPM: photons_per_iteration x (max_depth - 1%s) must stay below 2^32", xing ? " + TRHIP_SPPM_MAX_CROSSINGS" : "");
     const uint64_t Q = B * Qit;
     const uint32_t cap = (uint32_t)(((Q + kSeg - 1) / kSeg + 2 * kSegGran + kSegGran - 1) / kSegGran * kSegGran);
     const uint64_t Pphys = (uint64_t)cap * kSeg;
@@ -193,6 +202,26 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     // sppm.jl:166-171 stores and saves the image whenever `iteration % write_frequency == 0`: with a write callback no batch runs past such an iteration (the image of
     // iteration k is built from the pixels as they are after k iterations — Ld is folded per batch), and the host gets the image there
     const bool periodic = write_cb != nullptr && write_frequency > 0;
+    // the crossing cap (th_sppm.h): no image leaves a call in which a camera path or a photon met more than kMaxCrossings material-less surfaces.  In a job the
+    // counts are summed over the ranks first (the photons are sharded), so that the ranks fail together.
+    auto over_cap = [&]() -> int {
+        if (!xing) return 0;
+        unsigned long long over[2] = {0ull, 0ull};
+        const void* src = ctr->sppm_over_cap;
+        if (ctx->comm.comm && ctx->comm.n_ranks > 1) {
+            if (int rc = ensure(ctx, ctx->cb_rc, sizeof over)) return rc;
+            NCCL_TRY(ctx, rccl_api()->AllReduce(ctr->sppm_over_cap, ctx->cb_rc.p, 2, ncclUint64, ncclSum, ctx->comm.comm, st));
+            src = ctx->cb_rc.p;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(over, src, sizeof over, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (over[0] == 0 && over[1] == 0) return 0;
+        ctx->sp_pixels = 0;  // (nothing for trhip_sppm_state either)
+        return fail(ctx, TRHIP_ERR_UNSUPPORTED,
+                    "SPPM: %llu camera paths and %llu photons cross more than %u material-less surfaces (TRHIP_SPPM_MAX_CROSSINGS = %u); the reference follows every crossing, "
+                    "this build refuses the call",
+                    over[0], over[1], kMaxCrossings, kMaxCrossings);
+    };
     uint32_t nb = 0;
     for (uint32_t it0 = 1; it0 <= n_iterations; it0 += nb) {
         nb = (uint32_t)std::min<uint64_t>(B, n_iterations - it0 + 1);
@@ -209,23 +238,29 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         hipLaunchKernelGGL(k_sppm_raygen, dim3(grid_for(ctx, (uint64_t)nb * n, 8)), blk, 0, st, dsp, nb * n, n, W, seed, it0, pq[0], cap, ctr);
         tm.end(0, st);
         int cur = 0;
-        for (int depth = 1; depth <= max_depth; ++depth) {
+        // step s traces the paths of depth s - (their crossings): without material-less primitives step == depth.  Only step 1 holds camera rays alone, the rays the
+        // far_hint cull form is proven for (th_trace3c.h); crossings spawn their rays at steps >= 2.
+        for (int step = 1; step <= n_steps; ++step) {
             tm.begin(1, st);
-            launch_trace(ctx, st, scene, false, SegQueue{ctr->n_queue[depth - 1], cap, 0u}, pq[cur].o, pq[cur].d, nullptr,
-                         TraceOut{hits, nullptr, nullptr, nullptr, 0u, depth == 1 && far_camera(scene, sensor) ? 1u : 0u}, ctr->work_closest[depth - 1], ctr, pp.overflow[0].p);
+            launch_trace(ctx, st, scene, false, SegQueue{ctr->n_queue[step - 1], cap, 0u}, pq[cur].o, pq[cur].d, nullptr,
+                         TraceOut{hits, nullptr, nullptr, nullptr, 0u, step == 1 && far_camera(scene, sensor) ? 1u : 0u}, ctr->work_closest[step - 1], ctr, pp.overflow[0].p);
             tm.end(1, st);
             tm.begin(2, st);
-            if (has_directional_light(scene) && scene->dev.tri_tan)
-                hipLaunchKernelGGL((k_shade_sppm<true, true>), g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, hits, vp_all, terms, ctr, depth, max_depth, seed, it0, n, W);
+            if (xing && has_directional_light(scene))  // (TAN = true serves scenes without tangents too)
+                hipLaunchKernelGGL((k_shade_sppm<true, true, true>), g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, hits, vp_all, terms, ctr, step, max_depth, seed, it0, n, W);
+            else if (xing)
+                hipLaunchKernelGGL((k_shade_sppm<true, false, true>), g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, hits, vp_all, terms, ctr, step, max_depth, seed, it0, n, W);
+            else if (has_directional_light(scene) && scene->dev.tri_tan)
+                hipLaunchKernelGGL((k_shade_sppm<true, true>), g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, hits, vp_all, terms, ctr, step, max_depth, seed, it0, n, W);
             else if (has_directional_light(scene))
-                hipLaunchKernelGGL((k_shade_sppm<false, true>), g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, hits, vp_all, terms, ctr, depth, max_depth, seed, it0, n, W);
+                hipLaunchKernelGGL((k_shade_sppm<false, true>), g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, hits, vp_all, terms, ctr, step, max_depth, seed, it0, n, W);
             else if (scene->dev.tri_tan)
-                hipLaunchKernelGGL(k_shade_sppm<true>, g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, hits, vp_all, terms, ctr, depth, max_depth, seed, it0, n, W);
+                hipLaunchKernelGGL(k_shade_sppm<true>, g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, hits, vp_all, terms, ctr, step, max_depth, seed, it0, n, W);
             else
-                hipLaunchKernelGGL(k_shade_sppm<false>, g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, hits, vp_all, terms, ctr, depth, max_depth, seed, it0, n, W);
+                hipLaunchKernelGGL(k_shade_sppm<false>, g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], sq, cap, hits, vp_all, terms, ctr, step, max_depth, seed, it0, n, W);
             tm.end(2, st);
             tm.begin(3, st);
-            launch_trace(ctx, st, scene, true, SegQueue{ctr->n_shadow[depth - 1], cap, 0u}, sq.o, sq.d, nullptr, TraceOut{nullptr, terms, sq.c, nullptr, 0u, 0u, 0u, nullptr, 1u}, ctr->work_shadow[depth - 1], ctr,
+            launch_trace(ctx, st, scene, true, SegQueue{ctr->n_shadow[step - 1], cap, 0u}, sq.o, sq.d, nullptr, TraceOut{nullptr, terms, sq.c, nullptr, 0u, 0u, 0u, nullptr, 1u}, ctr->work_shadow[step - 1], ctr,
                          pp.overflow[0].p);
             tm.end(3, st);
             cur ^= 1;
@@ -244,16 +279,18 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
             hipLaunchKernelGGL(k_photon_gen, dim3(grid_for(ctx, NP, 8)), blk, 0, st, scene->dev, ldist, NP, halton_base, pq[0], cap, ctr, (uint32_t)P, p_lo, p_hi);
             tm.end(0, st);
             cur = 0;
-            for (int depth = 1; depth <= max_depth; ++depth) {
+            for (int step = 1; step <= n_steps; ++step) {
                 tm.begin(1, st);
-                launch_trace(ctx, st, scene, false, SegQueue{ctr->n_queue[depth - 1], cap, 0u}, pq[cur].o, pq[cur].d, nullptr, TraceOut{hits, nullptr, nullptr, nullptr}, ctr->work_closest[depth - 1],
+                launch_trace(ctx, st, scene, false, SegQueue{ctr->n_queue[step - 1], cap, 0u}, pq[cur].o, pq[cur].d, nullptr, TraceOut{hits, nullptr, nullptr, nullptr}, ctr->work_closest[step - 1],
                              ctr, pp.overflow[0].p);
                 tm.end(1, st);
                 tm.begin(2, st);
-                if (scene->dev.tri_tan)
-                    hipLaunchKernelGGL(k_shade_photon<true>, g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], cap, hits, rec, NP, ctr, depth, max_depth, halton_base);
+                if (xing)
+                    hipLaunchKernelGGL((k_shade_photon<true, true>), g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], cap, hits, rec, NP, ctr, step, max_depth, halton_base);
+                else if (scene->dev.tri_tan)
+                    hipLaunchKernelGGL(k_shade_photon<true>, g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], cap, hits, rec, NP, ctr, step, max_depth, halton_base);
                 else
-                    hipLaunchKernelGGL(k_shade_photon<false>, g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], cap, hits, rec, NP, ctr, depth, max_depth, halton_base);
+                    hipLaunchKernelGGL(k_shade_photon<false>, g_shade, blk, 0, st, scene->dev, pq[cur], pq[cur ^ 1], cap, hits, rec, NP, ctr, step, max_depth, halton_base);
                 tm.end(2, st);
                 cur ^= 1;
             }
@@ -269,13 +306,13 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
             hipLaunchKernelGGL(k_sppm_grid_setup, dim3(1), dim3(64), 0, st, grid);
             const dim3 g_rec(grid_for(ctx, (uint64_t)P * ndep, 8));
             if (n_lights)
-                hipLaunchKernelGGL(k_sppm_hit_bin, g_rec, blk, 0, st, (const float4*)rec.p, (const uint8_t*)rec.valid, NP, j * (uint32_t)P, (uint32_t)P, (uint32_t)(max_depth - 1), n, grid, counts,
+                hipLaunchKernelGGL(k_sppm_hit_bin, g_rec, blk, 0, st, (const float4*)rec.p, (const uint8_t*)rec.valid, NP, j * (uint32_t)P, (uint32_t)P, (uint32_t)rec_depths, n, grid, counts,
                                    (const uint32_t*)starts, entries, 0);
             hipLaunchKernelGGL(k_sppm_scan_tiles, dim3(n_tiles), blk, 0, st, (const uint32_t*)counts, starts, n, tile_sums);
             hipLaunchKernelGGL(k_sppm_scan, dim3(1), dim3(1024), 0, st, (const uint32_t*)tile_sums, tile_offsets, n_tiles, grid);
             hipLaunchKernelGGL(k_sppm_scan_add, g_pix, blk, 0, st, starts, n, (const uint32_t*)tile_offsets, n_tiles);
             if (n_lights)
-                hipLaunchKernelGGL(k_sppm_hit_bin, g_rec, blk, 0, st, (const float4*)rec.p, (const uint8_t*)rec.valid, NP, j * (uint32_t)P, (uint32_t)P, (uint32_t)(max_depth - 1), n, grid, counts,
+                hipLaunchKernelGGL(k_sppm_hit_bin, g_rec, blk, 0, st, (const float4*)rec.p, (const uint8_t*)rec.valid, NP, j * (uint32_t)P, (uint32_t)P, (uint32_t)rec_depths, n, grid, counts,
                                    (const uint32_t*)starts, entries, 1);
             tm.end(6, st);
             tm.begin(5, st);
@@ -307,6 +344,7 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
             hipLaunchKernelGGL(k_sppm_image, g_pix, blk, 0, st, n, it_done, (uint64_t)P, px, (float4*)ctx->film.p);  // _sppm_to_image(i, pixels, iteration)
             tm.end(4, st);
             HIP_TRY(ctx, hipStreamSynchronize(st));
+            if (int rc = over_cap()) return rc;
             HIP_TRY(ctx, hipMemcpy(out_xyzw, ctx->film.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
             int rc_cb = write_cb(write_user, it_done, out_xyzw);
             if (ctx->comm.comm && ctx->comm.n_ranks > 1) {
@@ -329,6 +367,7 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     HIP_TRY(ctx, hipEventRecord(e1, st));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (int rc = over_cap()) return rc;
     HIP_TRY(ctx, hipMemcpy(out_xyzw, ctx->film.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
     GridInfo gi;
     HIP_TRY(ctx, hipMemcpy(&gi, grid, sizeof gi, hipMemcpyDeviceToHost));
