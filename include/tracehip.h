@@ -111,6 +111,18 @@ int trhip_scene_add_directional_light(trhip_scene* scene, const float I[3], cons
  * already holds Trace.jl's BVHAccel hands its nodes over with trhip_scene_set_bvh (what TraceHIP.jl does). */
 int trhip_scene_commit(trhip_scene* scene, int max_node_primitives);
 
+/* A relit view of a committed scene: Scene(new_lights, the same BVHAccel) without building its geometry again.  *out shares `base`'s committed geometry (trees, primitive
+ * and shading records, materials, the accelerator and its certificate data), belongs to base's context, starts with NO lights and is not committed.  Add lights with
+ * trhip_scene_add_*_light, then trhip_scene_commit(*out, max_node_primitives): on a view it runs only the light stage (uploads the lights and orders the any-hit tests by
+ * them) and max_node_primitives must be what the geometry was committed with.  Renders on the view return, bit for bit, what a fresh commit of the same primitives with
+ * those lights returns.  A relit view can be relit in turn (same geometry).  The geometry is reference-counted: freeing base leaves its views working.  Committing base
+ * again (after adding primitives or materials, say) gives base new geometry; earlier views keep theirs.  Context options read at commit time do not apply to a view: it
+ * has its base's trees, trhip_scene_bvh_mode and trhip_scene_bvh_note.  On a view, adding materials or primitives and trhip_scene_set_bvh are refused
+ * (TRHIP_ERR_INVALID), and so is trhip_scene_set_bvh on a scene whose geometry a live view still shares.  TRHIP_ERR_INVALID when base is not committed. */
+int trhip_scene_relight(const trhip_scene* base, trhip_scene** out);
+/* An identifier of the committed geometry a handle holds: two handles return the same id exactly when they share it (0: never committed). */
+int trhip_scene_geometry_id(const trhip_scene* scene, uint64_t* id);
+
 /* BVHAccel construction alone, on the host (no GPU needed): builder 0 = the library's binned SAH, 2 = the REFERENCE's construction node for node
  * (accel/bvh.jl:87-206 + partition! Trace.jl:128-137, quirks kept — SURVEY.md A.6; what trhip_scene_commit builds under option "bvh_builder" = 2).
  * prim_bounds: n_prims * 6 (world_bound of each primitive: min xyz, max xyz).  Outputs in the layout of trhip_scene_get_bvh; *n_nodes_inout = capacity

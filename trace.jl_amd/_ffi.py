@@ -113,6 +113,8 @@ SIGNATURES = {
     "trhip_scene_add_spot_light": (C.c_int, [_VP, _F, _F, _F, C.c_float, C.c_float]),
     "trhip_scene_add_directional_light": (C.c_int, [_VP, _F, _F, C.c_float]),
     "trhip_scene_commit": (C.c_int, [_VP, C.c_int]),
+    "trhip_scene_relight": (C.c_int, [_VP, C.POINTER(_VP)]),
+    "trhip_scene_geometry_id": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
     "trhip_build_bvh_host": (C.c_int, [C.c_int, _F, C.c_uint32, C.c_int, _F, _U32, _U32, _U32, _U32, _U32]),
     "trhip_scene_bvh_size": (C.c_int, [_VP, _U32, _U32]),
     "trhip_scene_get_bvh": (C.c_int, [_VP, _F, _U32, _U32, _U32]),

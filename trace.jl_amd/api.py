@@ -450,13 +450,22 @@ class Scene:  # Trace.jl:176-187
         self.aggregate = aggregate
         self._flat = None
         self._bound = None
+        self._base = None  # with_lights: the scene whose committed geometry this one shares
+
+    def with_lights(self, lights) -> "Scene":
+        """Scene(lights, self.aggregate) that shares this scene's committed geometry: its flatten() flattens this scene on the context if needed, then takes a relit view
+        of it (trhip_scene_relight) and commits only the new lights.  Renders are bit for bit a fresh Scene(lights, self.aggregate)'s.  The geometry is the one this scene
+        was committed with: primitives changed in place or options changed since do not apply to it (Scene(lights, aggregate) commits in full)."""
+        s = Scene(lights, self.aggregate)
+        s._base = self
+        return s
 
     @property
     def bound(self) -> np.ndarray:
         """scene.bound = world_bound(aggregate) (Trace.jl:183, accel/bvh.jl:208-210), as 6 Float32s p_min, p_max: the root box of the reference's BVH, i.e.
         the union of every primitive's world_bound (nested BVHs through their own root boxes), Bounds3() = (Inf, -Inf) without primitives."""
         if self._bound is None:
-            self._bound = _primitives_bound(self.aggregate.primitives)
+            self._bound = self._base.bound if self._base is not None else _primitives_bound(self.aggregate.primitives)
         return self._bound.copy()
 
     def flatten(self, ctx: Optional[_ffi.Context] = None) -> "FlatScene":
@@ -464,7 +473,10 @@ class Scene:  # Trace.jl:176-187
         if self._flat is not None and self._flat.light_keys != [_light_key(l) for l in self.lights]:
             self._flat = None
         if self._flat is None or (ctx is not None and self._flat.ctx is not ctx):
-            self._flat = FlatScene(self, ctx or _ffi.default_context())
+            if self._base is not None:  # with_lights: the base's committed geometry, this scene's lights (a light change relights again)
+                self._flat = FlatScene.relight(self._base.flatten(ctx), self)
+            else:
+                self._flat = FlatScene(self, ctx or _ffi.default_context())
         return self._flat
 
 
@@ -712,6 +724,24 @@ class FlatScene:
                 i = j
             else:
                 raise TraceHipError(f"unsupported shape {type(p.shape).__name__}")
+        self._add_lights(scene)
+        ctx.check(L.trhip_scene_commit(self._h, scene.aggregate.max_node_primitives))
+
+    @classmethod
+    def relight(cls, base: "FlatScene", scene: Scene) -> "FlatScene":
+        """A relit view of the committed `base` (trhip_scene_relight) with `scene`'s lights: the light stage of a commit alone, the geometry shared."""
+        L = _ffi.lib()
+        self = cls.__new__(cls)
+        self.ctx = base.ctx
+        self._h = C.c_void_p()
+        self.n_prims = base.n_prims
+        self.ctx.check(L.trhip_scene_relight(base._h, C.byref(self._h)))
+        self._add_lights(scene)
+        self.ctx.check(L.trhip_scene_commit(self._h, scene.aggregate.max_node_primitives))
+        return self
+
+    def _add_lights(self, scene: Scene):
+        L, ctx = _ffi.lib(), self.ctx
         self.light_keys = [_light_key(l) for l in scene.lights]
         for l in scene.lights:
             m, im = _ffi.f32(l.light_to_world.m), _ffi.f32(l.light_to_world.inv_m)
@@ -724,7 +754,6 @@ class FlatScene:
                 ctx.check(L.trhip_scene_add_directional_light(self._h, _ffi.fptr(I), _ffi.fptr(_ffi.f32(l.direction)), float(f32(l.world_radius))))
             else:
                 raise TraceHipError(f"unsupported light {type(l).__name__}")
-        ctx.check(L.trhip_scene_commit(self._h, scene.aggregate.max_node_primitives))
 
     def _add_triangles(self, ctx, mesh, idx, mats, flip, ks):
         """One trhip_scene_add_triangles(_ex) call; ks = the triangle numbers of `idx` inside the mesh (None: all, in order) — the corner uvs follow them."""
@@ -751,6 +780,13 @@ class FlatScene:
         order = np.empty(npr.value, dtype=np.uint32)
         self.ctx.check(L.trhip_scene_get_bvh(self._h, _ffi.fptr(bounds), _ffi.u32ptr(a), _ffi.u32ptr(flags), _ffi.u32ptr(order)))
         return bounds, a, flags, order
+
+    @property
+    def geometry_id(self) -> int:
+        """Which committed geometry this flat scene holds (trhip_scene_geometry_id): equal for a scene and its relit views (Scene.with_lights), new for every full commit."""
+        out = C.c_uint64()
+        self.ctx.check(_ffi.lib().trhip_scene_geometry_id(self._h, C.byref(out)))
+        return out.value
 
     def bvh_note(self) -> str:
         """Why a default commit holds one tree instead of two (trhip_scene_bvh_note); "" when it holds both."""

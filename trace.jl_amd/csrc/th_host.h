@@ -147,39 +147,63 @@ struct HostPrim {
     uint32_t sphere_id;  // for spheres
 };
 
-struct trhip_scene {
-    trhip_ctx* ctx = nullptr;
+inline void release(DevBuf& b);
+
+// What a commit derives from the primitives alone: the host records, both trees and every device buffer made from them.  A scene holds it through a shared_ptr: its relit
+// views (trhip_scene_relight) share it, each with its own lights.  The device buffers are released with the last handle that holds them.
+struct SceneGeometry {
+    uint64_t id = 0;  // trhip_scene_geometry_id: a new value for every tree this geometry is committed with (0 = never committed)
+    int max_node_primitives = -1;  // what the last trhip_scene_commit built the trees with (-1: a caller's tree alone, trhip_scene_set_bvh)
     std::vector<MaterialRec> materials;
     std::vector<HostPrim> prims;  // caller order
     // the two optional mesh arrays (shapes/triangle_mesh.jl:11-14), beside the primitives and only when some mesh carries them (no scene of the reference does):
     // prim_tan[9 i ..] = primitive i's vertex tangents (PRIM_HAS_TANGENTS), prim_uv[7 i ..] = its corner (u, v)s and a "has" flag; empty = none
     std::vector<float> prim_tan, prim_uv;
-    bool has_materialless_prim = false;  // set at commit: some GeometricPrimitive has no material (path and Whitted refuse such a scene; SPPM crosses it, th_sppm.h XING; the trace entry points accept it)
     std::vector<SphereRec> spheres;
     std::vector<HostAABB> sphere_bounds;
-    std::vector<LightRec> lights;
     FlatBVH bvh;
-    bool committed = false;
+    // ---- hybrid mode (th_trace3c.h): `bvh` above is the CANONICAL tree (the reference's construction, or the host's own tree) — slots, shading records, the inspection API
+    // and the answers are its; `acc` is the library's tree over the same primitives, which most rays walk instead
+    FlatBVH acc;  // order[k] = caller primitive of accelerator slot k; empty without an accelerator
+    // the any-hit pre-pass candidates (th_trace2.h, k_any_occluders): the largest triangles' ordered slots by area and their leaves' boxes; the light stage orders them
+    std::vector<uint32_t> occ_slots;
+    std::vector<float> occ_boxes;
     DevBuf d_leaf_boxes;  // one-leaf scenes: the boxes of the leaf's triangles in slot order (th_leaf2.h)
-    DevBuf d_nodes, d_prims, d_nrm, d_tan, d_shade, d_spheres, d_materials, d_lights, d_wnodes;
+    DevBuf d_nodes, d_prims, d_nrm, d_tan, d_shade, d_spheres, d_materials, d_wnodes, d_w8nodes, d_w8tris;
+    DevBuf d_acc_w4nodes;  // the accelerator four children wide (th_trace3c4.h)
+    DevBuf d_acc_wnodes, d_acc_prims, d_slot_boxes, d_sphere_boxes, d_sphere_slots, d_sphere_cert;
+    SceneGeometry() = default;
+    SceneGeometry(const SceneGeometry&) = delete;
+    SceneGeometry& operator=(const SceneGeometry&) = delete;
+    ~SceneGeometry() {
+        for (DevBuf* b : {&d_leaf_boxes, &d_nodes, &d_prims, &d_nrm, &d_tan, &d_shade, &d_spheres, &d_materials, &d_wnodes, &d_w8nodes, &d_w8tris, &d_acc_w4nodes, &d_acc_wnodes,
+                          &d_acc_prims, &d_slot_boxes, &d_sphere_boxes, &d_sphere_slots, &d_sphere_cert})
+            release(*b);
+    }
+};
+
+struct trhip_scene {
+    trhip_ctx* ctx = nullptr;
+    std::shared_ptr<SceneGeometry> g = std::make_shared<SceneGeometry>();
+    bool relit = false;  // a relit view (trhip_scene_relight): its geometry is fixed, a commit runs the light stage alone
+    bool has_materialless_prim = false;  // set at commit: some GeometricPrimitive has no material (path and Whitted refuse such a scene; SPPM crosses it, th_sppm.h XING; the trace entry points accept it)
+    std::vector<LightRec> lights;
+    bool committed = false;
+    // ---- what the light stage (tu_scene.hip, commit_lights) owns: the light records and the any-hit test orders computed from them
+    DevBuf d_lights, d_leaf_order, d_acc_leaf_order, d_occ_slots, d_occ_boxes;
+    uint32_t n_occluders = 0;     // the scene's largest triangles, tested first by any-hit rays (th_trace2.h, k_any_occluders)
+    // ---- views of the geometry (pointers into g's buffers; the light pointers and orders patched in by the light stage)
     DeviceScene dev{};
     WideScene wide{};
-    DevBuf d_occ_slots, d_occ_boxes, d_w8nodes, d_w8tris, d_leaf_order;
     Wide8Scene w8{};              // the 8-wide view of the triangles' subtree (th_wide8.h / th_trace8.h)
     uint32_t w8_nodes = 0, w8_depth = 0;
-    uint32_t n_occluders = 0;     // the scene's largest triangles, tested first by any-hit rays (th_trace2.h, k_any_occluders)
     bool partial_spheres = false;  // some sphere is clipped (z range or ϕ_max): traversal kernels with the general sphere test
     bool wide_ok = false;
     bool w8_ok = false;            // the 8-wide view exists (th_trace8.h)
     bool literal_only = false;     // a caller-supplied BVH whose boxes do not nest (trhip_scene_set_bvh): literal kernels only
-    // ---- hybrid mode (th_trace3c.h): `bvh` above is the CANONICAL tree (the reference's construction, or the host's own tree) — slots, shading records, the inspection API
-    // and the answers are its; `acc` is the library's tree over the same primitives, which most rays walk instead
-    FlatBVH acc;                   // order[k] = caller primitive of accelerator slot k; empty without an accelerator
     bool hybrid_ok = false;        // the accelerator exists and its leaves carry the canonical leaves' boxes bit for bit
     std::string bvh_note;          // why a default commit ended with one tree (trhip_scene_bvh_note)
     int bvh_mode = 0;              // what trhip_scene_commit / trhip_scene_set_bvh built: 0 the library's tree alone, 1 the canonical (reference / host) tree alone, 2 both
-    DevBuf d_acc_w4nodes;  // the accelerator four children wide (th_trace3c4.h)
-    DevBuf d_acc_wnodes, d_acc_prims, d_slot_boxes, d_sphere_boxes, d_sphere_slots, d_sphere_cert, d_acc_leaf_order;
     WideScene wide_acc{};
     DeviceScene dev_acc{};         // dev with the accelerator's primitive records
     CertScene cert{};

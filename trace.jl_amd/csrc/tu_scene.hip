@@ -216,15 +216,15 @@ float det3(const float* m) {  // rows of the upper-left 3x3 of a row-major 4x4
 
 // does the subtree rooted at flat node `root` hold a sphere?  (depth-first layout: the subtree is a contiguous index range)
 bool has_sphere_subtree(const trhip_scene* s, uint32_t root) {
-    const uint32_t n_nodes = (uint32_t)s->bvh.a.size(), n_prims = (uint32_t)s->bvh.order.size();
+    const uint32_t n_nodes = (uint32_t)s->g->bvh.a.size(), n_prims = (uint32_t)s->g->bvh.order.size();
     if (root >= n_nodes) return true;
     // end of the subtree: follow second children until a leaf
     uint32_t end = root;
-    while ((s->bvh.flags[end] & 3u) != 3u) end = s->bvh.a[end];
+    while ((s->g->bvh.flags[end] & 3u) != 3u) end = s->g->bvh.a[end];
     for (uint32_t i = root; i <= end && i < n_nodes; ++i)
-        if ((s->bvh.flags[i] & 3u) == 3u)
-            for (uint32_t k = s->bvh.a[i]; k < s->bvh.a[i] + (s->bvh.flags[i] >> 2) && k < n_prims; ++k)
-                if (s->prims[s->bvh.order[k]].kind == 1) return true;
+        if ((s->g->bvh.flags[i] & 3u) == 3u)
+            for (uint32_t k = s->g->bvh.a[i]; k < s->g->bvh.a[i] + (s->g->bvh.flags[i] >> 2) && k < n_prims; ++k)
+                if (s->g->prims[s->g->bvh.order[k]].kind == 1) return true;
     return false;
 }
 }  // namespace
@@ -232,18 +232,18 @@ bool has_sphere_subtree(const trhip_scene* s, uint32_t root) {
 int upload_scene(trhip_scene* s) {
     trhip_ctx* ctx = s->ctx;
     CommitClock clk;
-    const uint32_t n_nodes = (uint32_t)s->bvh.a.size(), n_prims = (uint32_t)s->bvh.order.size();
+    const uint32_t n_nodes = (uint32_t)s->g->bvh.a.size(), n_prims = (uint32_t)s->g->bvh.order.size();
     RawArray<float4> nodes((size_t)n_nodes * 2), prims((size_t)n_prims * 3), nrm((size_t)n_prims * 3);  // every element is written below
     parallel_for(n_nodes, [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; ++i) {
-            const float* b = &s->bvh.bounds[6 * i];
-            nodes[2 * i] = make_float4(b[0], b[1], b[2], __builtin_bit_cast(float, s->bvh.a[i]));
-            nodes[2 * i + 1] = make_float4(b[3], b[4], b[5], __builtin_bit_cast(float, s->bvh.flags[i]));
+            const float* b = &s->g->bvh.bounds[6 * i];
+            nodes[2 * i] = make_float4(b[0], b[1], b[2], __builtin_bit_cast(float, s->g->bvh.a[i]));
+            nodes[2 * i + 1] = make_float4(b[3], b[4], b[5], __builtin_bit_cast(float, s->g->bvh.flags[i]));
         }
     });
     parallel_for(n_prims, [&](size_t k0, size_t k1) {
         for (size_t k = k0; k < k1; ++k) {
-            const HostPrim& p = s->prims[s->bvh.order[k]];
+            const HostPrim& p = s->g->prims[s->g->bvh.order[k]];
             if (p.kind == 1) {
                 prims[3 * k] = make_float4(__builtin_bit_cast(float, p.sphere_id), 0, 0, __builtin_bit_cast(float, p.meta));
                 prims[3 * k + 1] = prims[3 * k + 2] = make_float4(0, 0, 0, 0);
@@ -253,48 +253,48 @@ int upload_scene(trhip_scene* s) {
                 prims[3 * k + 1] = make_float4(p.v[3], p.v[4], p.v[5], 0);
                 prims[3 * k + 2] = make_float4(p.v[6], p.v[7], p.v[8], 0);
                 const uint32_t mat = p.meta & PRIM_MATERIAL_MASK;
-                const bool fast = mat != PRIM_NO_MATERIAL && mat < s->materials.size() && s->materials[mat].set[1].n == 1 && s->materials[mat].set[1].lobe[0].kind == LOBE_LAMBERT_R;
+                const bool fast = mat != PRIM_NO_MATERIAL && mat < s->g->materials.size() && s->g->materials[mat].set[1].n == 1 && s->g->materials[mat].set[1].lobe[0].kind == LOBE_LAMBERT_R;
                 if (fast) prims[3 * k].w = __builtin_bit_cast(float, p.meta | PRIM_FAST);
-                for (int j = 0; j < 3; ++j) nrm[3 * k + j] = make_float4(p.n[3 * j], p.n[3 * j + 1], p.n[3 * j + 2], fast ? s->materials[mat].set[1].lobe[0].r[j] : 0.0f);
+                for (int j = 0; j < 3; ++j) nrm[3 * k + j] = make_float4(p.n[3 * j], p.n[3 * j + 1], p.n[3 * j + 2], fast ? s->g->materials[mat].set[1].lobe[0].r[j] : 0.0f);
             }
         }
     });
     clk.tick("upload: node / prim records");
-    if (int rc = upload(ctx, s->d_nodes, nodes.data(), nodes.size() * sizeof(float4))) return rc;
-    if (int rc = upload(ctx, s->d_prims, prims.data(), prims.size() * sizeof(float4))) return rc;
-    if (int rc = upload(ctx, s->d_nrm, nrm.data(), nrm.size() * sizeof(float4))) return rc;
+    if (int rc = upload(ctx, s->g->d_nodes, nodes.data(), nodes.size() * sizeof(float4))) return rc;
+    if (int rc = upload(ctx, s->g->d_prims, prims.data(), prims.size() * sizeof(float4))) return rc;
+    if (int rc = upload(ctx, s->g->d_nrm, nrm.data(), nrm.size() * sizeof(float4))) return rc;
     clk.tick("upload: 3 copies");
     // the two optional mesh arrays (no scene of the reference sets them): tangents stay resident for the shading kernels, (u, v)s only feed k_shade_constants
-    const bool any_tan = !s->prim_tan.empty(), any_uv = !s->prim_uv.empty();
-    if (any_tan) s->prim_tan.resize(9 * s->prims.size(), 0.0f);  // primitives added after the last mesh with tangents / (u, v)s: zeros
-    if (any_uv) s->prim_uv.resize(7 * s->prims.size(), 0.0f);
+    const bool any_tan = !s->g->prim_tan.empty(), any_uv = !s->g->prim_uv.empty();
+    if (any_tan) s->g->prim_tan.resize(9 * s->g->prims.size(), 0.0f);  // primitives added after the last mesh with tangents / (u, v)s: zeros
+    if (any_uv) s->g->prim_uv.resize(7 * s->g->prims.size(), 0.0f);
     s->has_materialless_prim = false;
-    for (const HostPrim& p : s->prims) s->has_materialless_prim = s->has_materialless_prim || (p.meta & PRIM_MATERIAL_MASK) == PRIM_NO_MATERIAL;
+    for (const HostPrim& p : s->g->prims) s->has_materialless_prim = s->has_materialless_prim || (p.meta & PRIM_MATERIAL_MASK) == PRIM_NO_MATERIAL;
     s->dev.tri_tan = nullptr;
     if (any_tan) {
         std::vector<float4> tan((size_t)n_prims * 3, make_float4(0, 0, 0, 0));
         parallel_for(n_prims, [&](size_t k0, size_t k1) {
             for (size_t k = k0; k < k1; ++k) {
-                const uint32_t id = s->bvh.order[k];
-                const HostPrim& p = s->prims[id];
-                const float* tg = &s->prim_tan[9 * (size_t)id];
+                const uint32_t id = s->g->bvh.order[k];
+                const HostPrim& p = s->g->prims[id];
+                const float* tg = &s->g->prim_tan[9 * (size_t)id];
                 if (p.kind == 0 && (p.meta & PRIM_HAS_TANGENTS))
                     for (int j = 0; j < 3; ++j) tan[3 * k + j] = make_float4(tg[3 * j], tg[3 * j + 1], tg[3 * j + 2], 0.0f);
             }
         });
-        if (int rc = upload(ctx, s->d_tan, tan.data(), tan.size() * sizeof(float4))) return rc;
-        s->dev.tri_tan = (const float4*)s->d_tan.p;
+        if (int rc = upload(ctx, s->g->d_tan, tan.data(), tan.size() * sizeof(float4))) return rc;
+        s->dev.tri_tan = (const float4*)s->g->d_tan.p;
     } else {
-        release(s->d_tan);
+        release(s->g->d_tan);
     }
     DevBuf d_uv;
     if (any_uv) {
         std::vector<float4> uvs((size_t)n_prims * 2, make_float4(0, 0, 0, 0));
         parallel_for(n_prims, [&](size_t k0, size_t k1) {
             for (size_t k = k0; k < k1; ++k) {
-                const uint32_t id = s->bvh.order[k];
-                const float* uv = &s->prim_uv[7 * (size_t)id];
-                if (s->prims[id].kind == 0 && uv[6] != 0.0f) {
+                const uint32_t id = s->g->bvh.order[k];
+                const float* uv = &s->g->prim_uv[7 * (size_t)id];
+                if (s->g->prims[id].kind == 0 && uv[6] != 0.0f) {
                     uvs[2 * k] = make_float4(uv[0], uv[1], uv[2], uv[3]);
                     uvs[2 * k + 1] = make_float4(uv[4], uv[5], 1.0f, 0.0f);
                 }
@@ -306,32 +306,31 @@ int upload_scene(trhip_scene* s) {
         }
     }
     {  // the shading kernels' interleaved view (th_scene.h): one 128-byte line per slot, put together on the device from the two arrays just uploaded
-        if (int rc = ensure(ctx, s->d_shade, (size_t)n_prims * 8 * sizeof(float4))) {
+        if (int rc = ensure(ctx, s->g->d_shade, (size_t)n_prims * 8 * sizeof(float4))) {
             release(d_uv);
             return rc;
         }
-        hipLaunchKernelGGL(k_shade_constants, dim3(std::max(1u, std::min((n_prims + kBlock - 1) / kBlock, 4096u))), dim3(kBlock), 0, ctx->stream, (float4*)s->d_shade.p, (const float4*)s->d_prims.p, (const float4*)s->d_nrm.p, (const float4*)d_uv.p, n_prims);
+        hipLaunchKernelGGL(k_shade_constants, dim3(std::max(1u, std::min((n_prims + kBlock - 1) / kBlock, 4096u))), dim3(kBlock), 0, ctx->stream, (float4*)s->g->d_shade.p, (const float4*)s->g->d_prims.p, (const float4*)s->g->d_nrm.p, (const float4*)d_uv.p, n_prims);
         const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(ctx->stream);
         release(d_uv);
         HIP_TRY(ctx, e1);
         HIP_TRY(ctx, e2);
     }
     clk.tick("upload: shade records");
-    if (int rc = upload(ctx, s->d_spheres, s->spheres.data(), s->spheres.size() * sizeof(SphereRec))) return rc;
-    if (int rc = upload(ctx, s->d_materials, s->materials.data(), s->materials.size() * sizeof(MaterialRec))) return rc;
-    if (int rc = upload(ctx, s->d_lights, s->lights.data(), s->lights.size() * sizeof(LightRec))) return rc;
-    s->dev.nodes = (const float4*)s->d_nodes.p;
-    s->dev.prims = (const float4*)s->d_prims.p;
-    s->dev.tri_nrm = (const float4*)s->d_nrm.p;
-    s->dev.shade = (const float4*)s->d_shade.p;
-    s->dev.spheres = (const SphereRec*)s->d_spheres.p;
-    s->dev.materials = (const MaterialRec*)s->d_materials.p;
-    s->dev.lights = (const LightRec*)s->d_lights.p;
+    if (int rc = upload(ctx, s->g->d_spheres, s->g->spheres.data(), s->g->spheres.size() * sizeof(SphereRec))) return rc;
+    if (int rc = upload(ctx, s->g->d_materials, s->g->materials.data(), s->g->materials.size() * sizeof(MaterialRec))) return rc;
+    s->dev.nodes = (const float4*)s->g->d_nodes.p;
+    s->dev.prims = (const float4*)s->g->d_prims.p;
+    s->dev.tri_nrm = (const float4*)s->g->d_nrm.p;
+    s->dev.shade = (const float4*)s->g->d_shade.p;
+    s->dev.spheres = (const SphereRec*)s->g->d_spheres.p;
+    s->dev.materials = (const MaterialRec*)s->g->d_materials.p;
+    s->dev.lights = nullptr;  // (the light stage's: commit_lights)
     s->dev.n_nodes = n_nodes;
     s->dev.n_prims = n_prims;
-    s->dev.n_spheres = (uint32_t)s->spheres.size();
-    s->dev.n_materials = (uint32_t)s->materials.size();
-    s->dev.n_lights = (uint32_t)s->lights.size();
+    s->dev.n_spheres = (uint32_t)s->g->spheres.size();
+    s->dev.n_materials = (uint32_t)s->g->materials.size();
+    s->dev.n_lights = 0;
     // ---- children-in-parent nodes for k_trace2 (th_trace2.h) ----
     bool has_empty_leaf = false;
     s->wide_ok = false;
@@ -339,7 +338,7 @@ int upload_scene(trhip_scene* s) {
     s->wide.root_ref = kRefNone;
     if (n_nodes > 0 && n_prims < (1u << 24) && !s->literal_only) {
         std::vector<uint32_t> widx;
-        const uint32_t n_int = wide_node_order(s->bvh, ctx->node_layout, widx);
+        const uint32_t n_int = wide_node_order(s->g->bvh, ctx->node_layout, widx);
         bool ok = n_int < (1u << 24);
         RawArray<float4> wn((size_t)n_int * 4);  // every interior node writes its four records below (layout 1: the alignment gaps are zeroed first)
         if (ctx->node_layout == 1 && ok) std::memset((void*)wn.data(), 0, (size_t)n_int * 4 * sizeof(float4));
@@ -347,7 +346,7 @@ int upload_scene(trhip_scene* s) {
         // subtrees that hold a sphere keep the reference's loose slab test (th_trace2.h, slab_test2): the fp32 sphere quadratic
         // (sphere.jl:120-150) accepts rays that pass the sphere at a distance far beyond the tight test's margin
         std::vector<uint8_t> has_sphere(n_nodes, 0);
-        if (!s->spheres.empty()) {
+        if (!s->g->spheres.empty()) {
             // the ordered slots that hold spheres (the .w lane of a slot's first record carries PRIM_SPHERE)
             std::vector<uint32_t> sphere_slots;
             std::mutex lock;
@@ -367,8 +366,8 @@ int upload_scene(trhip_scene* s) {
                 // — fails the checks below and takes the bottom-up pass.)
                 auto leftmost = [&](uint32_t i, uint32_t& slot) {
                     for (uint32_t guard = 0; guard < 4096u && i < n_nodes; ++guard) {
-                        if ((s->bvh.flags[i] & 3u) == 3u) {
-                            slot = s->bvh.a[i];
+                        if ((s->g->bvh.flags[i] & 3u) == 3u) {
+                            slot = s->g->bvh.a[i];
                             return true;
                         }
                         ++i;
@@ -381,11 +380,11 @@ int upload_scene(trhip_scene* s) {
                     bool found = false;
                     for (uint32_t guard = 0; guard < 4096u && i < n_nodes; ++guard) {
                         has_sphere[i] = 1;
-                        if ((s->bvh.flags[i] & 3u) == 3u) {
-                            found = k - s->bvh.a[i] < (s->bvh.flags[i] >> 2);
+                        if ((s->g->bvh.flags[i] & 3u) == 3u) {
+                            found = k - s->g->bvh.a[i] < (s->g->bvh.flags[i] >> 2);
                             break;
                         }
-                        const uint32_t second = s->bvh.a[i];
+                        const uint32_t second = s->g->bvh.a[i];
                         uint32_t lo2 = 0;
                         if (second <= i + 1 || second >= n_nodes || !leftmost(second, lo2)) break;
                         i = k >= lo2 ? second : i + 1;
@@ -399,11 +398,11 @@ int upload_scene(trhip_scene* s) {
             }
             if (!marked)  // many spheres, or a layout the shortcut does not understand: bottom-up over all nodes
                 for (uint32_t i = n_nodes; i-- > 0;) {
-                    if ((s->bvh.flags[i] & 3u) == 3u) {
-                        const uint32_t first = s->bvh.a[i], cnt = s->bvh.flags[i] >> 2;
+                    if ((s->g->bvh.flags[i] & 3u) == 3u) {
+                        const uint32_t first = s->g->bvh.a[i], cnt = s->g->bvh.flags[i] >> 2;
                         for (uint32_t k = first; k < first + cnt && k < n_prims; ++k) has_sphere[i] |= (__builtin_bit_cast(uint32_t, prims[3 * (size_t)k].w) & PRIM_SPHERE) != 0;
                     } else {
-                        has_sphere[i] = has_sphere[i + 1] | (s->bvh.a[i] < n_nodes ? has_sphere[s->bvh.a[i]] : 1);
+                        has_sphere[i] = has_sphere[i + 1] | (s->g->bvh.a[i] < n_nodes ? has_sphere[s->g->bvh.a[i]] : 1);
                     }
                 }
         }
@@ -411,18 +410,18 @@ int upload_scene(trhip_scene* s) {
         parallel_for(n_nodes, [&](size_t i0, size_t i1) {
             static const float kNanBox[6] = {NAN, NAN, NAN, NAN, NAN, NAN};
             for (size_t i = i0; i < i1; ++i) {
-                if ((s->bvh.flags[i] & 3u) == 3u) continue;
-                const uint32_t c[2] = {(uint32_t)i + 1, s->bvh.a[i]};
+                if ((s->g->bvh.flags[i] & 3u) == 3u) continue;
+                const uint32_t c[2] = {(uint32_t)i + 1, s->g->bvh.a[i]};
                 uint32_t ref[2], cnt[2];
                 for (int k = 0; k < 2; ++k) {
-                    if ((s->bvh.flags[c[k]] & 3u) == 3u) {
-                        ref[k] = s->bvh.a[c[k]];
-                        cnt[k] = s->bvh.flags[c[k]] >> 2;
+                    if ((s->g->bvh.flags[c[k]] & 3u) == 3u) {
+                        ref[k] = s->g->bvh.a[c[k]];
+                        cnt[k] = s->g->bvh.flags[c[k]] >> 2;
                         if (cnt[k] == 0) {
                             // the reference's builder can emit a leaf of 0 primitives with the invalid bounds (+Inf, -Inf) (A.6, th_bvh_ref.h): no ray's box
                             // test passes on it (tx_min = +Inf, bounds.jl:186-188), so the child word is never read — any leaf-shaped word will do.
                             // An empty leaf with a REAL box (a foreign tree) could be "entered": the literal kernel walks those.
-                            const float* eb = &s->bvh.bounds[6 * (size_t)c[k]];
+                            const float* eb = &s->g->bvh.bounds[6 * (size_t)c[k]];
                             if (eb[0] == INFINITY && eb[1] == INFINITY && eb[2] == INFINITY && eb[3] == -INFINITY && eb[4] == -INFINITY && eb[5] == -INFINITY) {
                                 ref[k] = 0;
                                 cnt[k] = 1;
@@ -438,19 +437,19 @@ int upload_scene(trhip_scene* s) {
                         cnt[k] = 0;
                     }
                 }
-                const float* l = &s->bvh.bounds[6 * (size_t)c[0]];
-                const float* r = &s->bvh.bounds[6 * (size_t)c[1]];
+                const float* l = &s->g->bvh.bounds[6 * (size_t)c[0]];
+                const float* r = &s->g->bvh.bounds[6 * (size_t)c[1]];
                 // an empty leaf's box (+Inf, -Inf) goes in as NaNs: every comparison with a NaN product is false, so the child is missed by the select form of the box
                 // test (slab_test2) AND by the min / max forms (th_trace7.h), where min(+Inf x, -Inf x) would turn the inverted box into "everything"
-                if ((s->bvh.flags[c[0]] & 3u) == 3u && (s->bvh.flags[c[0]] >> 2) == 0u) l = kNanBox;
-                if ((s->bvh.flags[c[1]] & 3u) == 3u && (s->bvh.flags[c[1]] >> 2) == 0u) r = kNanBox;
+                if ((s->g->bvh.flags[c[0]] & 3u) == 3u && (s->g->bvh.flags[c[0]] >> 2) == 0u) l = kNanBox;
+                if ((s->g->bvh.flags[c[1]] & 3u) == 3u && (s->g->bvh.flags[c[1]] >> 2) == 0u) r = kNanBox;
                 float4* w = &wn[4 * (size_t)widx[i]];
                 w[0] = make_float4(l[0], l[1], l[2], l[3]);
                 w[1] = make_float4(l[4], l[5], r[0], r[1]);
                 w[2] = make_float4(r[2], r[3], r[4], r[5]);
                 // child word = ref | count << 24 (the stack entry format); meta = split axis | "subtree holds a sphere" bits 2 (first) / 3 (second)
                 w[3] = make_float4(__builtin_bit_cast(float, ref[0] | (cnt[0] << 24)), __builtin_bit_cast(float, ref[1] | (cnt[1] << 24)),
-                                   __builtin_bit_cast(float, (s->bvh.flags[i] & 3u) | ((uint32_t)has_sphere[c[0]] << 2) | ((uint32_t)has_sphere[c[1]] << 3)), 0.0f);
+                                   __builtin_bit_cast(float, (s->g->bvh.flags[i] & 3u) | ((uint32_t)has_sphere[c[0]] << 2) | ((uint32_t)has_sphere[c[1]] << 3)), 0.0f);
             }
         });
         ok = !bad;
@@ -460,8 +459,8 @@ int upload_scene(trhip_scene* s) {
         std::atomic<bool> loose{false};
         parallel_for(n_nodes, [&](size_t i0, size_t i1) {
             for (size_t i = i0; i < i1 && !loose; ++i) {
-                if ((s->bvh.flags[i] & 3u) != 3u) continue;
-                const uint32_t first = s->bvh.a[i], cnt = s->bvh.flags[i] >> 2;
+                if ((s->g->bvh.flags[i] & 3u) != 3u) continue;
+                const uint32_t first = s->g->bvh.a[i], cnt = s->g->bvh.flags[i] >> 2;
                 if (cnt == 0) continue;
                 HostAABB u;
                 u.reset();
@@ -478,25 +477,25 @@ int upload_scene(trhip_scene* s) {
                     }
                 }
                 if (sphere) continue;  // sphere leaves are reached through exact tests anyway
-                const float* b = &s->bvh.bounds[6 * i];
+                const float* b = &s->g->bvh.bounds[6 * i];
                 if (!(u.mn[0] == b[0] && u.mn[1] == b[1] && u.mn[2] == b[2] && u.mx[0] == b[3] && u.mx[1] == b[4] && u.mx[2] == b[5])) loose = true;
             }
         });
         const bool leaf_tight = !loose;
         if (ok) {
-            if (int rc = upload(ctx, s->d_wnodes, wn.data(), wn.size() * sizeof(float4))) return rc;
+            if (int rc = upload(ctx, s->g->d_wnodes, wn.data(), wn.size() * sizeof(float4))) return rc;
             s->wide.leaf_tight = leaf_tight ? 1u : 0u;
             // the smallest sphere, in world units (half the smallest extent of its world bound): how far outside itself its Float32 quadratic can report a hit
             float r_min = INFINITY;
-            for (const HostAABB& sb : s->sphere_bounds)
+            for (const HostAABB& sb : s->g->sphere_bounds)
                 for (int ax = 0; ax < 3; ++ax) r_min = std::fmin(r_min, 0.5f * (sb.mx[ax] - sb.mn[ax]));
-            s->wide.sphere_lag = (s->sphere_bounds.empty() || !(r_min > 0.0f)) ? 0.0f : 3.8e-6f / r_min;
-            s->wide.wnodes = (const float4*)s->d_wnodes.p;
+            s->wide.sphere_lag = (s->g->sphere_bounds.empty() || !(r_min > 0.0f)) ? 0.0f : 3.8e-6f / r_min;
+            s->wide.wnodes = (const float4*)s->g->d_wnodes.p;
             s->wide.n_wnodes = n_int;
-            std::memcpy(s->wide.root_box, &s->bvh.bounds[0], 6 * sizeof(float));
-            if ((s->bvh.flags[0] & 3u) == 3u) {
-                s->wide.root_ref = s->bvh.a[0];
-                s->wide.root_cnt = s->bvh.flags[0] >> 2;
+            std::memcpy(s->wide.root_box, &s->g->bvh.bounds[0], 6 * sizeof(float));
+            if ((s->g->bvh.flags[0] & 3u) == 3u) {
+                s->wide.root_ref = s->g->bvh.a[0];
+                s->wide.root_cnt = s->g->bvh.flags[0] >> 2;
                 ok = s->wide.root_cnt > 0 && s->wide.root_cnt <= 255;
             } else {
                 s->wide.root_ref = 0;
@@ -515,34 +514,34 @@ int upload_scene(trhip_scene* s) {
         // root -> {leaf of all spheres (flat node 1), triangles (flat node 2)} (compose_bvh)
         uint32_t sub_root = 0, n_sph = 0;
         bool shape_ok = true;
-        if (!s->spheres.empty()) {
-            n_sph = (uint32_t)s->spheres.size();
+        if (!s->g->spheres.empty()) {
+            n_sph = (uint32_t)s->g->spheres.size();
             sub_root = 2 * n_sph;
             shape_ok = n_sph <= (uint32_t)kW8MaxSpheres && sub_root < n_nodes;
             for (uint32_t i = 0; i < n_sph && shape_ok; ++i)
-                shape_ok = (s->bvh.flags[2 * i] & 3u) != 3u && (s->bvh.flags[2 * i] & 3u) == (s->bvh.flags[0] & 3u) && s->bvh.a[2 * i] == 2 * i + 2 &&
-                           s->bvh.flags[2 * i + 1] == ((1u << 2) | 3u) && s->bvh.a[2 * i + 1] == i && s->prims[s->bvh.order[i]].kind == 1;
+                shape_ok = (s->g->bvh.flags[2 * i] & 3u) != 3u && (s->g->bvh.flags[2 * i] & 3u) == (s->g->bvh.flags[0] & 3u) && s->g->bvh.a[2 * i] == 2 * i + 2 &&
+                           s->g->bvh.flags[2 * i + 1] == ((1u << 2) | 3u) && s->g->bvh.a[2 * i + 1] == i && s->g->prims[s->g->bvh.order[i]].kind == 1;
             shape_ok = shape_ok && !has_sphere_subtree(s, sub_root);
         }
         if (shape_ok) {
-            Wide8Host wh = build_wide8(s->bvh, sub_root, [&](uint32_t slot, float* v, uint32_t& meta) {
+            Wide8Host wh = build_wide8(s->g->bvh, sub_root, [&](uint32_t slot, float* v, uint32_t& meta) {
                 if (slot >= n_prims) return false;
-                const HostPrim& p = s->prims[s->bvh.order[slot]];
+                const HostPrim& p = s->g->prims[s->g->bvh.order[slot]];
                 if (p.kind != 0) return false;
                 std::memcpy(v, p.v, 9 * sizeof(float));
                 meta = p.meta;
                 return true;
             });
             if (wh.ok) {
-                if (int rc = upload(ctx, s->d_w8nodes, wh.nodes.data(), wh.nodes.size() * sizeof(uint32_t))) return rc;
-                if (int rc = upload(ctx, s->d_w8tris, wh.tris.data(), wh.tris.size() * sizeof(float))) return rc;
-                s->w8.nodes = (const uint4*)s->d_w8nodes.p;
-                s->w8.tris = (const float4*)s->d_w8tris.p;
-                std::memcpy(s->w8.root_box, &s->bvh.bounds[0], 6 * sizeof(float));
-                std::memcpy(s->w8.tri_box, &s->bvh.bounds[6 * (size_t)sub_root], 6 * sizeof(float));
-                for (uint32_t i = 0; i < n_sph; ++i) std::memcpy(s->w8.sph_box[i], &s->bvh.bounds[6 * (size_t)(2 * i + 1)], 6 * sizeof(float));
+                if (int rc = upload(ctx, s->g->d_w8nodes, wh.nodes.data(), wh.nodes.size() * sizeof(uint32_t))) return rc;
+                if (int rc = upload(ctx, s->g->d_w8tris, wh.tris.data(), wh.tris.size() * sizeof(float))) return rc;
+                s->w8.nodes = (const uint4*)s->g->d_w8nodes.p;
+                s->w8.tris = (const float4*)s->g->d_w8tris.p;
+                std::memcpy(s->w8.root_box, &s->g->bvh.bounds[0], 6 * sizeof(float));
+                std::memcpy(s->w8.tri_box, &s->g->bvh.bounds[6 * (size_t)sub_root], 6 * sizeof(float));
+                for (uint32_t i = 0; i < n_sph; ++i) std::memcpy(s->w8.sph_box[i], &s->g->bvh.bounds[6 * (size_t)(2 * i + 1)], 6 * sizeof(float));
                 s->w8.n_sph = n_sph;
-                s->w8.chain_axis = s->bvh.flags[0] & 3u;
+                s->w8.chain_axis = s->g->bvh.flags[0] & 3u;
                 s->w8_nodes = (uint32_t)(wh.nodes.size() / kW8NodeDwords);
                 s->w8_depth = wh.depth;
                 s->w8_ok = true;
@@ -552,7 +551,7 @@ int upload_scene(trhip_scene* s) {
 #endif
     clk.tick("upload: 8-wide view");
     // ---- one-leaf scenes: the boxes of the leaf's triangles, for the candidate masks of k_leaf_sorted (th_leaf2.h) ----
-    release(s->d_leaf_boxes);
+    release(s->g->d_leaf_boxes);
     if (s->wide_ok && s->wide.root_cnt > 0 && s->wide.root_cnt <= 30) {
         const uint32_t first = s->wide.root_ref, cnt = s->wide.root_cnt;
         std::vector<float> boxes(6 * (size_t)cnt, 0.0f);
@@ -568,55 +567,14 @@ int upload_scene(trhip_scene* s) {
             std::memcpy(&boxes[6 * (size_t)k], u.mn, 3 * sizeof(float));
             std::memcpy(&boxes[6 * (size_t)k + 3], u.mx, 3 * sizeof(float));
         }
-        if (int rc = upload(ctx, s->d_leaf_boxes, boxes.data(), boxes.size() * sizeof(float))) return rc;
+        if (int rc = upload(ctx, s->g->d_leaf_boxes, boxes.data(), boxes.size() * sizeof(float))) return rc;
     }
-    // ---- one-leaf scenes: the order in which any-hit rays try the leaf's primitives (th_trace2.h, k_any_leaf) ----
-    // A shadow ray runs from the surface THROUGH the light (t_max = Inf): what stops it at the latest is what the light sees, so the
-    // primitives subtending the largest solid angle at the lights come first (triangles: Van Oosterom & Strackee; spheres: the cap of
-    // their bounding sphere).  Any order gives the same boolean.
-    s->wide.leaf_order = nullptr;
-    if (s->wide_ok && s->wide.root_cnt > 1 && !s->lights.empty()) {
-        const uint32_t first = s->wide.root_ref, cnt = s->wide.root_cnt;
-        std::vector<std::pair<double, uint32_t>> ord;
-        for (uint32_t k = 0; k < cnt; ++k) {
-            const HostPrim& p = s->prims[s->bvh.order[first + k]];
-            double w = 0.0;
-            for (const LightRec& l : s->lights) {
-                const float* lp = l.position;
-                if (l.kind == 2) continue;  // a directional light has no position: it orders nothing (any order gives the same boolean)
-                if (p.kind == 1) {
-                    const HostAABB& b = s->sphere_bounds[p.sphere_id];
-                    double c[3], r = 0.0, d2 = 0.0;
-                    for (int a = 0; a < 3; ++a) {
-                        c[a] = 0.5 * ((double)b.mn[a] + b.mx[a]);
-                        r = std::max(r, 0.5 * ((double)b.mx[a] - b.mn[a]));
-                        d2 += (c[a] - lp[a]) * (c[a] - lp[a]);
-                    }
-                    w += d2 <= r * r ? 4.0 * 3.14159265358979 : 2.0 * 3.14159265358979 * (1.0 - std::sqrt(std::max(0.0, 1.0 - r * r / d2)));
-                } else {
-                    double r[3][3], len[3];
-                    for (int v = 0; v < 3; ++v) {
-                        for (int c = 0; c < 3; ++c) r[v][c] = (double)p.v[3 * v + c] - lp[c];
-                        len[v] = std::sqrt(r[v][0] * r[v][0] + r[v][1] * r[v][1] + r[v][2] * r[v][2]);
-                    }
-                    const double det = r[0][0] * (r[1][1] * r[2][2] - r[1][2] * r[2][1]) - r[0][1] * (r[1][0] * r[2][2] - r[1][2] * r[2][0]) + r[0][2] * (r[1][0] * r[2][1] - r[1][1] * r[2][0]);
-                    auto dot3 = [&](int a, int b) { return r[a][0] * r[b][0] + r[a][1] * r[b][1] + r[a][2] * r[b][2]; };
-                    const double den = len[0] * len[1] * len[2] + dot3(0, 1) * len[2] + dot3(0, 2) * len[1] + dot3(1, 2) * len[0];
-                    w += 2.0 * std::fabs(std::atan2(det, den));
-                }
-            }
-            ord.push_back({w, k});
-        }
-        std::stable_sort(ord.begin(), ord.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-        std::vector<uint32_t> order(cnt);
-        for (uint32_t k = 0; k < cnt; ++k) order[k] = ord[k].second;
-        if (int rc = upload(ctx, s->d_leaf_order, order.data(), order.size() * sizeof(uint32_t))) return rc;
-        s->wide.leaf_order = (const uint32_t*)s->d_leaf_order.p;
-    }
-    // ---- largest triangles: the any-hit pre-pass (th_trace2.h, k_any_occluders) ----
-    s->n_occluders = 0;
+    // ---- largest triangles: the candidates of the any-hit pre-pass (th_trace2.h, k_any_occluders); the light stage orders them (commit_lights) ----
+    s->g->occ_slots.clear();
+    s->g->occ_boxes.clear();
+    s->wide.leaf_order = nullptr;  // (the light stage's, as the occluders' order)
     if (s->wide_ok && s->wide.root_cnt == 0) {
-        const float* rb = &s->bvh.bounds[0];
+        const float* rb = &s->g->bvh.bounds[0];
         const double ex = (double)rb[3] - rb[0], ey = (double)rb[4] - rb[1], ez = (double)rb[5] - rb[2];
         const double face = std::max(ex * ey, std::max(ex * ez, ey * ez));
         std::vector<std::pair<double, uint32_t>> big;  // (area, ordered slot)
@@ -624,7 +582,7 @@ int upload_scene(trhip_scene* s) {
         parallel_for(n_prims, [&](size_t k0, size_t k1) {
             std::vector<std::pair<double, uint32_t>> mine;
             for (size_t k = k0; k < k1; ++k) {
-                const HostPrim& p = s->prims[s->bvh.order[k]];
+                const HostPrim& p = s->g->prims[s->g->bvh.order[k]];
                 if (p.kind != 0 || (p.meta & PRIM_DEGENERATE)) continue;
                 const double ax = (double)p.v[3] - p.v[0], ay = (double)p.v[4] - p.v[1], az = (double)p.v[5] - p.v[2];
                 const double bx = (double)p.v[6] - p.v[0], by = (double)p.v[7] - p.v[1], bz = (double)p.v[8] - p.v[2];
@@ -640,36 +598,13 @@ int upload_scene(trhip_scene* s) {
         if (!big.empty() && big.size() * 8 <= (size_t)n_prims) {  // a few walls around much else; not a scene that consists of large triangles
             std::sort(big.begin(), big.end(), [](const auto& a, const auto& b) { return a.first > b.first || (a.first == b.first && a.second < b.second); });
             if (big.size() > 16) big.resize(16);
-            // test order: a shadow ray runs from the surface THROUGH the light (t_max = Inf) — what stops it at the latest is what the light
-            // sees, so the triangles subtending the largest solid angle at the lights come first (Van Oosterom & Strackee)
-            auto solid_angle = [&](uint32_t k, const float* lp) {
-                const HostPrim& p = s->prims[s->bvh.order[k]];
-                double r[3][3], len[3];
-                for (int v = 0; v < 3; ++v) {
-                    for (int c = 0; c < 3; ++c) r[v][c] = (double)p.v[3 * v + c] - lp[c];
-                    len[v] = std::sqrt(r[v][0] * r[v][0] + r[v][1] * r[v][1] + r[v][2] * r[v][2]);
-                }
-                const double det = r[0][0] * (r[1][1] * r[2][2] - r[1][2] * r[2][1]) - r[0][1] * (r[1][0] * r[2][2] - r[1][2] * r[2][0]) + r[0][2] * (r[1][0] * r[2][1] - r[1][1] * r[2][0]);
-                auto dot3 = [&](int a, int b) { return r[a][0] * r[b][0] + r[a][1] * r[b][1] + r[a][2] * r[b][2]; };
-                const double den = len[0] * len[1] * len[2] + dot3(0, 1) * len[2] + dot3(0, 2) * len[1] + dot3(1, 2) * len[0];
-                return 2.0 * std::fabs(std::atan2(det, den));
-            };
-            if (!s->lights.empty()) {
-                for (auto& b : big) {
-                    double w = 0.0;
-                    for (const LightRec& l : s->lights)
-                        if (l.kind != 2) w += solid_angle(b.second, l.position);  // a directional light has no position
-                    b.first = w;
-                }
-                std::stable_sort(big.begin(), big.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-            }
             // the leaf that holds each of the (at most 16) chosen slots
             std::vector<std::atomic<uint32_t>> leaf_of(big.size());
             for (auto& l : leaf_of) l = 0xffffffffu;
             parallel_for(n_nodes, [&](size_t i0, size_t i1) {
                 for (size_t i = i0; i < i1; ++i) {
-                    if ((s->bvh.flags[i] & 3u) != 3u) continue;
-                    const uint32_t first = s->bvh.a[i], cnt = s->bvh.flags[i] >> 2;
+                    if ((s->g->bvh.flags[i] & 3u) != 3u) continue;
+                    const uint32_t first = s->g->bvh.a[i], cnt = s->g->bvh.flags[i] >> 2;
                     for (size_t q = 0; q < big.size(); ++q)
                         if (big[q].second - first < cnt) leaf_of[q] = (uint32_t)i;
                 }
@@ -680,22 +615,107 @@ int upload_scene(trhip_scene* s) {
                 const uint32_t leaf = leaf_of[q];
                 if (leaf == 0xffffffffu) continue;
                 slots.push_back(big[q].second);
-                for (int a = 0; a < 6; ++a) boxes.push_back(s->bvh.bounds[6 * (size_t)leaf + a]);
+                for (int a = 0; a < 6; ++a) boxes.push_back(s->g->bvh.bounds[6 * (size_t)leaf + a]);
             }
             if (slots.size() >= 6) {  // an enclosure (three quads or more); a lone floor stops few shadow rays and the pre-pass only costs (S-caustic)
-                if (int rc = upload(ctx, s->d_occ_slots, slots.data(), slots.size() * sizeof(uint32_t))) return rc;
-                if (int rc = upload(ctx, s->d_occ_boxes, boxes.data(), boxes.size() * sizeof(float))) return rc;
-                s->n_occluders = (uint32_t)slots.size();
+                s->g->occ_slots = std::move(slots);
+                s->g->occ_boxes = std::move(boxes);
             }
         }
     }
     clk.tick("upload: occluders");
+    return 0;
+}
+
+// ---- the light stage: what a commit derives from the lights (a relit view's commit runs it alone: trhip_scene_relight) ----------------------------------------------
+// A shadow ray runs from the surface THROUGH the light (t_max = Inf): what stops it at the latest is what the light sees, so any-hit rays try the primitives subtending the
+// largest solid angle at the lights first (triangles: Van Oosterom & Strackee; spheres: the cap of their bounding sphere).  Any order gives the same boolean.
+static double solid_angle_at_lights(const trhip_scene* s, const HostPrim& p) {
+    double w = 0.0;
+    for (const LightRec& l : s->lights) {
+        const float* lp = l.position;
+        if (l.kind == 2) continue;  // a directional light has no position: it orders nothing
+        if (p.kind == 1) {
+            const HostAABB& b = s->g->sphere_bounds[p.sphere_id];
+            double c[3], r = 0.0, d2 = 0.0;
+            for (int a = 0; a < 3; ++a) {
+                c[a] = 0.5 * ((double)b.mn[a] + b.mx[a]);
+                r = std::max(r, 0.5 * ((double)b.mx[a] - b.mn[a]));
+                d2 += (c[a] - lp[a]) * (c[a] - lp[a]);
+            }
+            w += d2 <= r * r ? 4.0 * 3.14159265358979 : 2.0 * 3.14159265358979 * (1.0 - std::sqrt(std::max(0.0, 1.0 - r * r / d2)));
+        } else {
+            double r[3][3], len[3];
+            for (int v = 0; v < 3; ++v) {
+                for (int c = 0; c < 3; ++c) r[v][c] = (double)p.v[3 * v + c] - lp[c];
+                len[v] = std::sqrt(r[v][0] * r[v][0] + r[v][1] * r[v][1] + r[v][2] * r[v][2]);
+            }
+            const double det = r[0][0] * (r[1][1] * r[2][2] - r[1][2] * r[2][1]) - r[0][1] * (r[1][0] * r[2][2] - r[1][2] * r[2][0]) + r[0][2] * (r[1][0] * r[2][1] - r[1][1] * r[2][0]);
+            auto dot3 = [&](int a, int b) { return r[a][0] * r[b][0] + r[a][1] * r[b][1] + r[a][2] * r[b][2]; };
+            const double den = len[0] * len[1] * len[2] + dot3(0, 1) * len[2] + dot3(0, 2) * len[1] + dot3(1, 2) * len[0];
+            w += 2.0 * std::fabs(std::atan2(det, den));
+        }
+    }
+    return w;
+}
+// positions 0 .. n - 1 of a list whose entry k is canonical slot slot_of(k), most subtended first (ties: list order)
+template <class SlotOf>
+static std::vector<uint32_t> any_hit_order(const trhip_scene* s, uint32_t n, SlotOf slot_of) {
+    std::vector<std::pair<double, uint32_t>> ord;
+    ord.reserve(n);
+    for (uint32_t k = 0; k < n; ++k) ord.push_back({solid_angle_at_lights(s, s->g->prims[s->g->bvh.order[slot_of(k)]]), k});
+    std::stable_sort(ord.begin(), ord.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
+    std::vector<uint32_t> order(n);
+    for (uint32_t k = 0; k < n; ++k) order[k] = ord[k].second;
+    return order;
+}
+static int commit_lights(trhip_scene* s) {
+    trhip_ctx* ctx = s->ctx;
+    CommitClock clk;
+    if (int rc = upload(ctx, s->d_lights, s->lights.data(), s->lights.size() * sizeof(LightRec))) return rc;
+    s->dev.lights = (const LightRec*)s->d_lights.p;
+    s->dev.n_lights = (uint32_t)s->lights.size();
+    s->dev_acc.lights = s->dev.lights;
+    s->dev_acc.n_lights = s->dev.n_lights;
+    // one-leaf scenes: the order in which any-hit rays try the leaf's primitives (th_trace2.h, k_any_leaf)
+    s->wide.leaf_order = nullptr;
+    if (s->wide_ok && s->wide.root_cnt > 1 && !s->lights.empty()) {
+        const uint32_t first = s->wide.root_ref;
+        const std::vector<uint32_t> order = any_hit_order(s, s->wide.root_cnt, [first](uint32_t k) { return first + k; });
+        if (int rc = upload(ctx, s->d_leaf_order, order.data(), order.size() * sizeof(uint32_t))) return rc;
+        s->wide.leaf_order = (const uint32_t*)s->d_leaf_order.p;
+    }
+    // the accelerator as one leaf over the canonical records (k_any_leaf_c): the same order over every canonical slot
+    s->wide_acc.leaf_order = nullptr;
+    if (s->hybrid_ok && s->wide_acc.root_cnt > 1 && !s->lights.empty()) {
+        const std::vector<uint32_t> order = any_hit_order(s, s->wide_acc.root_cnt, [](uint32_t k) { return k; });
+        if (int rc = upload(ctx, s->d_acc_leaf_order, order.data(), order.size() * sizeof(uint32_t))) return rc;
+        s->wide_acc.leaf_order = (const uint32_t*)s->d_acc_leaf_order.p;
+    }
+    // the largest triangles of the any-hit pre-pass, in the same order (their area order without lights)
+    s->n_occluders = 0;
+    const std::vector<uint32_t>& occ = s->g->occ_slots;
+    if (!occ.empty()) {
+        std::vector<uint32_t> pick(occ.size());
+        for (uint32_t q = 0; q < (uint32_t)occ.size(); ++q) pick[q] = q;
+        if (!s->lights.empty()) pick = any_hit_order(s, (uint32_t)occ.size(), [&occ](uint32_t q) { return occ[q]; });
+        std::vector<uint32_t> slots(occ.size());
+        std::vector<float> boxes(6 * occ.size());
+        for (size_t q = 0; q < occ.size(); ++q) {
+            slots[q] = occ[pick[q]];
+            std::memcpy(&boxes[6 * q], &s->g->occ_boxes[6 * (size_t)pick[q]], 6 * sizeof(float));
+        }
+        if (int rc = upload(ctx, s->d_occ_slots, slots.data(), slots.size() * sizeof(uint32_t))) return rc;
+        if (int rc = upload(ctx, s->d_occ_boxes, boxes.data(), boxes.size() * sizeof(float))) return rc;
+        s->n_occluders = (uint32_t)slots.size();
+    }
+    clk.tick("lights");
     s->committed = true;
     return 0;
 }
 
 // ---- the accelerator of the hybrid mode (th_trace3c.h) ------------------------------------------------------------------------------------------------
-// `s->bvh` (canonical: the reference's construction or the host's own tree) has been uploaded by upload_scene; `s->acc` is the library's tree over the same
+// `s->g->bvh` (canonical: the reference's construction or the host's own tree) has been uploaded by upload_scene; `s->g->acc` is the library's tree over the same
 // primitives (acc.order[k] = caller primitive).  Derives: the accelerator's primitive records in ITS leaf order with the canonical slot in the second
 // record's .w lane, its children-in-parent nodes, the per-sphere / per-slot canonical leaf boxes the certificate reads — and verifies what the certificate
 // assumes: every accelerator leaf has, bit for bit, the box of the canonical leaf of each of its primitives.  Anything that does not fit leaves
@@ -792,22 +812,22 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
     s->wide_acc.root_ref = kRefNone;
     s->cert = CertScene{};
     s->dev_acc = s->dev;
-    const uint32_t n_prims = (uint32_t)s->bvh.order.size(), n_cnodes = (uint32_t)s->bvh.a.size(), n_anodes = (uint32_t)s->acc.a.size();
-    if (!s->wide_ok || s->literal_only || n_prims == 0 || n_anodes == 0 || s->acc.order.size() != n_prims || n_prims >= (1u << 24)) return 0;
-    if (s->acc.max_depth > (uint32_t)(kStackLds + kStackSpill)) return 0;  // the certified walk's stack holds 64 entries like every other kernel's (a regrouped leaf adds levels)
+    const uint32_t n_prims = (uint32_t)s->g->bvh.order.size(), n_cnodes = (uint32_t)s->g->bvh.a.size(), n_anodes = (uint32_t)s->g->acc.a.size();
+    if (!s->wide_ok || s->literal_only || n_prims == 0 || n_anodes == 0 || s->g->acc.order.size() != n_prims || n_prims >= (1u << 24)) return 0;
+    if (s->g->acc.max_depth > (uint32_t)(kStackLds + kStackSpill)) return 0;  // the certified walk's stack holds 64 entries like every other kernel's (a regrouped leaf adds levels)
     if (s->wide.root_cnt > 0) return 0;  // the canonical tree is one leaf: nothing to accelerate
     // canonical slot of every caller primitive, and the box of the canonical leaf that holds each canonical slot
-    std::vector<uint32_t> cslot(s->prims.size(), 0xffffffffu);
-    for (uint32_t k = 0; k < n_prims; ++k) cslot[s->bvh.order[k]] = k;
+    std::vector<uint32_t> cslot(s->g->prims.size(), 0xffffffffu);
+    for (uint32_t k = 0; k < n_prims; ++k) cslot[s->g->bvh.order[k]] = k;
     std::vector<float> slot_box((size_t)n_prims * 6, 0.0f);
     std::vector<uint32_t> leaf_of_slot(n_prims, 0u);  // the canonical leaf (node index) that holds each canonical slot
     std::vector<uint8_t> covered(n_prims, 0);
     parallel_for(n_cnodes, [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; ++i) {
-            if ((s->bvh.flags[i] & 3u) != 3u) continue;
-            const uint32_t first = s->bvh.a[i], cnt = s->bvh.flags[i] >> 2;
+            if ((s->g->bvh.flags[i] & 3u) != 3u) continue;
+            const uint32_t first = s->g->bvh.a[i], cnt = s->g->bvh.flags[i] >> 2;
             for (uint32_t k = first; k < first + cnt && k < n_prims; ++k) {
-                std::memcpy(&slot_box[6 * (size_t)k], &s->bvh.bounds[6 * i], 6 * sizeof(float));
+                std::memcpy(&slot_box[6 * (size_t)k], &s->g->bvh.bounds[6 * i], 6 * sizeof(float));
                 leaf_of_slot[k] = (uint32_t)i;
                 covered[k] = 1;
             }
@@ -816,84 +836,48 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
     for (uint32_t k = 0; k < n_prims; ++k)
         if (!covered[k]) return 0;  // (a foreign tree that leaves a primitive out)
     for (uint32_t k = 0; k < n_prims; ++k)
-        if (s->acc.order[k] >= s->prims.size() || cslot[s->acc.order[k]] == 0xffffffffu) return 0;
+        if (s->g->acc.order[k] >= s->g->prims.size() || cslot[s->g->acc.order[k]] == 0xffffffffu) return 0;
     // per sphere: its canonical leaf's box
-    std::vector<float> sph_box(std::max<size_t>(1, s->spheres.size()) * 6, 0.0f);
+    std::vector<float> sph_box(std::max<size_t>(1, s->g->spheres.size()) * 6, 0.0f);
     for (uint32_t k = 0; k < n_prims; ++k) {
-        const HostPrim& p = s->prims[s->bvh.order[k]];
-        if (p.kind == 1 && p.sphere_id < s->spheres.size()) std::memcpy(&sph_box[6 * (size_t)p.sphere_id], &slot_box[6 * (size_t)k], 6 * sizeof(float));
+        const HostPrim& p = s->g->prims[s->g->bvh.order[k]];
+        if (p.kind == 1 && p.sphere_id < s->g->spheres.size()) std::memcpy(&sph_box[6 * (size_t)p.sphere_id], &slot_box[6 * (size_t)k], 6 * sizeof(float));
     }
-    std::vector<uint32_t> sph_slot(std::max<size_t>(1, s->spheres.size()), 0u);
+    std::vector<uint32_t> sph_slot(std::max<size_t>(1, s->g->spheres.size()), 0u);
     for (uint32_t k = 0; k < n_prims; ++k) {
-        const HostPrim& p = s->prims[s->bvh.order[k]];
-        if (p.kind == 1 && p.sphere_id < s->spheres.size()) sph_slot[p.sphere_id] = k;
+        const HostPrim& p = s->g->prims[s->g->bvh.order[k]];
+        if (p.kind == 1 && p.sphere_id < s->g->spheres.size()) sph_slot[p.sphere_id] = k;
     }
-    if (s->spheres.size() > kCertMaxSpheres) return 0;  // the certified walk tests EVERY sphere when it fetches a ray: a scene of many spheres keeps the canonical tree alone
-    if (int rc = upload(ctx, s->d_sphere_boxes, sph_box.data(), sph_box.size() * sizeof(float))) return rc;
-    if (int rc = upload(ctx, s->d_sphere_slots, sph_slot.data(), sph_slot.size() * sizeof(uint32_t))) return rc;
-    s->cert.sphere_boxes = (const float*)s->d_sphere_boxes.p;
-    s->cert.sphere_slots = (const uint32_t*)s->d_sphere_slots.p;
-    s->cert.n_spheres = (uint32_t)s->spheres.size();
+    if (s->g->spheres.size() > kCertMaxSpheres) return 0;  // the certified walk tests EVERY sphere when it fetches a ray: a scene of many spheres keeps the canonical tree alone
+    if (int rc = upload(ctx, s->g->d_sphere_boxes, sph_box.data(), sph_box.size() * sizeof(float))) return rc;
+    if (int rc = upload(ctx, s->g->d_sphere_slots, sph_slot.data(), sph_slot.size() * sizeof(uint32_t))) return rc;
+    s->cert.sphere_boxes = (const float*)s->g->d_sphere_boxes.p;
+    s->cert.sphere_slots = (const uint32_t*)s->g->d_sphere_slots.p;
+    s->cert.n_spheres = (uint32_t)s->g->spheres.size();
     {
-        std::vector<SphereCert> sc(std::max<size_t>(1, s->spheres.size()));
-        for (size_t k = 0; k < s->spheres.size(); ++k) {
+        std::vector<SphereCert> sc(std::max<size_t>(1, s->g->spheres.size()));
+        for (size_t k = 0; k < s->g->spheres.size(); ++k) {
             std::memcpy(sc[k].box, &sph_box[6 * k], 6 * sizeof(float));
-            sc[k].radius = s->spheres[k].radius;
+            sc[k].radius = s->g->spheres[k].radius;
             sc[k].slot = sph_slot[k];
-            std::memcpy(sc[k].o2w_inv, s->spheres[k].o2w_inv, 16 * sizeof(float));
-            sc[k].never_clipped = s->spheres[k].never_clipped;
+            std::memcpy(sc[k].o2w_inv, s->g->spheres[k].o2w_inv, 16 * sizeof(float));
+            sc[k].never_clipped = s->g->spheres[k].never_clipped;
             sc[k].pad[0] = sc[k].pad[1] = sc[k].pad[2] = 0u;
         }
-        if (int rc = upload(ctx, s->d_sphere_cert, sc.data(), sc.size() * sizeof(SphereCert))) return rc;
-        s->cert.sphere_cert = s->d_sphere_cert.p;
+        if (int rc = upload(ctx, s->g->d_sphere_cert, sc.data(), sc.size() * sizeof(SphereCert))) return rc;
+        s->cert.sphere_cert = s->g->d_sphere_cert.p;
     }
-    std::memcpy(s->wide_acc.root_box, &s->bvh.bounds[0], 6 * sizeof(float));  // the union of all primitives: the same box in every tree (bvh.jl:226 tests it first)
-    const bool one_leaf = n_anodes == 1 && (s->acc.flags[0] & 3u) == 3u;
+    std::memcpy(s->wide_acc.root_box, &s->g->bvh.bounds[0], 6 * sizeof(float));  // the union of all primitives: the same box in every tree (bvh.jl:226 tests it first)
+    const bool one_leaf = n_anodes == 1 && (s->g->acc.flags[0] & 3u) == 3u;
     if (one_leaf) {
         // every primitive in one leaf: walked over the CANONICAL records in canonical slot order (k_trace_leaf_c / k_any_leaf_c)
         if (n_prims > 255) return 0;
-        if (int rc = upload(ctx, s->d_slot_boxes, slot_box.data(), slot_box.size() * sizeof(float))) return rc;
-        s->cert.slot_boxes = (const float*)s->d_slot_boxes.p;
+        if (int rc = upload(ctx, s->g->d_slot_boxes, slot_box.data(), slot_box.size() * sizeof(float))) return rc;
+        s->cert.slot_boxes = (const float*)s->g->d_slot_boxes.p;
         s->wide_acc.root_ref = 0;
         s->wide_acc.root_cnt = n_prims;
         s->wide_acc.leaf_order = nullptr;
-        if (n_prims > 1 && !s->lights.empty()) {  // any-hit rays try what subtends the largest solid angle at the lights first (as k_any_leaf: any order gives the same boolean)
-            std::vector<std::pair<double, uint32_t>> ord;
-            for (uint32_t k = 0; k < n_prims; ++k) {
-                const HostPrim& p = s->prims[s->bvh.order[k]];
-                double w = 0.0;
-                for (const LightRec& l : s->lights) {
-                    const float* lp = l.position;
-                    if (l.kind == 2) continue;  // a directional light has no position: it orders nothing
-                    if (p.kind == 1) {
-                        const HostAABB& b = s->sphere_bounds[p.sphere_id];
-                        double c[3], r = 0.0, d2 = 0.0;
-                        for (int a = 0; a < 3; ++a) {
-                            c[a] = 0.5 * ((double)b.mn[a] + b.mx[a]);
-                            r = std::max(r, 0.5 * ((double)b.mx[a] - b.mn[a]));
-                            d2 += (c[a] - lp[a]) * (c[a] - lp[a]);
-                        }
-                        w += d2 <= r * r ? 4.0 * 3.14159265358979 : 2.0 * 3.14159265358979 * (1.0 - std::sqrt(std::max(0.0, 1.0 - r * r / d2)));
-                    } else {
-                        double r[3][3], len[3];
-                        for (int v = 0; v < 3; ++v) {
-                            for (int c = 0; c < 3; ++c) r[v][c] = (double)p.v[3 * v + c] - lp[c];
-                            len[v] = std::sqrt(r[v][0] * r[v][0] + r[v][1] * r[v][1] + r[v][2] * r[v][2]);
-                        }
-                        const double det = r[0][0] * (r[1][1] * r[2][2] - r[1][2] * r[2][1]) - r[0][1] * (r[1][0] * r[2][2] - r[1][2] * r[2][0]) + r[0][2] * (r[1][0] * r[2][1] - r[1][1] * r[2][0]);
-                        auto dot3 = [&](int a, int b) { return r[a][0] * r[b][0] + r[a][1] * r[b][1] + r[a][2] * r[b][2]; };
-                        const double den = len[0] * len[1] * len[2] + dot3(0, 1) * len[2] + dot3(0, 2) * len[1] + dot3(1, 2) * len[0];
-                        w += 2.0 * std::fabs(std::atan2(det, den));
-                    }
-                }
-                ord.push_back({w, k});
-            }
-            std::stable_sort(ord.begin(), ord.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-            std::vector<uint32_t> order(n_prims);
-            for (uint32_t k = 0; k < n_prims; ++k) order[k] = ord[k].second;
-            if (int rc = upload(ctx, s->d_acc_leaf_order, order.data(), order.size() * sizeof(uint32_t))) return rc;
-            s->wide_acc.leaf_order = (const uint32_t*)s->d_acc_leaf_order.p;
-        }
+        // (the any-hit order over its slots is the light stage's: commit_lights)
         s->hybrid_ok = true;
         clk.tick("accelerator: one leaf");
         return 0;
@@ -902,20 +886,20 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
     std::atomic<bool> bad{false};
     parallel_for(n_anodes, [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1 && !bad; ++i) {
-            if ((s->acc.flags[i] & 3u) != 3u) {
-                if (s->acc.a[i] <= i + 1 || s->acc.a[i] >= n_anodes) bad = true;
+            if ((s->g->acc.flags[i] & 3u) != 3u) {
+                if (s->g->acc.a[i] <= i + 1 || s->g->acc.a[i] >= n_anodes) bad = true;
                 continue;
             }
-            const uint32_t first = s->acc.a[i], cnt = s->acc.flags[i] >> 2;
+            const uint32_t first = s->g->acc.a[i], cnt = s->g->acc.flags[i] >> 2;
             if (cnt == 0 || cnt > 255 || (uint64_t)first + cnt > n_prims) {
                 bad = true;
                 continue;
             }
             for (uint32_t k = first; k < first + cnt; ++k)
-                if (std::memcmp(&s->acc.bounds[6 * i], &slot_box[6 * (size_t)cslot[s->acc.order[k]]], 6 * sizeof(float)) != 0) bad = true;
+                if (std::memcmp(&s->g->acc.bounds[6 * i], &slot_box[6 * (size_t)cslot[s->g->acc.order[k]]], 6 * sizeof(float)) != 0) bad = true;
         }
     });
-    if ((s->acc.flags[0] & 3u) == 3u) return 0;
+    if ((s->g->acc.flags[0] & 3u) == 3u) return 0;
     if (bad && conformed) return 0;  // (cannot happen: the conformed tree has the canonical leaf boxes by construction)
     if (bad) {
         // The library's builder draws its leaves where ITS cost function says (primitives with coincident centroids share one; a node that is not worth splitting stays
@@ -923,11 +907,11 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
         // accelerator is ours to change — its leaves are regrouped by canonical leaf (a leaf that straddles several becomes a small subtree), every leaf takes its canonical
         // leaf's box, the interior boxes are re-derived bottom-up (so they still nest).  A looser leaf box costs the accelerator a few visits, never an answer.
         FlatBVH out;
-        if (!conform_accelerator(s->acc, cslot, leaf_of_slot, slot_box, n_prims, out)) return 0;
-        s->acc = std::move(out);
+        if (!conform_accelerator(s->g->acc, cslot, leaf_of_slot, slot_box, n_prims, out)) return 0;
+        s->g->acc = std::move(out);
         return upload_accelerator_conformed(s);
     }
-    if (std::memcmp(&s->acc.bounds[0], &s->bvh.bounds[0], 6 * sizeof(float)) != 0) return 0;
+    if (std::memcmp(&s->g->acc.bounds[0], &s->g->bvh.bounds[0], 6 * sizeof(float)) != 0) return 0;
     clk.tick("accelerator: leaf boxes");
     // ---- per canonical slot, per sphere: where the reference's walk meets the primitive relative to the sphere (th_trace3c.h: a ray that starts inside a sphere only counts what
     //      the reference tests AFTER that sphere).  3 bits per sphere: the split axis of the canonical node where the two root paths part (3: they share a leaf) and whether the
@@ -936,27 +920,27 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
     {
         auto leftmost = [&](uint32_t i, uint32_t& slot) {
             for (uint32_t guard = 0; guard < 4096u && i < n_cnodes; ++guard) {
-                if ((s->bvh.flags[i] & 3u) == 3u) {
-                    slot = s->bvh.a[i];
+                if ((s->g->bvh.flags[i] & 3u) == 3u) {
+                    slot = s->g->bvh.a[i];
                     return true;
                 }
                 ++i;
             }
             return false;
         };
-        for (uint32_t sid = 0; sid < std::min<uint32_t>((uint32_t)s->spheres.size(), kCertOrderSpheres); ++sid) {  // (30 of the word's 32 bits; later spheres have no order bits: th_trace3c.h)
+        for (uint32_t sid = 0; sid < std::min<uint32_t>((uint32_t)s->g->spheres.size(), kCertOrderSpheres); ++sid) {  // (30 of the word's 32 bits; later spheres have no order bits: th_trace3c.h)
             const uint32_t ks = sph_slot[sid], sh = 3u * sid;
             uint32_t i = 0, lo = 0, hi = n_prims;
             bool ok = false;
             for (uint32_t guard = 0; guard < 4096u && i < n_cnodes; ++guard) {
-                if ((s->bvh.flags[i] & 3u) == 3u) {
-                    const uint32_t first = s->bvh.a[i], cnt = s->bvh.flags[i] >> 2;
+                if ((s->g->bvh.flags[i] & 3u) == 3u) {
+                    const uint32_t first = s->g->bvh.a[i], cnt = s->g->bvh.flags[i] >> 2;
                     ok = ks - first < cnt && first == lo && first + cnt == hi;
                     for (uint32_t k = first; ok && k < first + cnt; ++k)
                         if (k != ks) order_word[k] |= (3u | (k > ks ? 4u : 0u)) << sh;
                     break;
                 }
-                const uint32_t second = s->bvh.a[i], axis = s->bvh.flags[i] & 3u;
+                const uint32_t second = s->g->bvh.a[i], axis = s->g->bvh.flags[i] & 3u;
                 uint32_t lo2 = 0;
                 if (second <= i + 1 || second >= n_cnodes || !leftmost(second, lo2) || lo2 < lo || lo2 > hi) break;
                 if (ks >= lo2) {
@@ -977,8 +961,8 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
     std::vector<uint8_t> is_sphere(n_prims, 0);
     parallel_for(n_prims, [&](size_t k0, size_t k1) {
         for (size_t k = k0; k < k1; ++k) {
-            const HostPrim& p = s->prims[s->acc.order[k]];
-            const float cs = __builtin_bit_cast(float, cslot[s->acc.order[k]]);
+            const HostPrim& p = s->g->prims[s->g->acc.order[k]];
+            const float cs = __builtin_bit_cast(float, cslot[s->g->acc.order[k]]);
             if (p.kind == 1) {
                 aprims[3 * k] = make_float4(__builtin_bit_cast(float, p.sphere_id), 0, 0, __builtin_bit_cast(float, p.meta));
                 aprims[3 * k + 1] = make_float4(0, 0, 0, cs);
@@ -987,11 +971,11 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
             } else {
                 aprims[3 * k] = make_float4(p.v[0], p.v[1], p.v[2], __builtin_bit_cast(float, p.meta));
                 aprims[3 * k + 1] = make_float4(p.v[3], p.v[4], p.v[5], cs);
-                aprims[3 * k + 2] = make_float4(p.v[6], p.v[7], p.v[8], __builtin_bit_cast(float, order_word[cslot[s->acc.order[k]]]));
+                aprims[3 * k + 2] = make_float4(p.v[6], p.v[7], p.v[8], __builtin_bit_cast(float, order_word[cslot[s->g->acc.order[k]]]));
             }
         }
     });
-    if (int rc = upload(ctx, s->d_acc_prims, aprims.data(), aprims.size() * sizeof(float4))) return rc;
+    if (int rc = upload(ctx, s->g->d_acc_prims, aprims.data(), aprims.size() * sizeof(float4))) return rc;
     clk.tick("accelerator: primitive records");
     // ---- what the certificate's lower bound needs of the TRIANGLES (th_trace3c.h; spheres are never hidden from the walk): per axis the largest extent of a NON-FLAT triangle
     //      (the computed t of a primitive differs from the depth of the ray's point on it by at most the primitive's extent along the ray's dominant axis), and for FLAT ones
@@ -999,10 +983,10 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
     {
         std::mutex lock;
         float mle[3] = {0.0f, 0.0f, 0.0f}, sq = 0.0f;
-        parallel_for(s->prims.size(), [&](size_t i0, size_t i1) {
+        parallel_for(s->g->prims.size(), [&](size_t i0, size_t i1) {
             float m[3] = {0.0f, 0.0f, 0.0f}, q = 0.0f;
             for (size_t i = i0; i < i1; ++i) {
-                const HostPrim& p = s->prims[i];
+                const HostPrim& p = s->g->prims[i];
                 if (p.kind != 0 || (p.meta & PRIM_DEGENERATE)) continue;
                 float e[3];
                 for (int c = 0; c < 3; ++c) e[c] = std::fmax(std::fmax(p.v[c], p.v[3 + c]), p.v[6 + c]) - std::fmin(std::fmin(p.v[c], p.v[3 + c]), p.v[6 + c]);
@@ -1032,36 +1016,36 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
     }
     // children-in-parent nodes (as upload_scene's, th_trace2.h)
     std::vector<uint32_t> widx;
-    const uint32_t n_int = wide_node_order(s->acc, ctx->node_layout, widx);
+    const uint32_t n_int = wide_node_order(s->g->acc, ctx->node_layout, widx);
     if (n_int >= (1u << 24)) return 0;
     std::vector<uint8_t> has_sphere(n_anodes, 0);
     for (uint32_t i = n_anodes; i-- > 0;) {  // bottom-up (second children and first children both come later in the depth-first layout)
-        if ((s->acc.flags[i] & 3u) == 3u) {
-            const uint32_t first = s->acc.a[i], cnt = s->acc.flags[i] >> 2;
-            if (!s->spheres.empty())
+        if ((s->g->acc.flags[i] & 3u) == 3u) {
+            const uint32_t first = s->g->acc.a[i], cnt = s->g->acc.flags[i] >> 2;
+            if (!s->g->spheres.empty())
                 for (uint32_t k = first; k < first + cnt; ++k) has_sphere[i] |= is_sphere[k];
         } else {
-            has_sphere[i] = has_sphere[i + 1] | has_sphere[s->acc.a[i]];
+            has_sphere[i] = has_sphere[i + 1] | has_sphere[s->g->acc.a[i]];
         }
     }
     RawArray<float4> wn((size_t)n_int * 4);
     if (ctx->node_layout == 1) std::memset((void*)wn.data(), 0, (size_t)n_int * 4 * sizeof(float4));
     parallel_for(n_anodes, [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; ++i) {
-            if ((s->acc.flags[i] & 3u) == 3u) continue;
-            const uint32_t c[2] = {(uint32_t)i + 1, s->acc.a[i]};
+            if ((s->g->acc.flags[i] & 3u) == 3u) continue;
+            const uint32_t c[2] = {(uint32_t)i + 1, s->g->acc.a[i]};
             uint32_t ref[2], cnt[2];
             for (int k = 0; k < 2; ++k) {
-                if ((s->acc.flags[c[k]] & 3u) == 3u) {
-                    ref[k] = s->acc.a[c[k]];
-                    cnt[k] = s->acc.flags[c[k]] >> 2;
+                if ((s->g->acc.flags[c[k]] & 3u) == 3u) {
+                    ref[k] = s->g->acc.a[c[k]];
+                    cnt[k] = s->g->acc.flags[c[k]] >> 2;
                 } else {
                     ref[k] = widx[c[k]];
                     cnt[k] = 0;
                 }
             }
-            const float* l = &s->acc.bounds[6 * (size_t)c[0]];
-            const float* r = &s->acc.bounds[6 * (size_t)c[1]];
+            const float* l = &s->g->acc.bounds[6 * (size_t)c[0]];
+            const float* r = &s->g->acc.bounds[6 * (size_t)c[1]];
             float4* w = &wn[4 * (size_t)widx[i]];
             // the ACCELERATOR's layout: each axis' two planes side by side — {min x, max x, min y, max y}, {min z, max z | min x, max x}, {min y, max y, min z, max z} — so that
             // k_trace3c's packed instructions take a pair as it was loaded (th_trace3c.h "The step"); the canonical tree's nodes keep {min xyz, max xyz} (upload_scene)
@@ -1070,11 +1054,11 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
             w[2] = make_float4(r[1], r[4], r[2], r[5]);
             // child word = ref | count << 24 (the stack entry format); meta = split axis | "subtree holds a sphere" bits 2 (first) / 3 (second)
             w[3] = make_float4(__builtin_bit_cast(float, ref[0] | (cnt[0] << 24)), __builtin_bit_cast(float, ref[1] | (cnt[1] << 24)),
-                               __builtin_bit_cast(float, (s->acc.flags[i] & 3u) | ((uint32_t)has_sphere[c[0]] << 2) | ((uint32_t)has_sphere[c[1]] << 3)), 0.0f);
+                               __builtin_bit_cast(float, (s->g->acc.flags[i] & 3u) | ((uint32_t)has_sphere[c[0]] << 2) | ((uint32_t)has_sphere[c[1]] << 3)), 0.0f);
         }
     });
-    if (int rc = upload(ctx, s->d_acc_wnodes, wn.data(), wn.size() * sizeof(float4))) return rc;
-    s->wide_acc.wnodes = (const float4*)s->d_acc_wnodes.p;
+    if (int rc = upload(ctx, s->g->d_acc_wnodes, wn.data(), wn.size() * sizeof(float4))) return rc;
+    s->wide_acc.wnodes = (const float4*)s->g->d_acc_wnodes.p;
     s->wide_acc.n_wnodes = n_int;
     // ---- the same tree FOUR children wide (th_trace3c4.h): every other level of the binary tree folded into its parent, the widest child first (by surface area) while fewer
     //      than four slots are taken.  128 bytes per node = one L2 line: {min, max} pairs per axis of child 0 … 3 (six float4), the four child words (leaf: first primitive |
@@ -1092,9 +1076,9 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
         w4.resize(8);
         uint32_t max_depth4 = 0;
         std::vector<uint32_t> depth4{1u};  // per 4-wide node
-        bool ok4 = (s->acc.flags[0] & 3u) != 3u;
+        bool ok4 = (s->g->acc.flags[0] & 3u) != 3u;
         auto area = [&](uint32_t n) {
-            const float* b = &s->acc.bounds[6 * (size_t)n];
+            const float* b = &s->g->acc.bounds[6 * (size_t)n];
             const float dx = b[3] - b[0], dy = b[4] - b[1], dz = b[5] - b[2];
             return dx * dy + dx * dz + dy * dz;
         };
@@ -1112,19 +1096,19 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
             uint32_t kids[4];
             int nk = 2;
             kids[0] = f.node + 1;
-            kids[1] = s->acc.a[f.node];
+            kids[1] = s->g->acc.a[f.node];
             while (nk < 4) {
                 int best = -1;
                 float best_a = -1.0f;
                 for (int k = 0; k < nk; ++k)
-                    if ((s->acc.flags[kids[k]] & 3u) != 3u && area(kids[k]) > best_a) {
+                    if ((s->g->acc.flags[kids[k]] & 3u) != 3u && area(kids[k]) > best_a) {
                         best_a = area(kids[k]);
                         best = k;
                     }
                 if (best < 0) break;
                 const uint32_t c = kids[best];
                 kids[best] = c + 1;
-                kids[nk++] = s->acc.a[c];
+                kids[nk++] = s->g->acc.a[c];
             }
             float4 rec[8];
             const float qn = std::nanf("");
@@ -1133,15 +1117,15 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
             for (int k = 0; k < 24; ++k) planes[k] = qn;
             for (int k = 0; k < nk; ++k) {
                 const uint32_t c = kids[k];
-                const float* b = &s->acc.bounds[6 * (size_t)c];
+                const float* b = &s->g->acc.bounds[6 * (size_t)c];
                 for (int a = 0; a < 3; ++a) {
                     planes[6 * k + 2 * a] = b[a];
                     planes[6 * k + 2 * a + 1] = b[3 + a];
                 }
-                if ((s->acc.flags[c] & 3u) == 3u) {
-                    const uint32_t cnt = s->acc.flags[c] >> 2;
+                if ((s->g->acc.flags[c] & 3u) == 3u) {
+                    const uint32_t cnt = s->g->acc.flags[c] >> 2;
                     if (cnt == 0 || cnt > 255) ok4 = false;
-                    enc[k] = s->acc.a[c] | (cnt << 24);
+                    enc[k] = s->g->acc.a[c] | (cnt << 24);
                 } else {
                     const uint32_t idx = (uint32_t)(w4.size() / 8);
                     if (idx >= (1u << 24)) ok4 = false;
@@ -1216,15 +1200,15 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
                 q4[4 * n + 3] = make_float4(__builtin_bit_cast(float, words[0]), __builtin_bit_cast(float, words[1]), __builtin_bit_cast(float, words[2]), __builtin_bit_cast(float, words[3]));
             }
             if (ok4) {
-                if (int rc = upload(ctx, s->d_acc_w4nodes, q4.data(), q4.size() * sizeof(float4))) return rc;
-                s->wide_acc.w4nodes = (const float4*)s->d_acc_w4nodes.p;
+                if (int rc = upload(ctx, s->g->d_acc_w4nodes, q4.data(), q4.size() * sizeof(float4))) return rc;
+                s->wide_acc.w4nodes = (const float4*)s->g->d_acc_w4nodes.p;
                 s->wide_acc.n_w4nodes = (uint32_t)nn4;
             }
         }
 #else
         if (ok4 && 3 * (max_depth4 + 1) <= (uint32_t)kStack2Total) {
-            if (int rc = upload(ctx, s->d_acc_w4nodes, w4.data(), w4.size() * sizeof(float4))) return rc;
-            s->wide_acc.w4nodes = (const float4*)s->d_acc_w4nodes.p;
+            if (int rc = upload(ctx, s->g->d_acc_w4nodes, w4.data(), w4.size() * sizeof(float4))) return rc;
+            s->wide_acc.w4nodes = (const float4*)s->g->d_acc_w4nodes.p;
             s->wide_acc.n_w4nodes = (uint32_t)(w4.size() / 8);
         }
 #endif
@@ -1233,10 +1217,36 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
     s->wide_acc.root_ref = 0;
     s->wide_acc.root_cnt = 0;
     s->wide_acc.leaf_tight = s->wide.leaf_tight;
-    s->dev_acc.prims = (const float4*)s->d_acc_prims.p;
+    s->dev_acc.prims = (const float4*)s->g->d_acc_prims.p;
     s->hybrid_ok = true;
     clk.tick("accelerator: wnodes");
     return 0;
+}
+
+// ---- relit views (trhip_scene_relight) ----
+static uint64_t new_geometry_id() {
+    static std::atomic<uint64_t> next{1};
+    return next++;
+}
+// the geometry a relit view shares is fixed: adding to it is refused
+static int refuse_on_view(trhip_scene* s, const char* what) {
+    return fail(s->ctx, TRHIP_ERR_INVALID, "%s on a relit view: its geometry is its base scene's (trhip_scene_relight); add to the base and commit it, then relight again", what);
+}
+// before the geometry of a scene changes: when relit views share it, the scene continues on a copy of the caller's records (the views keep the committed geometry)
+static void own_geometry(trhip_scene* s) {
+    if (s->g.use_count() <= 1) return;
+    auto ng = std::make_shared<SceneGeometry>();
+    const SceneGeometry& o = *s->g;
+    ng->max_node_primitives = o.max_node_primitives;
+    ng->materials = o.materials;
+    ng->prims = o.prims;
+    ng->prim_tan = o.prim_tan;
+    ng->prim_uv = o.prim_uv;
+    ng->spheres = o.spheres;
+    ng->sphere_bounds = o.sphere_bounds;
+    ng->bvh = o.bvh;
+    ng->acc = o.acc;
+    s->g = std::move(ng);
 }
 
 extern "C" {
@@ -1251,38 +1261,23 @@ int trhip_scene_new(trhip_ctx* ctx, trhip_scene** out) {
 void trhip_scene_free(trhip_scene* s) {
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
-    release(s->d_nodes);
-    release(s->d_prims);
-    release(s->d_nrm);
-    release(s->d_leaf_boxes);
-    release(s->d_tan);
-    release(s->d_shade);
-    release(s->d_leaf_order);
-    release(s->d_spheres);
-    release(s->d_materials);
     release(s->d_lights);
-    release(s->d_wnodes);
+    release(s->d_leaf_order);
+    release(s->d_acc_leaf_order);
     release(s->d_occ_slots);
     release(s->d_occ_boxes);
-    release(s->d_w8nodes);
-    release(s->d_w8tris);
-    release(s->d_acc_wnodes);
-    release(s->d_acc_w4nodes);
-    release(s->d_acc_prims);
-    release(s->d_slot_boxes);
-    release(s->d_sphere_boxes);
-    release(s->d_sphere_slots);
-    release(s->d_sphere_cert);
-    release(s->d_acc_leaf_order);
+    s->g.reset();  // the geometry's buffers go with the last handle that holds them (~SceneGeometry)
     delete s;
 }
 int trhip_scene_add_material(trhip_scene* s, int kind, const float* params, int n_params, uint32_t* id_out) {
     if (!s || !params) return fail(s ? s->ctx : nullptr, TRHIP_ERR_INVALID, "null argument");
     MaterialRec m;
+    if (s->relit) return refuse_on_view(s, "trhip_scene_add_material");
     if (build_material(kind, params, n_params, m)) return fail(s->ctx, TRHIP_ERR_INVALID, "bad material kind %d / parameter count %d", kind, n_params);
-    if (s->materials.size() >= PRIM_NO_MATERIAL) return fail(s->ctx, TRHIP_ERR_INVALID, "too many materials");
-    s->materials.push_back(m);
-    if (id_out) *id_out = (uint32_t)s->materials.size() - 1;
+    own_geometry(s);
+    if (s->g->materials.size() >= PRIM_NO_MATERIAL) return fail(s->ctx, TRHIP_ERR_INVALID, "too many materials");
+    s->g->materials.push_back(m);
+    if (id_out) *id_out = (uint32_t)s->g->materials.size() - 1;
     s->committed = false;
     return 0;
 }
@@ -1293,14 +1288,15 @@ int trhip_scene_add_triangles(trhip_scene* s, const float* xyz, uint32_t n_verts
 int trhip_scene_add_triangles_ex(trhip_scene* s, const float* xyz, uint32_t n_verts, const uint32_t* idx, uint32_t n_tris, const float* normals, const float* tangents, const float* uv,
                                  const uint32_t* mat, int flip, uint32_t* first_out) {
     if (!s || !xyz || !idx) return fail(s ? s->ctx : nullptr, TRHIP_ERR_INVALID, "null argument");
-    const uint32_t first = (uint32_t)s->prims.size();
+    if (s->relit) return refuse_on_view(s, "trhip_scene_add_triangles");
+    const uint32_t first = (uint32_t)s->g->prims.size();
     // validate first (nothing is added when an index or a material is out of range), then fill the records on all cores
     std::atomic<uint32_t> bad_tri{0xffffffffu};
     parallel_for(n_tris, [&](size_t k0, size_t k1) {
         for (size_t k = k0; k < k1; ++k) {
             bool ok = true;
             for (int j = 0; j < 3; ++j) ok = ok && idx[3 * k + j] >= 1 && idx[3 * k + j] <= n_verts;
-            if (mat && mat[k] != PRIM_NO_MATERIAL && mat[k] >= s->materials.size()) ok = false;
+            if (mat && mat[k] != PRIM_NO_MATERIAL && mat[k] >= s->g->materials.size()) ok = false;
             if (!ok) {
                 uint32_t cur = bad_tri.load();
                 while ((uint32_t)k < cur && !bad_tri.compare_exchange_weak(cur, (uint32_t)k)) {
@@ -1317,10 +1313,11 @@ int trhip_scene_add_triangles_ex(trhip_scene* s, const float* xyz, uint32_t n_ve
         }
         return fail(s->ctx, TRHIP_ERR_INVALID, "triangle %u: material %u not defined", k, mat[k]);
     }
-    s->prims.resize((size_t)first + n_tris);
+    own_geometry(s);
+    s->g->prims.resize((size_t)first + n_tris);
     // the side arrays exist from the first mesh that brings tangents / (u, v)s on, one entry per primitive of the scene (zeros for the others)
-    if (tangents || !s->prim_tan.empty()) s->prim_tan.resize(9 * ((size_t)first + n_tris), 0.0f);
-    if (uv || !s->prim_uv.empty()) s->prim_uv.resize(7 * ((size_t)first + n_tris), 0.0f);
+    if (tangents || !s->g->prim_tan.empty()) s->g->prim_tan.resize(9 * ((size_t)first + n_tris), 0.0f);
+    if (uv || !s->g->prim_uv.empty()) s->g->prim_uv.resize(7 * ((size_t)first + n_tris), 0.0f);
     parallel_for(n_tris, [&](size_t k0, size_t k1) {
         for (size_t k = k0; k < k1; ++k) {
             HostPrim p;
@@ -1330,10 +1327,10 @@ int trhip_scene_add_triangles_ex(trhip_scene* s, const float* xyz, uint32_t n_ve
                 const uint32_t vi = idx[3 * k + j];
                 std::memcpy(&p.v[3 * j], &xyz[3 * (size_t)(vi - 1)], 3 * sizeof(float));
                 if (normals) std::memcpy(&p.n[3 * j], &normals[3 * (size_t)(vi - 1)], 3 * sizeof(float));
-                if (tangents) std::memcpy(&s->prim_tan[9 * ((size_t)first + k) + 3 * j], &tangents[3 * (size_t)(vi - 1)], 3 * sizeof(float));
+                if (tangents) std::memcpy(&s->g->prim_tan[9 * ((size_t)first + k) + 3 * j], &tangents[3 * (size_t)(vi - 1)], 3 * sizeof(float));
             }
             if (uv) {  // mesh.uv[t.i + j]: by corner position, not through the indices (triangle_mesh.jl:82)
-                float* dst = &s->prim_uv[7 * ((size_t)first + k)];
+                float* dst = &s->g->prim_uv[7 * ((size_t)first + k)];
                 std::memcpy(dst, &uv[6 * k], 6 * sizeof(float));
                 dst[6] = 1.0f;
             }
@@ -1343,7 +1340,7 @@ int trhip_scene_add_triangles_ex(trhip_scene* s, const float* xyz, uint32_t n_ve
             const f3 tn = cross(tv2 - tv0, tv1 - tv0);
             const bool degenerate = dot(tn, tn) == 0.0f;
             p.meta = (m & PRIM_MATERIAL_MASK) | (normals ? PRIM_HAS_NORMALS : 0u) | (tangents ? PRIM_HAS_TANGENTS : 0u) | (flip ? PRIM_FLIP : 0u) | (degenerate ? PRIM_DEGENERATE : 0u);
-            s->prims[(size_t)first + k] = p;
+            s->g->prims[(size_t)first + k] = p;
         }
     });
     if (first_out) *first_out = first;
@@ -1351,22 +1348,24 @@ int trhip_scene_add_triangles_ex(trhip_scene* s, const float* xyz, uint32_t n_ve
     return 0;
 }
 static int add_sphere_rec(trhip_scene* s, const float* o2w, const float* o2w_inv, int reverse, SphereRec r, uint32_t material, uint32_t* prim_out) {
-    if (material != PRIM_NO_MATERIAL && material >= s->materials.size()) return fail(s->ctx, TRHIP_ERR_INVALID, "material %u not defined", material);
+    if (s->relit) return refuse_on_view(s, "trhip_scene_add_sphere");
+    if (material != PRIM_NO_MATERIAL && material >= s->g->materials.size()) return fail(s->ctx, TRHIP_ERR_INVALID, "material %u not defined", material);
     std::memcpy(r.o2w, o2w, sizeof r.o2w);
     std::memcpy(r.o2w_inv, o2w_inv, sizeof r.o2w_inv);
     const bool swaps = det3(o2w) < 0.0f;  // transformations.jl:161-163
     r.flip = ((reverse != 0) != swaps) ? 1u : 0u;
     r.never_clipped = (!(r.z_min > -r.radius) && !(r.z_max < r.radius) && r.phi_max >= 2.0f * kPi) ? 1u : 0u;
     if (!r.never_clipped) s->partial_spheres = true;
+    own_geometry(s);
     HostPrim p;
     std::memset(&p, 0, sizeof p);
     p.kind = 1;
-    p.sphere_id = (uint32_t)s->spheres.size();
+    p.sphere_id = (uint32_t)s->g->spheres.size();
     p.meta = (material & PRIM_MATERIAL_MASK) | PRIM_SPHERE;
-    s->spheres.push_back(r);
-    s->sphere_bounds.push_back(sphere_world_bound(r));
-    if (prim_out) *prim_out = (uint32_t)s->prims.size();
-    s->prims.push_back(p);
+    s->g->spheres.push_back(r);
+    s->g->sphere_bounds.push_back(sphere_world_bound(r));
+    if (prim_out) *prim_out = (uint32_t)s->g->prims.size();
+    s->g->prims.push_back(p);
     s->committed = false;
     return 0;
 }
@@ -1444,12 +1443,12 @@ int trhip_scene_add_directional_light(trhip_scene* s, const float* I, const floa
 
 // world_bound of every primitive in caller order (triangle_mesh.jl:97, Shape.jl:17-19)
 static void primitive_bounds(const trhip_scene* s, std::vector<HostAABB>& pb) {
-    pb.resize(s->prims.size());
-    parallel_for(s->prims.size(), [&](size_t i0, size_t i1) {
+    pb.resize(s->g->prims.size());
+    parallel_for(s->g->prims.size(), [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; ++i) {
-            const HostPrim& p = s->prims[i];
+            const HostPrim& p = s->g->prims[i];
             if (p.kind == 1) {
-                pb[i] = s->sphere_bounds[p.sphere_id];
+                pb[i] = s->g->sphere_bounds[p.sphere_id];
             } else {
                 pb[i].reset();
                 for (int j = 0; j < 3; ++j) pb[i].grow_point(&p.v[3 * j]);
@@ -1492,22 +1491,25 @@ static int build_library_tree(trhip_ctx* ctx, const std::vector<HostAABB>& pb_bu
 }
 
 static void drop_accelerator(trhip_scene* s) {
-    s->acc = FlatBVH();
+    s->g->acc = FlatBVH();
     s->hybrid_ok = false;
     std::memset(&s->wide_acc, 0, sizeof s->wide_acc);
     s->wide_acc.root_ref = kRefNone;
-    release(s->d_acc_wnodes);
-    release(s->d_acc_w4nodes);
-    release(s->d_acc_prims);
-    release(s->d_slot_boxes);
+    release(s->g->d_acc_wnodes);
+    release(s->g->d_acc_w4nodes);
+    release(s->g->d_acc_prims);
+    release(s->g->d_slot_boxes);
     release(s->d_acc_leaf_order);
 }
 
-int trhip_scene_commit(trhip_scene* s, int max_node_primitives) {
-    if (s) s->bvh_note.clear();
+// the geometry stage of a full commit: both trees, every record and view derived from the primitives (the light stage follows: commit_lights)
+static int commit_geometry(trhip_scene* s, int max_node_primitives) {
+    s->bvh_note.clear();
     CommitClock clk;
-    if (!s) return fail(nullptr, TRHIP_ERR_INVALID, "null scene");
-    HIP_TRY(s->ctx, hipSetDevice(s->ctx->device));
+    own_geometry(s);
+    s->committed = false;
+    s->g->id = new_geometry_id();
+    s->g->max_node_primitives = max_node_primitives;
     std::vector<HostAABB> pb;
     primitive_bounds(s, pb);
     clk.tick("commit: primitive bounds");
@@ -1517,7 +1519,7 @@ int trhip_scene_commit(trhip_scene* s, int max_node_primitives) {
     // quadratic accepts rays far outside their box and can raise t_max (A.18) — out of the triangles' subtree, which the 8-wide
     // kernel then walks with conservative interior boxes (th_wide8.h).  The leaf-size hint is a hint (bvh.jl:159-165 decides by cost).
     std::vector<uint32_t> sph_ids, tri_ids;
-    for (size_t i = 0; i < s->prims.size(); ++i) (s->prims[i].kind == 1 ? sph_ids : tri_ids).push_back((uint32_t)i);
+    for (size_t i = 0; i < s->g->prims.size(); ++i) (s->g->prims[i].kind == 1 ? sph_ids : tri_ids).push_back((uint32_t)i);
     const int mode = s->ctx->bvh_builder;
     const bool want_chain = s->ctx->compose_spheres > 0 || (s->ctx->compose_spheres < 0 && s->ctx->traversal == 4);
     const bool compose = mode != 2 && want_chain && !sph_ids.empty() && sph_ids.size() <= (size_t)kW8MaxSpheres && tri_ids.size() >= 2 && pb.size() > s->ctx->tiny_scene_prims;
@@ -1539,7 +1541,7 @@ int trhip_scene_commit(trhip_scene* s, int max_node_primitives) {
         });
         if (want_hybrid) lib_rc = build_library_tree(s->ctx, pb, max_node_primitives, mode, false, lib_tree);
         try {
-            s->bvh = ref_job.get();
+            s->g->bvh = ref_job.get();
         } catch (const RefBVHBuilder::DepthExceeded& e) {
             ok = false;
             why = "BVH depth exceeds the 64-entry traversal stack (a node at depth " + std::to_string(e.depth) + "; bvh.jl:222 throws a BoundsError there)";
@@ -1554,13 +1556,13 @@ int trhip_scene_commit(trhip_scene* s, int max_node_primitives) {
             if (int rc = upload_scene(s)) return rc;
             if (!want_hybrid) return 0;
             if (lib_rc) return lib_rc;
-            s->acc = std::move(lib_tree);
+            s->g->acc = std::move(lib_tree);
             if (int rc = upload_accelerator(s)) return rc;
             if (s->hybrid_ok) {
                 s->bvh_mode = 2;
             } else {
                 drop_accelerator(s);
-                s->bvh_note = s->spheres.size() > kCertMaxSpheres ? "more than 32 spheres: every ray walks the canonical tree (th_trace3c.h kCertMaxSpheres)"
+                s->bvh_note = s->g->spheres.size() > kCertMaxSpheres ? "more than 32 spheres: every ray walks the canonical tree (th_trace3c.h kCertMaxSpheres)"
                                                                   : "no accelerator: the library's tree could not be conformed to the canonical leaves, or the canonical tree is a single leaf";
             }
             return 0;
@@ -1577,14 +1579,14 @@ int trhip_scene_commit(trhip_scene* s, int max_node_primitives) {
     }
     const std::vector<HostAABB>& pb_build = compose ? pb_sub : pb;
     if (lib_rc == 0 && !compose && !want_chain) {
-        s->bvh = std::move(lib_tree);  // (the reference's construction failed: the tree built beside it, same arguments, is the one to keep)
-    } else if (int rc = build_library_tree(s->ctx, pb_build, max_node_primitives, mode, want_chain, s->bvh)) {
+        s->g->bvh = std::move(lib_tree);  // (the reference's construction failed: the tree built beside it, same arguments, is the one to keep)
+    } else if (int rc = build_library_tree(s->ctx, pb_build, max_node_primitives, mode, want_chain, s->g->bvh)) {
         return rc;
     }
     clk.tick("commit: tree");
     if (compose) {
         // flat layout (bvh.jl:187-206): chain node i at 2 i = interior {leaf of sphere i at 2 i + 1, rest at 2 i + 2}; the triangles' subtree at 2 n_sph
-        FlatBVH sub = std::move(s->bvh), out;
+        FlatBVH sub = std::move(s->g->bvh), out;
         const uint32_t n_sph = (uint32_t)sph_ids.size(), n_sub = (uint32_t)sub.a.size();
         std::vector<HostAABB> rest(n_sph + 1);
         std::memcpy(rest[n_sph].mn, &sub.bounds[0], 3 * sizeof(float));
@@ -1627,10 +1629,10 @@ int trhip_scene_commit(trhip_scene* s, int max_node_primitives) {
         out.order.reserve(pb.size());
         for (uint32_t k : sub.order) out.order.push_back(tri_ids[k]);
         out.max_depth = sub.max_depth + n_sph;
-        s->bvh = std::move(out);
+        s->g->bvh = std::move(out);
     }
-    if (s->bvh.max_depth > (uint32_t)(kStackLds + kStackSpill))
-        return fail(s->ctx, TRHIP_ERR_UNSUPPORTED, "BVH depth %u exceeds the 64-entry traversal stack (bvh.jl:222)", s->bvh.max_depth);
+    if (s->g->bvh.max_depth > (uint32_t)(kStackLds + kStackSpill))
+        return fail(s->ctx, TRHIP_ERR_UNSUPPORTED, "BVH depth %u exceeds the 64-entry traversal stack (bvh.jl:222)", s->g->bvh.max_depth);
     s->literal_only = false;
     s->bvh_mode = 0;
     if (int rc = upload_scene(s)) return rc;
@@ -1638,13 +1640,48 @@ int trhip_scene_commit(trhip_scene* s, int max_node_primitives) {
     // four-wide certified walk: the same tree rides along as its own accelerator (mode 3).  The answers are the canonical tree's own walk's, as always; explicit requests
     // (bvh_builder 0 / 3) keep the single tree.
     if (mode < 0 && s->ctx->wide4 && !want_chain && !compose && s->wide_ok && s->wide.root_cnt == 0) {
-        s->acc = s->bvh;
+        s->g->acc = s->g->bvh;
         if (int rc = upload_accelerator(s)) return rc;
         if (s->hybrid_ok && s->wide_acc.w4nodes)
             s->bvh_mode = 3;
         else
             drop_accelerator(s);
     }
+    return 0;
+}
+int trhip_scene_commit(trhip_scene* s, int max_node_primitives) {
+    if (!s) return fail(nullptr, TRHIP_ERR_INVALID, "null scene");
+    HIP_TRY(s->ctx, hipSetDevice(s->ctx->device));
+    if (s->relit) {  // the geometry is the base's, committed: the light stage alone
+        if (max_node_primitives != s->g->max_node_primitives && s->g->max_node_primitives >= 0)
+            return fail(s->ctx, TRHIP_ERR_INVALID, "relit view: max_node_primitives %d, its geometry was committed with %d", max_node_primitives, s->g->max_node_primitives);
+        return commit_lights(s);
+    }
+    if (int rc = commit_geometry(s, max_node_primitives)) return rc;
+    return commit_lights(s);
+}
+int trhip_scene_relight(const trhip_scene* base, trhip_scene** out) {
+    if (!base || !out) return fail(base ? base->ctx : nullptr, TRHIP_ERR_INVALID, "null argument");
+    if (!base->committed) return fail(base->ctx, TRHIP_ERR_INVALID, "trhip_scene_relight: the base scene is not committed (commit it, or commit the relit view it came from, first)");
+    auto v = new trhip_scene(*base);  // the geometry (shared) and its views; the light stage's buffers are the view's own, made at its commit
+    v->relit = true;
+    v->committed = false;
+    v->lights.clear();
+    v->d_lights = DevBuf{};
+    v->d_leaf_order = DevBuf{};
+    v->d_acc_leaf_order = DevBuf{};
+    v->d_occ_slots = DevBuf{};
+    v->d_occ_boxes = DevBuf{};
+    v->n_occluders = 0;
+    v->dev.lights = v->dev_acc.lights = nullptr;
+    v->dev.n_lights = v->dev_acc.n_lights = 0;
+    v->wide.leaf_order = v->wide_acc.leaf_order = nullptr;
+    *out = v;
+    return 0;
+}
+int trhip_scene_geometry_id(const trhip_scene* s, uint64_t* id) {
+    if (!s || !id) return fail(s ? s->ctx : nullptr, TRHIP_ERR_INVALID, "null argument");
+    *id = s->g->id;
     return 0;
 }
 int trhip_build_bvh_host(int builder, const float* prim_bounds, uint32_t n_prims, int max_node_primitives, float* node_bounds, uint32_t* node_a, uint32_t* node_flags, uint32_t* n_nodes_inout,
@@ -1679,16 +1716,16 @@ int trhip_build_bvh_host(int builder, const float* prim_bounds, uint32_t n_prims
 }
 int trhip_scene_bvh_size(const trhip_scene* s, uint32_t* n_nodes, uint32_t* n_prims) {
     if (!s) return TRHIP_ERR_INVALID;
-    if (n_nodes) *n_nodes = (uint32_t)s->bvh.a.size();
-    if (n_prims) *n_prims = (uint32_t)s->bvh.order.size();
+    if (n_nodes) *n_nodes = (uint32_t)s->g->bvh.a.size();
+    if (n_prims) *n_prims = (uint32_t)s->g->bvh.order.size();
     return 0;
 }
 int trhip_scene_get_bvh(const trhip_scene* s, float* bounds, uint32_t* a, uint32_t* flags, uint32_t* order) {
     if (!s) return TRHIP_ERR_INVALID;
-    if (bounds) std::memcpy(bounds, s->bvh.bounds.data(), s->bvh.bounds.size() * sizeof(float));
-    if (a) std::memcpy(a, s->bvh.a.data(), s->bvh.a.size() * sizeof(uint32_t));
-    if (flags) std::memcpy(flags, s->bvh.flags.data(), s->bvh.flags.size() * sizeof(uint32_t));
-    if (order) std::memcpy(order, s->bvh.order.data(), s->bvh.order.size() * sizeof(uint32_t));
+    if (bounds) std::memcpy(bounds, s->g->bvh.bounds.data(), s->g->bvh.bounds.size() * sizeof(float));
+    if (a) std::memcpy(a, s->g->bvh.a.data(), s->g->bvh.a.size() * sizeof(uint32_t));
+    if (flags) std::memcpy(flags, s->g->bvh.flags.data(), s->g->bvh.flags.size() * sizeof(uint32_t));
+    if (order) std::memcpy(order, s->g->bvh.order.data(), s->g->bvh.order.size() * sizeof(uint32_t));
     return 0;
 }
 int trhip_scene_bvh_note(const trhip_scene* s, char* buf, size_t n) {
@@ -1699,24 +1736,26 @@ int trhip_scene_bvh_note(const trhip_scene* s, char* buf, size_t n) {
 int trhip_scene_bvh_mode(const trhip_scene* s, int* mode, uint32_t* accel_nodes, uint32_t* accel_depth) {
     if (!s) return TRHIP_ERR_INVALID;
     if (mode) *mode = s->bvh_mode;
-    if (accel_nodes) *accel_nodes = s->hybrid_ok ? (uint32_t)s->acc.a.size() : 0u;
-    if (accel_depth) *accel_depth = s->hybrid_ok ? s->acc.max_depth : 0u;
+    if (accel_nodes) *accel_nodes = s->hybrid_ok ? (uint32_t)s->g->acc.a.size() : 0u;
+    if (accel_depth) *accel_depth = s->hybrid_ok ? s->g->acc.max_depth : 0u;
     return 0;
 }
 int trhip_scene_get_accelerator(const trhip_scene* s, float* bounds, uint32_t* a, uint32_t* flags, uint32_t* order) {
     if (!s) return TRHIP_ERR_INVALID;
     if (!s->hybrid_ok) return fail(s->ctx, TRHIP_ERR_INVALID, "the scene has no accelerator tree (trhip_scene_bvh_mode)");
-    if (bounds) std::memcpy(bounds, s->acc.bounds.data(), s->acc.bounds.size() * sizeof(float));
-    if (a) std::memcpy(a, s->acc.a.data(), s->acc.a.size() * sizeof(uint32_t));
-    if (flags) std::memcpy(flags, s->acc.flags.data(), s->acc.flags.size() * sizeof(uint32_t));
-    if (order) std::memcpy(order, s->acc.order.data(), s->acc.order.size() * sizeof(uint32_t));
+    if (bounds) std::memcpy(bounds, s->g->acc.bounds.data(), s->g->acc.bounds.size() * sizeof(float));
+    if (a) std::memcpy(a, s->g->acc.a.data(), s->g->acc.a.size() * sizeof(uint32_t));
+    if (flags) std::memcpy(flags, s->g->acc.flags.data(), s->g->acc.flags.size() * sizeof(uint32_t));
+    if (order) std::memcpy(order, s->g->acc.order.data(), s->g->acc.order.size() * sizeof(uint32_t));
     return 0;
 }
 int trhip_scene_set_bvh(trhip_scene* s, const float* bounds, const uint32_t* a, const uint32_t* flags, uint32_t n_nodes, const uint32_t* order, uint32_t n_prims) {
     if (!s || !bounds || !a || !flags || !order) return fail(s ? s->ctx : nullptr, TRHIP_ERR_INVALID, "null argument");
+    if (s->relit) return refuse_on_view(s, "trhip_scene_set_bvh");
+    if (s->g.use_count() > 1) return fail(s->ctx, TRHIP_ERR_INVALID, "trhip_scene_set_bvh: the scene's geometry is shared with a relit view (trhip_scene_relight); free the views first");
     if (n_nodes == 0) return fail(s->ctx, TRHIP_ERR_INVALID, "empty node array");
     for (uint32_t i = 0; i < n_prims; ++i)
-        if (order[i] >= s->prims.size()) return fail(s->ctx, TRHIP_ERR_INVALID, "prim_order[%u] = %u out of range", i, order[i]);
+        if (order[i] >= s->g->prims.size()) return fail(s->ctx, TRHIP_ERR_INVALID, "prim_order[%u] = %u out of range", i, order[i]);
     // The array must be ONE tree in the reference's depth-first layout (bvh.jl:187-206): the subtree of node i is the index range
     // [i, end): first child i + 1 .. a[i] - 1, second child a[i] .. end - 1.  Anything else (a[i] <= i + 1 closes a cycle: the
     // traversal kernels would never end) is rejected here; so is a tree deeper than the 64-entry stack, where the reference
@@ -1741,10 +1780,10 @@ int trhip_scene_set_bvh(trhip_scene* s, const float* bounds, const uint32_t* a, 
             const uint32_t cnt = flags[i] >> 2;
             if ((uint64_t)a[i] + cnt > n_prims) return fail(s->ctx, TRHIP_ERR_INVALID, "leaf %u references primitives outside the list", i);
             for (uint32_t k = a[i]; k < a[i] + cnt && nested; ++k) {
-                const HostPrim& p = s->prims[order[k]];
+                const HostPrim& p = s->g->prims[order[k]];
                 HostAABB pb;
                 if (p.kind == 1) {
-                    pb = s->sphere_bounds[p.sphere_id];
+                    pb = s->g->sphere_bounds[p.sphere_id];
                 } else {
                     pb.reset();
                     for (int j = 0; j < 3; ++j) pb.grow_point(&p.v[3 * j]);
@@ -1763,23 +1802,25 @@ int trhip_scene_set_bvh(trhip_scene* s, const float* bounds, const uint32_t* a, 
     }
     if (max_depth > (uint32_t)(kStackLds + kStackSpill))
         return fail(s->ctx, TRHIP_ERR_UNSUPPORTED, "BVH depth %u exceeds the 64-entry traversal stack (bvh.jl:222 throws a BoundsError there)", max_depth);
-    s->bvh.bounds.assign(bounds, bounds + 6 * (size_t)n_nodes);
-    s->bvh.a.assign(a, a + n_nodes);
-    s->bvh.flags.assign(flags, flags + n_nodes);
-    s->bvh.order.assign(order, order + n_prims);
-    s->bvh.max_depth = max_depth;
+    s->g->bvh.bounds.assign(bounds, bounds + 6 * (size_t)n_nodes);
+    s->g->bvh.a.assign(a, a + n_nodes);
+    s->g->bvh.flags.assign(flags, flags + n_nodes);
+    s->g->bvh.order.assign(order, order + n_prims);
+    s->g->bvh.max_depth = max_depth;
     // The default kernels' shortcuts (tight slab clauses, largest-triangle pre-pass, wide nodes: th_trace2.h, th_trace8.h) are exact
     // only when boxes nest; a foreign tree that does not is walked by the literal kernels (the reference's loop, op for op).
     s->literal_only = !nested;
     HIP_TRY(s->ctx, hipSetDevice(s->ctx->device));
     drop_accelerator(s);
+    s->committed = false;
+    s->g->id = new_geometry_id();
     s->bvh_mode = 1;
     if (int rc = upload_scene(s)) return rc;
     // The host's own tree is the canonical one (Trace.jl's BVHAccel through TraceHIP.jl): under the default / hybrid builder the library's tree over the same
     // primitives rides along as the accelerator (th_trace3c.h) — same answers, most rays on the cheaper tree.  Needs every primitive in the tree exactly once.
     const int mode = s->ctx->bvh_builder;
     const bool want_chain = s->ctx->compose_spheres > 0 || (s->ctx->compose_spheres < 0 && s->ctx->traversal == 4);
-    if ((mode == 4 || mode < 0) && !want_chain && nested && n_prims == s->prims.size()) {
+    if ((mode == 4 || mode < 0) && !want_chain && nested && n_prims == s->g->prims.size()) {
         std::vector<uint8_t> seen(n_prims, 0);
         bool perm = true;
         for (uint32_t i = 0; i < n_prims && perm; ++i) {
@@ -1789,7 +1830,7 @@ int trhip_scene_set_bvh(trhip_scene* s, const float* bounds, const uint32_t* a, 
         if (perm) {
             std::vector<HostAABB> pb;
             primitive_bounds(s, pb);
-            if (int rc = build_library_tree(s->ctx, pb, 1, mode, false, s->acc)) return rc;
+            if (int rc = build_library_tree(s->ctx, pb, 1, mode, false, s->g->acc)) return rc;
             if (int rc = upload_accelerator(s)) return rc;
             if (s->hybrid_ok)
                 s->bvh_mode = 2;
@@ -1797,7 +1838,7 @@ int trhip_scene_set_bvh(trhip_scene* s, const float* bounds, const uint32_t* a, 
                 drop_accelerator(s);
         }
     }
-    return 0;
+    return commit_lights(s);
 }
 
 }  // extern "C"

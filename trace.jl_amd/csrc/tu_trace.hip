@@ -23,10 +23,10 @@ WideScene wide_view(const trhip_ctx* ctx, const trhip_scene* sc) {
     // k_trace3's postponed leaves need a non-increasing t_max: the rays that can see it raised start inside (or on) a sphere (A.18) — inside its world bound
     // grown by a thousandth of its size
     w.spec_spheres = 0xffffffffu;
-    if (ctx->trace3_spec && sc->sphere_bounds.size() <= 8) {
-        w.spec_spheres = (uint32_t)sc->sphere_bounds.size();
-        for (size_t k = 0; k < sc->sphere_bounds.size(); ++k) {
-            const HostAABB& b = sc->sphere_bounds[k];
+    if (ctx->trace3_spec && sc->g->sphere_bounds.size() <= 8) {
+        w.spec_spheres = (uint32_t)sc->g->sphere_bounds.size();
+        for (size_t k = 0; k < sc->g->sphere_bounds.size(); ++k) {
+            const HostAABB& b = sc->g->sphere_bounds[k];
             for (int a = 0; a < 3; ++a) {
                 const float grow = 1e-3f * (b.mx[a] - b.mn[a]) + 1e-6f * std::fmax(std::fabs(b.mn[a]), std::fabs(b.mx[a])) + 1e-30f;
                 w.spec_box[k][a] = b.mn[a] - grow;
@@ -228,8 +228,8 @@ void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool an
         if (sc->wide.root_cnt > 0 && ctx->debug_trace_budget == 0 && ctx->leaf_kernel) {  // one-leaf scene: the dedicated kernel (th_trace2.h, k_trace_leaf)
             const dim3 lgrid(ctx->num_cu * 8);
 #ifdef TRHIP_EXPERIMENTS
-            if (ctx->leaf_sorted && sc->d_leaf_boxes.p && sc->wide.root_cnt <= 30 && ctx->slab_margin_log2 > 0) {  // rays grouped by what they can hit (th_leaf2.h)
-                const float* lb = (const float*)sc->d_leaf_boxes.p;
+            if (ctx->leaf_sorted && sc->g->d_leaf_boxes.p && sc->wide.root_cnt <= 30 && ctx->slab_margin_log2 > 0) {  // rays grouped by what they can hit (th_leaf2.h)
+                const float* lb = (const float*)sc->g->d_leaf_boxes.p;
                 const WideScene wsv = wide_view(ctx, sc);
 #define TH_LEAF2(A, C, F) hipLaunchKernelGGL((k_leaf_sorted<A, C, F>), lgrid, block, 0, st, sc->dev, wsv, q, ro, rd, tmax, out, ctr, lb)
                 if (any) {

@@ -252,11 +252,12 @@ def goblet_mesh(n_theta: int = 256, n_profile: int = 172):
     return verts, (tris + 1).astype(np.uint32).reshape(-1), nrm.astype(np.float32)
 
 
-def caustic_scene(model: str = "", n_theta: int = 256, n_profile: int = 172):
+def caustic_scene(model: str = "", n_theta: int = 256, n_profile: int = 172, eta: float = 1.25):
     """docs/code/caustic_glass.jl:5-79: glass object on a plastic floor under a SpotLight.  ``model``: path of a PLY to load
-    with load_triangle_mesh (the reference's caustic-glass.ply); empty = the procedural goblet of the same size."""
+    with load_triangle_mesh (the reference's caustic-glass.ply); empty = the procedural goblet of the same size.  ``eta``: the glass's
+    index (caustic_moving.jl:12 uses 1.2)."""
     glass = T.GlassMaterial(T.ConstantTexture(T.RGBSpectrum(1.0)), T.ConstantTexture(T.RGBSpectrum(1.0)), T.ConstantTexture(0.0), T.ConstantTexture(0.0),
-                            T.ConstantTexture(1.25), True)
+                            T.ConstantTexture(eta), True)
     plastic = T.PlasticMaterial(T.ConstantTexture(T.RGBSpectrum(0.6399999857, 0.6399999857, 0.6399999857)),
                                 T.ConstantTexture(T.RGBSpectrum(0.1000000015, 0.1000000015, 0.1000000015)), T.ConstantTexture(0.010408001), True)
     prims = []
@@ -278,6 +279,21 @@ def caustic_scene(model: str = "", n_theta: int = 256, n_profile: int = 172):
     light_to_world = T.translate([4.5, 0, -101]) * T.translate(frm) * T.inv(T.Transformation(m))
     lights = [T.SpotLight(light_to_world, T.RGBSpectrum(60.0), 30.0, 20.0)]
     return T.Scene(lights, T.BVHAccel(prims, 1))
+
+
+def caustic_moving_lights(shift: float):
+    """docs/code/caustic_moving.jl:58-89: the two lights of the frame with this `shift` (the script's 0:0.1:5): a PointLight above the glass and the SpotLight
+    that moves up with the shift.  The geometry is caustic_scene(model, eta=1.2); the camera caustic_camera."""
+    frm, to = np.float32([0, 0.5 + shift, 0]), np.float32([-5, 0, 5])  # Point3f(0, 0.5 + shift, 0): the Float64 sum rounded once
+    d = (to - frm) / np.float32(np.sqrt(np.float32(((to - frm) ** 2).sum())))
+    d, du, dv = T.coordinate_system(d)
+    m = np.eye(4, dtype=np.float32)
+    m[0, :3], m[1, :3], m[2, :3] = du, dv, d
+    light_to_world = T.translate([4.5, 0, -101]) * T.translate(frm) * T.inv(T.Transformation(m))
+    cone_angle, cone_delta = np.float32(30.0), np.float32(10.0)
+    spot_i = np.float32([0.988235, 0.972549, 0.57647]) * np.float32(60.0)
+    return [T.PointLight(T.translate([2.5, 10, -100]), T.RGBSpectrum(np.float32(1.0) * np.float32(20.0))),
+            T.SpotLight(light_to_world, T.RGBSpectrum(*spot_i), cone_angle, cone_angle - cone_delta)]
 
 
 def caustic_camera(resolution: int = 1024, filename: str = ""):
