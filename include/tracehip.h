@@ -242,6 +242,60 @@ int trhip_render_whitted_device(trhip_ctx* ctx, const trhip_scene* scene, const 
  * (film.jl:68-73).  Parity tests compare this with the oracle bit-for-bit. */
 int trhip_last_sample_radiance(trhip_ctx* ctx, float* out_rgb, uint64_t n_floats);
 
+/* ---- first-hit feature buffers (since ABI 3001, added without a version change: nothing existing moved) -------------------
+ * What a denoiser, a compositor, an object picker or an edge-aware upscaler wants beside the beauty frame: for every camera
+ * sample of a frame the closest hit of its camera ray — depth, position, geometric and shading normal, base colour, primitive
+ * and material id — and the same values filtered onto the film.  The reference has no such output; the entry points below are
+ * this library's.  The camera samples are exactly those of the path renderer for the same (sensor, spp, seed, sample_offset):
+ * same stream keys, same get_camera_sample dimensions (sampler/sampler.jl:135-139), same generate_ray (camera/perspective.jl:85-114).
+ * Every camera ray is traced once, through the closest-hit walk the scene's commit selected (so the hit is the reference's
+ * intersect!(bvh, ray)); there are no bounces, no shadow rays and no BSDF: lights are ignored (a scene without any is fine) and
+ * primitives without a material are accepted.
+ *
+ * trhip_aov_sample: one camera sample, 80 bytes = five 16-byte words, 16-byte aligned:
+ *   offset  0  t, prim, b1, b2      exactly the trhip_hit of the camera ray (+Inf, -1, 0, 0 on a miss)
+ *   offset 16  p[3], material       hit position as the hit-geometry entry point gives it; material = the id the primitive was added
+ *                                   with (int32), -1 on a miss and for a primitive without a material
+ *   offset 32  n[3], pad0           geometric normal, then a zero word
+ *   offset 48  ns[3], pad1          shading normal, then a zero word
+ *   offset 64  albedo[3], pad2      base colour, then a zero word
+ * On a miss everything but t, prim and material is zero.  (Seventeen 32-bit values do not fit four 16-byte words: the record is five.)
+ * Base colour is a DEFINITION OF THIS LIBRARY (the reference has none): the constant texture a material's main lobe is built from,
+ * clamped as materials/material.jl clamps it before building the BSDF (clamp(spectrum), spectrum.jl:34-38: to [0, +Inf)) —
+ *   TRHIP_MATTE Kd, TRHIP_MIRROR Kr, TRHIP_PLASTIC Kd, TRHIP_GLASS Kt unless it is black after the clamp, then Kr; no material: zero.
+ * Records are indexed like the per-sample radiance: [s * n_sample_pixels + (y - sb.min.y) * sb_width + (x - sb.min.x)].
+ *
+ * out_planes: (crop height) * (crop width) * 3 float4 in film.pixels (y, x) order, plane-minor ([y][x][plane][4]):
+ *   plane 0 = (sum w * albedo.rgb, sum w over ALL samples)       — its .w is bit for bit the filter_weight_sum of the path renderer
+ *   plane 1 = (sum w * ns.xyz,     sum w over HITTING samples)
+ *   plane 2 = (sum w * p.xyz,      sum w * t)
+ * w is the film's own weight of the (sample, pixel) pair (add_sample!'s table lookup, film.jl:134-164), samples reach a pixel in the film
+ * pass's order (tile k, sample pixel, sample index; one partial sum per tile as merge_film_tile! adds them, film.jl:182-193), only hitting
+ * samples enter the sums (except plane 0's weight).  The sums are NOT normalised and no colour conversion is applied: the host divides
+ * (the Lanczos lobes are negative, so what a ratio means is the caller's business).  The planes are additive over sample_offset shards:
+ * the film all-reduce over 3 * n_pixels "pixels" sums them across the ranks of a multi-GPU job.
+ * Either output may be NULL (both: TRHIP_ERR_INVALID).  A frame whose per-sample buffers (152 bytes per camera sample) do not fit in free
+ * HBM is refused with TRHIP_ERR_UNSUPPORTED: there are no bands here.  The call fills trhip_stats: camera_samples, closest_rays,
+ * fallback_rays, traversal, ms_raygen / ms_trace_closest / ms_fallback / ms_shade (the resolve kernel) / ms_film (the gather) and the launch counts.
+ * The _device variant takes DEVICE pointers for both outputs. */
+typedef struct {
+    float t;
+    int32_t prim;
+    float b1, b2;
+    float p[3];
+    int32_t material;
+    float n[3];
+    uint32_t pad0;
+    float ns[3];
+    uint32_t pad1;
+    float albedo[3];
+    uint32_t pad2;
+} trhip_aov_sample;
+int trhip_render_aov(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset,
+                     float* out_planes, trhip_aov_sample* out_samples, trhip_stats* stats);
+int trhip_render_aov_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset,
+                            void* d_out_planes, void* d_out_samples, trhip_stats* stats);
+
 /* SPPMIntegrator(camera, initial_search_radius, max_depth, n_iterations, photons_per_iteration)(scene)
  * (integrators/sppm.jl:108-173): per iteration a camera pass to the first diffuse vertex, a hash grid over the visible
  * points, a photon pass (Halton / radical_inverse, sampler/sampling.jl:43-60) and the Float64 pixel update; afterwards

@@ -90,6 +90,29 @@ def comm_unique_id() -> bytes:
 
 HIT_DTYPE = np.dtype([("t", np.float32), ("prim", np.int32), ("b1", np.float32), ("b2", np.float32)])
 
+
+class AovSample(C.Structure):
+    """trhip_aov_sample: one camera sample of a feature-buffer frame (80 bytes, five 16-byte words)"""
+    _fields_ = [
+        ("t", C.c_float),
+        ("prim", C.c_int32),
+        ("b1", C.c_float),
+        ("b2", C.c_float),
+        ("p", C.c_float * 3),
+        ("material", C.c_int32),
+        ("n", C.c_float * 3),
+        ("pad0", C.c_uint32),
+        ("ns", C.c_float * 3),
+        ("pad1", C.c_uint32),
+        ("albedo", C.c_float * 3),
+        ("pad2", C.c_uint32),
+    ]
+
+
+# the same record as a numpy structured dtype (AOVIntegrator.samples)
+AOV_DTYPE = np.dtype([("t", np.float32), ("prim", np.int32), ("b1", np.float32), ("b2", np.float32), ("p", np.float32, 3), ("material", np.int32), ("n", np.float32, 3), ("pad0", np.uint32),
+                      ("ns", np.float32, 3), ("pad1", np.uint32), ("albedo", np.float32, 3), ("pad2", np.uint32)])
+
 _F = C.POINTER(C.c_float)
 _U32 = C.POINTER(C.c_uint32)
 _VP = C.c_void_p
@@ -128,6 +151,8 @@ SIGNATURES = {
     "trhip_render_path_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(Stats)]),
     "trhip_render_whitted_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(Stats)]),
     "trhip_last_sample_radiance": (C.c_int, [_VP, _F, C.c_uint64]),
+    "trhip_render_aov": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _F, _VP, C.POINTER(Stats)]),
+    "trhip_render_aov_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, _VP, C.POINTER(Stats)]),
     "trhip_render_sppm": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats)]),
     "trhip_render_sppm_ex": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats), C.c_uint32, SPPM_WRITE_FN, _VP]),
     "trhip_sppm_state": (C.c_int, [_VP, _F, _F, _F, C.POINTER(C.c_double), C.POINTER(C.c_int64), _F, _F, _F, C.POINTER(C.c_int64)]),
@@ -277,6 +302,63 @@ class Context:
     def __del__(self):
         try:
             self.close()
+        except Exception:
+            pass
+
+
+class DeviceBuffer:
+    """A plain HIP device allocation for the *_device entry points, for hosts that do not hold a torch tensor: hipMalloc / hipMemcpy / hipFree of the HIP runtime
+    libtracehip.so is linked against.  `ptr` is the device address."""
+    _hip = None
+
+    @classmethod
+    def _rt(cls):
+        if cls._hip is None:
+            lib()  # libtracehip.so has loaded the runtime: open that very copy
+            path = "libamdhip64.so"
+            with open("/proc/self/maps") as maps:
+                for line in maps:
+                    if "libamdhip64.so" in line:
+                        path = line.split()[-1]
+                        break
+            h = C.CDLL(path)
+            h.hipMalloc.argtypes, h.hipMalloc.restype = [C.POINTER(_VP), C.c_size_t], C.c_int
+            h.hipFree.argtypes, h.hipFree.restype = [_VP], C.c_int
+            h.hipMemcpy.argtypes, h.hipMemcpy.restype = [_VP, _VP, C.c_size_t, C.c_int], C.c_int
+            h.hipMemset.argtypes, h.hipMemset.restype = [_VP, C.c_int, C.c_size_t], C.c_int
+            cls._hip = h
+        return cls._hip
+
+    def __init__(self, nbytes: int):
+        self.nbytes = int(nbytes)
+        p = _VP()
+        rc = self._rt().hipMalloc(C.byref(p), max(self.nbytes, 16))
+        if rc:
+            raise TraceHipError(f"hipMalloc of {self.nbytes} bytes failed ({rc})")
+        self.ptr = p.value
+
+    def zero(self):
+        if self._rt().hipMemset(self.ptr, 0, self.nbytes):
+            raise TraceHipError("hipMemset failed")
+        return self
+
+    def to_host(self, dtype, shape) -> np.ndarray:
+        out = np.empty(shape, dtype=dtype)
+        if out.nbytes != self.nbytes:
+            raise TraceHipError(f"{out.nbytes} bytes asked of a {self.nbytes}-byte device buffer")
+        rc = self._rt().hipMemcpy(out.ctypes.data_as(_VP), self.ptr, self.nbytes, 2)  # hipMemcpyDeviceToHost (blocking)
+        if rc:
+            raise TraceHipError(f"hipMemcpy failed ({rc})")
+        return out
+
+    def free(self):
+        if getattr(self, "ptr", None):
+            self._rt().hipFree(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
         except Exception:
             pass
 

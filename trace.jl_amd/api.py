@@ -934,6 +934,98 @@ class PathIntegrator(_SamplerIntegrator):
     _entry_device = "trhip_render_path_device"
 
 
+# ---- first-hit feature buffers (include/tracehip.h, trhip_render_aov) -----------------------------------------------------------------
+def base_colour(material) -> np.ndarray:
+    """The base colour of a material as the feature buffers report it — a definition of this library (the reference has none): the constant texture the
+    material's main lobe is built from, clamped like materials/material.jl clamps it before building the BSDF (clamp(spectrum), spectrum.jl:34-38):
+    Matte Kd, Mirror Kr, Plastic Kd, Glass Kt unless it is black after the clamp (then Kr), no material zero."""
+    def clamped(tex):
+        return np.array([_jl_clamp(np.float32(x), np.float32(0.0), np.float32(np.inf)) for x in _tex_rgb(tex)], dtype=np.float32)
+    if material is None:
+        return np.zeros(3, np.float32)
+    if isinstance(material, (MatteMaterial, PlasticMaterial)):
+        return clamped(material.Kd)
+    if isinstance(material, MirrorMaterial):
+        return clamped(material.Kr)
+    if isinstance(material, GlassMaterial):
+        kt = clamped(material.Kt)
+        return kt if not np.all(kt == 0) else clamped(material.Kr)
+    raise TraceHipError(f"unsupported material {type(material).__name__}")
+
+
+def primitive_materials(scene: "Scene"):
+    """Per primitive in caller order (what prim_order of FlatScene.bvh() indexes): the material id FlatScene gives it (-1 without a material) and its base colour."""
+    ids, cols, seen = [], [], {}
+    for p in splice_nested(scene.aggregate.primitives):
+        m = p.material
+        if m is not None and id(m) not in seen:
+            seen[id(m)] = len(seen)
+        k = p.mesh.n_triangles if isinstance(p, MeshPrimitives) else 1
+        ids += [-1 if m is None else seen[id(m)]] * k
+        cols += [base_colour(m)] * k
+    return np.array(ids, np.int32), np.array(cols, np.float32).reshape(-1, 3)
+
+
+class AOVResult(dict):
+    """What AOVIntegrator.render returns: a dict whose keys are also attributes."""
+    __getattr__ = dict.__getitem__
+
+
+class AOVIntegrator:
+    """First-hit feature buffers of a frame (trhip_render_aov): depth, position, normals, base colour, ids — drawn with the camera samples of PathIntegrator for
+    the same camera and sampler and filtered by the same film filter, so that they line up with the beauty frame at every antialiased edge.  No bounces, no
+    lights, no BSDF: scenes without lights or with material-less primitives are fine."""
+
+    def __init__(self, camera: PerspectiveCamera, sampler: SeededSampler):
+        self.camera, self.sampler = camera, sampler
+        self.stats: Optional[_ffi.Stats] = None
+
+    def _sample_shape(self):
+        sb = self.camera.film.get_sample_bounds()
+        return int(sb.p_max[1] - sb.p_min[1]) + 1, int(sb.p_max[0] - sb.p_min[0]) + 1
+
+    def _call(self, scene, ctx, planes, samples, device):
+        flat = scene.flatten(ctx)
+        ctx = flat.ctx
+        sn, st, smp = self.camera.sensor(), _ffi.Stats(), self.sampler
+        entry = _ffi.lib().trhip_render_aov_device if device else _ffi.lib().trhip_render_aov
+        ctx.check(entry(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, planes, samples, C.byref(st)))
+        self.stats = st
+
+    def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None):
+        """The filtered planes.  Returns an AOVResult with `planes` (H, W, 3, 4: the raw, un-normalised sums of include/tracehip.h) and, each divided by its own
+        weight where that weight is not zero (zero elsewhere), `albedo` (H, W, 3; by the weight of all samples), `normal`, `position` (H, W, 3) and `depth` (H, W)
+        (by the weight of the hitting samples), and `alpha` = hit weight / total weight.  With ``device_out`` (a device pointer to H * W * 12 floats) the planes are
+        written there, nothing is copied to the host and None is returned."""
+        if device_out is not None:
+            self._call(scene, ctx, C.c_void_p(device_out), None, True)
+            return None
+        h, w = self.camera.film.size
+        planes = np.empty((h, w, 3, 4), dtype=np.float32)
+        self._call(scene, ctx, _ffi.fptr(planes), None, False)
+        return self.normalise(planes)
+
+    @staticmethod
+    def normalise(planes: np.ndarray) -> AOVResult:
+        planes = np.asarray(planes, np.float32)
+        w_all, w_hit = planes[..., 0, 3], planes[..., 1, 3]
+
+        def ratio(num, den):
+            den = den[..., None] if num.ndim > den.ndim else den
+            out = np.zeros(num.shape, np.float32)
+            np.divide(num, den, out=out, where=np.broadcast_to(den != 0, num.shape))
+            return out
+        return AOVResult(planes=planes, albedo=ratio(planes[..., 0, :3], w_all), normal=ratio(planes[..., 1, :3], w_hit), position=ratio(planes[..., 2, :3], w_hit),
+                         depth=ratio(planes[..., 2, 3], w_hit), alpha=ratio(w_hit, w_all))
+
+    def samples(self, scene: Scene, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
+        """The per-sample records, (spp, sb_h, sb_w) of _ffi.AOV_DTYPE: the trhip_hit of every camera ray, hit position, material id, geometric and shading normal, base colour."""
+        sbh, sbw = self._sample_shape()
+        out = np.empty((self.sampler.samples_per_pixel, sbh, sbw), dtype=_ffi.AOV_DTYPE)
+        self._call(scene, ctx, None, out.ctypes.data_as(C.c_void_p), False)
+        return out
+
+
 # ---- SPPM and the DirectionalLight -------------------------------------------------------------------------------------------------
 def _to_Y(c) -> np.float32:  # spectrum.jl:64-66
     c = np.asarray(c, np.float32)

@@ -2,7 +2,7 @@
 // handles of include/tracehip.h, error / buffer helpers, and the functions one unit calls in another.  Units (each compiled on its own
 // and linked into the one shared object): tu_api.hip (context, options, communicator), tu_scene.hip (scene flattening, commit, upload),
 // tu_lbvh.hip (BVH build on the device), tu_trace.hip / tu_trace3.hip / tu_trace8.hip (traversal launches and entry points),
-// tu_path.hip (PathIntegrator frames, film), tu_whitted.hip, tu_sppm.hip.
+// tu_path.hip (PathIntegrator frames, film), tu_aov.hip (first-hit feature buffers), tu_whitted.hip, tu_sppm.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -134,6 +134,7 @@ struct trhip_ctx {
     DevBuf fdesc;   // film_block 3: one SplatDesc (16 B) per camera sample of the band (th_kernels.h, k_film_descriptors)
     DevBuf poison;  // one byte per camera sample of the band: ShadeStream::poison
     DevBuf cert_cold;  // k_trace3c's CertCold (th_trace3c.h)
+    DevBuf aov_rec;    // trhip_render_aov: the frame's per-sample records (th_aov.h, 80 B per camera sample)
     DevBuf cb_rc;      // one word: a host callback's return code, max-reduced over the ranks of a job (tu_sppm.hip)
     DevBuf ov8[2], fb_list[2], fb_counts[2];  // k_trace8: global stack levels, fallback lists + their counters / work cursors ([closest | any])
     Comm comm;  // multi-GPU job this context belongs to (trhip_comm_init); n_ranks == 1 without one
@@ -155,6 +156,7 @@ struct SceneGeometry {
     uint64_t id = 0;  // trhip_scene_geometry_id: a new value for every tree this geometry is committed with (0 = never committed)
     int max_node_primitives = -1;  // what the last trhip_scene_commit built the trees with (-1: a caller's tree alone, trhip_scene_set_bvh)
     std::vector<MaterialRec> materials;
+    std::vector<float> base_colour;  // 4 floats per material: its base colour (include/tracehip.h, trhip_aov_sample) and a zero
     std::vector<HostPrim> prims;  // caller order
     // the two optional mesh arrays (shapes/triangle_mesh.jl:11-14), beside the primitives and only when some mesh carries them (no scene of the reference does):
     // prim_tan[9 i ..] = primitive i's vertex tangents (PRIM_HAS_TANGENTS), prim_uv[7 i ..] = its corner (u, v)s and a "has" flag; empty = none
@@ -169,14 +171,14 @@ struct SceneGeometry {
     std::vector<uint32_t> occ_slots;
     std::vector<float> occ_boxes;
     DevBuf d_leaf_boxes;  // one-leaf scenes: the boxes of the leaf's triangles in slot order (th_leaf2.h)
-    DevBuf d_nodes, d_prims, d_nrm, d_tan, d_shade, d_spheres, d_materials, d_wnodes, d_w8nodes, d_w8tris;
+    DevBuf d_nodes, d_prims, d_nrm, d_tan, d_shade, d_spheres, d_materials, d_base_colour, d_wnodes, d_w8nodes, d_w8tris;
     DevBuf d_acc_w4nodes;  // the accelerator four children wide (th_trace3c4.h)
     DevBuf d_acc_wnodes, d_acc_prims, d_slot_boxes, d_sphere_boxes, d_sphere_slots, d_sphere_cert;
     SceneGeometry() = default;
     SceneGeometry(const SceneGeometry&) = delete;
     SceneGeometry& operator=(const SceneGeometry&) = delete;
     ~SceneGeometry() {
-        for (DevBuf* b : {&d_leaf_boxes, &d_nodes, &d_prims, &d_nrm, &d_tan, &d_shade, &d_spheres, &d_materials, &d_wnodes, &d_w8nodes, &d_w8tris, &d_acc_w4nodes, &d_acc_wnodes,
+        for (DevBuf* b : {&d_leaf_boxes, &d_nodes, &d_prims, &d_nrm, &d_tan, &d_shade, &d_spheres, &d_materials, &d_base_colour, &d_wnodes, &d_w8nodes, &d_w8tris, &d_acc_w4nodes, &d_acc_wnodes,
                           &d_acc_prims, &d_slot_boxes, &d_sphere_boxes, &d_sphere_slots, &d_sphere_cert})
             release(*b);
     }

@@ -47,6 +47,7 @@ void trhip_shutdown(trhip_ctx* ctx) {
     release(ctx->fdesc);
     release(ctx->film_side);
     release(ctx->cert_cold);
+    release(ctx->aov_rec);
     release(ctx->cb_rc);
     for (auto& pp : ctx->pipes) {
         for (auto& a : pp.q)

@@ -198,6 +198,16 @@ int build_material(int kind, const float* p, int n, MaterialRec& m) {
     return 0;
 }
 
+// A material's base colour (include/tracehip.h, trhip_aov_sample): the texture its main lobe is built from, after the clamp build_material applies to it
+void material_base_colour(int kind, const float* p, float* out) {
+    clamp_rgb(p, out);  // Matte Kd, Mirror Kr, Plastic Kd; Glass Kr
+    if (kind == TRHIP_GLASS) {
+        float t[3];
+        clamp_rgb(p + 3, t);
+        if (!black(t)) set_rgb(out, t);
+    }
+}
+
 // world_bound(sphere) = object_to_world(object_bound) (Shape.jl:17-19, transformations.jl:141-143)
 HostAABB sphere_world_bound(const SphereRec& s) {
     HostAABB b;
@@ -319,6 +329,7 @@ int upload_scene(trhip_scene* s) {
     clk.tick("upload: shade records");
     if (int rc = upload(ctx, s->g->d_spheres, s->g->spheres.data(), s->g->spheres.size() * sizeof(SphereRec))) return rc;
     if (int rc = upload(ctx, s->g->d_materials, s->g->materials.data(), s->g->materials.size() * sizeof(MaterialRec))) return rc;
+    if (int rc = upload(ctx, s->g->d_base_colour, s->g->base_colour.data(), s->g->base_colour.size() * sizeof(float))) return rc;
     s->dev.nodes = (const float4*)s->g->d_nodes.p;
     s->dev.prims = (const float4*)s->g->d_prims.p;
     s->dev.tri_nrm = (const float4*)s->g->d_nrm.p;
@@ -1239,6 +1250,7 @@ static void own_geometry(trhip_scene* s) {
     const SceneGeometry& o = *s->g;
     ng->max_node_primitives = o.max_node_primitives;
     ng->materials = o.materials;
+    ng->base_colour = o.base_colour;
     ng->prims = o.prims;
     ng->prim_tan = o.prim_tan;
     ng->prim_uv = o.prim_uv;
@@ -1277,6 +1289,9 @@ int trhip_scene_add_material(trhip_scene* s, int kind, const float* params, int 
     own_geometry(s);
     if (s->g->materials.size() >= PRIM_NO_MATERIAL) return fail(s->ctx, TRHIP_ERR_INVALID, "too many materials");
     s->g->materials.push_back(m);
+    float base[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    material_base_colour(kind, params, base);
+    s->g->base_colour.insert(s->g->base_colour.end(), base, base + 4);
     if (id_out) *id_out = (uint32_t)s->g->materials.size() - 1;
     s->committed = false;
     return 0;
