@@ -296,6 +296,43 @@ int trhip_render_aov(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
 int trhip_render_aov_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset,
                             void* d_out_planes, void* d_out_samples, trhip_stats* stats);
 
+/* ---- edge-avoiding denoiser for path / Whitted films (since ABI 3001, added without a version change: nothing existing moved) ----
+ * An à-trous wavelet filter after Dammertz et al. 2010 ("Edge-Avoiding À-Trous Wavelet Transform for fast Global Illumination
+ * Filtering") on the film state of a path or Whitted render, guided by the three planes of trhip_render_aov for the same sensor,
+ * spp, seed and sample offset.  The reference has no such pass; the arithmetic is this library's and is specified, operation by
+ * operation, in docs/design/12-denoise.md: every step is one Float32 operation in a fixed order, `/` and sqrt correctly rounded, no
+ * transcendental function, so the output is reproducible bit for bit.  The edge-stopping function is Tukey's biweight,
+ * g(x) = x < 1 ? (1 - x*x)^2 : 0, in place of exp: a neighbour across a hard edge weighs exactly 0.
+ *   xyzw      height * width float4, exactly what trhip_render_path / trhip_render_whitted wrote
+ *   planes    height * width * 3 float4, exactly what trhip_render_aov wrote
+ *   out_xyzw  the layout of xyzw; may be xyzw itself
+ * A pixel is a SURFACE pixel when its filter weight, its total plane weight and its hit weight are positive, the hit weight is at
+ * least min_coverage times the total weight, and its normal, position and colour are finite.  Only surface pixels are filtered and
+ * only surface pixels are read as neighbours; every other pixel (a miss — the library has no environment light —, a silhouette
+ * pixel under min_coverage, a NaN) is returned with its input bits.  The .w lane (the filter weight sum) is always returned as given.
+ * iterations = 0 copies.  The step of iteration i is 2^i pixels and its colour sigma is sigma_colour * 2^-i.
+ * TRHIP_ERR_INVALID: a null pointer, a zero dimension, iterations > 6, a sigma or albedo_floor that is not finite and > 0,
+ * min_coverage outside [0, 1], unknown flag bits, reserved != 0.  TRHIP_ERR_UNSUPPORTED: the working set (80 bytes per pixel) does
+ * not fit in free HBM; the film is not split into bands.  stats (may be NULL): ms_total, ms_film / launches_film over all of the
+ * call's kernels, and their parts in ms_sub / launches_sub: [0] prepare, [1] the iterations, [2] finish.  The _device variant takes DEVICE pointers for the three images.
+ * trhip_denoise_default_params needs no context and no GPU. */
+#define TRHIP_DENOISE_DEMODULATE 1u /* divide by the base colour (clamped below by albedo_floor) before filtering, multiply after */
+typedef struct {
+    uint32_t iterations;      /* 0..6; 0 = copy */
+    uint32_t flags;           /* bit 0: TRHIP_DENOISE_DEMODULATE */
+    float sigma_colour;       /* on |dY| of the (demodulated) linear RGB; halved every iteration */
+    float sigma_normal;       /* on 1 - n_p . n_q */
+    float sigma_plane;        /* on |n_p . (p_q - p_p)|, world units */
+    float albedo_floor;       /* lower clamp of the base colour used for demodulation */
+    float min_coverage;       /* a pixel is a surface pixel when hit weight >= min_coverage * total weight */
+    uint32_t reserved;        /* 0 */
+} trhip_denoise_params;       /* 32 bytes */
+int trhip_denoise_default_params(trhip_denoise_params* out);
+int trhip_denoise(trhip_ctx* ctx, const float* xyzw, const float* planes, uint32_t width, uint32_t height, const trhip_denoise_params* params,
+                  float* out_xyzw, trhip_stats* stats);
+int trhip_denoise_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, uint32_t width, uint32_t height, const trhip_denoise_params* params,
+                         void* d_out_xyzw, trhip_stats* stats);
+
 /* SPPMIntegrator(camera, initial_search_radius, max_depth, n_iterations, photons_per_iteration)(scene)
  * (integrators/sppm.jl:108-173): per iteration a camera pass to the first diffuse vertex, a hash grid over the visible
  * points, a photon pass (Halton / radical_inverse, sampler/sampling.jl:43-60) and the Float64 pixel update; afterwards
@@ -447,6 +484,8 @@ int trhip_film_allreduce(trhip_ctx* ctx, void* d_xyzw, uint64_t n_pixels);
  *     16-byte splat descriptor per sample (pixel range + filter-table indices, the same Float32 operations done once per sample instead of
  *     once per thread the sample reaches; filter radius <= 3, else 2; measured 20 % slower than 2); same film bit for bit.
  * "film_tiled" (0/1): LDS-staged film gather (default 0: measured slower).
+ * "denoise_lds" (bit mask 0..3, default 3): bit i set = iteration i of trhip_denoise (i = 0, 1: steps 1, 2) stages its blocks' pixels and halo in LDS
+ *     instead of gathering them from memory (measured 7 % and 3 % faster); same result bit for bit (th_denoise.h).
  * "film_transpose" (0/1): film pass on pixel-group-major copies of the per-sample radiance / film positions (default 0: no gain).
  * "leaf_kernel" (0/1): one-leaf scenes (tiny_scene_prims) run the dedicated uniform-walk kernel instead of traversal 2 (default 1).
  * "band_tile_rows": PathIntegrator frames whose per-sample buffers (24 B per camera sample) do not fit in HBM are rendered in bands of

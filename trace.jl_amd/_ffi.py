@@ -113,6 +113,23 @@ class AovSample(C.Structure):
 AOV_DTYPE = np.dtype([("t", np.float32), ("prim", np.int32), ("b1", np.float32), ("b2", np.float32), ("p", np.float32, 3), ("material", np.int32), ("n", np.float32, 3), ("pad0", np.uint32),
                       ("ns", np.float32, 3), ("pad1", np.uint32), ("albedo", np.float32, 3), ("pad2", np.uint32)])
 
+
+class DenoiseParams(C.Structure):
+    """trhip_denoise_params (32 bytes)"""
+    _fields_ = [
+        ("iterations", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("sigma_colour", C.c_float),
+        ("sigma_normal", C.c_float),
+        ("sigma_plane", C.c_float),
+        ("albedo_floor", C.c_float),
+        ("min_coverage", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
+DENOISE_DEMODULATE = 1  # TRHIP_DENOISE_DEMODULATE
+
 _F = C.POINTER(C.c_float)
 _U32 = C.POINTER(C.c_uint32)
 _VP = C.c_void_p
@@ -153,6 +170,9 @@ SIGNATURES = {
     "trhip_last_sample_radiance": (C.c_int, [_VP, _F, C.c_uint64]),
     "trhip_render_aov": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _F, _VP, C.POINTER(Stats)]),
     "trhip_render_aov_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, _VP, C.POINTER(Stats)]),
+    "trhip_denoise_default_params": (C.c_int, [C.POINTER(DenoiseParams)]),
+    "trhip_denoise": (C.c_int, [_VP, _F, _F, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _F, C.POINTER(Stats)]),
+    "trhip_denoise_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _VP, C.POINTER(Stats)]),
     "trhip_render_sppm": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats)]),
     "trhip_render_sppm_ex": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats), C.c_uint32, SPPM_WRITE_FN, _VP]),
     "trhip_sppm_state": (C.c_int, [_VP, _F, _F, _F, C.POINTER(C.c_double), C.POINTER(C.c_int64), _F, _F, _F, C.POINTER(C.c_int64)]),
@@ -340,6 +360,15 @@ class DeviceBuffer:
     def zero(self):
         if self._rt().hipMemset(self.ptr, 0, self.nbytes):
             raise TraceHipError("hipMemset failed")
+        return self
+
+    def from_host(self, a: np.ndarray):
+        a = np.ascontiguousarray(a)
+        if a.nbytes != self.nbytes:
+            raise TraceHipError(f"{a.nbytes} bytes given to a {self.nbytes}-byte device buffer")
+        rc = self._rt().hipMemcpy(self.ptr, a.ctypes.data_as(_VP), self.nbytes, 1)  # hipMemcpyHostToDevice (blocking)
+        if rc:
+            raise TraceHipError(f"hipMemcpy failed ({rc})")
         return self
 
     def to_host(self, dtype, shape) -> np.ndarray:

@@ -1026,6 +1026,63 @@ class AOVIntegrator:
         return out
 
 
+# ---- edge-avoiding denoiser (include/tracehip.h, trhip_denoise) ----------------------------------------------------------------------------
+class Denoiser:
+    """Edge-avoiding à-trous filter (Dammertz et al. 2010, Tukey's biweight as the edge-stopping function) for the film of a PathIntegrator or WhittedIntegrator render,
+    guided by the planes of AOVIntegrator for the same camera and sampler (trhip_denoise; docs/design/12-denoise.md).  Fields left at None come from
+    trhip_denoise_default_params.  Pixels that are no surface pixels — misses, silhouette pixels with less than min_coverage hit weight, NaNs — are returned untouched."""
+
+    def __init__(self, iterations: Optional[int] = None, demodulate: bool = True, sigma_colour: Optional[float] = None, sigma_normal: Optional[float] = None,
+                 sigma_plane: Optional[float] = None, albedo_floor: Optional[float] = None, min_coverage: Optional[float] = None):
+        p = _ffi.DenoiseParams()
+        rc = _ffi.lib().trhip_denoise_default_params(C.byref(p))
+        if rc:
+            raise TraceHipError(f"trhip_denoise_default_params failed ({rc})")
+        for name, value in (("iterations", iterations), ("sigma_colour", sigma_colour), ("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane), ("albedo_floor", albedo_floor),
+                            ("min_coverage", min_coverage)):
+            if value is not None:
+                setattr(p, name, value)
+        p.flags = _ffi.DENOISE_DEMODULATE if demodulate else 0
+        self.params = p
+        self.stats: Optional[_ffi.Stats] = None
+        self.render_stats = None  # (path, aov, denoise) Stats of the last render()
+
+    def denoise(self, xyzw: np.ndarray, planes: np.ndarray, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
+        """xyzw: (H, W, 4) as PathIntegrator.render returns it; planes: (H, W, 3, 4) as AOVIntegrator.render(...).planes.  Returns the denoised (H, W, 4)."""
+        xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
+        if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
+            raise TraceHipError(f"denoise: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
+        ctx = ctx or _ffi.default_context()
+        h, w = xyzw.shape[:2]
+        out, st = np.empty_like(xyzw), _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_denoise(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(planes), w, h, C.byref(self.params), _ffi.fptr(out), C.byref(st)))
+        self.stats = st
+        return out
+
+    def denoise_device(self, d_xyzw: int, d_planes: int, width: int, height: int, d_out: int, ctx: Optional[_ffi.Context] = None) -> None:
+        """The same on device pointers (d_out may equal d_xyzw); nothing is copied to the host."""
+        ctx = ctx or _ffi.default_context()
+        st = _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_denoise_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), int(width), int(height), C.byref(self.params), C.c_void_p(d_out), C.byref(st)))
+        self.stats = st
+
+    def render(self, scene: Scene, camera: PerspectiveCamera, sampler: SeededSampler, max_depth: int, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
+        """Path frame and feature planes with the same sampler settings, both left on the device, denoised there; returns xyzw (H, W, 4), ready for film.set_xyzw / save."""
+        ctx = scene.flatten(ctx).ctx
+        h, w = camera.film.size
+        d_film, d_planes = _ffi.DeviceBuffer(h * w * 16), _ffi.DeviceBuffer(h * w * 48)
+        try:
+            path, aov = PathIntegrator(camera, sampler, max_depth), AOVIntegrator(camera, sampler)
+            path.render(scene, ctx, device_out=d_film.ptr)
+            aov.render(scene, ctx, device_out=d_planes.ptr)
+            self.denoise_device(d_film.ptr, d_planes.ptr, w, h, d_film.ptr, ctx)
+            self.render_stats = (path.stats, aov.stats, self.stats)
+            return d_film.to_host(np.float32, (h, w, 4))
+        finally:
+            d_film.free()
+            d_planes.free()
+
+
 # ---- SPPM and the DirectionalLight -------------------------------------------------------------------------------------------------
 def _to_Y(c) -> np.float32:  # spectrum.jl:64-66
     c = np.asarray(c, np.float32)

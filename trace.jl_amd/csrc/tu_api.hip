@@ -48,6 +48,8 @@ void trhip_shutdown(trhip_ctx* ctx) {
     release(ctx->film_side);
     release(ctx->cert_cold);
     release(ctx->aov_rec);
+    release(ctx->dn_work);
+    release(ctx->dn_in);
     release(ctx->cb_rc);
     for (auto& pp : ctx->pipes) {
         for (auto& a : pp.q)
@@ -245,6 +247,8 @@ int trhip_set_option(trhip_ctx* ctx, const char* name, int64_t value) {
         ctx->film_swizzle = value != 0;
     else if (!std::strcmp(name, "film_tiled"))
         ctx->film_tiled = value != 0;
+    else if (!std::strcmp(name, "denoise_lds"))
+        ctx->denoise_lds = (int)(value & 3);
     else if (!std::strcmp(name, "pipelines")) {
         if (value < 1 || value > kMaxPipes) return fail(ctx, TRHIP_ERR_INVALID, "pipelines must be in 1..%d", kMaxPipes);
         ctx->pipelines = (int)value;

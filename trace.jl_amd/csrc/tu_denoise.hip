@@ -1,0 +1,136 @@
+// tu_denoise.hip — trhip_denoise: the edge-avoiding à-trous filter of th_denoise.h on a film and its feature planes.  No scene, no traversal: an image-space pass.
+#include "th_host.h"
+#include "th_denoise.h"
+
+#include <cmath>
+
+namespace {
+
+static_assert(sizeof(trhip_denoise_params) == 32, "trhip_denoise_params layout");
+
+constexpr uint32_t kDnMaxIterations = 6;
+constexpr size_t kDnBytesPerPixel = 80;  // {n, flag} {p, 0} {c, Y} x 2 {a, 0}
+
+bool positive_finite(float v) { return std::isfinite(v) && v > 0.0f; }
+
+int check_params(trhip_ctx* ctx, const trhip_denoise_params* p) {
+    if (p->iterations > kDnMaxIterations) return fail(ctx, TRHIP_ERR_INVALID, "trhip_denoise: iterations = %u, at most %u", p->iterations, kDnMaxIterations);
+    if (p->flags & ~(uint32_t)TRHIP_DENOISE_DEMODULATE) return fail(ctx, TRHIP_ERR_INVALID, "trhip_denoise: unknown flag bits 0x%x", p->flags & ~(uint32_t)TRHIP_DENOISE_DEMODULATE);
+    if (!positive_finite(p->sigma_colour)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_denoise: sigma_colour must be finite and > 0");
+    if (!positive_finite(p->sigma_normal)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_denoise: sigma_normal must be finite and > 0");
+    if (!positive_finite(p->sigma_plane)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_denoise: sigma_plane must be finite and > 0");
+    if (!positive_finite(p->albedo_floor)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_denoise: albedo_floor must be finite and > 0");
+    if (!(p->min_coverage >= 0.0f && p->min_coverage <= 1.0f)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_denoise: min_coverage must lie in [0, 1]");
+    if (p->reserved != 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_denoise: reserved must be 0");
+    return 0;
+}
+
+int denoise_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, uint32_t width, uint32_t height, const trhip_denoise_params* prm, void* out, bool is_device, trhip_stats* stats) {
+    if (!ctx || !xyzw || !planes || !prm || !out) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
+    if (width == 0 || height == 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_denoise: empty film (%u x %u)", width, height);
+    if (int rc = check_params(ctx, prm)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t npix = (uint64_t)width * height;
+    const size_t film_bytes = (size_t)npix * sizeof(float4), planes_bytes = 3 * film_bytes;
+    const uint32_t bx = (width + kDnTile - 1) / kDnTile, by = (height + kDnTile - 1) / kDnTile;
+    {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+        const size_t held = ctx->dn_work.bytes + ctx->dn_in.bytes;  // reused below
+        const double need = (double)npix * kDnBytesPerPixel + (is_device ? 0.0 : (double)(film_bytes + planes_bytes));
+        if (by > 65535u || need > 0.9 * (double)(free_b + held))
+            return fail(ctx, TRHIP_ERR_UNSUPPORTED, "trhip_denoise: the working set of a %u x %u film (%.1f GB, 80 B per pixel) does not fit in free HBM (%.1f GB free); there are no bands here", width,
+                        height, need * 1e-9, (double)(free_b + held) * 1e-9);
+    }
+    if (int rc = ensure(ctx, ctx->dn_work, (size_t)npix * kDnBytesPerPixel)) return rc;
+    const float4* d_beauty = (const float4*)xyzw;
+    const float4* d_planes = (const float4*)planes;
+    float4* d_out = (float4*)out;
+    if (!is_device) {  // the film's copy is denoised in place
+        if (int rc = ensure(ctx, ctx->dn_in, film_bytes + planes_bytes)) return rc;
+        HIP_TRY(ctx, hipMemcpy(ctx->dn_in.p, xyzw, film_bytes, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy((char*)ctx->dn_in.p + film_bytes, planes, planes_bytes, hipMemcpyHostToDevice));
+        d_beauty = d_out = (float4*)ctx->dn_in.p;
+        d_planes = (const float4*)((char*)ctx->dn_in.p + film_bytes);
+    }
+    float4* gn = (float4*)ctx->dn_work.p;
+    float4 *gp = gn + npix, *col[2] = {gn + 2 * npix, gn + 3 * npix}, *alb = gn + 4 * npix;
+    hipStream_t st = ctx->stream;
+    const uint32_t demodulate = prm->flags & TRHIP_DENOISE_DEMODULATE;
+
+    Timer tm(ctx, ctx->timing && stats);
+    hipEvent_t e0, e1;
+    HIP_TRY(ctx, hipEventCreate(&e0));
+    HIP_TRY(ctx, hipEventCreate(&e1));
+    HIP_TRY(ctx, hipEventRecord(e0, st));
+    if (prm->iterations == 0) {
+        if (d_out != d_beauty) HIP_TRY(ctx, hipMemcpyAsync(d_out, d_beauty, film_bytes, hipMemcpyDeviceToDevice, st));
+    } else {
+        const int lin_grid = grid_for(ctx, npix, 8);
+        tm.begin(5, st);
+        hipLaunchKernelGGL(k_denoise_prepare, dim3(lin_grid), dim3(kBlock), 0, st, d_beauty, d_planes, npix, demodulate, prm->albedo_floor, prm->min_coverage, gn, gp, col[0], alb);
+        tm.end(5, st);
+        DenoiseWeights sg{prm->sigma_colour, prm->sigma_normal, prm->sigma_plane};
+        for (uint32_t i = 0; i < prm->iterations; ++i) {
+            const float4* cin = col[i & 1];
+            float4* cout = col[(i & 1) ^ 1];
+            const dim3 grid(bx, by), block(kDnTile * kDnTile);
+            const bool lds = i < 2 && ((ctx->denoise_lds >> i) & 1);  // steps 1 and 2: measured faster staged, step 4 slower (profiles/r9/denoise.txt)
+            tm.begin(6, st);
+            if (lds && i == 0)
+                hipLaunchKernelGGL((k_denoise_atrous_lds<1>), grid, block, 0, st, gn, gp, cin, cout, (int)width, (int)height, sg);
+            else if (lds)
+                hipLaunchKernelGGL((k_denoise_atrous_lds<2>), grid, block, 0, st, gn, gp, cin, cout, (int)width, (int)height, sg);
+            else
+                hipLaunchKernelGGL(k_denoise_atrous, grid, block, 0, st, gn, gp, cin, cout, (int)width, (int)height, 1 << i, sg);
+            tm.end(6, st);
+            sg.sigma_colour *= 0.5f;
+        }
+        tm.begin(7, st);
+        hipLaunchKernelGGL(k_denoise_finish, dim3(lin_grid), dim3(kBlock), 0, st, d_beauty, gn, col[prm->iterations & 1], alb, npix, demodulate, d_out);
+        tm.end(7, st);
+    }
+    HIP_TRY(ctx, hipEventRecord(e1, st));
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (!is_device) HIP_TRY(ctx, hipMemcpy(out, d_out, film_bytes, hipMemcpyDeviceToHost));
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        stats->ms_total = ms;
+        for (int k = 0; k < 3; ++k) {  // prepare, the iterations, finish
+            stats->ms_sub[k] = tm.total(5 + k, &stats->launches_sub[k]);
+            stats->ms_film += stats->ms_sub[k];
+            stats->launches_film += stats->launches_sub[k];
+        }
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trhip_denoise_default_params(trhip_denoise_params* out) {
+    if (!out) return fail(nullptr, TRHIP_ERR_INVALID, "null argument");
+    std::memset(out, 0, sizeof *out);
+    out->iterations = 5;
+    out->flags = TRHIP_DENOISE_DEMODULATE;
+    out->sigma_colour = 4.0f;  // the three sigmas: the sweep of profiles/r9/denoise.txt
+    out->sigma_normal = 0.25f;
+    out->sigma_plane = 0.1f;
+    out->albedo_floor = 1.0f / 64.0f;
+    out->min_coverage = 0.5f;
+    return 0;
+}
+int trhip_denoise(trhip_ctx* ctx, const float* xyzw, const float* planes, uint32_t width, uint32_t height, const trhip_denoise_params* prm, float* out_xyzw, trhip_stats* st) {
+    return denoise_impl(ctx, xyzw, planes, width, height, prm, out_xyzw, false, st);
+}
+int trhip_denoise_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, uint32_t width, uint32_t height, const trhip_denoise_params* prm, void* d_out_xyzw, trhip_stats* st) {
+    return denoise_impl(ctx, d_xyzw, d_planes, width, height, prm, d_out_xyzw, true, st);
+}
+
+}  // extern "C"
