@@ -342,6 +342,7 @@ def test_the_library_names_the_closest_hit_kernel_it_launches(T):
     """trhip_closest_kernel_name: launch_trace's own decision for the scene under the context's current options — what bench.py's roofline and its PMC filter name.  The
     frame's statistics (trhip_stats.traversal) must agree with the name."""
     cases = [({}, T.scenes.mesh_scene(48), "k_trace3c4", 9), ({"wide4": 0}, T.scenes.mesh_scene(48), "k_trace3c", 9), ({}, T.scenes.cornell_scene(), "k_trace_leaf_c", 9),
+             ({"count_visits": 1}, T.scenes.mesh_scene(48), "k_trace3c4", 9),
              ({"bvh_builder": 0}, T.scenes.mesh_scene(48), "k_trace3", 3), ({"bvh_builder": 0}, T.scenes.cornell_scene(), "k_trace_leaf", 5)]
     for opts, scene, name, trav in cases:
         c = T.Context(0)
@@ -356,6 +357,8 @@ def test_the_library_names_the_closest_hit_kernel_it_launches(T):
             if name.startswith("k_trace3c"):
                 c.set_option("hybrid", 0)  # the same scene, every ray on the canonical tree
                 assert flat.closest_kernel_name() == "k_trace3"
+                integ.render(scene, c)
+                assert int(integ.stats.traversal) == 3, (opts, integ.stats.traversal)
                 c.set_option("hybrid", 1)
                 c.set_option("traversal", 1)  # the literal loop walks the canonical tree
                 assert flat.closest_kernel_name() == "k_trace_closest"

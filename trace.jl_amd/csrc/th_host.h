@@ -390,6 +390,15 @@ int build_bvh_device_sah(trhip_ctx* ctx, const std::vector<HostAABB>& pb, int ma
 int trace_grid(const trhip_ctx* ctx);
 int ensure_overflow(trhip_ctx* ctx);
 WideScene wide_view(const trhip_ctx* ctx, const trhip_scene* sc);
+// The closest-hit kernel family a launch on this scene runs (closest_kernel: the ONE place that decides it — launch_trace and launch_trace3c branch on the answer, traversal_info and
+// trhip_closest_kernel_name report it), and whether it takes its BIG variant (scenes larger than the last-level cache; the visit-counting kernels have none).  Trace3d, Trace4,
+// Trace7 and Trace8 are kernels of the EXPERIMENTS build.
+enum class ClosestKernel { Literal, Trace2, Leaf, Trace3, Trace3c, Trace3c4, LeafC, Trace3d, Trace4, Trace7, Trace8 };
+struct ClosestChoice {
+    ClosestKernel kernel;
+    bool big;
+};
+ClosestChoice closest_kernel(const trhip_ctx* ctx, const trhip_scene* sc, bool cnt, bool indirect);
 void traversal_info(const trhip_ctx* ctx, const trhip_scene* sc, uint32_t* trav, uint32_t* node_bytes);
 void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool any, SegQueue q, const float4* ro, const float4* rd, const float* tmax, TraceOut out, uint32_t* work_cursors,
                   Counters* ctr, void* overflow_slab = nullptr);
@@ -404,7 +413,7 @@ void launch_trace4(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool a
 bool hybrid_active(const trhip_ctx* ctx, const trhip_scene* sc);
 const char* hybrid_idle_reason(const trhip_ctx* ctx, const trhip_scene* sc);
 WideScene wide_view_acc(const trhip_ctx* ctx, const trhip_scene* sc);
-void launch_trace3c(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool cnt, bool full_only, bool big, const SegQueue& q, const float4* ro, const float4* rd, const float* tmax,
+void launch_trace3c(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, ClosestChoice pick, bool cnt, bool full_only, const SegQueue& q, const float4* ro, const float4* rd, const float* tmax,
                     const TraceOut& out, uint32_t* work_cursors, uint2* ov, Counters* ctr, const FallbackList& fb);
 void launch_leaf_c(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool any, bool cnt, bool full_only, const SegQueue& q, const float4* ro, const float4* rd, const float* tmax,
                    const TraceOut& out, Counters* ctr, const FallbackList& fb);

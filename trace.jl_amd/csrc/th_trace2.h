@@ -45,7 +45,8 @@ constexpr int kStack2Total = 64;
 #define TH_TRACE3_LDS_ANY 10
 #endif
 constexpr int kStack3MinLds = TH_TRACE3_LDS_CLOSEST < TH_TRACE3_LDS_ANY ? TH_TRACE3_LDS_CLOSEST : TH_TRACE3_LDS_ANY;
-constexpr int kStackMinLds = kStack2Lds < kStack3MinLds ? kStack2Lds : kStack3MinLds;  // the global overflow slab holds the levels above this
+constexpr int kStackMinLds = kStack2Lds < kStack3MinLds ? kStack2Lds : kStack3MinLds;  // the global overflow slab holds the levels above this (the walks defined after this header
+                                                                                       // — th_trace3c.h, th_trace3c4.h, th_trace4.h — assert their own LDS levels against the slab beside them)
 // levels per thread of the global overflow slab every traversal launch gets (the EXPERIMENTS build's two-rays-per-lane kernel, th_trace4.h with 8 LDS levels, needs 2 x 56)
 #ifdef TRHIP_EXPERIMENTS
 constexpr int kStackSlabLevels = (kStack2Total - kStackMinLds) > 112 ? (kStack2Total - kStackMinLds) : 112;

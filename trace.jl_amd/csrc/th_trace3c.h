@@ -77,6 +77,7 @@ namespace th {
 #ifndef TH_TRACE3C_LDS
 #define TH_TRACE3C_LDS 11
 #endif
+static_assert(kStackSlabLevels >= kStack2Total - TH_TRACE3C_LDS, "the overflow slab (th_trace2.h kStackSlabLevels) holds k_trace3c's levels above its LDS stack");
 #ifndef TH_TRACE3C_LEAF_WAIT
 #define TH_TRACE3C_LEAF_WAIT 32
 #endif
@@ -685,10 +686,8 @@ __global__ __launch_bounds__(kBlock, (BIG || (AXIS && TH_TRACE3C_AXIS_LESS)) ? T
 #ifndef TH_TRACE_LEAF_C_WAVES
 #define TH_TRACE_LEAF_C_WAVES TH_TRACE_LEAF_WAVES
 #endif
-#ifndef TH_LEAF_C_DEFER
-#define TH_LEAF_C_DEFER 2  // 1: the canonical leaf boxes are tested once per ray, for the candidate it ends up holding; 0: for every candidate as it is found (round 4); 2: 1 with the spheres in
-                           // a loop of their own and a branch-free triangle loop (round 6: S-cornell closest-hit 18.9 -> 17.65 ms per 64 spp, 17.5 -> 15.9 without the second stream; 60 VGPRs)
-#endif
+// (Two earlier bodies — the canonical leaf box tested for every candidate as it is found (round 4), and once per ray on one generic sphere / triangle candidate record — removed; last
+// present in c7463b7 as TH_LEAF_C_DEFER 0 / 1.  This one, round 6: S-cornell closest-hit 18.9 -> 17.65 ms per 64 spp, 17.5 -> 15.9 without the second stream; 60 VGPRs.)
 template <bool COUNT, bool FULL_ONLY>
 __global__ __launch_bounds__(kBlock, FULL_ONLY ? TH_TRACE_LEAF_C_WAVES : 4) void k_trace_leaf_c(DeviceScene sc /* canonical records */, WideScene ws /* root box; root_ref / root_cnt = all slots */,
                                                                               CertScene cs, SegQueue q, const float4* __restrict__ ro, const float4* __restrict__ rd,
@@ -733,12 +732,13 @@ __global__ __launch_bounds__(kBlock, FULL_ONLY ? TH_TRACE_LEAF_C_WAVES : 4) void
                 live = slab_test2(ws.root_box[0], ws.root_box[1], ws.root_box[2], ws.root_box[3], ws.root_box[4], ws.root_box[5], o, inv_d, 0.0f, false, negx, negy, negz, tmin) && tmin < t_lim;
         }
         bool found = false, sticky = false;
-#if TH_LEAF_C_DEFER == 2
-        // LEAN (round 6): the spheres first, in a loop of their own (the scene's sphere list), then the triangles in a loop whose body is the test and five selects — the generic
+        // The spheres first, in a loop of their own (the scene's sphere list), then the triangles in a loop whose body is the test and five selects — the generic
         // candidate record (one path for sphere and triangle candidates) and its lane masks cost 1.44 x k_trace_leaf's instructions per primitive (profiles/r6).  The order in
         // which candidates are met is free (header: the acceptance rule flags what the order could decide).
         uint32_t best_slot = 0u;
-        float4 best_r4 = make_float4(kInf, __int_as_float(-1), 0.0f, 0.0f);
+        float4 best_r4 = make_float4(kInf, __int_as_float(-1), 0.0f, 0.0f);  // the record the ray holds, stored once at the end (stored at every acceptance: 17.9 against 17.4 ms per 64 spp
+                                                                             // on S-cornell).  Measured and dropped (profiles/r5/r5_trace3c4_experiments.txt): the leaf-box clauses in front
+                                                                             // of every primitive (11.9 -> 4.7 tests per ray, 19.1 ms), the next slot's scalar loads issued a slot ahead (18.9 ms)
 #pragma unroll 1
         for (uint32_t ks = 0; ks < cs.n_spheres; ++ks) {
             if (__ballot(live) == 0ull) break;
@@ -802,130 +802,6 @@ __global__ __launch_bounds__(kBlock, FULL_ONLY ? TH_TRACE_LEAF_C_WAVES : 4) void
             if (!slab_test2(bx[0], bx[1], bx[2], bx[3], bx[4], bx[5], o, inv_d, 0.0f, false, negx, negy, negz, ex) || !(ex <= (sticky ? 0.0f : t_max + dt))) flagged = true;
         }
         if (valid && found && !flagged) out.hits[idx] = best_r4;
-#elif TH_LEAF_C_DEFER
-        // The leaf boxes are looked at ONCE, for the candidate the ray ends up holding (header "one-leaf accelerator"): a candidate the reference cannot reach (its own test
-        // passes, the t_max-free clauses on its leaf's box do not) may ride as the incumbent for a while — whatever it displaced or hid lies farther than what finally holds the
-        // ray, or the final check sends the ray to the reference-order walk.
-        uint32_t best_slot = 0u;
-        float4 best_r4 = make_float4(kInf, __int_as_float(-1), 0.0f, 0.0f);  // the record the ray holds, stored once at the end (stored at every acceptance: 17.9 against 17.4 ms per 64 spp
-                                                                             // on S-cornell).  Measured and dropped (profiles/r5/r5_trace3c4_experiments.txt): the leaf-box clauses in front
-                                                                             // of every primitive (11.9 -> 4.7 tests per ray, 19.1 ms), the next slot's scalar loads issued a slot ahead (18.9 ms)
-#pragma unroll 1
-        for (uint32_t k = 0; k < cnt; ++k) {
-            if (__ballot(live) == 0ull) break;
-            const uint32_t slot = first + k;  // wave-uniform: scalar loads
-            const float4 p0 = uniform_load(sc.prims, 3 * slot);
-            const uint32_t meta = __float_as_uint(p0.w);
-            float t_c = 0.0f;
-            float4 r4 = make_float4(0.0f, __int_as_float((int)slot), 0.0f, 0.0f);
-            bool cand = false, inside = false;
-            if (meta & PRIM_SPHERE) {
-                const SphereRec sr = uniform_load(sc.spheres, __float_as_uint(p0.x));
-                if (live) {
-                    if (COUNT) np++;
-                    const int r = sphere_candidate_c<FULL_ONLY>(sr, o, d, t_lim, t_c);
-                    if (r == 1 || r == 3) {
-                        cand = true;
-                        inside = r == 3;
-                        r4.x = t_c;
-                    } else if (r == 2) {
-                        flagged = true;  // a clipped sphere (or a NaN root) on the ray's line: the order decides
-                    }
-                }
-            } else if (!(meta & PRIM_DEGENERATE)) {
-                const float4 p1 = uniform_load(sc.prims, 3 * slot + 1), p2 = uniform_load(sc.prims, 3 * slot + 2);
-                if (live) {
-                    if (COUNT) np++;
-                    TriTest tt;
-                    if (tri_intersect_sheared<true>(mk3(p0.x, p0.y, p0.z), mk3(p1.x, p1.y, p1.z), mk3(p2.x, p2.y, p2.z), o, shear, t_lim, &tt)) {
-                        cand = true;
-                        t_c = tt.t;
-                        r4 = make_float4(out.bary_mode ? tt.bary.z : tt.t, __int_as_float((int)slot), tt.bary.x, tt.bary.y);
-                    }
-                }
-            } else if (COUNT && live) {
-                np++;
-            }
-            if (cand) {
-                // accepted iff it lies 2 dt below the incumbent (the ray's own t_max at first) and no sphere the ray started inside of holds the ray (that one the reference
-                // takes whatever t_max is: what it tests afterwards is the order's business)
-                if (sticky || !(t_c <= t_max - 2.0f * dt)) {
-                    flagged = true;
-                } else {
-                    t_max = t_c;
-                    t_lim = t_c + 2.0f * dt;
-                    found = true;
-                    sticky = inside;
-                    best_slot = slot;
-                    best_r4 = r4;
-                }
-            }
-            if (flagged) live = false;
-        }
-        if (valid && found && !flagged) {  // the reference reaches the holder's leaf (bounds.jl:186-198 on its box, t_max aside) and enters it by t + dt (the guard); a sphere entered from inside: its box holds the origin
-            const float* bx = cs.slot_boxes + 6 * (size_t)best_slot;
-            float ex;
-            if (COUNT) nn++;
-            if (!slab_test2(bx[0], bx[1], bx[2], bx[3], bx[4], bx[5], o, inv_d, 0.0f, false, negx, negy, negz, ex) || !(ex <= (sticky ? 0.0f : t_max + dt))) flagged = true;
-        }
-        if (valid && found && !flagged) out.hits[idx] = best_r4;
-#else
-#pragma unroll 1
-        for (uint32_t k = 0; k < cnt; ++k) {
-            if (__ballot(live) == 0ull) break;
-            const uint32_t slot = first + k;  // wave-uniform: scalar loads
-            const float4 p0 = uniform_load(sc.prims, 3 * slot);
-            const uint32_t meta = __float_as_uint(p0.w);
-            float t_c = 0.0f;
-            float4 r4 = make_float4(0.0f, __int_as_float((int)slot), 0.0f, 0.0f);
-            bool cand = false, inside = false, clipped = false;
-            if (meta & PRIM_SPHERE) {
-                const SphereRec sr = uniform_load(sc.spheres, __float_as_uint(p0.x));
-                if (live) {
-                    if (COUNT) np++;
-                    const int r = sphere_candidate_c<FULL_ONLY>(sr, o, d, t_lim, t_c);
-                    if (r == 1 || r == 3) {
-                        cand = true;
-                        inside = r == 3;
-                        r4.x = t_c;
-                    } else if (r == 2) {
-                        clipped = true;  // — but only a sphere the reference can reach at all (its leaf's t_max-free clauses) makes the order matter
-                    }
-                }
-            } else if (!(meta & PRIM_DEGENERATE)) {
-                const float4 p1 = uniform_load(sc.prims, 3 * slot + 1), p2 = uniform_load(sc.prims, 3 * slot + 2);
-                if (live) {
-                    if (COUNT) np++;
-                    TriTest tt;
-                    if (tri_intersect_sheared<true>(mk3(p0.x, p0.y, p0.z), mk3(p1.x, p1.y, p1.z), mk3(p2.x, p2.y, p2.z), o, shear, t_lim, &tt)) {
-                        cand = true;
-                        t_c = tt.t;
-                        r4 = make_float4(out.bary_mode ? tt.bary.z : tt.t, __int_as_float((int)slot), tt.bary.x, tt.bary.y);
-                    }
-                }
-            } else if (COUNT && live) {
-                np++;
-            }
-            if (__ballot(cand | clipped) != 0ull) {  // (a few primitives per ray: the box of the primitive's canonical leaf is fetched only now — wave-uniform, scalar loads)
-                const float* bx = cs.slot_boxes + 6 * (size_t)slot;
-                const float b0 = uniform_load(bx, 0), b1 = uniform_load(bx, 1), b2 = uniform_load(bx, 2), b3 = uniform_load(bx, 3), b4 = uniform_load(bx, 4), b5 = uniform_load(bx, 5);
-                float ex;
-                if (COUNT && cand) nn++;
-                if ((cand | clipped) && slab_test2(b0, b1, b2, b3, b4, b5, o, inv_d, 0.0f, false, negx, negy, negz, ex)) {  // the reference reaches this primitive's leaf at all
-                    if (clipped || sticky || !(t_c <= t_max - 2.0f * dt) || !(ex <= t_c + dt)) {
-                        flagged = true;
-                    } else {
-                        t_max = t_c;
-                        t_lim = t_c + 2.0f * dt;
-                        found = true;
-                        sticky = inside;
-                        out.hits[idx] = r4;  // stored at once (a later accepted candidate overwrites it; a flagged ray's record is rewritten by the fallback walk)
-                    }
-                }
-            }
-            if (flagged) live = false;
-        }
-#endif
         const bool to_fb = valid && flagged;
         if (__ballot(to_fb) != 0ull) {
             uint32_t fseg = __builtin_amdgcn_readfirstlane((gtid >> 6) % kSeg);

@@ -21,62 +21,33 @@ namespace th {
 #ifndef TH_TRACE3C4_WAVES
 #define TH_TRACE3C4_WAVES 5
 #endif
-#ifndef TH_TRACE3C4_FETCH_BURST
-#define TH_TRACE3C4_FETCH_BURST 1
-#endif
-// 1: phase B tests ONE primitive per lane and round (a leaf of n primitives takes n rounds; the lanes of a short leaf go back to the node steps instead of idling through the longest
-// leaf of the wave): 66.2 against 67.8 ms on S-mesh, 49.5 against 50.2 on S-blob; thresholds 24 / 40, 4 / 16 node steps per round, majority vote: 68.6 / 67.4, 66.6 / 66.2, 66.1
-// 1: a refill skips the root box test and takes 1 / d[kz] from the reciprocal direction it already holds (-35 VALU instructions per refill: 67.0 -> 65.6 ms, bit-equal)
-#ifndef TH_TRACE3C4_REFILL_LEAN
-#define TH_TRACE3C4_REFILL_LEAN 1
-#endif
-#ifndef TH_TRACE3C4_LEAF_ONE
-#define TH_TRACE3C4_LEAF_ONE 1
-#endif
+// Phase B tests ONE primitive per lane and round (a leaf of n primitives takes n rounds; the lanes of a short leaf go back to the node steps instead of idling through the longest
+// leaf of the wave): 66.2 against 67.8 ms on S-mesh, 49.5 against 50.2 on S-blob; thresholds 24 / 40, 4 / 16 node steps per round, majority vote: 68.6 / 67.4, 66.6 / 66.2, 66.1.
+// A refill skips the root box test and takes 1 / d[kz] from the reciprocal direction it already holds (-35 VALU instructions per refill: 67.0 -> 65.6 ms, bit-equal).
+// (The whole-leaf round, the refill with the root box test and the fetch without its burst were the losing halves of three switches: removed; last present in c7463b7.)
 #ifndef TH_TRACE3C4_LDS
 #define TH_TRACE3C4_LDS 12  // (13 until the top of the tree moved into LDS, TH_TRACE3C4_TOP below: 36 nodes beside 12 levels beat 18 beside 13)
 #endif
-// CONSERVATIVE steps (round 6; built, exact, SLOWER: compiled out — profiles/r6/r6_trace3c4_experiments.txt).  The certificate needs the reference's exact clauses only where a
-// LEAF is decided (th_trace3c.h header: candidates are defined by their canonical leaf's box); which boxes a walk passes through, and in which order, is free as long as (a) every
-// box that holds a candidate's leaf is entered and (b) a box is culled only on a lower bound of what it holds.  TH_TRACE3C4_CHEAP = 2 tests all four children — leaf or interior —
-// with ONE conservative slab test and moves the exact clauses to the moment a primitive test reports a hit (a ray has one or two of those; it has ~49 box tests):
-//   * per ray and axis, c_lo = -(o + em') x (1 / d) and c_hi = -(o - em') x (1 / d): one v_pk_fma_f32 per plane pair gives the slab distances of the box grown by em' per axis,
-//     em' = 2^-19 (max |o| + D): what the fused form's rounding differs from the reference's fl(fl(plane - o) x (1 / d)) by (<= 2^-24 (2 |o| + 3 D + 3 em') |1 / d|: a tenth of it);
-//   * enter iff the reference's clauses FOLDED pass (x-y entry <= every exit; the tight clause — z entry <= the earlier x-y exit, grown by em on both sides — in place of
-//     bounds.jl:194's loose half; z exit > 0 and the grown x-y exit >= 0 in place of :198) and the entry lies below t_lim + mb.  Every clause of slab_test3 implies these, for the
-//     box itself and — the slab distances are monotonic in the planes — for every box inside it; the entry distance is a lower bound of the exact one of every box inside;
-//   * a primitive test that reports a hit below the relaxed limit is a CANDIDATE only if slab_test3's clauses pass on its leaf's canonical box: verified on the triangle's OWN
-//     box (from the vertices at hand; the clauses are monotonic in the box in float arithmetic, the leaf box holds the triangle's), whose exact entry distance — an upper
-//     bound of the leaf's — is what the guard (entry <= t + dt) reads; a hit whose own box fails sends the ray to the reference-order walk.  The t-cull of the leaf itself is
-//     left to the guard: a hit below t_lim inside a box whose exact entry is >= t_lim + mb cannot be accepted, it flags the ray.
-// TH_TRACE3C4_CHEAP = 3: the same on 64-byte QUANTISED nodes (four loads instead of seven; tu_scene.hip writes them when the library is compiled this way): plane = lo + q x scale,
-// one byte per plane rounded outwards, a power-of-two scale per axis and node; one v_perm_b32 per plane dword orders each byte pair {near, far} for the ray's signs.
-// Measured: 0 film values differ in either form; S-mesh closest-hit + 0.8 % (2) / + 11 % (3), S-blob + 5 % / + 14 %: the step trades VALU issue, L1 requests and primitive tests
-// against each other one for one.  0: the exact clauses per child, shipped.
-#ifndef TH_TRACE3C4_CHEAP
-#define TH_TRACE3C4_CHEAP 0
-#endif
+static_assert(kStackSlabLevels >= kStack2Total - TH_TRACE3C4_LDS, "the overflow slab (th_trace2.h kStackSlabLevels) holds k_trace3c4's levels above its LDS stack");
+// Tried in round 6, exact, SLOWER (profiles/r6/r6_trace3c4_experiments.txt, items 1 and 7); removed; last present in c7463b7 (TH_TRACE3C4_CHEAP there):
+//   * CONSERVATIVE steps: all four children, leaf or interior, on one fused slab test (a v_pk_fma_f32 per plane pair on the box grown by the rounding slack, the reference's
+//     clauses folded), the exact clauses moved to the moment a primitive test reports a hit and verified on the triangle's own box: 0 film values differ, S-mesh closest-hit
+//     + 0.8 %, S-blob + 5 %.  Growing every clause laterally by em instead: + 12 % boxes and + 58 % primitive tests on S-mesh, + 41 % / + 183 % on S-blob;
+//   * the same on 64-byte QUANTISED nodes (four loads instead of seven; one byte per plane rounded outwards, a power-of-two scale per axis and node, one v_perm_b32 per plane
+//     dword): 0 film values differ, S-mesh + 11 %, S-blob + 14 %.
+// The step trades VALU issue, L1 requests and primitive tests against each other one for one.  What ships is the exact clauses per child.
 // The TOP of the tree in LDS (round 6).  What a step pays for its node is not the bytes but the L1's address rate: each lane reads seven 16-byte pieces of its OWN 128-byte
-// line, one tag lookup per lane and instruction — an eighth load from the same line (no new L2 traffic) costs 4.3 % of the kernel (profiles/r6: 64.9 -> 67.7 ms, the step
-// 3 756 -> 3 916 cycles, the leaf rounds 3 460 -> 3 634 as well: they share the L1).  The first TH_TRACE3C4_TOP nodes of the array — the commit numbers the tree breadth-first
-// down to there: the root, its children, their children — are copied into LDS by every block when it starts; a lane whose node is one of them, and a lane that only pops,
-// reads LDS instead (same values, same arithmetic: nothing of the certificate is touched).  LDS is allocated in units of 1 280 bytes: five blocks per CU have 32 000 bytes each
-// (32 308 — 21 nodes beside 13 stack levels — ran four blocks per CU: every phase 10 % faster, the kernel 8 % slower).
+// line, one tag lookup per lane and instruction — an eighth load from the same line (no new L2 traffic; a diagnostic build, removed; last present in c7463b7) costs 4.3 % of
+// the kernel (profiles/r6: 64.9 -> 67.7 ms, the step 3 756 -> 3 916 cycles, the leaf rounds 3 460 -> 3 634 as well: they share the L1); a refill without its arithmetic
+// (approximate reciprocals, not exact; a diagnostic build, removed likewise) gains < 1 %.  The first TH_TRACE3C4_TOP nodes of the array — the commit numbers the tree
+// breadth-first down to there: the root, its children, their children — are copied into LDS by every block when it starts; a lane whose node is one of them, and a lane that
+// only pops, reads LDS instead (same values, same arithmetic: nothing of the certificate is touched).  LDS is allocated in units of 1 280 bytes: five blocks per CU have
+// 32 000 bytes each (32 308 — 21 nodes beside 13 stack levels — ran four blocks per CU: every phase 10 % faster, the kernel 8 % slower).
 // S-mesh closest-hit per 64 spp (frames without the second stream): none 66.1, 18 nodes + 13 stack levels 64.2, 36 + 12: 63.4, 54 + 11: 63.7, 72 + 10: 63.5 ms; S-blob 47.9 / 47.3 / 47.5 / 46.9 / 47.1.
 #ifndef TH_TRACE3C4_TOP
 #define TH_TRACE3C4_TOP 36
 #endif
-
-// a x b[H] + c, two per instruction (v_pk_fma_f32; IEEE, one rounding each)
-template <int H>
-TH_D v2f pk_fma_h(v2f a, v2f b, v2f c) {
-    v2f r;
-    if (H == 0)
-        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    else
-        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
+static_assert(TH_TRACE3C4_TOP > 0, "the walk reads the top of the tree from LDS (the form without it: removed; last present in c7463b7)");
 
 template <bool COUNT, bool FULL_ONLY, bool BIG = false, bool AXIS = false>
 __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceScene sc /* prims: the accelerator's order */, WideScene ws /* the accelerator */, CertHot ch,
@@ -93,15 +64,11 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
     __shared__ uint32_t s_st[kBlock];
     __shared__ float s_ex[kBlock];
     __shared__ SegView sv;
-#if TH_TRACE3C4_TOP && TH_TRACE3C4_CHEAP == 3
-    __shared__ float4 s_top[TH_TRACE3C4_TOP * 4];  // (64-byte quantised records: four 16-byte pieces each)
-    const uint32_t n_top = min((uint32_t)TH_TRACE3C4_TOP, ws.n_w4nodes);
-    for (uint32_t i = threadIdx.x; i < n_top * 4u; i += kBlock) s_top[i] = ws.w4nodes[i];
-#elif TH_TRACE3C4_TOP
     __shared__ float4 s_top[TH_TRACE3C4_TOP * 7];
+    // LDS is allocated in units of 1 280 bytes: five blocks per CU have 32 000 bytes each (header "TOP": one block fewer per CU is 8 % of the kernel)
+    static_assert(sizeof(s_stk) + sizeof(s_top) + sizeof(s_idx) + sizeof(s_st) + sizeof(s_ex) + sizeof(SegView) <= 32000, "k_trace3c4's shared arrays no longer fit five blocks per CU");
     const uint32_t n_top = min((uint32_t)TH_TRACE3C4_TOP, ws.n_w4nodes);
     for (uint32_t i = threadIdx.x; i < n_top * 7u; i += kBlock) s_top[i] = ws.w4nodes[8u * (i / 7u) + i % 7u];  // (seg_load's barrier publishes it)
-#endif
     seg_load(q, sv);
     const uint32_t tid = threadIdx.x;
     const uint32_t gthreads = gridDim.x * kBlock;
@@ -115,15 +82,6 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
     f3 o = splat3(0.0f), inv_d = splat3(0.0f);
     float em = 0.0f;
     RayShear shear{0, 0.0f, 0.0f, 0.0f};
-#if TH_TRACE3C4_CHEAP
-    v2f cx = v2f{0.0f, 0.0f}, cy = v2f{0.0f, 0.0f}, cz = v2f{0.0f, 0.0f};  // per axis {-(o + em') / d, -(o - em') / d}: the CHEAP step's addends
-#if TH_TRACE3C4_CHEAP >= 2
-    float gxz = 0.0f, gyz = 0.0f;  // em x (|1 / d.x| + |1 / d.z|), em x (|1 / d.y| + |1 / d.z|): the tight clause's growth, both sides at once
-#endif
-#if TH_TRACE3C4_CHEAP == 3
-    uint32_t sel_xy = 0x03020100u, sel_zx = 0x03020100u, sel_yz = 0x03020100u;  // v_perm_b32 selectors: a dword's two {low plane, high plane} byte pairs in {near, far} order for this ray's signs
-#endif
-#endif
     // (the direction signs are read off inv_d where they are needed: a ray with a zero component, the one case where sign(1 / d) is not sign(d), never walks here)
 #define negx (inv_d.x < 0.0f)
 #define negy (inv_d.y < 0.0f)
@@ -262,19 +220,12 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
                             st_rec = __float_as_uint(__hip_atomic_load(recp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
                             t_rec = __hip_atomic_load(recp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         }
-#if TH_TRACE3C4_FETCH_BURST
                         asm volatile("" ::"v"(o4.x), "v"(d4.x), "v"(t_own), "v"(st_rec), "v"(t_rec));
-#endif
                         o = mk3(o4.x, o4.y, o4.z);
                         const f3 d = mk3(d4.x, d4.y, d4.z);
-#ifdef TH_DIAG_FAST_REFILL  // DIAGNOSTIC (results NOT exact): what a refill without its arithmetic would cost — approximate reciprocals, the margin from the origin's first coordinate alone
-                        inv_d = mk3(__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y), __builtin_amdgcn_rcpf(d.z));
-                        em = (fabsf(ws.root_box[3] - o.x) + fabsf(ws.root_box[0] - o.x)) * ws.tight_scale;
-#else
                         inv_d = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
                         em = slab_margin(ws.root_box, ws.tight_scale, o);
-#endif
-                        shear = TH_TRACE3C4_REFILL_LEAN ? ray_shear(d, inv_d) : ray_shear(d);
+                        shear = ray_shear(d, inv_d);
                         const float dt = margin_t();
                         const float mkz_ = (shear.kz == 0 ? ch.mle[0] : (shear.kz == 1 ? ch.mle[1] : ch.mle[2])) * fabsf(shear.sz);
                         mkz = mkz_;
@@ -286,45 +237,17 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
                         // what the certificate does not cover goes to the reference-order walk at once: a zero or non-finite direction component (0 x Inf = NaN in the slab
                         // products), a non-finite origin or margin, a NaN t_max — and near-axis-parallel rays, whose scalar margin would make the walk overshoot every hit
                         // (kCertCap; with AXIS the margin is per axis: no cap)
-#if TH_TRACE3C4_CHEAP
-                        // the CHEAP step's per-ray addends (header); reach = what a plane x (1 / d) product can be: kept far from overflow (Inf - Inf = NaN would close every box)
-                        const float o_max = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
-                        const float reach = o_max + em * uniform_load(&cold->inv_tight, 0);
-#if TH_TRACE3C4_CHEAP >= 2
-                        const float emc = 1.9073486328125e-6f * reach;  // (the fused form's rounding slack alone: the tight clause's own growth is applied where that clause is)
-                        gxz = em * fabsf(inv_d.x) + em * fabsf(inv_d.z);
-                        gyz = em * fabsf(inv_d.y) + em * fabsf(inv_d.z);
-#else
-#error "TH_TRACE3C4_CHEAP: 0 (the exact step, shipped), 2 (folded clauses + fused products) or 3 (2 on 64-byte quantised nodes)"
-#endif
-                        cx = v2f{-(o.x + emc) * inv_d.x, -(o.x - emc) * inv_d.x};
-                        cy = v2f{-(o.y + emc) * inv_d.y, -(o.y - emc) * inv_d.y};
-                        cz = v2f{-(o.z + emc) * inv_d.z, -(o.z - emc) * inv_d.z};
-#if TH_TRACE3C4_CHEAP == 3
-                        // QUANTISED nodes: the addends in {near plane, far plane} order (the step brings the plane bytes into that order with one v_perm_b32 per dword: no min / max)
-                        if (negx) cx = v2f{cx.y, cx.x};
-                        if (negy) cy = v2f{cy.y, cy.x};
-                        if (negz) cz = v2f{cz.y, cz.x};
-                        sel_xy = (negx ? 0x0001u : 0x0100u) | (negy ? 0x02030000u : 0x03020000u);
-                        sel_zx = (negz ? 0x0001u : 0x0100u) | (negx ? 0x02030000u : 0x03020000u);
-                        sel_yz = (negy ? 0x0001u : 0x0100u) | (negz ? 0x02030000u : 0x03020000u);
-#endif
-                        const bool cheap_ok = reach * inv_max() < 1e36f;
-#else
-                        const bool cheap_ok = true;
-#endif
-                        const bool plain = cheap_ok && d.x != 0.0f && d.y != 0.0f && d.z != 0.0f && mb < kInf && fabsf(o.x) < kInf && fabsf(o.y) < kInf && fabsf(o.z) < kInf && fabsf(inv_d.x) < kInf &&
+                        const bool plain = d.x != 0.0f && d.y != 0.0f && d.z != 0.0f && mb < kInf && fabsf(o.x) < kInf && fabsf(o.y) < kInf && fabsf(o.z) < kInf && fabsf(inv_d.x) < kInf &&
                                            fabsf(inv_d.y) < kInf && fabsf(inv_d.z) < kInf && t_own == t_own && (AXIS || mb - mkz_ <= kCertCap * mkz_ + dt);
-                        float tmin = 0.0f;
                         if (!plain) {
                             to_fb = true;
                             active = false;
                             if (COUNT) n_why[0]++;
-                        } else if (ws.root_ref != kRefNone && (TH_TRACE3C4_REFILL_LEAN || slab_test2(ws.root_box[0], ws.root_box[1], ws.root_box[2], ws.root_box[3], ws.root_box[4], ws.root_box[5], o, inv_d, em, false, negx, negy, negz, tmin))) {
-                            // (REFILL_LEAN: the root box (bvh.jl:226) is not tested — the root of a four-wide tree is interior, each of its children's boxes lies inside it and every clause is
+                        } else if (ws.root_ref != kRefNone) {
+                            // (the root box (bvh.jl:226) is not tested — the root of a four-wide tree is interior, each of its children's boxes lies inside it and every clause is
                             // monotonic in the box: a ray that fails the root fails all four children in its first step)
                             cur = ws.root_ref | (ws.root_cnt << 24);  // (the root is not culled by t: the reference's clause `tmin < t_max` holds whenever anything inside can be accepted)
-                            s_ex[tid] = tmin;
+                            s_ex[tid] = 0.0f;
                             // the sphere pre-pass of the chunk left this ray's state in its hit record: an accepted sphere (the incumbent), the sphere it starts inside of, or
                             // "to the reference-order walk"
                             bool flagged = false;
@@ -358,12 +281,8 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
         // ---- phase A: interior steps and pops; lanes holding a leaf wait (k_trace3's schedule).  A lane WITHOUT a node (both children failed and the stack top was dead, a leaf
         //      that left a dead top) takes part in the step's tail instead of a pop section of its own: the tail reads the stack top anyway (k_trace3's in-step pop) — one entry per
         //      round, dead ones dropped; what is left of the pop section is the delivery of the rays whose stack is empty ----
-#if TH_TRACE3C4_LEAF_ONE
         // (phase B tests ONE primitive per lane and round: a round goes to the side most lanes wait on)
         const bool run_a = (uint32_t)__popcll(__ballot(active && (cur < kLeafBit || cur == kRefNone))) > (uint32_t)TH_TRACE3C_LEAF_WAIT || __ballot(active && cur >= kLeafBit && cur != kRefNone) == 0ull;
-#else
-        const bool run_a = true;
-#endif
 #pragma unroll 1
         for (int it = 0; run_a && it < TH_TRACE3C_MAX_A; ++it) {
 #ifdef TH_DIAG_PHASES
@@ -390,21 +309,6 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
             if (stepping || (active && cur == kRefNone)) {
                 // interior: one 128-byte line, four child boxes.  Every lane of the section loads — a lane that only pops reads the root's line (always cached) and ignores it: loads under
                 // `if (stepping)` into zero-initialised registers cost 28 v_mov per step (the compiler keeps the zeros alive across the stack-top read between the loads and their use)
-#if TH_TRACE3C4_CHEAP == 3
-                // QUANTISED node: 64 bytes = four loads {lo.xyz, scale.x | 16 plane bytes | 8 plane bytes, scale.yz | four child words} (tu_scene.hip upload_accelerator)
-                float4 a0, a1, a2, a6;
-                const uint32_t ncur = stepping ? cur : 0u;
-#if TH_TRACE3C4_TOP
-                if (ncur < n_top) {
-                    const float4* tp = s_top + 4u * ncur;
-                    a0 = tp[0], a1 = tp[1], a2 = tp[2], a6 = tp[3];
-                } else
-#endif
-                {
-                    const float4* np = ws.w4nodes + 4 * (size_t)ncur;
-                    a0 = np[0], a1 = np[1], a2 = np[2], a6 = np[3];
-                }
-#elif TH_TRACE3C4_TOP
                 // a node of the top of the tree, and the placeholder of a lane that only pops, from LDS (header "TOP"); both sides of the branch define all seven values
                 float4 a0, a1, a2, a3, a4, a5, a6;
                 const uint32_t ncur = stepping ? cur : 0u;
@@ -415,16 +319,6 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
                     const float4* np = ws.w4nodes + 8 * (size_t)ncur;
                     a0 = np[0], a1 = np[1], a2 = np[2], a3 = np[3], a4 = np[4], a5 = np[5], a6 = np[6];
                 }
-#else
-                const float4* np = ws.w4nodes + 8 * (size_t)(stepping ? cur : 0u);
-                const float4 a0 = np[0], a1 = np[1], a2 = np[2], a3 = np[3], a4 = np[4], a5 = np[5], a6 = np[6];
-#endif
-#if defined(TH_TRACE3C4_DUMMY_LOAD) && !TH_TRACE3C4_TOP  // DIAGNOSTIC: an eighth 16-byte load from the same line (no new L2 traffic): does the step pay for the L1's address rate?
-                {
-                    const float4 a7 = np[7];
-                    asm volatile("" ::"v"(a7.x), "v"(a7.y), "v"(a7.z), "v"(a7.w));
-                }
-#endif
                 uint32_t top_enc = kRefNone;
                 float top_tm = kInf;
                 if (sp > 0) {
@@ -445,57 +339,6 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
                 if (stepping) {
                     if (COUNT) nn += 4;
                     const float t_push = t_lim + mkz;  // (AXIS: the per-axis form of the bound, against the entry distance of the box grown by growth — launches whose rays start far outside the scene)
-#if TH_TRACE3C4_CHEAP == 3
-                    const float grow = AXIS ? growth() : 0.0f;
-                    const float ax_x = grow * fabsf(inv_d.x), ax_y = grow * fabsf(inv_d.y), ax_z = grow * fabsf(inv_d.z);
-                    // plane = lo + q x scale (q: one byte, rounded outwards at commit), so its slab distance is q x (scale / d) + ((lo - o -+ em') / d): per node three products and three
-                    // fused pairs, per plane pair two byte conversions and one fused pair — after one v_perm_b32 per dword has put each byte pair into {near, far} order for this ray
-                    const v2f i_xy = v2f{inv_d.x, inv_d.y}, i_z = v2f{inv_d.z, inv_d.z};
-                    const v2f S_xy = v2f{a0.w * inv_d.x, a2.z * inv_d.y}, S_z = v2f{a2.w * inv_d.z, 0.0f};
-                    const v2f Cx = pk_fma_h<0>(v2f{a0.x, a0.x}, i_xy, cx), Cy = pk_fma_h<1>(v2f{a0.y, a0.y}, i_xy, cy), Cz = pk_fma_h<0>(v2f{a0.z, a0.z}, i_z, cz);
-                    const uint32_t d0 = __builtin_amdgcn_perm(__float_as_uint(a1.x), __float_as_uint(a1.x), sel_xy), d1 = __builtin_amdgcn_perm(__float_as_uint(a1.y), __float_as_uint(a1.y), sel_zx),
-                                   d2 = __builtin_amdgcn_perm(__float_as_uint(a1.z), __float_as_uint(a1.z), sel_yz), d3 = __builtin_amdgcn_perm(__float_as_uint(a1.w), __float_as_uint(a1.w), sel_xy),
-                                   d4 = __builtin_amdgcn_perm(__float_as_uint(a2.x), __float_as_uint(a2.x), sel_zx), d5 = __builtin_amdgcn_perm(__float_as_uint(a2.y), __float_as_uint(a2.y), sel_yz);
-                    auto lo_pair = [](uint32_t dw) { return v2f{(float)(dw & 0xffu), (float)((dw >> 8) & 0xffu)}; };       // v_cvt_f32_ubyte0 / 1
-                    auto hi_pair = [](uint32_t dw) { return v2f{(float)((dw >> 16) & 0xffu), (float)(dw >> 24)}; };          // v_cvt_f32_ubyte2 / 3
-                    // one child, leaf or interior: {near, far} slab distances per axis, the folded clauses of CHEAP = 2 (header); an empty slot (child word kRefNone) is never entered
-                    auto child = [&](v2f qx, v2f qy, v2f qz, uint32_t word) {
-                        const v2f Tx = pk_fma_h<0>(qx, S_xy, Cx), Ty = pk_fma_h<1>(qy, S_xy, Cy), Tz = pk_fma_h<0>(qz, S_z, Cz);
-                        const float nx = Tx.x, fx = Tx.y, ny = Ty.x, fy = Ty.y, nz = Tz.x, fz = Tz.y;
-                        const float A = amax(nx, ny), t_out = amin3(fx, fy, fz), t_in = amax(A, nz);
-                        const float Bp = amin(fx + gxz, fy + gyz);
-                        bool enter = (A <= t_out) && (nz <= Bp) && (fz > 0.0f) && (Bp >= 0.0f) && (t_in < t_pop) && (word != kRefNone);
-                        if constexpr (AXIS) enter = enter && (amax3(nx - ax_x, ny - ax_y, nz - ax_z) < t_push);
-                        return enter ? t_in : kInf;
-                    };
-                    uint32_t e0 = __float_as_uint(a6.x), e1 = __float_as_uint(a6.y), e2 = __float_as_uint(a6.z), e3 = __float_as_uint(a6.w);
-                    float k0 = child(lo_pair(d0), hi_pair(d0), lo_pair(d1), e0);
-                    float k1 = child(hi_pair(d1), lo_pair(d2), hi_pair(d2), e1);
-                    float k2 = child(lo_pair(d3), hi_pair(d3), lo_pair(d4), e2);
-                    float k3 = child(hi_pair(d4), lo_pair(d5), hi_pair(d5), e3);
-#else
-#if TH_TRACE3C4_CHEAP
-                    const float grow = AXIS ? growth() : 0.0f;
-                    const float ax_x = grow * fabsf(inv_d.x), ax_y = grow * fabsf(inv_d.y), ax_z = grow * fabsf(inv_d.z);
-                    const v2f i_xy = v2f{inv_d.x, inv_d.y}, i_z = v2f{inv_d.z, inv_d.z};
-                    // one child, leaf or interior: the slab distances of its box grown by em' (one fused instruction per plane pair), the standard overlap test; the sort key is a lower
-                    // bound of the exact entry distance of everything inside (header "CHEAP").  An empty slot's NaN planes fail every comparison.
-                    auto child = [&](v2f X, v2f Y, v2f Z) {
-                        const v2f Tx = pk_fma_h<0>(X, i_xy, cx), Ty = pk_fma_h<1>(Y, i_xy, cy), Tz = pk_fma_h<0>(Z, i_z, cz);
-                        const float nx = amin(Tx.x, Tx.y), fx = amax(Tx.x, Tx.y), ny = amin(Ty.x, Ty.y), fy = amax(Ty.x, Ty.y), nz = amin(Tz.x, Tz.y), fz = amax(Tz.x, Tz.y);
-#if TH_TRACE3C4_CHEAP >= 2
-                        // the reference's clauses FOLDED (x-y entry <= every exit: bounds.jl:188 and the first half of :194) on the box grown by the rounding slack, the tight
-                        // clause (z entry <= the earlier x-y exit, grown by em on both sides) in place of :194's loose half, z exit > 0 and the grown x-y exit >= 0 in place of :198:
-                        // each is implied by slab_test3 passing on the box or on any box inside it; visits as the exact clauses' (the lateral growth of CHEAP = 1 cost + 12 % boxes and
-                        // + 58 % primitive tests on S-mesh, + 41 % / + 183 % on S-blob: profiles/r6)
-                        const float A = amax(nx, ny), t_out = amin3(fx, fy, fz), t_in = amax(A, nz);
-                        const float Bp = amin(fx + gxz, fy + gyz);
-                        bool enter = (A <= t_out) && (nz <= Bp) && (fz > 0.0f) && (Bp >= 0.0f) && (t_in < t_pop);
-#endif
-                        if constexpr (AXIS) enter = enter && (amax3(nx - ax_x, ny - ax_y, nz - ax_z) < t_push);
-                        return enter ? t_in : kInf;
-                    };
-#else
                     const v2f p_a = v2f{o.x, o.y}, p_b = v2f{o.z, inv_d.x}, p_c = v2f{inv_d.y, inv_d.z};
                     const float gx = em * fabsf(inv_d.x), gy = em * fabsf(inv_d.y), gz = em * fabsf(inv_d.z);
                     const float grow = AXIS ? growth() : 0.0f;
@@ -519,13 +362,11 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
                         if constexpr (AXIS) enter = enter && (amax3(nx - ax_x, ny - ax_y, nz - ax_z) < t_push);
                         return enter ? t_in : kInf;
                     };
-#endif
                     float k0 = child(v2f{a0.x, a0.y}, v2f{a0.z, a0.w}, v2f{a1.x, a1.y});
                     float k1 = child(v2f{a1.z, a1.w}, v2f{a2.x, a2.y}, v2f{a2.z, a2.w});
                     float k2 = child(v2f{a3.x, a3.y}, v2f{a3.z, a3.w}, v2f{a4.x, a4.y});
                     float k3 = child(v2f{a4.z, a4.w}, v2f{a5.x, a5.y}, v2f{a5.z, a5.w});
                     uint32_t e0 = __float_as_uint(a6.x), e1 = __float_as_uint(a6.y), e2 = __float_as_uint(a6.z), e3 = __float_as_uint(a6.w);
-#endif  // TH_TRACE3C4_CHEAP == 3
                     // nearest first (a five-comparator network on {key, child word}); a child that is not entered sorts last
 #define TH_CSWAP(ka, kb, ea, eb)              \
     {                                         \
@@ -568,11 +409,7 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
                         ex_new = top_tm;
                     }
                 }
-#if !TH_TRACE3C4_CHEAP
                 s_ex[tid] = ex_new;
-#else
-                (void)ex_new;
-#endif
             }
 #ifdef TH_DIAG_PHASES
             ph_cyc[2] += __builtin_readcyclecounter() - ph_t_node;
@@ -592,7 +429,7 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
             const uint32_t leaf_ref = cur & 0x00ffffffu, leaf_cnt = cur >> 24;
             uint32_t top_enc = kRefNone;
             float top_tm = kInf;
-            if (sp > 0 && (!TH_TRACE3C4_LEAF_ONE || leaf_cnt == 1u)) {
+            if (sp > 0 && leaf_cnt == 1u) {  // (the last primitive of the leaf: the round ends in a pop)
                 if (sp - 1 < kLds) {
                     const uint2 e = s_stk[sp - 1][tid];
                     top_enc = e.x;
@@ -605,7 +442,9 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
             }
             // (requesting primitive k + 1's records before primitive k is tested — one round trip per leaf instead of one per primitive — costs 12 live registers and measured 74.7 against
             // 67.8 ms: the kernel is VALU-bound at 97 % busy, the latency was already hidden)
-            for (uint32_t k = 0; k < (TH_TRACE3C4_LEAF_ONE ? 1u : leaf_cnt); ++k) {
+            // ONE primitive per round: the first of what is left of the leaf.  (A loop of one trip: as straight-line code the compiler lays the round out differently, ten instructions
+            // more per kernel; the form of c7463b7, where the whole-leaf round set the trip count, keeps the device code bit for bit.)
+            for (uint32_t k = 0; k < 1u; ++k) {
                 const uint32_t slot = leaf_ref + k;
                 const float4 p0 = sc.prims[3 * slot];
                 const float4 p1 = sc.prims[3 * slot + 1], p2 = sc.prims[3 * slot + 2];
@@ -625,34 +464,11 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
                         const bool second = (ow & 4u) != 0u;  // the primitive sits in the second child there (axis 3: in the sphere's own leaf, behind it)
                         counts = ax == 3u ? second : (second != (ax == 0u ? negx : (ax == 1u ? negy : negz)));  // bvh.jl:239-246: the second child is visited first iff d[axis] < 0
                     }
-#if TH_TRACE3C4_CHEAP
-                    // the step let this leaf in on the conservative test: the hit is a candidate only if the reference's clauses pass on its leaf's canonical box (header
-                    // "CHEAP").  They are evaluated on the TRIANGLE's own box, from the vertices at hand — no load: the leaf box holds it, and every clause of slab_test3 is
-                    // monotonic in the box IN FLOAT ARITHMETIC (fl(fl(plane - o) x (1 / d)) is a monotonic function of the plane; so are fl(far + g) and fl(near - g)): passing
-                    // on the triangle's box implies passing on the leaf's, and the leaf's exact entry distance is <= the triangle box's, which the guard reads.  A hit whose own
-                    // box fails (the ray grazes it within rounding) says nothing about the leaf box: the ray goes to the reference-order walk.
-                    float ex_leaf = 0.0f;
-                    bool unverified = false;
-                    if (counts) {
-                        const v2f bx = v2f{amin3(p0.x, p1.x, p2.x), amax3(p0.x, p1.x, p2.x)}, by = v2f{amin3(p0.y, p1.y, p2.y), amax3(p0.y, p1.y, p2.y)}, bz = v2f{amin3(p0.z, p1.z, p2.z), amax3(p0.z, p1.z, p2.z)};
-                        const v2f p_a = v2f{o.x, o.y}, p_b = v2f{o.z, inv_d.x}, p_c = v2f{inv_d.y, inv_d.z};
-                        const v2f Tx = pk_mul_h<1>(pk_sub_h<0>(bx, p_a), p_b), Ty = pk_mul_h<0>(pk_sub_h<1>(by, p_a), p_c), Tz = pk_mul_h<1>(pk_sub_h<0>(bz, p_b), p_c);
-                        const float nx = amin(Tx.x, Tx.y), fx = amax(Tx.x, Tx.y), ny = amin(Ty.x, Ty.y), fy = amax(Ty.x, Ty.y), nz = amin(Tz.x, Tz.y), fz = amax(Tz.x, Tz.y);
-                        const float a = amax(nx, ny), b = amax(fx, fy);        // bounds.jl:189-190
-                        ex_leaf = amax(a, nz);                                 // :196
-                        const float t_out = amin(fz, b);                       // :197
-                        const bool ref = !(nx > fy) && !(ny > fx) && !(a > fz) && !(nz > b) && (t_out > 0.0f);  // :188, :194, :198
-                        const float exit_xy = amin(fx + em * fabsf(inv_d.x), fy + em * fabsf(inv_d.y));
-                        unverified = !(ref && !(nz - em * fabsf(inv_d.z) > exit_xy) && !(exit_xy < 0.0f));
-                    }
-#else
                     const float ex_leaf = s_ex[tid];
-                    const bool unverified = false;
-#endif
                     if (counts) {
                         const float dt = margin_t();
                         // accepted iff it lies 2 dt below the incumbent (t_lim - 4 dt; the ray's own t_max at first) AND its leaf box lets the reference in by t + dt (the guard); a NaN fails
-                        if (unverified || !(tt.t <= t_lim - 4.0f * dt) || !(ex_leaf <= tt.t + dt)) {
+                        if (!(tt.t <= t_lim - 4.0f * dt) || !(ex_leaf <= tt.t + dt)) {
                             if (COUNT && !flagged) why = 2u;
                             flagged = true;
                         } else if (!flagged) {
@@ -663,7 +479,7 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
                     }
                 }
             }
-            cur = (TH_TRACE3C4_LEAF_ONE && !flagged && leaf_cnt > 1u) ? ((leaf_ref + 1u) | ((leaf_cnt - 1u) << 24)) : kRefNone;  // LEAF_ONE: the rest of the leaf in the next rounds
+            cur = (!flagged && leaf_cnt > 1u) ? ((leaf_ref + 1u) | ((leaf_cnt - 1u) << 24)) : kRefNone;  // the rest of the leaf in the next rounds
             if (cur != kRefNone) {
             } else if (flagged) {  // the reference-order walk decides this ray
                 active = false;
@@ -675,9 +491,7 @@ __global__ __launch_bounds__(kBlock, TH_TRACE3C4_WAVES) void k_trace3c4(DeviceSc
                 const float t_pop = t_lim + mb;  // (mb holds the growth term in either form: the step's own t_pop)
                 if (top_tm < t_pop && sp < kStack2Total) {
                     cur = top_enc;
-#if !TH_TRACE3C4_CHEAP
                     s_ex[tid] = top_tm;
-#endif
                 }
             }
         }

@@ -38,68 +38,59 @@ WideScene wide_view(const trhip_ctx* ctx, const trhip_scene* sc) {
 }
 
 // k_trace8 takes the launch (traversal 4) only with the tight slab clauses on and a single pipeline; otherwise k_trace3 walks the 32-byte boxes.
-// One place for the rule: launch_trace and the byte model of trhip_stats (traversal_info) must agree.
 #ifdef TRHIP_EXPERIMENTS
+static constexpr bool kExperimentsBuild = true;
 static bool uses_trace8(const trhip_ctx* ctx, const trhip_scene* sc) { return ctx->traversal == 4 && sc->w8_ok && ctx->slab_margin_log2 > 0 && ctx->pipelines <= 1; }
-#else  // traversals 4, 6, 7, leaf_sorted, leaf_queue: kernels of the EXPERIMENTS build (trhip_set_option refuses them here)
-static bool uses_trace8(const trhip_ctx*, const trhip_scene*) { return false; }
-#endif
-
 // k_trace7 (traversal 7) takes the closest-hit launches of scenes with a hierarchy when the tight slab clauses are on (its margins derive from them)
-#ifdef TRHIP_EXPERIMENTS
 static bool uses_trace7(const trhip_ctx* ctx, const trhip_scene* sc) { return ctx->traversal == 7 && sc->wide_ok && sc->wide.root_cnt == 0 && ctx->slab_margin_log2 > 0 && ctx->pipelines <= 1; }
-#else
+#else  // traversals 4, 6, 7, leaf_sorted, leaf_queue: kernels of the EXPERIMENTS build (trhip_set_option refuses them here)
+static constexpr bool kExperimentsBuild = false;
+static bool uses_trace8(const trhip_ctx*, const trhip_scene*) { return false; }
 static bool uses_trace7(const trhip_ctx*, const trhip_scene*) { return false; }
 #endif
 
-#ifdef TRHIP_EXPERIMENTS
-static constexpr bool kExperimentsBuild = true;
-#else
-static constexpr bool kExperimentsBuild = false;
-#endif
-// which kernel launch_trace picks for this scene, and the bytes one unit of the visit counters stands for (trhip_stats)
-void traversal_info(const trhip_ctx* ctx, const trhip_scene* sc, uint32_t* trav, uint32_t* node_bytes) {
-    uint32_t t = 1, nb = 32;
-    if (hybrid_active(ctx, sc)) {
-        *trav = 9;  // the certified walk on the accelerator tree + the reference-order walk of the flagged rays on the canonical tree (th_trace3c.h)
-        *node_bytes = sc->wide_acc.root_cnt > 0 ? 0 : 32;
-        return;
-    }
-    if (ctx->traversal >= 2 && sc->wide_ok) {
-        if (sc->wide.root_cnt > 0 && ctx->leaf_kernel && ctx->debug_trace_budget == 0) {
-            t = 5;
-            nb = 0;
-        } else if (sc->wide.root_cnt > 0) {
-            t = 2;
-        } else if (uses_trace8(ctx, sc)) {
-            t = 4;
-            nb = 96;
-        } else if (ctx->traversal == 6) {
-            t = 6;
-        } else if (uses_trace7(ctx, sc)) {
-            t = 7;
-        } else {
-            t = ctx->traversal >= 3 ? 3 : 2;
-        }
-    }
-    *trav = t;
-    *node_bytes = nb;
+// scenes larger than the last-level cache (256 MB of MALL) walk with one wave per SIMD fewer (the BIG variants): 64 bytes per node, 48 per primitive
+static bool exceeds_llc(uint32_t n_wnodes, uint32_t n_prims) { return (size_t)n_wnodes * 64u + (size_t)n_prims * 48u > ((size_t)256 << 20); }
+
+// closest-hit rays on the canonical tree alone: scenes without an accelerator, options that leave it idle, indirect queues, and a hybrid launch whose lists could not be allocated
+static ClosestChoice canonical_kernel(const trhip_ctx* ctx, const trhip_scene* sc, bool cnt) {
+    if (!(ctx->traversal >= 2 && sc->wide_ok)) return {ClosestKernel::Literal, false};
+    if (sc->wide.root_cnt > 0)  // a single-leaf scene has nothing to postpone
+        return {ctx->leaf_kernel && ctx->debug_trace_budget == 0 ? ClosestKernel::Leaf : ClosestKernel::Trace2, false};
+    if (ctx->traversal == 2) return {ClosestKernel::Trace2, false};
+    if (ctx->traversal == 6 && kExperimentsBuild) return {ClosestKernel::Trace4, false};
+    const bool big = !cnt && exceeds_llc(sc->wide.n_wnodes, sc->dev.n_prims);  // (k_trace7 and k_trace8 hand rays back to k_trace3: their BIG is its)
+    return {uses_trace8(ctx, sc) ? ClosestKernel::Trace8 : (uses_trace7(ctx, sc) ? ClosestKernel::Trace7 : ClosestKernel::Trace3), big};
 }
 
-// The name of the kernel a closest-hit launch on this scene runs under the context's CURRENT options (launch_trace's own decisions, restated in one place for the
-// measurement side: a profile filter or a roofline must name the kernel that ran, not the one the option string suggests).
+ClosestChoice closest_kernel(const trhip_ctx* ctx, const trhip_scene* sc, bool cnt, bool indirect) {
+    if (!hybrid_active(ctx, sc) || indirect) return canonical_kernel(ctx, sc, cnt);
+    // the certified walk on the accelerator tree; the rays it flags go through k_trace3 on the canonical tree right after (th_trace3c.h)
+    if (sc->wide_acc.root_cnt > 0) return {ClosestKernel::LeafC, false};
+    const bool big = !cnt && exceeds_llc(sc->wide_acc.n_wnodes, sc->dev.n_prims);
+    if (kExperimentsBuild && ctx->leaf_queue && !big) return {ClosestKernel::Trace3d, false};  // option "leaf_queue": the same walk with queued leaves (th_trace3d.h)
+    return {ctx->wide4 && sc->wide_acc.w4nodes ? ClosestKernel::Trace3c4 : ClosestKernel::Trace3c, big};  // four children wide (th_trace3c4.h): one form for every launch
+}
+
+// per kernel family: its name, the value of trhip_stats.traversal, and the bytes one unit of the visit counters stands for (ClosestKernel's order)
+static const struct {
+    const char* name;
+    uint32_t trav, node_bytes;
+} kClosestInfo[] = {{"k_trace_closest", 1, 32}, {"k_trace2", 2, 32},   {"k_trace_leaf", 5, 0}, {"k_trace3", 3, 32}, {"k_trace3c", 9, 32}, {"k_trace3c4", 9, 32},
+                    {"k_trace_leaf_c", 9, 0},   {"k_trace3d", 9, 32},  {"k_trace4", 6, 32},    {"k_trace7", 7, 32}, {"k_trace8", 4, 96}};
+
+// which kernel launch_trace picks for this scene under the context's current options, as trhip_stats reports it
+void traversal_info(const trhip_ctx* ctx, const trhip_scene* sc, uint32_t* trav, uint32_t* node_bytes) {
+    const auto& info = kClosestInfo[(int)closest_kernel(ctx, sc, ctx->count_visits, false).kernel];
+    *trav = info.trav;
+    *node_bytes = info.node_bytes;
+}
+
+// The name of the kernel a closest-hit launch on this scene runs under the context's CURRENT options (a profile filter or a roofline must name the kernel that ran, not the one
+// the option string suggests).
 extern "C" __attribute__((visibility("default"))) int trhip_closest_kernel_name(const trhip_ctx* ctx, const trhip_scene* sc, char* buf, size_t n) {
     if (!ctx || !sc || !buf || !n) return TRHIP_ERR_INVALID;
-    const char* name = "k_trace_closest";
-    if (hybrid_active(ctx, sc)) {
-        name = sc->wide_acc.root_cnt > 0 ? "k_trace_leaf_c" : ((ctx->wide4 && sc->wide_acc.w4nodes && !(kExperimentsBuild && ctx->leaf_queue)) ? "k_trace3c4" : (kExperimentsBuild && ctx->leaf_queue ? "k_trace3d" : "k_trace3c"));
-    } else {
-        uint32_t t = 1, nb = 0;
-        traversal_info(ctx, sc, &t, &nb);
-        static const char* const kNames[] = {"k_trace_closest", "k_trace_closest", "k_trace2", "k_trace3", "k_trace8", "k_trace_leaf", "k_trace4", "k_trace7"};
-        name = kNames[t < 8 ? t : 0];
-    }
-    std::snprintf(buf, n, "%s", name);
+    std::snprintf(buf, n, "%s", kClosestInfo[(int)closest_kernel(ctx, sc, ctx->count_visits, false).kernel].name);
     return 0;
 }
 
@@ -108,14 +99,15 @@ extern "C" __attribute__((visibility("default"))) int trhip_closest_kernel_name(
 void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool any, SegQueue q, const float4* ro, const float4* rd, const float* tmax, TraceOut out, uint32_t* work_cursors,
                   Counters* ctr, void* overflow_slab) {
     const dim3 grid(trace_grid(ctx)), block(kBlock);
-    const bool v2 = ctx->traversal >= 2 && sc->wide_ok;
     const bool cnt = ctx->count_visits;
     const bool full_only = !sc->partial_spheres;  // no clipped sphere in the scene: kernels without the Float64 atan2 path
+    ClosestChoice pick = closest_kernel(ctx, sc, cnt, q.indirect != nullptr);  // (any-hit rays take the same family's any-hit kernel, where it has one)
+    const bool certified = pick.kernel == ClosestKernel::LeafC || pick.kernel == ClosestKernel::Trace3c || pick.kernel == ClosestKernel::Trace3c4 || pick.kernel == ClosestKernel::Trace3d;
     // ---- hybrid mode (th_trace3c.h): the scene holds the canonical tree (the reference's construction / the host's own) AND the library's tree as an accelerator.
     //      Closest-hit rays walk the accelerator with the order-independence certificate; the rays it flags come back on fallback lists that k_trace3 walks on the
     //      canonical tree right after.  Any-hit rays of a one-leaf accelerator likewise (only rays with a zero direction component need the canonical tree); any-hit
     //      rays of a hierarchy take the canonical path below (pre-pass on the largest triangles + k_trace3 on the canonical tree).
-    if (hybrid_active(ctx, sc) && !q.indirect && (!any || sc->wide_acc.root_cnt > 0)) {
+    if (certified && (!any || pick.kernel == ClosestKernel::LeafC)) {
         const int w = any ? 1 : 0;
         const uint32_t fcap = q.counts ? q.cap : (q.n_dense + kSeg - 1) / kSeg;
         const size_t ctr_words = 2 * (size_t)kSeg * kCtrStride;  // counts, then the work cursors of the fallback launch
@@ -124,23 +116,21 @@ void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool an
             (void)hipMemsetAsync(fcounts, 0, ctr_words * sizeof(uint32_t), st);
             const FallbackList fb{(uint32_t*)ctx->fb_list[w].p, fcounts, fcap};
             uint2* ov = (uint2*)(overflow_slab ? overflow_slab : ctx->overflow.p);
-            const size_t canon_bytes = (size_t)sc->wide.n_wnodes * 64u + (size_t)sc->dev.n_prims * 48u;
-            if (sc->wide_acc.root_cnt > 0) {
+            if (pick.kernel == ClosestKernel::LeafC)
                 launch_leaf_c(ctx, st, sc, any, cnt, full_only, q, ro, rd, tmax, out, ctr, fb);
-            } else {
-                const bool big = !cnt && (size_t)sc->wide_acc.n_wnodes * 64u + (size_t)sc->dev.n_prims * 48u > ((size_t)256 << 20);
-                launch_trace3c(ctx, st, sc, cnt, full_only, big, q, ro, rd, tmax, out, work_cursors, ov, ctr, fb);
-            }
+            else
+                launch_trace3c(ctx, st, sc, pick, cnt, full_only, q, ro, rd, tmax, out, work_cursors, ov, ctr, fb);
             // the flagged rays, in the reference's order on the canonical tree (already counted: no_total)
             const SegQueue fq{fcounts, fcap, 0u, fb.list, 1u};
             if (!any && ctx->active_timer) ctx->active_timer->mark_fallback(st);
             if (!any && cnt && ctr) hipLaunchKernelGGL(k_hybrid_count_mark, dim3(1), dim3(1), 0, st, ctr, 0);
-            launch_trace3(ctx, st, sc, any, cnt, full_only, !any && !cnt && canon_bytes > ((size_t)256 << 20), fq, ro, rd, tmax, out, fcounts + (size_t)kSeg * kCtrStride, ov, ctr);
+            launch_trace3(ctx, st, sc, any, cnt, full_only, !any && !cnt && exceeds_llc(sc->wide.n_wnodes, sc->dev.n_prims), fq, ro, rd, tmax, out, fcounts + (size_t)kSeg * kCtrStride, ov, ctr);
             if (!any && cnt && ctr) hipLaunchKernelGGL(k_hybrid_count_mark, dim3(1), dim3(1), 0, st, ctr, 1);
             return;
         }
     }
-    if (v2 && ctx->traversal >= 3 && sc->wide.root_cnt == 0) {  // k_trace8 / k_trace3; a single-leaf scene has nothing to postpone and runs k_trace_leaf / k_trace2
+    if (certified) pick = canonical_kernel(ctx, sc, cnt);  // any-hit rays of a hierarchy; a launch whose fallback lists could not be allocated
+    if (pick.kernel == ClosestKernel::Trace3 || pick.kernel == ClosestKernel::Trace4 || pick.kernel == ClosestKernel::Trace7 || pick.kernel == ClosestKernel::Trace8) {
         uint2* ov = (uint2*)(overflow_slab ? overflow_slab : ctx->overflow.p);
         if (any && sc->n_occluders && ctx->occluder_pretest && ctx->pipelines <= 1 && !q.indirect) {
             // the largest triangles first (k_any_occluders); what they do not stop goes through per-segment survivor lists
@@ -163,7 +153,7 @@ void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool an
         }
 #ifdef TRHIP_EXPERIMENTS
         // ---- traversal 4: 8-wide nodes (th_trace8.h); the rays it does not take come back on a fallback list that k_trace3 walks below ----
-        if (uses_trace8(ctx, sc)) {
+        if (pick.kernel == ClosestKernel::Trace8) {
             const int w = any ? 1 : 0;
             const uint32_t fcap = q.counts ? q.cap : q.n_dense;
             const size_t entries = (size_t)fcap * (q.counts ? kSeg : 1);
@@ -183,7 +173,7 @@ void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool an
         }
         // ---- traversal 7: closest-hit rays front to back (th_trace7.h); the rays whose answer depends on the visiting order come back on ONE fallback list
         //      (segment 0 of a SegQueue whose other segments are empty) that k_trace3 walks below ----
-        if (!any && uses_trace7(ctx, sc) && !q.indirect) {
+        if (!any && pick.kernel == ClosestKernel::Trace7 && !q.indirect) {
             // kSeg lists of `fcap` entries: together as many as the queue holds rays (a wave whose list is full moves on to the next one)
             const uint32_t fcap = q.counts ? q.cap : (q.n_dense + kSeg - 1) / kSeg;
             const size_t ctr_words = 2 * (size_t)kSeg * kCtrStride;  // counts, then the work cursors of the fallback launch
@@ -191,19 +181,17 @@ void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool an
                 uint32_t* fcounts = (uint32_t*)ctx->fb_counts[0].p;
                 (void)hipMemsetAsync(fcounts, 0, ctr_words * sizeof(uint32_t), st);
                 const FallbackList fb{(uint32_t*)ctx->fb_list[0].p, fcounts, fcap};
-                const bool big7 = !cnt && (size_t)sc->wide.n_wnodes * 64u + (size_t)sc->dev.n_prims * 48u > ((size_t)256 << 20);
-                launch_trace7(ctx, st, sc, cnt, full_only, big7, q, ro, rd, tmax, out, work_cursors, ov, ctr, fb);
+                launch_trace7(ctx, st, sc, cnt, full_only, pick.big, q, ro, rd, tmax, out, work_cursors, ov, ctr, fb);
                 q = SegQueue{fcounts, fcap, 0u, fb.list, 1u};
                 work_cursors = fcounts + (size_t)kSeg * kCtrStride;
             }
         }
-        if (ctx->traversal == 6) {  // two rays per lane (th_trace4.h)
+        if (pick.kernel == ClosestKernel::Trace4) {  // two rays per lane (th_trace4.h)
             launch_trace4(ctx, st, sc, any, cnt, full_only, q, ro, rd, tmax, out, work_cursors, ov, ctr);
             return;
         }
 #endif
-        // scenes larger than the last-level cache (256 MB of MALL): one wave per SIMD fewer (k_trace3's BIG variant)
-        const bool big = !any && !cnt && (size_t)sc->wide.n_wnodes * 64u + (size_t)sc->dev.n_prims * 48u > ((size_t)256 << 20);
+        const bool big = !any && pick.big;  // (k_trace3's BIG variant)
         if (any && hybrid_active(ctx, sc) && (ctx->any_on_accelerator > 0 || (ctx->any_on_accelerator < 0 && out.any_acc_hint)) && sc->wide_acc.root_cnt == 0) {
             // any-hit rays of a two-tree scene (TraceOut::zero_mode): the library's tree for every ray without a zero direction component, the canonical tree for the rest
             const size_t words = 16 + (size_t)kSeg * kCtrStride;  // the flag, then the second launch's work cursors
@@ -224,8 +212,8 @@ void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool an
         launch_trace3(ctx, st, sc, any, cnt, full_only, big, q, ro, rd, tmax, out, work_cursors, ov, ctr);
         return;
     }
-    if (v2) {
-        if (sc->wide.root_cnt > 0 && ctx->debug_trace_budget == 0 && ctx->leaf_kernel) {  // one-leaf scene: the dedicated kernel (th_trace2.h, k_trace_leaf)
+    if (pick.kernel != ClosestKernel::Literal) {
+        if (pick.kernel == ClosestKernel::Leaf) {  // one-leaf scene: the dedicated kernel (th_trace2.h, k_trace_leaf)
             const dim3 lgrid(ctx->num_cu * 8);
 #ifdef TRHIP_EXPERIMENTS
             if (ctx->leaf_sorted && sc->g->d_leaf_boxes.p && sc->wide.root_cnt <= 30 && ctx->slab_margin_log2 > 0) {  // rays grouped by what they can hit (th_leaf2.h)

@@ -64,7 +64,7 @@ static CertScene cert_view(const trhip_ctx* ctx, const trhip_scene* sc) {
             hipLaunchKernelGGL((k_trace3c<CNTV, FULLV, BIGV, false>), grid, block, 0, st, sc->dev_acc, wide_view_acc(ctx, sc), hot, cold, q, ro, rd, tmax, out, work_cursors, ov, ctr); \
     } while (0)
 
-void launch_trace3c(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool cnt, bool full_only, bool big, const SegQueue& q, const float4* ro, const float4* rd, const float* tmax,
+void launch_trace3c(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, ClosestChoice pick, bool cnt, bool full_only, const SegQueue& q, const float4* ro, const float4* rd, const float* tmax,
                     const TraceOut& out, uint32_t* work_cursors, uint2* ov, Counters* ctr, const FallbackList& fb) {
     const dim3 grid(trace_grid(ctx)), block(kBlock);
     const CertScene cv = cert_view(ctx, sc);
@@ -85,7 +85,7 @@ void launch_trace3c(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool 
     hipLaunchKernelGGL(k_store_cert_cold, dim3(1), dim3(1), 0, st, cold, cc);
     const CertHot hot{kCertDt * cv.inv_tight, kCertGrow * cv.inv_tight, kCertFlat * cv.sq_flat, cv.n_spheres, (const SphereCert*)cv.sphere_cert, {cv.mle_small[0], cv.mle_small[1], cv.mle_small[2]}};
 #ifdef TRHIP_EXPERIMENTS
-    if (ctx->leaf_queue && !big) {  // option "leaf_queue": the same walk with queued leaves (th_trace3d.h)
+    if (pick.kernel == ClosestKernel::Trace3d) {  // option "leaf_queue": the same walk with queued leaves (th_trace3d.h)
         if (cnt) {
             if (full_only) TH_LAUNCH3D(true, true); else TH_LAUNCH3D(true, false);
         } else {
@@ -95,7 +95,7 @@ void launch_trace3c(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool 
     }
 #endif
     const WideScene wv4 = wide_view_acc(ctx, sc);
-    if (ctx->wide4 && wv4.w4nodes) {  // the accelerator four children wide (th_trace3c4.h): one form for every launch
+    if (pick.kernel == ClosestKernel::Trace3c4) {  // the accelerator four children wide (th_trace3c4.h): one form for every launch
 #define TH_LAUNCH3C4(CNTV, FULLV, BIGV)                                                                                                                                     \
     do {                                                                                                                                                                \
         if (out.far_hint)                                                                                                                                               \
@@ -105,7 +105,7 @@ void launch_trace3c(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool 
     } while (0)
         if (cnt) {
             if (full_only) TH_LAUNCH3C4(true, true, false); else TH_LAUNCH3C4(true, false, false);
-        } else if (big) {
+        } else if (pick.big) {
             if (full_only) TH_LAUNCH3C4(false, true, true); else TH_LAUNCH3C4(false, false, true);
         } else {
             if (full_only) TH_LAUNCH3C4(false, true, false); else TH_LAUNCH3C4(false, false, false);
@@ -115,7 +115,7 @@ void launch_trace3c(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool 
     }
     if (cnt) {
         if (full_only) TH_LAUNCH3C(true, true, false); else TH_LAUNCH3C(true, false, false);
-    } else if (big) {
+    } else if (pick.big) {
         if (full_only) TH_LAUNCH3C(false, true, true); else TH_LAUNCH3C(false, false, true);
     } else {
         if (full_only) TH_LAUNCH3C(false, true, false); else TH_LAUNCH3C(false, false, false);
