@@ -296,6 +296,45 @@ int trhip_render_aov(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
 int trhip_render_aov_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset,
                             void* d_out_planes, void* d_out_samples, trhip_stats* stats);
 
+/* ---- ambient occlusion (since ABI 3001, added without a version change: nothing existing moved) ------------------------------
+ * The picture of bare geometry: no lights, no BSDF, primitives without a material accepted (pbrt's `ao` integrator; the reference
+ * has none, the definition below is this library's; docs/design/13-ao.md).  The camera samples are exactly those of
+ * trhip_render_path / trhip_render_aov for the same (sensor, spp, seed, sample_offset).  For a camera sample with stream key `key`:
+ *   1. The camera ray goes through the scene's closest-hit walk, as in trhip_render_aov.
+ *        miss: L = (background, background, background);   a hit whose interaction cannot be rebuilt: L = 0.
+ *   2. Otherwise, with p, ns of the hit (the hit-geometry entry point's values) and wo = -d:
+ *        nf = face_forward(ns, wo);  coordinate_system(nf, s, t)                                      (Trace.jl:170, :139-146)
+ *        u  = (ts_uniform(key, ts_vertex_dim(0, TS_V_BSDF_U0)), ts_uniform(key, ts_vertex_dim(0, TS_V_BSDF_U1)))
+ *        wl = cosine_sample_hemisphere(u)                                                             (Trace.jl:48-73, sin / cos of trace_detmath.h)
+ *        wi = (s * wl.x + t * wl.y) + nf * wl.z                      per component, in that order
+ *        the occlusion ray is spawn_ray(si, wi) (Trace.jl:206-211) with a finite reach: o = p + 1e-6f * wi, d = wi, t_max = max_distance,
+ *        time = the camera ray's (scenes are static: it acts on nothing)
+ *   3. occluded = intersect_p(bvh, ray): the scene's any-hit walk with the ray's own t_max.  max_distance = +Inf is allowed, and the default.
+ *   4. v = occluded ? 0 : 1 (the cosine pdf cancels cos / pi).  L = (v, v, v); with TRHIP_AO_ALBEDO, L = v * base colour (trhip_aov_sample's
+ *      definition; a primitive without a material gives 0).
+ *   5. The per-sample L goes through the path renderer's film pass unchanged (NaN rule, rgb_to_xyz, weights, tile order).
+ * Hence out_xyzw is bit for bit what trhip_film_accumulate makes of the same samples, its .w is the path frame's filter_weight_sum (so the
+ * film goes into trhip_denoise with the planes of trhip_render_aov), films are additive over sample_offset shards (a multi-GPU job uses the
+ * film reduce), and ONE occlusion ray is traced per camera sample: quality comes from spp.  trhip_last_sample_radiance returns this call's L.
+ * Lights are ignored; a scene without any is fine.  TRHIP_ERR_INVALID: a null pointer, an uncommitted scene, spp == 0, max_distance NaN or
+ * <= 0, background not finite or negative, unknown flag bits, reserved != 0 (the parameter block is checked first, before any handle).
+ * A frame whose per-sample buffers do not fit in free HBM is refused with TRHIP_ERR_UNSUPPORTED: there are no bands here.
+ * trhip_stats: camera_samples, closest_rays, shadow_rays (the occlusion rays: one per hit), fallback_rays, traversal, ms_raygen /
+ * ms_trace_closest / ms_fallback / ms_shade (the spawn kernel) / ms_trace_any / ms_film and the launch counts, n_batches = 1,
+ * max_depth_reached = 1.  The _device variant takes a DEVICE pointer for the film.  trhip_ao_default_params needs no context and no GPU. */
+#define TRHIP_AO_ALBEDO 1u /* L = v * base colour instead of (v, v, v) */
+typedef struct {
+    float max_distance;       /* reach of the occlusion rays: > 0 or +Inf */
+    float background;         /* radiance of a camera ray that misses: finite, >= 0 */
+    uint32_t flags;           /* bit 0: TRHIP_AO_ALBEDO */
+    uint32_t reserved;        /* 0 */
+} trhip_ao_params;            /* 16 bytes */
+int trhip_ao_default_params(trhip_ao_params* out); /* {+Inf, 0, 0, 0} */
+int trhip_render_ao(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset,
+                    const trhip_ao_params* params, float* out_xyzw, trhip_stats* stats);
+int trhip_render_ao_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset,
+                           const trhip_ao_params* params, void* d_out_xyzw, trhip_stats* stats);
+
 /* ---- edge-avoiding denoiser for path / Whitted films (since ABI 3001, added without a version change: nothing existing moved) ----
  * An à-trous wavelet filter after Dammertz et al. 2010 ("Edge-Avoiding À-Trous Wavelet Transform for fast Global Illumination
  * Filtering") on the film state of a path or Whitted render, guided by the three planes of trhip_render_aov for the same sensor,

@@ -130,6 +130,19 @@ class DenoiseParams(C.Structure):
 
 DENOISE_DEMODULATE = 1  # TRHIP_DENOISE_DEMODULATE
 
+
+class AoParams(C.Structure):
+    """trhip_ao_params (16 bytes)"""
+    _fields_ = [
+        ("max_distance", C.c_float),
+        ("background", C.c_float),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+AO_ALBEDO = 1  # TRHIP_AO_ALBEDO
+
 _F = C.POINTER(C.c_float)
 _U32 = C.POINTER(C.c_uint32)
 _VP = C.c_void_p
@@ -170,6 +183,9 @@ SIGNATURES = {
     "trhip_last_sample_radiance": (C.c_int, [_VP, _F, C.c_uint64]),
     "trhip_render_aov": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _F, _VP, C.POINTER(Stats)]),
     "trhip_render_aov_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, _VP, C.POINTER(Stats)]),
+    "trhip_ao_default_params": (C.c_int, [C.POINTER(AoParams)]),
+    "trhip_render_ao": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(AoParams), _F, C.POINTER(Stats)]),
+    "trhip_render_ao_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(AoParams), _VP, C.POINTER(Stats)]),
     "trhip_denoise_default_params": (C.c_int, [C.POINTER(DenoiseParams)]),
     "trhip_denoise": (C.c_int, [_VP, _F, _F, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _F, C.POINTER(Stats)]),
     "trhip_denoise_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _VP, C.POINTER(Stats)]),

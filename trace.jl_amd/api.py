@@ -1026,6 +1026,45 @@ class AOVIntegrator:
         return out
 
 
+# ---- ambient occlusion (include/tracehip.h, trhip_render_ao) ---------------------------------------------------------------------------
+class AmbientOcclusionIntegrator(_SamplerIntegrator):
+    """The picture of bare geometry (trhip_render_ao; docs/design/13-ao.md): the camera samples of PathIntegrator for the same camera and sampler, one cosine-distributed
+    occlusion ray of reach `max_distance` from every first hit, radiance 1 where it escapes and 0 where it is stopped (times the base colour with ``albedo``), `background`
+    where the camera ray misses.  No lights, no BSDF: a scene without lights or with material-less primitives renders.  One occlusion ray per camera sample: quality comes
+    from the sampler's samples_per_pixel.  The film has the path frame's weights, so it goes through Denoiser.denoise with AOVIntegrator's planes."""
+
+    def __init__(self, camera: PerspectiveCamera, sampler: SeededSampler, max_distance: float = math.inf, albedo: bool = False, background: float = 0.0):
+        super().__init__(camera, sampler, 1)
+        max_distance, background = float(max_distance), float(background)
+        if not max_distance > 0.0:
+            raise TraceHipError(f"AmbientOcclusionIntegrator: max_distance must be > 0 or inf, not {max_distance}")
+        if not (background >= 0.0 and math.isfinite(background)):
+            raise TraceHipError(f"AmbientOcclusionIntegrator: background must be finite and >= 0, not {background}")
+        p = _ffi.AoParams()
+        rc = _ffi.lib().trhip_ao_default_params(C.byref(p))
+        if rc:
+            raise TraceHipError(f"trhip_ao_default_params failed ({rc})")
+        p.max_distance, p.background, p.flags = max_distance, background, _ffi.AO_ALBEDO if albedo else 0
+        self.params = p
+
+    def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None) -> np.ndarray:
+        """Render into camera.film (and return xyzw, H x W x 4).  With ``device_out`` (a device pointer to H * W * 4 floats) the film accumulators are written there
+        instead, nothing is copied to the host and None is returned."""
+        flat = scene.flatten(ctx)
+        ctx = flat.ctx
+        sn, st, smp, L = self.camera.sensor(), _ffi.Stats(), self.sampler, _ffi.lib()
+        if device_out is not None:
+            ctx.check(L.trhip_render_ao_device(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, C.byref(self.params), C.c_void_p(device_out), C.byref(st)))
+            self.stats = st
+            return None
+        h, w = self.camera.film.size
+        out = np.empty((h, w, 4), dtype=np.float32)
+        ctx.check(L.trhip_render_ao(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, C.byref(self.params), _ffi.fptr(out), C.byref(st)))
+        self.stats = st
+        self.camera.film.set_xyzw(out)
+        return out
+
+
 # ---- edge-avoiding denoiser (include/tracehip.h, trhip_denoise) ----------------------------------------------------------------------------
 class Denoiser:
     """Edge-avoiding à-trous filter (Dammertz et al. 2010, Tukey's biweight as the edge-stopping function) for the film of a PathIntegrator or WhittedIntegrator render,

@@ -2,7 +2,7 @@
 // handles of include/tracehip.h, error / buffer helpers, and the functions one unit calls in another.  Units (each compiled on its own
 // and linked into the one shared object): tu_api.hip (context, options, communicator), tu_scene.hip (scene flattening, commit, upload),
 // tu_lbvh.hip (BVH build on the device), tu_trace.hip / tu_trace3.hip / tu_trace8.hip (traversal launches and entry points),
-// tu_path.hip (PathIntegrator frames, film), tu_aov.hip (first-hit feature buffers), tu_denoise.hip (the à-trous filter), tu_whitted.hip, tu_sppm.hip.
+// tu_path.hip (PathIntegrator frames, film), tu_aov.hip (first-hit feature buffers), tu_ao.hip (ambient occlusion), tu_denoise.hip (the à-trous filter), tu_whitted.hip, tu_sppm.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -135,6 +135,7 @@ struct trhip_ctx {
     DevBuf poison;  // one byte per camera sample of the band: ShadeStream::poison
     DevBuf cert_cold;  // k_trace3c's CertCold (th_trace3c.h)
     DevBuf aov_rec;    // trhip_render_aov: the frame's per-sample records (th_aov.h, 80 B per camera sample)
+    DevBuf ao_tmax;    // trhip_render_ao: the reach of every occlusion ray, beside the any-hit queue sq (th_ao.h, 4 B per queue entry)
     DevBuf dn_work, dn_in;  // trhip_denoise: guides, two colour buffers and the base colour (th_denoise.h, 80 B per pixel); the host entry point's copy of film and planes
     int denoise_lds = 3;    // bit i: iteration i (step 2^i, i < 2) of trhip_denoise runs the LDS-staged kernel (option "denoise_lds")
     DevBuf cb_rc;      // one word: a host callback's return code, max-reduced over the ranks of a job (tu_sppm.hip)

@@ -48,6 +48,7 @@ void trhip_shutdown(trhip_ctx* ctx) {
     release(ctx->film_side);
     release(ctx->cert_cold);
     release(ctx->aov_rec);
+    release(ctx->ao_tmax);
     release(ctx->dn_work);
     release(ctx->dn_in);
     release(ctx->cb_rc);

@@ -393,6 +393,9 @@ end
 
 (i::PathIntegrator)(scene::Trace.Scene) = render!(:trhip_render_path, i, scene)
 
+# AmbientOcclusionIntegrator (trhip_render_ao) and its parameter block live in a file of their own, with their own ccall manifest (tests/golden/julia_shim_ao_calls.json)
+include("TraceHIPAO.jl")
+
 # SPPMIntegrator (integrators/sppm.jl:132-173) on the device: trhip_render_sppm returns the film after set_image!
 # (film.jl:195-202).  `seed` selects the seeded stream of the camera pass (the reference draws from the global RNG there).
 # The reference's periodic image (sppm.jl:166-171: every iteration that write_frequency divides is stored in the film and saved): the library calls back with the
