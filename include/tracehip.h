@@ -372,6 +372,50 @@ int trhip_denoise(trhip_ctx* ctx, const float* xyzw, const float* planes, uint32
 int trhip_denoise_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, uint32_t width, uint32_t height, const trhip_denoise_params* params,
                          void* d_out_xyzw, trhip_stats* stats);
 
+/* ---- temporal reprojection for moving-camera previews (since ABI 3001, added without a version change: nothing existing moved) ----
+ * The first step of SVGF (Schied et al. 2017, "Spatiotemporal Variance-Guided Filtering", section 4.1): the previous frame's accumulated
+ * colour is fetched through the PREVIOUS camera at the world position of each pixel's surface, validated against the feature planes, and
+ * blended with the new frame; trhip_denoise then filters the result with the current frame's planes.  Image-space: no scene, no traversal.
+ * The arithmetic is specified, operation by operation, in docs/design/14-temporal.md and is bit-reproducible like the denoiser's.
+ *
+ * trhip_sensor_world_to_pixel: out12 = M, a row-major 3 x 4 matrix.  For a world point p, h_i = ((M[i][0]*p.x + M[i][1]*p.y) + M[i][2]*p.z) +
+ * M[i][3]; (h.x / h.z, h.y / h.z) is p's position in film-ARRAY pixel coordinates — 0-based, integers at pixel centres, [y][x] as in out_xyzw —
+ * valid iff h.z > 0 (p in front of the camera).  Built in Float64 from raster_to_camera, camera_to_world and crop_min, each entry rounded to
+ * Float32 once; depth of field is ignored (the lens centre is the projection centre).  A singular matrix: TRHIP_ERR_INVALID.  No context, no GPU.
+ *
+ * trhip_temporal:
+ *   xyzw, planes, out_xyzw   as in trhip_denoise; out_xyzw may be xyzw itself
+ *   history, out_history     height * width * 3 float4, plane-minor like planes: (c.rgb, N) accumulated linear RGB and history length,
+ *                            (n.xyz, 1 if surface else 0), (p.xyz, 0).  history may be NULL (first frame, or after a change of lights or film size)
+ * Per pixel: a pixel that is no surface pixel (trhip_denoise's rule, min_coverage) is returned with its input bits and a zero history record.
+ * A surface pixel at world position p is projected with prev_world_to_pixel; the four history pixels around that position are bilinear taps, a
+ * tap counting when it lies inside the image, was a surface pixel with N > 0, 1 - n.n_q < sigma_normal and |n.(p_q - p)| < sigma_plane.  With
+ * c_h, N_h the weighted means over the counting taps: N' = min(N_h + 1, max_history), c' = c_h + (c - c_h) / N'; without any (or h.z <= 0, a
+ * position that is not finite or beyond 2^20, a result that is not finite): c' = c, N' = 1.  out_xyzw = (rgb_to_xyz(c') * w, w): the .w lane
+ * is returned as given, so the output goes into trhip_denoise, film.set_xyzw and save.  Scenes are static; lighting changes are NOT detected:
+ * pass history = NULL after one.
+ * TRHIP_ERR_INVALID: params NULL, an entry of prev_world_to_pixel not finite, max_history not finite or < 1, flags != 0, a sigma not finite
+ * and > 0, min_coverage outside [0, 1], reserved != 0 (the parameter block is checked first, before any handle); then a null pointer (history
+ * excepted), a zero dimension, out_history overlapping history, planes, xyzw or out_xyzw.  TRHIP_ERR_UNSUPPORTED: the host variant's device
+ * copies (160 bytes per pixel) do not fit in free HBM.  stats (may be NULL): ms_total, ms_film, launches_film = 1.  The _device variant takes
+ * DEVICE pointers for the five images.  trhip_temporal_default_params needs no context and no GPU; it leaves prev_world_to_pixel zero (no
+ * history is found through it). */
+typedef struct {
+    float prev_world_to_pixel[12]; /* trhip_sensor_world_to_pixel of the PREVIOUS frame's sensor */
+    float max_history;             /* cap of the history length: finite, >= 1 */
+    float sigma_normal;            /* a tap is accepted when 1 - n.n_q   < sigma_normal */
+    float sigma_plane;             /* ... and |n.(p_q - p)| < sigma_plane, world units */
+    float min_coverage;            /* the denoiser's surface-pixel rule, [0, 1] */
+    uint32_t flags;                /* 0 */
+    uint32_t reserved;             /* 0 */
+} trhip_temporal_params;           /* 72 bytes */
+int trhip_sensor_world_to_pixel(const trhip_sensor* sensor, float out12[12]);
+int trhip_temporal_default_params(trhip_temporal_params* out);
+int trhip_temporal(trhip_ctx* ctx, const float* xyzw, const float* planes, const float* history, uint32_t width, uint32_t height, const trhip_temporal_params* params,
+                   float* out_xyzw, float* out_history, trhip_stats* stats);
+int trhip_temporal_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_history, uint32_t width, uint32_t height, const trhip_temporal_params* params,
+                          void* d_out_xyzw, void* d_out_history, trhip_stats* stats);
+
 /* SPPMIntegrator(camera, initial_search_radius, max_depth, n_iterations, photons_per_iteration)(scene)
  * (integrators/sppm.jl:108-173): per iteration a camera pass to the first diffuse vertex, a hash grid over the visible
  * points, a photon pass (Halton / radical_inverse, sampler/sampling.jl:43-60) and the Float64 pixel update; afterwards
@@ -525,6 +569,8 @@ int trhip_film_allreduce(trhip_ctx* ctx, void* d_xyzw, uint64_t n_pixels);
  * "film_tiled" (0/1): LDS-staged film gather (default 0: measured slower).
  * "denoise_lds" (bit mask 0..3, default 3): bit i set = iteration i of trhip_denoise (i = 0, 1: steps 1, 2) stages its blocks' pixels and halo in LDS
  *     instead of gathering them from memory (measured 7 % and 3 % faster); same result bit for bit (th_denoise.h).
+ * "temporal_patch" (0/1, default 1): which lane of trhip_temporal's kernel computes which pixel — 0 film order (a wave is 64 pixels of a row), 1 the à-trous
+ *     kernel's patches of 16 x 4 pixels per wave (measured 11 % faster); same result bit for bit (th_temporal.h).
  * "film_transpose" (0/1): film pass on pixel-group-major copies of the per-sample radiance / film positions (default 0: no gain).
  * "leaf_kernel" (0/1): one-leaf scenes (tiny_scene_prims) run the dedicated uniform-walk kernel instead of traversal 2 (default 1).
  * "band_tile_rows": PathIntegrator frames whose per-sample buffers (24 B per camera sample) do not fit in HBM are rendered in bands of

@@ -143,6 +143,20 @@ class AoParams(C.Structure):
 
 AO_ALBEDO = 1  # TRHIP_AO_ALBEDO
 
+
+class TemporalParams(C.Structure):
+    """trhip_temporal_params (72 bytes)"""
+    _fields_ = [
+        ("prev_world_to_pixel", C.c_float * 12),
+        ("max_history", C.c_float),
+        ("sigma_normal", C.c_float),
+        ("sigma_plane", C.c_float),
+        ("min_coverage", C.c_float),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 _F = C.POINTER(C.c_float)
 _U32 = C.POINTER(C.c_uint32)
 _VP = C.c_void_p
@@ -189,6 +203,10 @@ SIGNATURES = {
     "trhip_denoise_default_params": (C.c_int, [C.POINTER(DenoiseParams)]),
     "trhip_denoise": (C.c_int, [_VP, _F, _F, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _F, C.POINTER(Stats)]),
     "trhip_denoise_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), _VP, C.POINTER(Stats)]),
+    "trhip_sensor_world_to_pixel": (C.c_int, [C.POINTER(Sensor), _F]),
+    "trhip_temporal_default_params": (C.c_int, [C.POINTER(TemporalParams)]),
+    "trhip_temporal": (C.c_int, [_VP, _F, _F, _F, C.c_uint32, C.c_uint32, C.POINTER(TemporalParams), _F, _F, C.POINTER(Stats)]),
+    "trhip_temporal_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(TemporalParams), _VP, _VP, C.POINTER(Stats)]),
     "trhip_render_sppm": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats)]),
     "trhip_render_sppm_ex": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats), C.c_uint32, SPPM_WRITE_FN, _VP]),
     "trhip_sppm_state": (C.c_int, [_VP, _F, _F, _F, C.POINTER(C.c_double), C.POINTER(C.c_int64), _F, _F, _F, C.POINTER(C.c_int64)]),

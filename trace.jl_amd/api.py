@@ -593,6 +593,16 @@ class PerspectiveCamera:  # camera/perspective.jl:11-40, 58-80
         s.scale = float(f.scale)
         return s
 
+    def world_to_pixel(self) -> np.ndarray:
+        """The 3 x 4 Float32 matrix M of trhip_sensor_world_to_pixel: with h = M (p, 1) for a world point p, (h.x / h.z, h.y / h.z) is p's position in film-array pixel
+        coordinates (0-based, integers at pixel centres, [y][x] as in xyzw), valid iff h.z > 0.  Host arithmetic: no context, no GPU."""
+        out = np.empty(12, dtype=np.float32)
+        sn = self.sensor()
+        rc = _ffi.lib().trhip_sensor_world_to_pixel(C.byref(sn), _ffi.fptr(out))
+        if rc:
+            raise TraceHipError(_ffi.lib().trhip_last_error(None).decode() or f"trhip_sensor_world_to_pixel failed ({rc})")
+        return out.reshape(3, 4)
+
 
 def get_film(camera: PerspectiveCamera) -> Film:  # perspective.jl:83
     return camera.film
@@ -1120,6 +1130,113 @@ class Denoiser:
         finally:
             d_film.free()
             d_planes.free()
+
+
+# ---- temporal reprojection (include/tracehip.h, trhip_temporal) ------------------------------------------------------------------------------
+class TemporalAccumulator:
+    """Blends a path frame with the previous frame's accumulated colour, fetched through the previous camera and validated against the feature planes (trhip_temporal;
+    docs/design/14-temporal.md).  Fields left at None come from trhip_temporal_default_params (max_history 8, sigma_normal 0.25, sigma_plane 0.1, min_coverage 0.5).
+    The history is a (H, W, 3, 4) array: (c.rgb, N), (n, surface flag), (p, 0).  Scenes are static and lighting changes are not detected: pass history=None after one."""
+
+    def __init__(self, max_history: Optional[float] = None, sigma_normal: Optional[float] = None, sigma_plane: Optional[float] = None, min_coverage: Optional[float] = None):
+        p = _ffi.TemporalParams()
+        rc = _ffi.lib().trhip_temporal_default_params(C.byref(p))
+        if rc:
+            raise TraceHipError(f"trhip_temporal_default_params failed ({rc})")
+        for name, value in (("max_history", max_history), ("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane), ("min_coverage", min_coverage)):
+            if value is not None:
+                setattr(p, name, value)
+        self.params = p
+        self.stats: Optional[_ffi.Stats] = None
+
+    def _params_for(self, prev_camera) -> _ffi.TemporalParams:
+        """`prev_camera`: the previous frame's PerspectiveCamera, its world_to_pixel() matrix, or None (zeros: nothing is found through it)."""
+        p = _ffi.TemporalParams.from_buffer_copy(self.params)
+        if prev_camera is not None:
+            m = prev_camera.world_to_pixel() if hasattr(prev_camera, "world_to_pixel") else _ffi.f32(prev_camera)
+            if m.size != 12:
+                raise TraceHipError(f"TemporalAccumulator: the previous camera's matrix must be 3 x 4, not {m.shape}")
+            p.prev_world_to_pixel[:] = m.reshape(-1).tolist()
+        return p
+
+    def accumulate(self, xyzw: np.ndarray, planes: np.ndarray, history: Optional[np.ndarray], prev_camera, ctx: Optional[_ffi.Context] = None):
+        """xyzw: (H, W, 4) as PathIntegrator.render returns it; planes: (H, W, 3, 4) as AOVIntegrator.render(...).planes; history: the second result of the previous
+        frame's call, or None.  Returns (xyzw, history) of this frame; the xyzw goes into Denoiser.denoise with the same planes."""
+        xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
+        if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
+            raise TraceHipError(f"accumulate: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
+        if history is not None:
+            history = _ffi.f32(history)
+            if history.shape != planes.shape:
+                raise TraceHipError(f"accumulate: history must be {planes.shape} like planes, not {history.shape}")
+        ctx = ctx or _ffi.default_context()
+        h, w = xyzw.shape[:2]
+        out, out_history, st, p = np.empty_like(xyzw), np.empty_like(planes), _ffi.Stats(), self._params_for(prev_camera)
+        ctx.check(_ffi.lib().trhip_temporal(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(planes), _ffi.fptr(history) if history is not None else None, w, h, C.byref(p), _ffi.fptr(out),
+                                            _ffi.fptr(out_history), C.byref(st)))
+        self.stats = st
+        return out, out_history
+
+    def accumulate_device(self, d_xyzw: int, d_planes: int, d_history: Optional[int], width: int, height: int, prev_camera, d_out: int, d_out_history: int,
+                          ctx: Optional[_ffi.Context] = None) -> None:
+        """The same on device pointers (d_out may equal d_xyzw, d_history may be None); nothing is copied to the host."""
+        ctx = ctx or _ffi.default_context()
+        st, p = _ffi.Stats(), self._params_for(prev_camera)
+        ctx.check(_ffi.lib().trhip_temporal_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), C.c_void_p(d_history) if d_history else None, int(width), int(height), C.byref(p),
+                                                   C.c_void_p(d_out), C.c_void_p(d_out_history), C.byref(st)))
+        self.stats = st
+
+
+class PreviewSession:
+    """A moving-camera preview of a static scene: frame k is the path film and the feature planes at sample_offset = sampler.sample_offset + k * spp, temporal accumulation
+    against the previous frame's history and camera, then the à-trous filter with this frame's planes — all on the device, the buffers kept between frames.
+    `reset()` drops the history (the frame counter goes on, so the next frame's noise is new): call it after Scene.with_lights, since the pass does not detect lighting
+    changes; a film of another size resets as well.  A frame without history is filtered as Denoiser.render filters it, bit for bit."""
+
+    def __init__(self, scene: Scene, sampler: SeededSampler, max_depth: int, denoiser: Optional["Denoiser"] = None, temporal: Optional[TemporalAccumulator] = None):
+        self.scene, self.sampler, self.max_depth = scene, sampler, int(max_depth)
+        self.denoiser = denoiser if denoiser is not None else Denoiser()
+        self.temporal = temporal if temporal is not None else TemporalAccumulator()
+        self.frame = 0
+        self._size = None
+        self._buffers = None     # film, planes, accumulated film, history x 2
+        self._prev_matrix = None  # world_to_pixel of the camera whose history is held; None: no history
+        self.render_stats = None  # (path, aov, temporal, denoise) Stats of the last render()
+
+    def reset(self) -> None:
+        self._prev_matrix = None
+
+    def close(self) -> None:
+        for b in self._buffers or ():
+            b.free()
+        self._buffers, self._size, self._prev_matrix = None, None, None
+
+    def render(self, camera: PerspectiveCamera, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
+        """The next frame through `camera`; returns xyzw (H, W, 4), ready for film.set_xyzw / save."""
+        ctx = self.scene.flatten(ctx).ctx
+        h, w = camera.film.size
+        if self._size != (h, w):
+            self.close()
+            self._size = (h, w)
+            self._buffers = [_ffi.DeviceBuffer(h * w * n) for n in (16, 48, 16, 48, 48)]
+        d_film, d_planes, d_acc = self._buffers[:3]
+        d_prev, d_next = self._buffers[3 + (self.frame & 1)], self._buffers[3 + ((self.frame & 1) ^ 1)]
+        spp = self.sampler.samples_per_pixel
+        sampler = SeededSampler(spp, seed=self.sampler.seed, sample_offset=self.sampler.sample_offset + self.frame * spp)
+        path, aov = PathIntegrator(camera, sampler, self.max_depth), AOVIntegrator(camera, sampler)
+        path.render(self.scene, ctx, device_out=d_film.ptr)
+        aov.render(self.scene, ctx, device_out=d_planes.ptr)
+        prev_matrix, matrix = self._prev_matrix, camera.world_to_pixel()
+        had_history = prev_matrix is not None
+        self._prev_matrix = None  # (until this frame's history is complete)
+        self.temporal.accumulate_device(d_film.ptr, d_planes.ptr, d_prev.ptr if had_history else None, w, h, prev_matrix, d_acc.ptr, d_next.ptr, ctx)
+        # without history the accumulated film is the frame itself up to the rounding of XYZ -> RGB -> XYZ: the frame's own bits are filtered then
+        self.denoiser.denoise_device((d_acc if had_history else d_film).ptr, d_planes.ptr, w, h, d_acc.ptr, ctx)
+        self.render_stats = (path.stats, aov.stats, self.temporal.stats, self.denoiser.stats)
+        out = d_acc.to_host(np.float32, (h, w, 4))
+        self._prev_matrix = matrix
+        self.frame += 1
+        return out
 
 
 # ---- SPPM and the DirectionalLight -------------------------------------------------------------------------------------------------

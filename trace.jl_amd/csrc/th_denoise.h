@@ -28,33 +28,42 @@ TH_D float dn_tukey(float x) {
 TH_D bool dn_finite(float x) { return fabs_(x) < kInf; }  // false for NaN too
 TH_D bool dn_finite3(f3 v) { return dn_finite(v.x) && dn_finite(v.y) && dn_finite(v.z); }
 
+// Steps 1-6 of Prepare (docs/design/12-denoise.md) for one pixel: B the film pixel, P0..P2 its planes.  Returns the surface flag; n, p, c (and a, with demodulation) are
+// meaningful only when it is true.  Shared with the temporal pass (th_temporal.h), which calls it without demodulation.
+TH_D bool dn_prepare_pixel(const float4& B, const float4& P0, const float4& P1, const float4& P2, uint32_t demodulate, float albedo_floor, float min_coverage, f3& n, f3& p, f3& c, f3& a) {
+    const float W = B.w, A = P0.w, H = P1.w;
+    bool surface = W > 0.0f && A > 0.0f && H > 0.0f && H >= min_coverage * A;
+    n = mk3(0.0f, 0.0f, 0.0f), p = n, c = n, a = n;
+    if (surface) {
+        const float iH = 1.0f / H;
+        n = mk3(P1.x, P1.y, P1.z) * iH;
+        const float len = sqrt_(dot(n, n));
+        surface = len > 0.0f;
+        n = n / len;
+        p = mk3(P2.x, P2.y, P2.z) * iH;
+        const float iW = 1.0f / W;
+        c = xyz_to_rgb(mk3(B.x, B.y, B.z) * iW);
+        if (demodulate) {
+            const float iA = 1.0f / A;
+            a = mk3(P0.x, P0.y, P0.z) * iA;
+            a.x = a.x > albedo_floor ? a.x : albedo_floor;
+            a.y = a.y > albedo_floor ? a.y : albedo_floor;
+            a.z = a.z > albedo_floor ? a.z : albedo_floor;
+            c = c / a;
+        }
+        surface = surface && dn_finite3(n) && dn_finite3(p) && dn_finite3(c);
+    }
+    return surface;
+}
+
 // One pixel per lane, pixels in film order.  planes: [pixel][3] float4 as trhip_render_aov writes them.
+template <int TH_ONE_COPY = 0>
 __global__ __launch_bounds__(kBlock) void k_denoise_prepare(const float4* __restrict__ beauty, const float4* __restrict__ planes, uint64_t npix, uint32_t demodulate, float albedo_floor,
                                                             float min_coverage, float4* __restrict__ gn, float4* __restrict__ gp, float4* __restrict__ col, float4* __restrict__ alb) {
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < npix; i += (uint64_t)gridDim.x * kBlock) {
         const float4 B = beauty[i], P0 = planes[3 * i], P1 = planes[3 * i + 1], P2 = planes[3 * i + 2];
-        const float W = B.w, A = P0.w, H = P1.w;
-        bool surface = W > 0.0f && A > 0.0f && H > 0.0f && H >= min_coverage * A;
-        f3 n = mk3(0.0f, 0.0f, 0.0f), p = n, c = n, a = n;
-        if (surface) {
-            const float iH = 1.0f / H;
-            n = mk3(P1.x, P1.y, P1.z) * iH;
-            const float len = sqrt_(dot(n, n));
-            surface = len > 0.0f;
-            n = n / len;
-            p = mk3(P2.x, P2.y, P2.z) * iH;
-            const float iW = 1.0f / W;
-            c = xyz_to_rgb(mk3(B.x, B.y, B.z) * iW);
-            if (demodulate) {
-                const float iA = 1.0f / A;
-                a = mk3(P0.x, P0.y, P0.z) * iA;
-                a.x = a.x > albedo_floor ? a.x : albedo_floor;
-                a.y = a.y > albedo_floor ? a.y : albedo_floor;
-                a.z = a.z > albedo_floor ? a.z : albedo_floor;
-                c = c / a;
-            }
-            surface = surface && dn_finite3(n) && dn_finite3(p) && dn_finite3(c);
-        }
+        f3 n, p, c, a;
+        const bool surface = dn_prepare_pixel(B, P0, P1, P2, demodulate, albedo_floor, min_coverage, n, p, c, a);
         if (!surface) n = p = c = a = mk3(0.0f, 0.0f, 0.0f);  // never read as a neighbour, carried through the iterations, replaced by the input at the end
         gn[i] = make_float4(n.x, n.y, n.z, surface ? 1.0f : 0.0f);
         gp[i] = make_float4(p.x, p.y, p.z, 0.0f);
@@ -74,6 +83,7 @@ TH_D float dn_kernel(int d) { return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.
 
 // Plain gather.  Lane (lx, ly) of a 16 x 16 block: a wave is a 16 x 4 patch, so a tap of a wave reads four runs of 256 contiguous bytes per array.  The three loads of a tap are
 // issued whether or not the tap counts (at a clamped address), so that the loads of a row of taps are in flight together; what is added is decided afterwards.
+template <int TH_ONE_COPY = 0>
 __global__ __launch_bounds__(kDnTile* kDnTile) void k_denoise_atrous(const float4* __restrict__ gn, const float4* __restrict__ gp, const float4* __restrict__ cin, float4* __restrict__ cout,
                                                                       int width, int height, int step, DenoiseWeights sg) {
     const int x = (int)blockIdx.x * kDnTile + (int)(threadIdx.x & (kDnTile - 1)), y = (int)blockIdx.y * kDnTile + (int)(threadIdx.x / kDnTile);
@@ -175,6 +185,7 @@ __global__ __launch_bounds__(kDnTile* kDnTile) void k_denoise_atrous_lds(const f
 }
 
 // out may be the beauty buffer itself: a lane reads its pixel before it writes it and touches no other.
+template <int TH_ONE_COPY = 0>
 __global__ __launch_bounds__(kBlock) void k_denoise_finish(const float4* beauty, const float4* __restrict__ gn, const float4* __restrict__ col, const float4* __restrict__ alb, uint64_t npix,
                                                            uint32_t demodulate, float4* out) {
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < npix; i += (uint64_t)gridDim.x * kBlock) {

@@ -2,7 +2,7 @@
 // handles of include/tracehip.h, error / buffer helpers, and the functions one unit calls in another.  Units (each compiled on its own
 // and linked into the one shared object): tu_api.hip (context, options, communicator), tu_scene.hip (scene flattening, commit, upload),
 // tu_lbvh.hip (BVH build on the device), tu_trace.hip / tu_trace3.hip / tu_trace8.hip (traversal launches and entry points),
-// tu_path.hip (PathIntegrator frames, film), tu_aov.hip (first-hit feature buffers), tu_ao.hip (ambient occlusion), tu_denoise.hip (the à-trous filter), tu_whitted.hip, tu_sppm.hip.
+// tu_path.hip (PathIntegrator frames, film), tu_aov.hip (first-hit feature buffers), tu_ao.hip (ambient occlusion), tu_denoise.hip (the à-trous filter), tu_temporal.hip (temporal reprojection), tu_whitted.hip, tu_sppm.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -138,6 +138,8 @@ struct trhip_ctx {
     DevBuf ao_tmax;    // trhip_render_ao: the reach of every occlusion ray, beside the any-hit queue sq (th_ao.h, 4 B per queue entry)
     DevBuf dn_work, dn_in;  // trhip_denoise: guides, two colour buffers and the base colour (th_denoise.h, 80 B per pixel); the host entry point's copy of film and planes
     int denoise_lds = 3;    // bit i: iteration i (step 2^i, i < 2) of trhip_denoise runs the LDS-staged kernel (option "denoise_lds")
+    DevBuf tp_in;           // trhip_temporal's host entry point: its copy of film, planes, history and the new history (th_temporal.h, 160 B per pixel)
+    int temporal_patch = 1; // trhip_temporal's lane-to-pixel mapping: 0 film order, 1 patches of 16 x 4 per wave, measured 11 % faster (option "temporal_patch", profiles/r11/temporal.txt)
     DevBuf cb_rc;      // one word: a host callback's return code, max-reduced over the ranks of a job (tu_sppm.hip)
     DevBuf ov8[2], fb_list[2], fb_counts[2];  // k_trace8: global stack levels, fallback lists + their counters / work cursors ([closest | any])
     Comm comm;  // multi-GPU job this context belongs to (trhip_comm_init); n_ranks == 1 without one

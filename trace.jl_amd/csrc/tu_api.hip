@@ -51,6 +51,7 @@ void trhip_shutdown(trhip_ctx* ctx) {
     release(ctx->ao_tmax);
     release(ctx->dn_work);
     release(ctx->dn_in);
+    release(ctx->tp_in);
     release(ctx->cb_rc);
     for (auto& pp : ctx->pipes) {
         for (auto& a : pp.q)
@@ -250,6 +251,8 @@ int trhip_set_option(trhip_ctx* ctx, const char* name, int64_t value) {
         ctx->film_tiled = value != 0;
     else if (!std::strcmp(name, "denoise_lds"))
         ctx->denoise_lds = (int)(value & 3);
+    else if (!std::strcmp(name, "temporal_patch"))
+        ctx->temporal_patch = value != 0;
     else if (!std::strcmp(name, "pipelines")) {
         if (value < 1 || value > kMaxPipes) return fail(ctx, TRHIP_ERR_INVALID, "pipelines must be in 1..%d", kMaxPipes);
         ctx->pipelines = (int)value;

@@ -1,0 +1,192 @@
+// tu_temporal.hip — trhip_temporal: the reprojection pass of th_temporal.h on a film, its feature planes and the previous frame's history; and trhip_sensor_world_to_pixel, the
+// host arithmetic that gives the pass its matrix.  No scene, no traversal: an image-space pass.
+#include "th_host.h"
+#include "th_temporal.h"
+
+#include <cmath>
+
+namespace {
+
+static_assert(sizeof(trhip_temporal_params) == 72, "trhip_temporal_params layout");
+
+constexpr size_t kTpHostBytesPerPixel = 160;  // the host entry point's copies: film 16, planes 48, history 48, new history 48
+
+bool positive_finite(float v) { return std::isfinite(v) && v > 0.0f; }
+
+int check_params(trhip_ctx* ctx, const trhip_temporal_params* p) {
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(p->prev_world_to_pixel[i])) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: prev_world_to_pixel[%d] is not finite", i);
+    if (!(std::isfinite(p->max_history) && p->max_history >= 1.0f)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: max_history must be finite and >= 1");
+    if (p->flags != 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: unknown flag bits 0x%x", p->flags);
+    if (!positive_finite(p->sigma_normal)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: sigma_normal must be finite and > 0");
+    if (!positive_finite(p->sigma_plane)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: sigma_plane must be finite and > 0");
+    if (!(p->min_coverage >= 0.0f && p->min_coverage <= 1.0f)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: min_coverage must lie in [0, 1]");
+    if (p->reserved != 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: reserved must be 0");
+    return 0;
+}
+
+bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && a0 < b0 + nb && b0 < a0 + na;
+}
+
+int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const void* history, uint32_t width, uint32_t height, const trhip_temporal_params* prm, void* out, void* out_history,
+                  bool is_device, trhip_stats* stats) {
+    // the parameter block first, before any handle is looked at: none of it needs a device
+    if (!prm) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
+    if (int rc = check_params(ctx, prm)) return rc;
+    if (!ctx || !xyzw || !planes || !out || !out_history) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
+    if (width == 0 || height == 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: empty film (%u x %u)", width, height);
+    const uint64_t npix = (uint64_t)width * height;
+    const size_t film_bytes = (size_t)npix * sizeof(float4), planes_bytes = 3 * film_bytes;
+    if (overlap(out_history, planes_bytes, history, planes_bytes) || overlap(out_history, planes_bytes, planes, planes_bytes) || overlap(out_history, planes_bytes, xyzw, film_bytes) ||
+        overlap(out_history, planes_bytes, out, film_bytes))
+        return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: out_history overlaps an input or out_xyzw");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint32_t bx = (width + kDnTile - 1) / kDnTile, by = (height + kDnTile - 1) / kDnTile;
+    const uint64_t lin_blocks = (npix + kDnTile * kDnTile - 1) / (kDnTile * kDnTile);
+    {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+        const size_t held = ctx->tp_in.bytes;  // reused below
+        const double need = is_device ? 0.0 : (double)npix * kTpHostBytesPerPixel;
+        if (by > 65535u || lin_blocks > 0x7fffffffull || need > 0.9 * (double)(free_b + held))
+            return fail(ctx, TRHIP_ERR_UNSUPPORTED, "trhip_temporal: the images of a %u x %u film (%.1f GB, 160 B per pixel) do not fit in free HBM (%.1f GB free); there are no bands here", width,
+                        height, need * 1e-9, (double)(free_b + held) * 1e-9);
+    }
+    const float4* d_beauty = (const float4*)xyzw;
+    const float4* d_planes = (const float4*)planes;
+    const float4* d_history = (const float4*)history;
+    float4* d_out = (float4*)out;
+    float4* d_out_history = (float4*)out_history;
+    if (!is_device) {  // the film's copy is accumulated in place
+        if (int rc = ensure(ctx, ctx->tp_in, (size_t)npix * kTpHostBytesPerPixel)) return rc;
+        char* base = (char*)ctx->tp_in.p;
+        HIP_TRY(ctx, hipMemcpy(base, xyzw, film_bytes, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(base + film_bytes, planes, planes_bytes, hipMemcpyHostToDevice));
+        if (history) HIP_TRY(ctx, hipMemcpy(base + film_bytes + planes_bytes, history, planes_bytes, hipMemcpyHostToDevice));
+        d_beauty = d_out = (float4*)base;
+        d_planes = (const float4*)(base + film_bytes);
+        d_history = history ? (const float4*)(base + film_bytes + planes_bytes) : nullptr;
+        d_out_history = (float4*)(base + film_bytes + 2 * planes_bytes);
+    }
+    TemporalConst k;
+    std::memcpy(k.m, prm->prev_world_to_pixel, sizeof k.m);
+    k.max_history = prm->max_history;
+    k.sigma_normal = prm->sigma_normal;
+    k.sigma_plane = prm->sigma_plane;
+    k.min_coverage = prm->min_coverage;
+    hipStream_t st = ctx->stream;
+
+    Timer tm(ctx, ctx->timing && stats);
+    hipEvent_t e0, e1;
+    HIP_TRY(ctx, hipEventCreate(&e0));
+    HIP_TRY(ctx, hipEventCreate(&e1));
+    HIP_TRY(ctx, hipEventRecord(e0, st));
+    tm.begin(5, st);
+    if (ctx->temporal_patch)  // measured 0.0347 ms against 0.0391 ms at 1024 x 1024 (profiles/r11/temporal.txt)
+        hipLaunchKernelGGL((k_temporal<true>), dim3(bx, by), dim3(kDnTile * kDnTile), 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, d_out, d_out_history);
+    else
+        hipLaunchKernelGGL((k_temporal<false>), dim3((uint32_t)lin_blocks), dim3(kDnTile * kDnTile), 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, d_out, d_out_history);
+    tm.end(5, st);
+    HIP_TRY(ctx, hipEventRecord(e1, st));
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (!is_device) {
+        HIP_TRY(ctx, hipMemcpy(out, d_out, film_bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out_history, d_out_history, planes_bytes, hipMemcpyDeviceToHost));
+    }
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        stats->ms_total = ms;
+        stats->ms_film = tm.total(5, &stats->launches_film);
+        stats->launches_film = 1;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return 0;
+}
+
+// Gauss-Jordan with partial pivoting on an n x n Float64 matrix (row-major, n <= 4); false when a pivot is zero or not finite.
+bool invert(const double* a, int n, double* inv) {
+    double m[4][8];
+    for (int r = 0; r < n; ++r)
+        for (int c = 0; c < n; ++c) {
+            m[r][c] = a[r * n + c];
+            m[r][n + c] = r == c ? 1.0 : 0.0;
+        }
+    for (int c = 0; c < n; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < n; ++r)
+            if (std::fabs(m[r][c]) > std::fabs(m[piv][c])) piv = r;
+        if (!(std::fabs(m[piv][c]) > 0.0) || !std::isfinite(m[piv][c])) return false;
+        for (int j = 0; j < 2 * n; ++j) std::swap(m[c][j], m[piv][j]);
+        const double d = m[c][c];
+        for (int j = 0; j < 2 * n; ++j) m[c][j] /= d;
+        for (int r = 0; r < n; ++r) {
+            if (r == c) continue;
+            const double f = m[r][c];
+            for (int j = 0; j < 2 * n; ++j) m[r][j] -= f * m[c][j];
+        }
+    }
+    for (int r = 0; r < n; ++r)
+        for (int c = 0; c < n; ++c) inv[r * n + c] = m[r][n + c];
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+// generate_ray (th_kernels.h) sends film position (rx, ry) along the camera-space direction A (rx, ry, 1), A = rows 0-2, columns 0, 1, 3 of raster_to_camera; hence
+// (rx, ry, 1) ~ A^-1 (camera_to_world^-1)[rows 0-2] (p, 1).  Film pixel X (1-based, crop_min <= X) has its centre at film position X + 0.5 and array index X - crop_min.
+int trhip_sensor_world_to_pixel(const trhip_sensor* sn, float out12[12]) {
+    if (!sn || !out12) return fail(nullptr, TRHIP_ERR_INVALID, "null argument");
+    double A[9], Ai[9], C[16], Ci[16];
+    for (int r = 0; r < 3; ++r) {
+        A[3 * r] = sn->raster_to_camera[4 * r];
+        A[3 * r + 1] = sn->raster_to_camera[4 * r + 1];
+        A[3 * r + 2] = sn->raster_to_camera[4 * r + 3];
+    }
+    for (int i = 0; i < 16; ++i) C[i] = sn->camera_to_world[i];
+    if (!invert(A, 3, Ai)) return fail(nullptr, TRHIP_ERR_INVALID, "trhip_sensor_world_to_pixel: raster_to_camera is singular");
+    if (!invert(C, 4, Ci)) return fail(nullptr, TRHIP_ERR_INVALID, "trhip_sensor_world_to_pixel: camera_to_world is singular");
+    double M[3][4];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) M[r][c] = (Ai[3 * r] * Ci[c] + Ai[3 * r + 1] * Ci[4 + c]) + Ai[3 * r + 2] * Ci[8 + c];
+    for (int c = 0; c < 4; ++c) {
+        M[0][c] -= ((double)sn->crop_min[0] + 0.5) * M[2][c];
+        M[1][c] -= ((double)sn->crop_min[1] + 0.5) * M[2][c];
+    }
+    float m[12];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) {
+            m[4 * r + c] = (float)M[r][c];
+            if (!std::isfinite(m[4 * r + c])) return fail(nullptr, TRHIP_ERR_INVALID, "trhip_sensor_world_to_pixel: the matrix is not finite in Float32");
+        }
+    std::memcpy(out12, m, sizeof m);
+    return 0;
+}
+
+int trhip_temporal_default_params(trhip_temporal_params* out) {
+    if (!out) return fail(nullptr, TRHIP_ERR_INVALID, "null argument");
+    std::memset(out, 0, sizeof *out);
+    // prev_world_to_pixel stays zero: h.z = 0 for every point, so a caller who forgets to fill it gets a frame without history, not a wrong one
+    out->max_history = 8.0f;  // the sweep of profiles/r11/temporal.txt: of 8, 16, 32, 64 the shortest did best on a 40-frame arc
+    out->sigma_normal = 0.25f;  // the denoiser's geometric sigmas (profiles/r9/denoise.txt)
+    out->sigma_plane = 0.1f;
+    out->min_coverage = 0.5f;
+    return 0;
+}
+int trhip_temporal(trhip_ctx* ctx, const float* xyzw, const float* planes, const float* history, uint32_t width, uint32_t height, const trhip_temporal_params* prm, float* out_xyzw,
+                   float* out_history, trhip_stats* st) {
+    return temporal_impl(ctx, xyzw, planes, history, width, height, prm, out_xyzw, out_history, false, st);
+}
+int trhip_temporal_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_history, uint32_t width, uint32_t height, const trhip_temporal_params* prm, void* d_out_xyzw,
+                          void* d_out_history, trhip_stats* st) {
+    return temporal_impl(ctx, d_xyzw, d_planes, d_history, width, height, prm, d_out_xyzw, d_out_history, true, st);
+}
+
+}  // extern "C"

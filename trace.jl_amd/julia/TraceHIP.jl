@@ -395,6 +395,8 @@ end
 
 # AmbientOcclusionIntegrator (trhip_render_ao) and its parameter block live in a file of their own, with their own ccall manifest (tests/golden/julia_shim_ao_calls.json)
 include("TraceHIPAO.jl")
+# TemporalAccumulator (trhip_temporal) and world_to_pixel, likewise (tests/golden/julia_shim_temporal_calls.json)
+include("TraceHIPTemporal.jl")
 
 # SPPMIntegrator (integrators/sppm.jl:132-173) on the device: trhip_render_sppm returns the film after set_image!
 # (film.jl:195-202).  `seed` selects the seeded stream of the camera pass (the reference draws from the global RNG there).
