@@ -264,9 +264,14 @@ def test_nested_bvh_as_primitive(T, ob, ctx):
 def test_banded_frame_equals_whole_frame(T, ob, ctx, rows):
     """A frame whose per-sample buffers do not fit in HBM (4096^2 x 1024 spp: 412 GB) is rendered in bands of whole tile rows into one
     film (option band_tile_rows forces it here): every film pixel still receives its tiles in the reference's k order, so the film is
-    the one-band film — and the oracle's — bit for bit, with every film-gather variant."""
+    the one-band film — and the oracle's — bit for bit, with every film-gather variant.  The bands trace the frame's rays, each once: every
+    additive counter of the banded frame's statistics equals the one-band frame's (the visit counts and the fallback reasons under
+    "count_visits", zeros without it), and n_batches counts the bands.  prims_tested_shadow is not compared: the any-hit pre-pass counts a
+    record once per WAVE (include/tracehip.h), and bands pack the same shadow rays into other waves (measured with one tile row per band:
+    11287 against the one-band frame's 10030)."""
     scene, cam = T.scenes.cornell_scene(), T.scenes.cornell_camera(100)
-    whole = T.PathIntegrator(cam, T.SeededSampler(3, seed=12), 5).render(scene, ctx).copy()
+    whole_integ = T.PathIntegrator(cam, T.SeededSampler(3, seed=12), 5)
+    whole = whole_integ.render(scene, ctx).copy()
     osc = ob.OracleScene.from_scene(scene, bvh=scene.flatten(ctx).bvh())
     ref, _, st_ref = osc.render(cam, "path", 3, 5, seed=12, threads=ob.lib().orc_num_threads())
     assert_bits_equal(whole, ref, "one band vs oracle")
@@ -281,3 +286,29 @@ def test_banded_frame_equals_whole_frame(T, ob, ctx, rows):
             ctx.set_option("film_block", 5)
         assert_bits_equal(banded, whole, f"bands of {rows} tile rows, film_block {film_block}")
         assert integ.stats.camera_samples == 102 * 102 * 3 and integ.stats.closest_rays == st_ref.closest_rays and integ.stats.launches_film == -(-7 // rows)
+        assert_counters_equal(integ.stats, whole_integ.stats, -(-7 // rows), f"bands of {rows} tile rows, film_block {film_block}")
+    ctx.set_option("count_visits", 1)
+    try:
+        counted_whole = T.PathIntegrator(cam, T.SeededSampler(3, seed=12), 5)
+        assert_bits_equal(counted_whole.render(scene, ctx), whole, "one band, count_visits")
+        ctx.set_option("band_tile_rows", rows)
+        counted = T.PathIntegrator(cam, T.SeededSampler(3, seed=12), 5)
+        assert_bits_equal(counted.render(scene, ctx), whole, f"bands of {rows} tile rows, count_visits")
+    finally:
+        ctx.set_option("band_tile_rows", 0)
+        ctx.set_option("count_visits", 0)
+    assert counted_whole.stats.nodes_visited > 0 and counted_whole.stats.nodes_visited_shadow > 0
+    assert_counters_equal(counted.stats, counted_whole.stats, -(-7 // rows), f"bands of {rows} tile rows, count_visits")
+
+
+ADDITIVE_COUNTERS = ("camera_samples", "closest_rays", "shadow_rays", "nodes_visited", "prims_tested", "nodes_visited_shadow", "fallback_rays", "nodes_visited_fallback",
+                     "prims_tested_fallback")  # (not prims_tested_shadow: see test_banded_frame_equals_whole_frame)
+
+
+def assert_counters_equal(banded, whole, n_bands, what):
+    got = {f: getattr(banded, f) for f in ADDITIVE_COUNTERS}
+    want = {f: getattr(whole, f) for f in ADDITIVE_COUNTERS}
+    print(what, got, list(banded.count_sub), banded.n_batches)
+    assert got == want, f"{what}: {got} != {want}"
+    assert list(banded.count_sub) == list(whole.count_sub), f"{what}: count_sub {list(banded.count_sub)} != {list(whole.count_sub)}"
+    assert banded.n_batches == n_bands and whole.n_batches == 1, f"{what}: n_batches {banded.n_batches}, {whole.n_batches}"

@@ -1,8 +1,9 @@
 // th_host.h — what the translation units of libtracehip.so share on the host side: the context and scene objects behind the opaque
 // handles of include/tracehip.h, error / buffer helpers, and the functions one unit calls in another.  Units (each compiled on its own
 // and linked into the one shared object): tu_api.hip (context, options, communicator), tu_scene.hip (scene flattening, commit, upload),
-// tu_lbvh.hip (BVH build on the device), tu_trace.hip / tu_trace3.hip / tu_trace8.hip (traversal launches and entry points),
-// tu_path.hip (PathIntegrator frames, film), tu_aov.hip (first-hit feature buffers), tu_ao.hip (ambient occlusion), tu_denoise.hip (the à-trous filter), tu_temporal.hip (temporal reprojection), tu_whitted.hip, tu_sppm.hip.
+// tu_lbvh.hip (BVH build on the device), tu_trace.hip / tu_trace3.hip / tu_trace3c.hip / tu_trace7.hip / tu_trace8.hip (traversal launches and entry points),
+// tu_path.hip (PathIntegrator frames, film, and the out-of-line part of the frame scaffold below: the stats functions), tu_aov.hip (first-hit feature buffers),
+// tu_ao.hip (ambient occlusion; the two share their camera-ray front half, th_camera.h), tu_denoise.hip (the à-trous filter), tu_temporal.hip (temporal reprojection), tu_whitted.hip, tu_sppm.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -381,6 +382,78 @@ struct Timer {
         return ms;
     }
 };
+// The event pair around the device work of one call (trhip_stats.ms_total).  Owned: whichever way the function returns, the events go with it.
+struct FrameEvents {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    FrameEvents() = default;
+    FrameEvents(const FrameEvents&) = delete;
+    FrameEvents& operator=(const FrameEvents&) = delete;
+    ~FrameEvents() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    hipError_t begin(hipStream_t st) {  // creates the pair and records its first event
+        if (hipError_t e = hipEventCreate(&e0)) return e;
+        if (hipError_t e = hipEventCreate(&e1)) return e;
+        return hipEventRecord(e0, st);
+    }
+    hipError_t end(hipStream_t st) { return hipEventRecord(e1, st); }
+    float ms() const {  // after the stream has been synchronised
+        float t = 0;
+        (void)hipEventElapsedTime(&t, e0, e1);
+        return t;
+    }
+};
+// One owned event without timing: a point in one stream that other streams wait for.
+struct OwnedEvent {
+    hipEvent_t e = nullptr;
+    OwnedEvent() = default;
+    OwnedEvent(const OwnedEvent&) = delete;
+    OwnedEvent& operator=(const OwnedEvent&) = delete;
+    ~OwnedEvent() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t create() { return hipEventCreateWithFlags(&e, hipEventDisableTiming); }
+};
+
+// ---- the frame scaffold of the render entry points ----------------------------------------------------------------------------------
+// Physical queue layout: kSeg segments of this many entries (th_kernels.h "SegQueue").  A segment receives at most P / kSeg + O(kSegGran) entries per bounce by
+// construction; `extra_segment_entries` is what an integrator appends to a segment on top of that (the streaming frame's resumed rays).
+inline uint64_t queue_cap(uint64_t P, uint64_t extra_segment_entries = 0) {
+    return ((P + kSeg - 1) / kSeg + 2 * kSegGran + extra_segment_entries + kSegGran - 1) / kSegGran * kSegGran;
+}
+// what the path frames' pipes hold of a frame's queues: reused by the next frame, so it counts as available to it
+inline size_t held_in_pipes(const trhip_ctx* ctx) {
+    size_t held = 0;
+    for (auto& pp : ctx->pipes) {
+        held += pp.hits.bytes;
+        for (auto& a : pp.q)
+            for (auto& b : a) held += b.bytes;
+        for (auto& b : pp.sq) held += b.bytes;
+    }
+    return held;
+}
+// The one-batch entry points (aov, ao, denoise, temporal) refuse a frame that needs more than 0.9 of what is free plus what the context already holds for it (`held`, reused).
+// *free_gb is that sum, for the caller's sentence.
+inline int fits_in_hbm(trhip_ctx* ctx, double need, size_t held, bool* fits, double* free_gb) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+    *fits = !(need > 0.9 * (double)(free_b + held));
+    *free_gb = (double)(free_b + held) * 1e-9;
+    return 0;
+}
+// Where a call writes an image: the caller's pointer when that is device memory, otherwise ctx->film grown to hold it, which copy_back brings to the caller.
+inline int stage_output(trhip_ctx* ctx, void* out, bool out_is_device, size_t bytes, void** d) {
+    *d = out;
+    if (out_is_device) return 0;
+    if (int rc = ensure(ctx, ctx->film, bytes)) return rc;
+    *d = ctx->film.p;
+    return 0;
+}
+inline int copy_back(trhip_ctx* ctx, void* out, bool out_is_device, const void* d, size_t bytes) {
+    if (!out_is_device) HIP_TRY(ctx, hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
 
 // ---- functions one unit calls in another ---------------------------------------------------------------------------------------------
 // tu_scene.hip
@@ -431,6 +504,11 @@ bool film_uses_packed(const trhip_ctx* ctx, const DeviceSensor& ds);
 int ensure_film_samples(trhip_ctx* ctx, const DeviceSensor& ds, uint64_t total_slots);
 void launch_film(trhip_ctx* ctx, hipStream_t st, const DeviceSensor& ds, const DeviceSensor* dsp, const float4* L, uint64_t total_slots, uint32_t spp, uint64_t seed, uint32_t sample_offset,
                  float4* d_film, bool fused);
+// … the one place that turns device counters and event times into trhip_stats.  A frame's stats are: zeros, stats_add_counters for every Counters block it ran on,
+// stats_fill_times, and what only the caller knows (camera_samples, n_batches, max_depth_reached, an integrator's ms_sub / count_sub)
+void stats_add_counters(trhip_stats& s, const Counters& h);  // += the ray, node-visit and primitive-test totals, the fallback totals and the fallback reasons (count_sub)
+void stats_fill_times(trhip_ctx* ctx, const trhip_scene* sc, Timer& tm, const FrameEvents& ev, trhip_stats& s);  // ms_total, Timer classes 0-4, the fallback share, traversal_info
+void stats_accumulate(trhip_stats& sum, const trhip_stats& band);  // a banded frame: += every additive field; max_depth_reached, traversal, node_bytes as the last band has them
 // tu_whitted.hip
 int render_whitted_impl(trhip_ctx* ctx, const trhip_scene* scene, const DeviceSensor& ds, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
-                        void* d_film, trhip_stats* stats, double* ms_total);
+                        void* d_film, trhip_stats* stats);

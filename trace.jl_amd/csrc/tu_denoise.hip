@@ -34,13 +34,14 @@ int denoise_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, uint32_t 
     const size_t film_bytes = (size_t)npix * sizeof(float4), planes_bytes = 3 * film_bytes;
     const uint32_t bx = (width + kDnTile - 1) / kDnTile, by = (height + kDnTile - 1) / kDnTile;
     {
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
         const size_t held = ctx->dn_work.bytes + ctx->dn_in.bytes;  // reused below
         const double need = (double)npix * kDnBytesPerPixel + (is_device ? 0.0 : (double)(film_bytes + planes_bytes));
-        if (by > 65535u || need > 0.9 * (double)(free_b + held))
+        bool fits;
+        double free_gb;
+        if (int rc = fits_in_hbm(ctx, need, held, &fits, &free_gb)) return rc;
+        if (by > 65535u || !fits)
             return fail(ctx, TRHIP_ERR_UNSUPPORTED, "trhip_denoise: the working set of a %u x %u film (%.1f GB, 80 B per pixel) does not fit in free HBM (%.1f GB free); there are no bands here", width,
-                        height, need * 1e-9, (double)(free_b + held) * 1e-9);
+                        height, need * 1e-9, free_gb);
     }
     if (int rc = ensure(ctx, ctx->dn_work, (size_t)npix * kDnBytesPerPixel)) return rc;
     const float4* d_beauty = (const float4*)xyzw;
@@ -59,10 +60,8 @@ int denoise_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, uint32_t 
     const uint32_t demodulate = prm->flags & TRHIP_DENOISE_DEMODULATE;
 
     Timer tm(ctx, ctx->timing && stats);
-    hipEvent_t e0, e1;
-    HIP_TRY(ctx, hipEventCreate(&e0));
-    HIP_TRY(ctx, hipEventCreate(&e1));
-    HIP_TRY(ctx, hipEventRecord(e0, st));
+    FrameEvents ev;
+    HIP_TRY(ctx, ev.begin(st));
     if (prm->iterations == 0) {
         if (d_out != d_beauty) HIP_TRY(ctx, hipMemcpyAsync(d_out, d_beauty, film_bytes, hipMemcpyDeviceToDevice, st));
     } else {
@@ -90,23 +89,19 @@ int denoise_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, uint32_t 
         hipLaunchKernelGGL(k_denoise_finish, dim3(lin_grid), dim3(kBlock), 0, st, d_beauty, gn, col[prm->iterations & 1], alb, npix, demodulate, d_out);
         tm.end(7, st);
     }
-    HIP_TRY(ctx, hipEventRecord(e1, st));
+    HIP_TRY(ctx, ev.end(st));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (!is_device) HIP_TRY(ctx, hipMemcpy(out, d_out, film_bytes, hipMemcpyDeviceToHost));
     if (stats) {
         std::memset(stats, 0, sizeof *stats);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        stats->ms_total = ms;
+        stats->ms_total = ev.ms();
         for (int k = 0; k < 3; ++k) {  // prepare, the iterations, finish
             stats->ms_sub[k] = tm.total(5 + k, &stats->launches_sub[k]);
             stats->ms_film += stats->ms_sub[k];
             stats->launches_film += stats->launches_sub[k];
         }
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return 0;
 }
 

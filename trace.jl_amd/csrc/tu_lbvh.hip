@@ -90,12 +90,6 @@ int build_bvh_device_sah(trhip_ctx* ctx, const std::vector<HostAABB>& pb, int ma
             if (p) (void)hipFree(p);
         }
     };
-    struct Ev {
-        hipEvent_t e = nullptr;
-        ~Ev() {
-            if (e) (void)hipEventDestroy(e);
-        }
-    };
     const uint32_t pool = 2 * n, cap_active = n / kSahSmall + 2;
     Buf d_pb, d_cen, d_idx[2], d_pos[2], d_nb, d_nu, d_cnt, d_act, d_lvl, d_bins, d_flag, d_scan, d_tmp, d_fb, d_fa, d_ff;
     HIP_TRY(ctx, hipMalloc(&d_pb.p, (size_t)n * 6 * sizeof(float)));
@@ -116,12 +110,10 @@ int build_bvh_device_sah(trhip_ctx* ctx, const std::vector<HostAABB>& pb, int ma
     HIP_TRY(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const uint32_t*)d_flag.p, (uint32_t*)d_scan.p, (int)(n + 1), ctx->stream));
     HIP_TRY(ctx, hipMalloc(&d_tmp.p, tmp_bytes));
     hipStream_t st = ctx->stream;
-    Ev e0, e1;
-    HIP_TRY(ctx, hipEventCreate(&e0.e));
-    HIP_TRY(ctx, hipEventCreate(&e1.e));
+    FrameEvents ev;
     static_assert(sizeof(HostAABB) == 6 * sizeof(float), "HostAABB layout");
     HIP_TRY(ctx, hipMemcpyAsync(d_pb.p, pb.data(), (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipEventRecord(e0.e, st));
+    HIP_TRY(ctx, ev.begin(st));
     uint32_t* nu = (uint32_t*)d_nu.p;
     uint32_t* au = (uint32_t*)d_act.p;
     SahBuild b{};
@@ -198,11 +190,11 @@ int build_bvh_device_sah(trhip_ctx* ctx, const std::vector<HostAABB>& pb, int ma
     const SahFlat f{(float*)d_fb.p, (uint32_t*)d_fa.p, (uint32_t*)d_ff.p};
     hipLaunchKernelGGL(k_sah_flatten, gridt, blk, 0, st, b, total, f);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(e1.e, st));
+    HIP_TRY(ctx, ev.end(st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (ms_device) {
         float ms = 0.0f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, e0.e, e1.e));
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ev.e0, ev.e1));
         *ms_device = ms;
     }
     out.bounds.resize((size_t)total * 6);

@@ -151,6 +151,60 @@ void launch_film(trhip_ctx* ctx, hipStream_t st, const DeviceSensor& ds, const D
     }
 }
 
+// ---- the frame scaffold's out-of-line part (th_host.h) ----
+void stats_add_counters(trhip_stats& s, const Counters& h) {
+    s.closest_rays += h.closest_total;
+    s.shadow_rays += h.shadow_total;
+    s.nodes_visited += h.nodes_closest;
+    s.prims_tested += h.prims_closest;
+    s.nodes_visited_shadow += h.nodes_shadow;
+    s.prims_tested_shadow += h.prims_shadow;
+    s.fallback_rays += h.fallback_total;
+    s.nodes_visited_fallback += h.nodes_fallback;
+    s.prims_tested_fallback += h.prims_fallback;
+    for (int k = 0; k < 4; ++k) s.count_sub[k] += h.fallback_why[k];
+}
+void stats_fill_times(trhip_ctx* ctx, const trhip_scene* sc, Timer& tm, const FrameEvents& ev, trhip_stats& s) {
+    s.ms_total = ev.ms();
+    s.ms_raygen = tm.total(0, &s.launches_raygen);
+    s.ms_trace_closest = tm.total(1, &s.launches_trace_closest);
+    s.ms_fallback = tm.fallback_total(&s.launches_fallback);
+    s.ms_shade = tm.total(2, &s.launches_shade);
+    s.ms_trace_any = tm.total(3, &s.launches_trace_any);
+    s.ms_film = tm.total(4, &s.launches_film);
+    traversal_info(ctx, sc, &s.traversal, &s.node_bytes);
+}
+void stats_accumulate(trhip_stats& sum, const trhip_stats& band) {
+    sum.camera_samples += band.camera_samples;
+    sum.closest_rays += band.closest_rays;
+    sum.shadow_rays += band.shadow_rays;
+    sum.nodes_visited += band.nodes_visited;
+    sum.prims_tested += band.prims_tested;
+    sum.nodes_visited_shadow += band.nodes_visited_shadow;
+    sum.prims_tested_shadow += band.prims_tested_shadow;
+    sum.fallback_rays += band.fallback_rays;
+    sum.nodes_visited_fallback += band.nodes_visited_fallback;
+    sum.prims_tested_fallback += band.prims_tested_fallback;
+    for (int k = 0; k < 4; ++k) sum.count_sub[k] += band.count_sub[k];
+    sum.ms_total += band.ms_total;
+    sum.ms_raygen += band.ms_raygen;
+    sum.ms_trace_closest += band.ms_trace_closest;
+    sum.ms_fallback += band.ms_fallback;
+    sum.ms_shade += band.ms_shade;
+    sum.ms_trace_any += band.ms_trace_any;
+    sum.ms_film += band.ms_film;
+    sum.launches_raygen += band.launches_raygen;
+    sum.launches_trace_closest += band.launches_trace_closest;
+    sum.launches_fallback += band.launches_fallback;
+    sum.launches_shade += band.launches_shade;
+    sum.launches_trace_any += band.launches_trace_any;
+    sum.launches_film += band.launches_film;
+    sum.n_batches += band.n_batches;
+    sum.max_depth_reached = band.max_depth_reached;
+    sum.traversal = band.traversal;
+    sum.node_bytes = band.node_bytes;
+}
+
 namespace {
 // PathIntegrator as a STREAMING wavefront (th_trace2.h "streaming wavefront"): rounds instead of depths.  A round
 // traces every queued ray with a fetch budget, resumes the rays suspended in the round before, shades what finished (entries
@@ -168,7 +222,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
     if (total_slots >= (1ull << 31)) return 0;  // one batch: queue indices are 32-bit
     const uint64_t P = total_slots;
     const uint32_t list_cap = ctx->stream_list_cap ? ctx->stream_list_cap : (uint32_t)std::max<uint64_t>(65536, P / 128);
-    const uint32_t cap = (uint32_t)(((P + kSeg - 1) / kSeg + 2 * kSegGran + list_cap / kSeg + 64 + kSegGran - 1) / kSegGran * kSegGran);
+    const uint32_t cap = (uint32_t)queue_cap(P, list_cap / kSeg + 64);  // every segment keeps room for the resumed rays appended to it
     const uint64_t Pphys = (uint64_t)cap * kSeg;
     const size_t list_bytes = (size_t)list_cap * (4 * 16 + 16 + 4 + (size_t)kStack2Total * 8);
     const size_t terms_bytes = (size_t)max_depth * total_slots * sizeof(float4);
@@ -222,11 +276,8 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
             for (int f = 0; f < 7; ++f)
                 if (int rc = ensure(ctx, ctx->st_list[kind][pg][f], (size_t)list_cap * field_bytes[f])) return rc;
     const size_t film_bytes = (size_t)ds.film_w * ds.film_h * sizeof(float4);
-    void* d_film = out;
-    if (!out_is_device) {
-        if (int rc = ensure(ctx, ctx->film, film_bytes)) return rc;
-        d_film = ctx->film.p;
-    }
+    void* d_film;
+    if (int rc = stage_output(ctx, out, out_is_device, film_bytes, &d_film)) return rc;
     auto list_of = [&](int kind, int pg) {
         DevBuf* b = ctx->st_list[kind][pg];
         return SuspendList{(float4*)b[0].p, (float4*)b[1].p, (float4*)b[2].p, (float4*)b[3].p, (uint4*)b[4].p, (uint32_t*)b[5].p, (uint2*)b[6].p, list_cap};
@@ -245,14 +296,13 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
     uint32_t* frozen = (uint32_t*)ctx->st_frozen.p;
 
     Timer tm(ctx, ctx->timing && stats);
-    hipEvent_t e0, e1, ev_start;
-    HIP_TRY(ctx, hipEventCreate(&e0));
-    HIP_TRY(ctx, hipEventCreate(&e1));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ev_start, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventRecord(e0, st));
+    FrameEvents ev;
+    OwnedEvent ev_start;
+    HIP_TRY(ctx, ev_start.create());
+    HIP_TRY(ctx, ev.begin(st));
     HIP_TRY(ctx, hipMemsetAsync(terms, 0, terms_bytes, st));
-    HIP_TRY(ctx, hipEventRecord(ev_start, st));
-    HIP_TRY(ctx, hipStreamWaitEvent(ps, ev_start, 0));
+    HIP_TRY(ctx, hipEventRecord(ev_start.e, st));
+    HIP_TRY(ctx, hipStreamWaitEvent(ps, ev_start.e, 0));
     HIP_TRY(ctx, hipMemsetAsync(ctr, 0, sizeof(Counters), ps));
     HIP_TRY(ctx, hipMemsetAsync(lc, 0, 16 * sizeof(uint32_t), ps));
     tm.begin(0, ps);
@@ -316,12 +366,12 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
     //  poison; ctx->poison belongs to the classic path's two-stream mode alone)
     launch_film(ctx, st, ds, dsp, L, total_slots, spp, seed, sample_offset, (float4*)d_film, false);
     tm.end(4, st);
-    HIP_TRY(ctx, hipEventRecord(e1, st));
+    HIP_TRY(ctx, ev.end(st));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));
     ctx->last_L_count = total_slots;
     ctx->last_L_layout = 0;
-    if (!out_is_device) HIP_TRY(ctx, hipMemcpy(out, d_film, film_bytes, hipMemcpyDeviceToHost));
+    if (int rc = copy_back(ctx, out, out_is_device, d_film, film_bytes)) return rc;
     uint32_t left[8];
     HIP_TRY(ctx, hipMemcpy(left, lc, sizeof left, hipMemcpyDeviceToHost));
     if (stats) {
@@ -329,31 +379,11 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
         stats->camera_samples = total_slots;
         Counters h;
         HIP_TRY(ctx, hipMemcpy(&h, ctr, sizeof h, hipMemcpyDeviceToHost));
-        stats->closest_rays = h.closest_total;
-        stats->shadow_rays = h.shadow_total;
-        stats->nodes_visited = h.nodes_closest;
-        stats->prims_tested = h.prims_closest;
-        stats->nodes_visited_shadow = h.nodes_shadow;
-        stats->prims_tested_shadow = h.prims_shadow;
-        stats->fallback_rays = h.fallback_total;
-        stats->nodes_visited_fallback = h.nodes_fallback;
-        stats->prims_tested_fallback = h.prims_fallback;
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        stats->ms_total = ms;
-        stats->ms_raygen = tm.total(0, &stats->launches_raygen);
-        stats->ms_trace_closest = tm.total(1, &stats->launches_trace_closest);
-        stats->ms_fallback = tm.fallback_total(&stats->launches_fallback);
-        stats->ms_shade = tm.total(2, &stats->launches_shade);
-        stats->ms_trace_any = tm.total(3, &stats->launches_trace_any);
-        stats->ms_film = tm.total(4, &stats->launches_film);
+        stats_add_counters(*stats, h);
+        stats_fill_times(ctx, scene, tm, ev, *stats);
         stats->n_batches = 1;
         stats->max_depth_reached = (uint32_t)max_depth;
-        traversal_info(ctx, scene, &stats->traversal, &stats->node_bytes);
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipEventDestroy(ev_start);
     if (left[R & 1] || left[4 + (R & 1)]) return fail(ctx, TRHIP_ERR_HIP, "streaming wavefront: %u + %u rays still suspended after the drain rounds", left[R & 1], left[4 + (R & 1)]);
     return 0;
 }
@@ -395,33 +425,12 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         if (int rc = ensure_film_samples(ctx, ds, total_slots)) return rc;
         if (int rc = ensure(ctx, ctx->counters, sizeof(Counters))) return rc;
         const size_t fb = (size_t)ds.film_w * ds.film_h * sizeof(float4);
-        void* df = out;
-        if (!out_is_device) {
-            if (int rc = ensure(ctx, ctx->film, fb)) return rc;
-            df = ctx->film.p;
-        }
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        double ms = 0;
-        if (int rc = render_whitted_impl(ctx, scene, ds, sensor, spp, max_depth, seed, sample_offset, df, stats, &ms)) return rc;
+        void* df;
+        if (int rc = stage_output(ctx, out, out_is_device, fb, &df)) return rc;
+        if (int rc = render_whitted_impl(ctx, scene, ds, sensor, spp, max_depth, seed, sample_offset, df, stats)) return rc;
         ctx->last_L_count = total_slots;
         ctx->last_L_layout = 0;
-        if (!out_is_device) HIP_TRY(ctx, hipMemcpy(out, df, fb, hipMemcpyDeviceToHost));
-        if (stats) {
-            Counters h;
-            HIP_TRY(ctx, hipMemcpy(&h, ctx->counters.p, sizeof h, hipMemcpyDeviceToHost));
-            stats->camera_samples = total_slots;
-            stats->closest_rays = h.closest_total;
-            stats->shadow_rays = h.shadow_total;
-            stats->nodes_visited = h.nodes_closest;
-            stats->prims_tested = h.prims_closest;
-            stats->nodes_visited_shadow = h.nodes_shadow;
-            stats->prims_tested_shadow = h.prims_shadow;
-            stats->fallback_rays = h.fallback_total;
-            stats->ms_total = ms;
-            stats->max_depth_reached = (uint32_t)max_depth;
-        traversal_info(ctx, scene, &stats->traversal, &stats->node_bytes);
-        }
-        return 0;
+        return copy_back(ctx, out, out_is_device, df, fb);
     }
     if (!band && (ctx->streaming == 1 || (ctx->streaming < 0 && total_slots <= 96ull * scene->g->prims.size())) && ctx->traversal >= 2 && scene->wide_ok && scene->wide.root_cnt == 0 && scene->wide.root_ref != kRefNone && ctx->batch_paths == 0 && ctx->pipelines <= 1) {
         bool declined = false;
@@ -433,13 +442,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     if (batch_paths == 0) {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
-        size_t held = ctx->Lbuf.bytes + ctx->pfilm.bytes;  // reused below, so it counts as available
-        for (auto& pp : ctx->pipes) {
-            held += pp.hits.bytes;
-            for (auto& a : pp.q)
-                for (auto& b : a) held += b.bytes;
-            for (auto& b : pp.sq) held += b.bytes;
-        }
+        const size_t held = ctx->Lbuf.bytes + ctx->pfilm.bytes + held_in_pipes(ctx);  // reused below, so it counts as available
         const double avail = 0.85 * (double)(free_b + held) - (double)total_slots * (sizeof(float4) + sizeof(float2)) - 2.5e9;
         batch_paths = avail > 0 ? (uint64_t)(avail / 212.0) : npix;  // per path in flight: 2 x 3 queue float4 + 2 x 3 shadow float4 + 1 hit float4 + counters
     }
@@ -453,9 +456,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     const uint64_t n_batches_total = (spp + spp_batch - 1) / spp_batch;
     const int NP = (int)std::min<uint64_t>(want_pipes, n_batches_total);
     const uint64_t P = npix * spp_batch;
-    // physical queue layout: kSeg segments of `cap` entries (th_kernels.h "SegQueue"); a segment receives at most
-    // P/kSeg + O(kSegGran) entries per bounce by construction
-    const uint32_t cap = (uint32_t)(((P + kSeg - 1) / kSeg + 2 * kSegGran + kSegGran - 1) / kSegGran * kSegGran);
+    const uint32_t cap = (uint32_t)queue_cap(P);
     const uint64_t Pphys = (uint64_t)cap * kSeg;
     if (int rc = upload(ctx, ctx->sensor, &ds, sizeof ds)) return rc;
     if (int rc = upload(ctx, ctx->table, sensor->filter_table, 256 * sizeof(float))) return rc;
@@ -497,37 +498,33 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     if (int rc = ensure(ctx, ctx->Lbuf, l_slots * sizeof(float4))) return rc;
     if (int rc = ensure_film_samples(ctx, ds, total_slots)) return rc;
     const size_t film_bytes = (size_t)ds.film_w * ds.film_h * sizeof(float4);
-    void* d_film = out;
-    if (!out_is_device) {
-        if (int rc = ensure(ctx, ctx->film, film_bytes)) return rc;
-        d_film = ctx->film.p;
-    }
+    void* d_film;
+    if (int rc = stage_output(ctx, out, out_is_device, film_bytes, &d_film)) return rc;
     hipStream_t st = ctx->stream;
     const DeviceSensor* dsp = (const DeviceSensor*)ctx->sensor.p;
     float4* L = (float4*)ctx->Lbuf.p;
 
     hclk.tick("setup (budget, buffers)");
     Timer tm(ctx, ctx->timing && stats);
-    hipEvent_t e0, e1, ev_start;
-    HIP_TRY(ctx, hipEventCreate(&e0));
-    HIP_TRY(ctx, hipEventCreate(&e1));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ev_start, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventRecord(e0, st));
+    FrameEvents ev;
+    OwnedEvent ev_start;
+    HIP_TRY(ctx, ev_start.create());
+    HIP_TRY(ctx, ev.begin(st));
     FilmSideTable fside{nullptr, nullptr, 0};
     if (fused) {
         bool ok = false;
         fside = film_side_table(ctx, st, total_slots, &ok);
-        if (!ok) return TRHIP_ERR_HIP;
+        if (!ok) return fail(ctx, TRHIP_ERR_HIP, "the film pass's side table for %llu camera samples: %s", (unsigned long long)total_slots, ctx->err.c_str());
     } else {
         HIP_TRY(ctx, hipMemsetAsync(L, 0, total_slots * sizeof(float4), st));
     }
     HIP_TRY(ctx, hipMemsetAsync(ctx->poison.p, 0, l_slots, st));
-    HIP_TRY(ctx, hipEventRecord(ev_start, st));
+    HIP_TRY(ctx, hipEventRecord(ev_start.e, st));
     const int g_shade = ctx->num_cu * 8;
     const uint32_t bary_mode = (ctx->traversal >= 2 && scene->wide_ok) ? 1u : 0u;  // k_trace2 hands the barycentrics to the shading kernel
     uint32_t n_batches = 0;
     for (int pi = 0; pi < NP; ++pi) {
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipes[pi].st, ev_start, 0));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipes[pi].st, ev_start.e, 0));
         HIP_TRY(ctx, hipMemsetAsync(ctx->pipes[pi].counters.p, 0, sizeof(Counters), ctx->pipes[pi].st));
     }
     for (uint64_t s0 = 0; s0 < spp; s0 += spp_batch) {
@@ -599,42 +596,24 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     ctx->last_L_layout = fused ? 1u : 0u;
     ctx->last_L_npix = (uint32_t)npix;
     ctx->last_L_spp = spp;
-    HIP_TRY(ctx, hipEventRecord(e1, st));
+    HIP_TRY(ctx, ev.end(st));
     HIP_TRY(ctx, hipGetLastError());
     hclk.tick("enqueue");
     HIP_TRY(ctx, hipStreamSynchronize(st));
     hclk.tick("stream sync");
     ctx->last_L_count = total_slots;
-    if (!out_is_device) HIP_TRY(ctx, hipMemcpy(out, d_film, film_bytes, hipMemcpyDeviceToHost));
+    if (int rc = copy_back(ctx, out, out_is_device, d_film, film_bytes)) return rc;
     if (stats) {
         std::memset(stats, 0, sizeof *stats);
         stats->camera_samples = total_slots;
         for (int pi = 0; pi < NP; ++pi) {
             Counters h;
             HIP_TRY(ctx, hipMemcpy(&h, ctx->pipes[pi].counters.p, sizeof h, hipMemcpyDeviceToHost));
-            stats->closest_rays += h.closest_total;
-            stats->shadow_rays += h.shadow_total;
-            stats->nodes_visited += h.nodes_closest;
-            stats->prims_tested += h.prims_closest;
-            stats->nodes_visited_shadow += h.nodes_shadow;
-            stats->prims_tested_shadow += h.prims_shadow;
-            stats->fallback_rays += h.fallback_total;
-            stats->nodes_visited_fallback += h.nodes_fallback;
-            stats->prims_tested_fallback += h.prims_fallback;
-            for (int k = 0; k < 4; ++k) stats->count_sub[k] += h.fallback_why[k];
+            stats_add_counters(*stats, h);
         }
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        stats->ms_total = ms;
-        stats->ms_raygen = tm.total(0, &stats->launches_raygen);
-        stats->ms_trace_closest = tm.total(1, &stats->launches_trace_closest);
-        stats->ms_fallback = tm.fallback_total(&stats->launches_fallback);
-        stats->ms_shade = tm.total(2, &stats->launches_shade);
-        stats->ms_trace_any = tm.total(3, &stats->launches_trace_any);
-        stats->ms_film = tm.total(4, &stats->launches_film);
+        stats_fill_times(ctx, scene, tm, ev, *stats);
         stats->n_batches = n_batches;
         stats->max_depth_reached = (uint32_t)max_depth;
-        traversal_info(ctx, scene, &stats->traversal, &stats->node_bytes);
         // The certified walk's cliff: scenes made of near-ties (tiny coplanar triangles, rays in a wall's plane — tests/attack_scenes.py) send up to half of their rays to the
         // reference-order walk: exact, at about twice the closest-hit time.  Said once per context, and kept for trhip_accelerator_note.
         ctx->last_fallback_share = stats->closest_rays ? (double)stats->fallback_rays / (double)stats->closest_rays : 0.0;
@@ -645,9 +624,6 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         }
     }
     hclk.tick("counters + event times");
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipEventDestroy(ev_start);
     return 0;
 }
 
@@ -685,13 +661,7 @@ int render_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* se
         } else {
             size_t free_b = 0, total_b = 0;
             HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
-            size_t held = ctx->Lbuf.bytes + ctx->pfilm.bytes;
-            for (auto& pp : ctx->pipes) {
-                held += pp.hits.bytes;
-                for (auto& a : pp.q)
-                    for (auto& b : a) held += b.bytes;
-                for (auto& b : pp.sq) held += b.bytes;
-            }
+            const size_t held = ctx->Lbuf.bytes + ctx->pfilm.bytes + held_in_pipes(ctx);
             // half of what is free for the per-sample buffers, the rest for the wavefront queues (164 B per path in flight); 32-bit slot indices
             const double budget = std::min(0.5 * (double)(free_b + held), 4.0e9 * 24.0);
             rows_per_band = plan_rows_per_band(ds, spp, budget, film_uses_packed(ctx, ds) ? 17.0 : film_uses_desc(ctx, ds) ? 33.0 : 25.0);  // radiance (+ descriptor / film position) + poison byte
@@ -699,11 +669,8 @@ int render_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* se
     }
     if (rows_per_band >= ds.tiles_y) return render_impl_band(ctx, scene, sensor, integrator, spp, max_depth, seed, sample_offset, out, out_is_device, stats, nullptr);
     const size_t film_bytes = (size_t)ds.film_w * ds.film_h * sizeof(float4);
-    void* d_film = out;
-    if (!out_is_device) {
-        if (int rc = ensure(ctx, ctx->film, film_bytes)) return rc;
-        d_film = ctx->film.p;
-    }
+    void* d_film;
+    if (int rc = stage_output(ctx, out, out_is_device, film_bytes, &d_film)) return rc;
     trhip_stats sum;
     std::memset(&sum, 0, sizeof sum);
     uint32_t n_bands = 0;
@@ -711,38 +678,11 @@ int render_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* se
         const DeviceSensor b = band_of(ds, t0, rows_per_band);
         trhip_stats st;
         if (int rc = render_impl_band(ctx, scene, sensor, integrator, spp, max_depth, seed, sample_offset, d_film, true, &st, &b)) return rc;
-        sum.camera_samples += st.camera_samples;
-        sum.closest_rays += st.closest_rays;
-        sum.shadow_rays += st.shadow_rays;
-        sum.nodes_visited += st.nodes_visited;
-        sum.prims_tested += st.prims_tested;
-        sum.nodes_visited_shadow += st.nodes_visited_shadow;
-        sum.prims_tested_shadow += st.prims_tested_shadow;
-        sum.fallback_rays += st.fallback_rays;
-        sum.nodes_visited_fallback += st.nodes_visited_fallback;
-        sum.prims_tested_fallback += st.prims_tested_fallback;
-        sum.ms_fallback += st.ms_fallback;
-        sum.launches_fallback += st.launches_fallback;
-        for (int k = 0; k < 4; ++k) sum.count_sub[k] += st.count_sub[k];
-        sum.ms_total += st.ms_total;
-        sum.ms_raygen += st.ms_raygen;
-        sum.ms_trace_closest += st.ms_trace_closest;
-        sum.ms_shade += st.ms_shade;
-        sum.ms_trace_any += st.ms_trace_any;
-        sum.ms_film += st.ms_film;
-        sum.launches_raygen += st.launches_raygen;
-        sum.launches_trace_closest += st.launches_trace_closest;
-        sum.launches_shade += st.launches_shade;
-        sum.launches_trace_any += st.launches_trace_any;
-        sum.launches_film += st.launches_film;
-        sum.n_batches += st.n_batches;
-        sum.max_depth_reached = st.max_depth_reached;
-        sum.traversal = st.traversal;
-        sum.node_bytes = st.node_bytes;
+        stats_accumulate(sum, st);
     }
     ctx->last_L_count = 0;  // trhip_last_sample_radiance describes whole frames only
     ctx->last_L_layout = 0;
-    if (!out_is_device) HIP_TRY(ctx, hipMemcpy(out, d_film, film_bytes, hipMemcpyDeviceToHost));
+    if (int rc = copy_back(ctx, out, out_is_device, d_film, film_bytes)) return rc;
     if (stats) *stats = sum;
     return 0;
 }

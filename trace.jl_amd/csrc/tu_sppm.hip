@@ -96,7 +96,7 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     if ((uint64_t)P * ndep >= (1ull << 32))
         return fail(ctx, TRHIP_ERR_UNSUPPORTED, "SPPM: photons_per_iteration x (max_depth - 1%s) must stay below 2^32", xing ? " + TRHIP_SPPM_MAX_CROSSINGS" : "");
     const uint64_t Q = B * Qit;
-    const uint32_t cap = (uint32_t)(((Q + kSeg - 1) / kSeg + 2 * kSegGran + kSegGran - 1) / kSegGran * kSegGran);
+    const uint32_t cap = (uint32_t)queue_cap(Q);
     const uint64_t Pphys = (uint64_t)cap * kSeg;
     Pipe& pp = ctx->pipes[0];
     if (!pp.st) {
@@ -171,10 +171,8 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     uint32_t* hot_list = (uint32_t*)ctx->scratch[2].p;
 
     Timer tm(ctx, ctx->timing && stats);
-    hipEvent_t e0, e1;
-    HIP_TRY(ctx, hipEventCreate(&e0));
-    HIP_TRY(ctx, hipEventCreate(&e1));
-    HIP_TRY(ctx, hipEventRecord(e0, st));
+    FrameEvents ev;
+    HIP_TRY(ctx, ev.begin(st));
     // pixels = [SPPMPixel(radius = initial_search_radius) …] (:136-139)
     HIP_TRY(ctx, hipMemsetAsync(counts, 0, (size_t)n * sizeof(uint32_t), st));  // once per call: every iteration leaves them at zero again
     HIP_TRY(ctx, hipMemsetAsync(px.Ld, 0, (size_t)n * sizeof(float4), st));
@@ -364,7 +362,7 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     tm.begin(4, st);
     hipLaunchKernelGGL(k_sppm_image, g_pix, blk, 0, st, n, n_iterations, (uint64_t)P, px, (float4*)ctx->film.p);
     tm.end(4, st);
-    HIP_TRY(ctx, hipEventRecord(e1, st));
+    HIP_TRY(ctx, ev.end(st));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (int rc = over_cap()) return rc;
@@ -376,33 +374,18 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         Counters h;
         HIP_TRY(ctx, hipMemcpy(&h, ctr, sizeof h, hipMemcpyDeviceToHost));
         stats->camera_samples = (uint64_t)n * n_iterations;
-        stats->closest_rays = h.closest_total;
-        stats->shadow_rays = h.shadow_total;
-        stats->nodes_visited = h.nodes_closest;
-        stats->prims_tested = h.prims_closest;
-        stats->nodes_visited_shadow = h.nodes_shadow;
-        stats->prims_tested_shadow = h.prims_shadow;
-        stats->fallback_rays = h.fallback_total;
-        stats->nodes_visited_fallback = h.nodes_fallback;
-        stats->prims_tested_fallback = h.prims_fallback;
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        stats->ms_total = ms;
-        stats->ms_raygen = tm.total(0, &stats->launches_raygen);
-        stats->ms_trace_closest = tm.total(1, &stats->launches_trace_closest);
-        stats->ms_fallback = tm.fallback_total(&stats->launches_fallback);
+        stats_add_counters(*stats, h);
+        stats_fill_times(ctx, scene, tm, ev, *stats);
+        // ms_shade regrouped: class 2 is one of its four parts here
         stats->ms_sub[0] = tm.total(5, &stats->launches_sub[0]);  // photon gather
         stats->ms_sub[1] = tm.total(2, &stats->launches_sub[1]);  // camera / photon shading
         stats->ms_sub[2] = tm.total(6, &stats->launches_sub[2]);  // grid bounds, hit binning, scans
         stats->ms_sub[3] = tm.total(7, &stats->launches_sub[3]);  // Ld fold, pixel update
         stats->ms_shade = stats->ms_sub[0] + stats->ms_sub[1] + stats->ms_sub[2] + stats->ms_sub[3];
         stats->launches_shade = stats->launches_sub[0] + stats->launches_sub[1] + stats->launches_sub[2] + stats->launches_sub[3];
-        stats->ms_trace_any = tm.total(3, &stats->launches_trace_any);
-        stats->ms_film = tm.total(4, &stats->launches_film);
         stats->n_batches = n_batches;
         stats->max_depth_reached = (uint32_t)max_depth;
-        traversal_info(ctx, scene, &stats->traversal, &stats->node_bytes);
-        if (ctx->count_visits) {
+        if (ctx->count_visits) {  // the gather's counts take the place of the fallback reasons
             stats->count_sub[0] = gi.stat_candidates;
             stats->count_sub[1] = gi.stat_accepted;
             stats->count_sub[2] = gi.photon_hits;
@@ -418,8 +401,6 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
             prev_s = snap[4 * b + 3];
         }
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return 0;
 }
 }  // namespace

@@ -46,13 +46,14 @@ int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const vo
     const uint32_t bx = (width + kDnTile - 1) / kDnTile, by = (height + kDnTile - 1) / kDnTile;
     const uint64_t lin_blocks = (npix + kDnTile * kDnTile - 1) / (kDnTile * kDnTile);
     {
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
         const size_t held = ctx->tp_in.bytes;  // reused below
         const double need = is_device ? 0.0 : (double)npix * kTpHostBytesPerPixel;
-        if (by > 65535u || lin_blocks > 0x7fffffffull || need > 0.9 * (double)(free_b + held))
+        bool fits;
+        double free_gb;
+        if (int rc = fits_in_hbm(ctx, need, held, &fits, &free_gb)) return rc;
+        if (by > 65535u || lin_blocks > 0x7fffffffull || !fits)
             return fail(ctx, TRHIP_ERR_UNSUPPORTED, "trhip_temporal: the images of a %u x %u film (%.1f GB, 160 B per pixel) do not fit in free HBM (%.1f GB free); there are no bands here", width,
-                        height, need * 1e-9, (double)(free_b + held) * 1e-9);
+                        height, need * 1e-9, free_gb);
     }
     const float4* d_beauty = (const float4*)xyzw;
     const float4* d_planes = (const float4*)planes;
@@ -79,17 +80,15 @@ int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const vo
     hipStream_t st = ctx->stream;
 
     Timer tm(ctx, ctx->timing && stats);
-    hipEvent_t e0, e1;
-    HIP_TRY(ctx, hipEventCreate(&e0));
-    HIP_TRY(ctx, hipEventCreate(&e1));
-    HIP_TRY(ctx, hipEventRecord(e0, st));
+    FrameEvents ev;
+    HIP_TRY(ctx, ev.begin(st));
     tm.begin(5, st);
     if (ctx->temporal_patch)  // measured 0.0347 ms against 0.0391 ms at 1024 x 1024 (profiles/r11/temporal.txt)
         hipLaunchKernelGGL((k_temporal<true>), dim3(bx, by), dim3(kDnTile * kDnTile), 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, d_out, d_out_history);
     else
         hipLaunchKernelGGL((k_temporal<false>), dim3((uint32_t)lin_blocks), dim3(kDnTile * kDnTile), 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, d_out, d_out_history);
     tm.end(5, st);
-    HIP_TRY(ctx, hipEventRecord(e1, st));
+    HIP_TRY(ctx, ev.end(st));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (!is_device) {
@@ -98,14 +97,10 @@ int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const vo
     }
     if (stats) {
         std::memset(stats, 0, sizeof *stats);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        stats->ms_total = ms;
+        stats->ms_total = ev.ms();
         stats->ms_film = tm.total(5, &stats->launches_film);
         stats->launches_film = 1;
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return 0;
 }
 

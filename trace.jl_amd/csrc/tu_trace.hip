@@ -312,24 +312,18 @@ static int api_trace(trhip_ctx* ctx, const trhip_scene* sc, bool any, const void
                               (float*)ctx->scratch[2].p);
     Counters* ctr = (Counters*)ctx->counters.p;
     HIP_TRY(ctx, hipMemsetAsync(ctr, 0, sizeof(Counters), ctx->stream));
-    hipEvent_t e0, e1;
-    HIP_TRY(ctx, hipEventCreate(&e0));
-    HIP_TRY(ctx, hipEventCreate(&e1));
     repeat = std::max(1, std::min(repeat, kMaxDepth + 1));
     TraceOut out{any ? nullptr : (float4*)d_out, nullptr, nullptr, any ? (uint8_t*)d_out : nullptr};
-    HIP_TRY(ctx, hipEventRecord(e0, ctx->stream));
+    FrameEvents ev;
+    HIP_TRY(ctx, ev.begin(ctx->stream));
     if (n)
         for (int r = 0; r < repeat; ++r)  // every repetition uses its own (zeroed) work cursor
             launch_trace(ctx, ctx->stream, sc, any, SegQueue{nullptr, (uint32_t)n, (uint32_t)n}, (const float4*)ctx->scratch[0].p, (const float4*)ctx->scratch[1].p, (const float*)ctx->scratch[2].p,
                          out, any ? ctr->work_shadow[r] : ctr->work_closest[r], ctr);
-    HIP_TRY(ctx, hipEventRecord(e1, ctx->stream));
+    HIP_TRY(ctx, ev.end(ctx->stream));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    if (avg_ms) *avg_ms = ms / repeat;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    if (avg_ms) *avg_ms = ev.ms() / repeat;
     return 0;
 }
 int trhip_trace_closest(trhip_ctx* ctx, const trhip_scene* sc, const float* rays, uint64_t n, trhip_hit* out) {
@@ -371,8 +365,10 @@ int trhip_last_fallback_counts(trhip_ctx* ctx, uint64_t* out2) {
     if (!ctx || !out2 || !ctx->counters.p) return fail(ctx, TRHIP_ERR_INVALID, "no counters");
     Counters h;
     HIP_TRY(ctx, hipMemcpy(&h, ctx->counters.p, sizeof h, hipMemcpyDeviceToHost));
-    out2[0] = h.closest_total;
-    out2[1] = h.fallback_total;
+    trhip_stats s{};
+    stats_add_counters(s, h);
+    out2[0] = s.closest_rays;
+    out2[1] = s.fallback_rays;
     return 0;
 }
 

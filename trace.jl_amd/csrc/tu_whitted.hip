@@ -4,7 +4,7 @@
 
 // WhittedIntegrator: ray tree built level by level, folded bottom-up (th_whitted.h).
 int render_whitted_impl(trhip_ctx* ctx, const trhip_scene* scene, const DeviceSensor& ds, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
-                        void* d_film, trhip_stats* stats, double* ms_total) {
+                        void* d_film, trhip_stats* stats) {
     const uint64_t npix = (uint64_t)ds.sb_w * ds.sb_h;
     const uint64_t total_slots = npix * spp;
     const uint32_t n_lights = std::max<uint32_t>(1u, scene->dev.n_lights);
@@ -18,7 +18,7 @@ int render_whitted_impl(trhip_ctx* ctx, const trhip_scene* scene, const DeviceSe
         batch = avail > 0 ? (uint64_t)(avail / per_ray) : npix;
     }
     uint64_t spp_batch = std::min<uint64_t>(std::max<uint64_t>(1, batch / npix), spp);
-    auto phys_of = [&](uint64_t n1) { return (uint64_t)(((2 * n1 + kSeg - 1) / kSeg + 2 * kSegGran + kSegGran - 1) / kSegGran * kSegGran) * kSeg; };
+    auto phys_of = [&](uint64_t n1) { return queue_cap(2 * n1) * kSeg; };
     while (spp_batch > 1 && phys_of(npix * spp_batch) * (uint64_t)max_depth >= (1ull << 32)) spp_batch = (spp_batch + 1) / 2;  // node ids are 32-bit
     const uint64_t n1 = npix * spp_batch;
     const uint64_t Pphys = phys_of(n1);
@@ -51,10 +51,8 @@ int render_whitted_impl(trhip_ctx* ctx, const trhip_scene* scene, const DeviceSe
     float4* L = (float4*)ctx->Lbuf.p;
     float4* hits = (float4*)ctx->hits.p;
     Timer tm(ctx, ctx->timing && stats);
-    hipEvent_t e0, e1;
-    HIP_TRY(ctx, hipEventCreate(&e0));
-    HIP_TRY(ctx, hipEventCreate(&e1));
-    HIP_TRY(ctx, hipEventRecord(e0, st));
+    FrameEvents ev;
+    HIP_TRY(ctx, ev.begin(st));
     HIP_TRY(ctx, hipMemsetAsync(ctr, 0, sizeof(Counters), st));
     HIP_TRY(ctx, hipMemsetAsync(flags, 0, sizeof(WhittedFlags), st));
     HIP_TRY(ctx, hipMemsetAsync(L, 0, total_slots * sizeof(float4), st));
@@ -102,25 +100,21 @@ int render_whitted_impl(trhip_ctx* ctx, const trhip_scene* scene, const DeviceSe
     tm.begin(4, st);
     launch_film(ctx, st, ds, dsp, L, total_slots, spp, seed, sample_offset, (float4*)d_film, false);
     tm.end(4, st);
-    HIP_TRY(ctx, hipEventRecord(e1, st));
+    HIP_TRY(ctx, ev.end(st));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));
     WhittedFlags hf;
     HIP_TRY(ctx, hipMemcpy(&hf, flags, sizeof hf, hipMemcpyDeviceToHost));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    *ms_total = ms;
     if (stats) {
-        stats->ms_raygen = tm.total(0, &stats->launches_raygen);
-        stats->ms_trace_closest = tm.total(1, &stats->launches_trace_closest);
-        stats->ms_fallback = tm.fallback_total(&stats->launches_fallback);
-        stats->ms_shade = tm.total(2, &stats->launches_shade);
-        stats->ms_trace_any = tm.total(3, &stats->launches_trace_any);
-        stats->ms_film = tm.total(4, &stats->launches_film);
+        std::memset(stats, 0, sizeof *stats);
+        stats->camera_samples = total_slots;
+        Counters h;
+        HIP_TRY(ctx, hipMemcpy(&h, ctr, sizeof h, hipMemcpyDeviceToHost));
+        stats_add_counters(*stats, h);
+        stats_fill_times(ctx, scene, tm, ev, *stats);
         stats->n_batches = n_batches;
+        stats->max_depth_reached = (uint32_t)max_depth;
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (hf.overflow) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "Whitted ray tree outgrew its queues (more than 2 rays per camera ray at some depth): lower \"batch_paths\"");
     return 0;
 }
