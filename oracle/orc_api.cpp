@@ -146,6 +146,13 @@ int orc_scene_add_spot_light(void* sp, const float* l2w, const float* l2w_inv, c
     s->scene.lights.push_back(SpotLight(tf_from(l2w, l2w_inv), RGB(I[0], I[1], I[2]), total_width_deg, falloff_start_deg));
     return (int)s->scene.lights.size() - 1;
 }
+// direction3: the light's world-space direction as the constructor normalised it; world_radius: 0 unless the caller ran preprocess!.  Whitted and path renders only:
+// sample_le of a directional light is not restated, orc_sppm refuses the scene.
+int orc_scene_add_directional_light(void* sp, const float* I, const float* direction3, float world_radius) {
+    OrcScene* s = (OrcScene*)sp;
+    s->scene.lights.push_back(DirectionalLight(RGB(I[0], I[1], I[2]), V3(direction3[0], direction3[1], direction3[2]), world_radius));
+    return (int)s->scene.lights.size() - 1;
+}
 // Read back what the restated light constructors computed (position, cosines) for host-mirror cross-checks.
 int orc_scene_get_light(void* sp, int i, float* position3, float* cos2) {
     OrcScene* s = (OrcScene*)sp;
@@ -753,6 +760,11 @@ int orc_sppm_ex(void* sp, const orc_sensor* sn, float initial_radius, int max_de
         g_err = "scene not committed";
         return -1;
     }
+    for (const Light& l : s->scene.lights)
+        if (l.kind == Light::DIRECTIONAL) {
+            g_err = "orc_sppm: sample_le of a DirectionalLight is not restated";
+            return -1;
+        }
     const Film film = make_film(sn);
     const PerspectiveCamera cam = make_camera(sn);
     SPPMParams prm;

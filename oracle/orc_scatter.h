@@ -656,13 +656,14 @@ inline BSDF compute_scattering(const Material& m, const SurfaceInteraction& si, 
     return BSDF();
 }
 
-// ---- lights/{light,point,spot}.jl ------------------------------------------------------------------------------------
+// ---- lights/{light,point,spot,directional}.jl ------------------------------------------------------------------------
 struct Light {
-    enum Kind { POINT = 0, SPOT = 1 } kind = POINT;
+    enum Kind { POINT = 0, SPOT = 1, DIRECTIONAL = 2 } kind = POINT;
     Transformation light_to_world, world_to_light;
     RGB i;
-    V3 position;
+    V3 position;  // directional: the light's direction (world space, normalised by the constructor's caller: directional.jl:29)
     float cos_total_width = 0, cos_falloff_start = 0;
+    float world_radius = 0;  // directional: what preprocess! stored (directional.jl:35-37); 0 for a light nobody preprocessed
 };
 inline Light PointLight(const Transformation& l2w, RGB i) {  // point.jl:19-24
     Light l;
@@ -684,6 +685,15 @@ inline Light SpotLight(const Transformation& l2w, RGB i, float total_width_deg, 
     l.cos_falloff_start = tm_cosf(jl_deg2rad(falloff_start_deg));
     return l;
 }
+// directional.jl:6-33 with the fields the render reads: `direction` = normalize(light_to_world(direction)), world_radius as preprocess! left it
+inline Light DirectionalLight(RGB i, V3 direction_world, float world_radius) {
+    Light l;
+    l.kind = Light::DIRECTIONAL;
+    l.i = i;
+    l.position = direction_world;
+    l.world_radius = world_radius;
+    return l;
+}
 // spot.jl:32-40
 inline float spot_falloff(const Light& s, V3 w) {
     const V3 wl = normalize(s.world_to_light.vec(w));
@@ -700,9 +710,18 @@ struct LightSample {
     V3 p0, p1;  // VisibilityTester end points (light.jl:12-15)
     float time = 0;
 };
-// point.jl:50-58, spot.jl:22-30
+// point.jl:50-58, spot.jl:22-30, directional.jl:39-47
 inline LightSample sample_li(const Light& l, V3 ref_p, float ref_time) {
     LightSample s;
+    if (l.kind == Light::DIRECTIONAL) {  // Li = I, wi = direction, pdf = 1; the tester aims at outside_point = ref.p .+ direction .* (2 * world_radius) (:42)
+        s.wi = l.position;
+        s.pdf = 1.0f;
+        s.p0 = ref_p;
+        s.p1 = ref_p + l.position * (2.0f * l.world_radius);
+        s.time = ref_time;
+        s.radiance = l.i;
+        return s;
+    }
     s.wi = normalize(l.position - ref_p);
     s.pdf = 1.0f;
     s.p0 = ref_p;
@@ -714,9 +733,10 @@ inline LightSample sample_li(const Light& l, V3 ref_p, float ref_time) {
         s.radiance = l.i * spot_falloff(l, -s.wi) / distance_squared(l.position, ref_p);
     return s;
 }
-// point.jl:74-76, spot.jl:42-44
+// point.jl:74-76, spot.jl:42-44, directional.jl:54-56
 inline RGB light_power(const Light& l) {
     if (l.kind == Light::POINT) return 4.0f * PI_F * l.i;
+    if (l.kind == Light::DIRECTIONAL) return l.i * PI_F * l.world_radius * l.world_radius;
     return l.i * 2.0f * PI_F * (1.0f - 0.5f * (l.cos_falloff_start + l.cos_total_width));
 }
 

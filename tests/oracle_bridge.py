@@ -53,6 +53,7 @@ def lib():
             "orc_scene_add_sphere": (C.c_int, [_VP, _F, _F, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]),
             "orc_scene_add_point_light": (C.c_int, [_VP, _F, _F, _F]),
             "orc_scene_add_spot_light": (C.c_int, [_VP, _F, _F, _F, C.c_float, C.c_float]),
+            "orc_scene_add_directional_light": (C.c_int, [_VP, _F, _F, C.c_float]),
             "orc_scene_get_light": (C.c_int, [_VP, C.c_int, _F, _F]),
             "orc_scene_commit_reference_bvh": (C.c_int, [_VP, C.c_int]),
             "orc_scene_commit_external_bvh": (C.c_int, [_VP, _F, _U32, _U32, C.c_uint32, _U32, C.c_uint32]),
@@ -196,6 +197,10 @@ class OracleScene:
         m, im, i = f32a(l2w.m), f32a(l2w.inv_m), f32a(I)
         return lib().orc_scene_add_spot_light(self.h, fp(m), fp(im), fp(i), total, falloff)
 
+    def add_directional_light(self, I, direction_world, world_radius):
+        i, d = f32a(I), f32a(direction_world)
+        return lib().orc_scene_add_directional_light(self.h, fp(i), fp(d), float(np.float32(world_radius)))
+
     def commit_reference(self, max_node_primitives: int = 1):
         rc = lib().orc_scene_commit_reference_bvh(self.h, max_node_primitives)
         if rc:
@@ -274,6 +279,8 @@ class OracleScene:
         for l in scene.lights:
             if isinstance(l, T.PointLight):
                 s.add_point_light(l.light_to_world, l.i.c)
+            elif isinstance(l, T.DirectionalLight):
+                s.add_directional_light(l.i.c, l.direction, l.world_radius)  # the fields as they stand: preprocessed or not
             else:
                 s.add_spot_light(l.light_to_world, l.i.c, float(l.total_width), float(l.falloff_start))
         if bvh is None:
