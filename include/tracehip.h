@@ -416,6 +416,40 @@ int trhip_temporal(trhip_ctx* ctx, const float* xyzw, const float* planes, const
 int trhip_temporal_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_history, uint32_t width, uint32_t height, const trhip_temporal_params* params,
                           void* d_out_xyzw, void* d_out_history, trhip_stats* stats);
 
+/* ---- variance clipping of the reprojected history (since ABI 3001, added without a version change: nothing existing moved) ----
+ * trhip_temporal with the standard remedy for stale history (Salvi 2016, "An excursion in temporal supersampling"): before the blend, the
+ * reprojected history colour is confined to mean +- clip_gamma * sd of the NEW frame's colours in a window around the pixel.  A history that
+ * no longer fits the frame — old lighting after trhip_scene_relight, blur and view-dependent shading carried along — is cut back in one frame
+ * instead of fading at 1 - 1/max_history per frame.  Specified operation by operation in docs/design/15-temporal-clip.md; bit-reproducible.
+ *
+ * trhip_temporal_clip: the images, the overlap rules and stats as in trhip_temporal.  Per surface pixel with n, p, c: over the window dy = -R..R
+ * outer, dx = -R..R inner (R = clip_radius), the centre counts, another position counts when it lies inside the image, is a surface pixel,
+ * 1 - n.n_q < base.sigma_normal and |n.(p_q - p)| < base.sigma_plane; over the counting positions m1 += c_q, m2 += c_q * c_q, cnt += 1 per
+ * channel, in that order.  mean = m1 / cnt, var = max(m2 / cnt - mean * mean, 0), sd = sqrt(var), lo = mean - gamma * sd, hi = mean + gamma * sd.
+ * trhip_temporal's c_h is then replaced by (c_h < lo) ? lo : ((c_h > hi) ? hi : c_h) per channel and everything else, N' included, goes on as
+ * there.  Comparisons with NaN are false: clip_gamma = +Inf gives trhip_temporal's result bit for bit.  The history length is not shortened
+ * when a clip fires.  out_xyzw may be xyzw: the _device variant then writes through a film held by the context (16 bytes per pixel, one
+ * device-to-device copy more), since a window reads its neighbours' film pixels.  The option "temporal_patch" has no effect on this pass.
+ * TRHIP_ERR_INVALID: params NULL; trhip_temporal's refusals on base, in its order; clip_gamma NaN or < 0; clip_radius not 1, 2 or 3; flags != 0;
+ * reserved != 0 (all of the parameter block is checked first, before any handle); then trhip_temporal's refusals of pointers, sizes and overlaps.
+ * TRHIP_ERR_UNSUPPORTED: the host variant's device copies (176 bytes per pixel) do not fit in free HBM.
+ * trhip_temporal_clip_default_params needs no context and no GPU: base as trhip_temporal_default_params fills it, clip_gamma = 4 and
+ * clip_radius = 3 — of the swept cells that clip (gamma 0.5, 1, 2, 4 x R 1, 2, 3) the one with the lowest geometric mean of the four moving-camera
+ * ratios at max_history 8 (profiles/r12/temporal_clip.txt).  On a moving camera no cell beats not clipping; after a change of lights the default
+ * leaves 0.28 of the unclipped error in the first frame, gamma = 1 with R = 1 leaves 0.09 and costs 1.46 x the unclipped error on the arcs. */
+typedef struct {
+    trhip_temporal_params base;    /* as trhip_temporal takes it; base.flags and base.reserved must be 0 */
+    float clip_gamma;              /* >= 0 or +Inf; +Inf: trhip_temporal's result bit for bit */
+    uint32_t clip_radius;          /* 1, 2 or 3: a window of 3 x 3, 5 x 5 or 7 x 7 pixels */
+    uint32_t flags;                /* 0 */
+    uint32_t reserved;             /* 0 */
+} trhip_temporal_clip_params;      /* 88 bytes */
+int trhip_temporal_clip_default_params(trhip_temporal_clip_params* out);
+int trhip_temporal_clip(trhip_ctx* ctx, const float* xyzw, const float* planes, const float* history, uint32_t width, uint32_t height, const trhip_temporal_clip_params* params,
+                        float* out_xyzw, float* out_history, trhip_stats* stats);
+int trhip_temporal_clip_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_history, uint32_t width, uint32_t height,
+                               const trhip_temporal_clip_params* params, void* d_out_xyzw, void* d_out_history, trhip_stats* stats);
+
 /* SPPMIntegrator(camera, initial_search_radius, max_depth, n_iterations, photons_per_iteration)(scene)
  * (integrators/sppm.jl:108-173): per iteration a camera pass to the first diffuse vertex, a hash grid over the visible
  * points, a photon pass (Halton / radical_inverse, sampler/sampling.jl:43-60) and the Float64 pixel update; afterwards
@@ -570,7 +604,8 @@ int trhip_film_allreduce(trhip_ctx* ctx, void* d_xyzw, uint64_t n_pixels);
  * "denoise_lds" (bit mask 0..3, default 3): bit i set = iteration i of trhip_denoise (i = 0, 1: steps 1, 2) stages its blocks' pixels and halo in LDS
  *     instead of gathering them from memory (measured 7 % and 3 % faster); same result bit for bit (th_denoise.h).
  * "temporal_patch" (0/1, default 1): which lane of trhip_temporal's kernel computes which pixel — 0 film order (a wave is 64 pixels of a row), 1 the à-trous
- *     kernel's patches of 16 x 4 pixels per wave (measured 11 % faster); same result bit for bit (th_temporal.h).
+ *     kernel's patches of 16 x 4 pixels per wave (measured 11 % faster); same result bit for bit (th_temporal.h).  No effect on
+ *     trhip_temporal_clip, whose kernel has the patch mapping only.
  * "film_transpose" (0/1): film pass on pixel-group-major copies of the per-sample radiance / film positions (default 0: no gain).
  * "leaf_kernel" (0/1): one-leaf scenes (tiny_scene_prims) run the dedicated uniform-walk kernel instead of traversal 2 (default 1).
  * "band_tile_rows": PathIntegrator frames whose per-sample buffers (24 B per camera sample) do not fit in HBM are rendered in bands of

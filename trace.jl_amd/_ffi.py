@@ -157,6 +157,17 @@ class TemporalParams(C.Structure):
     ]
 
 
+class TemporalClipParams(C.Structure):
+    """trhip_temporal_clip_params (88 bytes)"""
+    _fields_ = [
+        ("base", TemporalParams),
+        ("clip_gamma", C.c_float),
+        ("clip_radius", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 _F = C.POINTER(C.c_float)
 _U32 = C.POINTER(C.c_uint32)
 _VP = C.c_void_p
@@ -207,6 +218,9 @@ SIGNATURES = {
     "trhip_temporal_default_params": (C.c_int, [C.POINTER(TemporalParams)]),
     "trhip_temporal": (C.c_int, [_VP, _F, _F, _F, C.c_uint32, C.c_uint32, C.POINTER(TemporalParams), _F, _F, C.POINTER(Stats)]),
     "trhip_temporal_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(TemporalParams), _VP, _VP, C.POINTER(Stats)]),
+    "trhip_temporal_clip_default_params": (C.c_int, [C.POINTER(TemporalClipParams)]),
+    "trhip_temporal_clip": (C.c_int, [_VP, _F, _F, _F, C.c_uint32, C.c_uint32, C.POINTER(TemporalClipParams), _F, _F, C.POINTER(Stats)]),
+    "trhip_temporal_clip_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(TemporalClipParams), _VP, _VP, C.POINTER(Stats)]),
     "trhip_render_sppm": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats)]),
     "trhip_render_sppm_ex": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats), C.c_uint32, SPPM_WRITE_FN, _VP]),
     "trhip_sppm_state": (C.c_int, [_VP, _F, _F, _F, C.POINTER(C.c_double), C.POINTER(C.c_int64), _F, _F, _F, C.POINTER(C.c_int64)]),

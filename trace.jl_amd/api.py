@@ -1136,13 +1136,33 @@ class Denoiser:
 class TemporalAccumulator:
     """Blends a path frame with the previous frame's accumulated colour, fetched through the previous camera and validated against the feature planes (trhip_temporal;
     docs/design/14-temporal.md).  Fields left at None come from trhip_temporal_default_params (max_history 8, sigma_normal 0.25, sigma_plane 0.1, min_coverage 0.5).
-    The history is a (H, W, 3, 4) array: (c.rgb, N), (n, surface flag), (p, 0).  Scenes are static and lighting changes are not detected: pass history=None after one."""
+    The history is a (H, W, 3, 4) array: (c.rgb, N), (n, surface flag), (p, 0).  Scenes are static and lighting changes are not detected: pass history=None after one.
 
-    def __init__(self, max_history: Optional[float] = None, sigma_normal: Optional[float] = None, sigma_plane: Optional[float] = None, min_coverage: Optional[float] = None):
-        p = _ffi.TemporalParams()
-        rc = _ffi.lib().trhip_temporal_default_params(C.byref(p))
-        if rc:
-            raise TraceHipError(f"trhip_temporal_default_params failed ({rc})")
+    `clip_gamma` / `clip_radius`: with either given, the reprojected history colour is first confined to mean +- clip_gamma * sd of the new frame's colours in a window of
+    (2 clip_radius + 1)^2 pixels (trhip_temporal_clip; docs/design/15-temporal-clip.md), the other coming from trhip_temporal_clip_default_params; a history that no longer
+    fits the frame, as after a change of lights, is then cut back within a frame.  clip_gamma = inf gives the unclipped result bit for bit.  With both None nothing changes:
+    `params` is a TemporalParams and the calls go through trhip_temporal."""
+
+    def __init__(self, max_history: Optional[float] = None, sigma_normal: Optional[float] = None, sigma_plane: Optional[float] = None, min_coverage: Optional[float] = None,
+                 clip_gamma: Optional[float] = None, clip_radius: Optional[int] = None):
+        self.clip_params: Optional[_ffi.TemporalClipParams] = None
+        if clip_gamma is None and clip_radius is None:
+            p = _ffi.TemporalParams()
+            rc = _ffi.lib().trhip_temporal_default_params(C.byref(p))
+            if rc:
+                raise TraceHipError(f"trhip_temporal_default_params failed ({rc})")
+        else:
+            cp = _ffi.TemporalClipParams()
+            rc = _ffi.lib().trhip_temporal_clip_default_params(C.byref(cp))
+            if rc:
+                raise TraceHipError(f"trhip_temporal_clip_default_params failed ({rc})")
+            if clip_gamma is not None:
+                cp.clip_gamma = clip_gamma
+            if clip_radius is not None:
+                if int(clip_radius) != clip_radius or not 0 <= clip_radius < 2 ** 32:
+                    raise TraceHipError(f"TemporalAccumulator: clip_radius must be 1, 2 or 3, not {clip_radius!r}")
+                cp.clip_radius = int(clip_radius)
+            self.clip_params, p = cp, cp.base  # p is a view of cp.base: the fields set below land in the block that is passed
         for name, value in (("max_history", max_history), ("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane), ("min_coverage", min_coverage)):
             if value is not None:
                 setattr(p, name, value)
@@ -1159,6 +1179,11 @@ class TemporalAccumulator:
             p.prev_world_to_pixel[:] = m.reshape(-1).tolist()
         return p
 
+    def _clip_params_for(self, prev_camera) -> _ffi.TemporalClipParams:
+        cp = _ffi.TemporalClipParams.from_buffer_copy(self.clip_params)
+        cp.base = self._params_for(prev_camera)
+        return cp
+
     def accumulate(self, xyzw: np.ndarray, planes: np.ndarray, history: Optional[np.ndarray], prev_camera, ctx: Optional[_ffi.Context] = None):
         """xyzw: (H, W, 4) as PathIntegrator.render returns it; planes: (H, W, 3, 4) as AOVIntegrator.render(...).planes; history: the second result of the previous
         frame's call, or None.  Returns (xyzw, history) of this frame; the xyzw goes into Denoiser.denoise with the same planes."""
@@ -1171,9 +1196,11 @@ class TemporalAccumulator:
                 raise TraceHipError(f"accumulate: history must be {planes.shape} like planes, not {history.shape}")
         ctx = ctx or _ffi.default_context()
         h, w = xyzw.shape[:2]
-        out, out_history, st, p = np.empty_like(xyzw), np.empty_like(planes), _ffi.Stats(), self._params_for(prev_camera)
-        ctx.check(_ffi.lib().trhip_temporal(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(planes), _ffi.fptr(history) if history is not None else None, w, h, C.byref(p), _ffi.fptr(out),
-                                            _ffi.fptr(out_history), C.byref(st)))
+        out, out_history, st = np.empty_like(xyzw), np.empty_like(planes), _ffi.Stats()
+        clipped = self.clip_params is not None
+        p = self._clip_params_for(prev_camera) if clipped else self._params_for(prev_camera)
+        entry = _ffi.lib().trhip_temporal_clip if clipped else _ffi.lib().trhip_temporal
+        ctx.check(entry(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(planes), _ffi.fptr(history) if history is not None else None, w, h, C.byref(p), _ffi.fptr(out), _ffi.fptr(out_history), C.byref(st)))
         self.stats = st
         return out, out_history
 
@@ -1181,17 +1208,21 @@ class TemporalAccumulator:
                           ctx: Optional[_ffi.Context] = None) -> None:
         """The same on device pointers (d_out may equal d_xyzw, d_history may be None); nothing is copied to the host."""
         ctx = ctx or _ffi.default_context()
-        st, p = _ffi.Stats(), self._params_for(prev_camera)
-        ctx.check(_ffi.lib().trhip_temporal_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), C.c_void_p(d_history) if d_history else None, int(width), int(height), C.byref(p),
-                                                   C.c_void_p(d_out), C.c_void_p(d_out_history), C.byref(st)))
+        st, clipped = _ffi.Stats(), self.clip_params is not None
+        p = self._clip_params_for(prev_camera) if clipped else self._params_for(prev_camera)
+        entry = _ffi.lib().trhip_temporal_clip_device if clipped else _ffi.lib().trhip_temporal_device
+        ctx.check(entry(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), C.c_void_p(d_history) if d_history else None, int(width), int(height), C.byref(p), C.c_void_p(d_out),
+                        C.c_void_p(d_out_history), C.byref(st)))
         self.stats = st
 
 
 class PreviewSession:
     """A moving-camera preview of a static scene: frame k is the path film and the feature planes at sample_offset = sampler.sample_offset + k * spp, temporal accumulation
     against the previous frame's history and camera, then the à-trous filter with this frame's planes — all on the device, the buffers kept between frames.
-    `reset()` drops the history (the frame counter goes on, so the next frame's noise is new): call it after Scene.with_lights, since the pass does not detect lighting
-    changes; a film of another size resets as well.  A frame without history is filtered as Denoiser.render filters it, bit for bit."""
+    `reset()` drops the history (the frame counter goes on, so the next frame's noise is new): call it after Scene.with_lights, since the unclipped pass does not detect
+    lighting changes; a film of another size resets as well.  A frame without history is filtered as Denoiser.render filters it, bit for bit.
+    With `temporal=TemporalAccumulator(clip_gamma=...)` the history is clipped to the new frame's neighbourhood colours, and `session.scene = scene.with_lights(...)` between
+    frames needs no reset(): render() flattens `self.scene` every frame, and a history lit the old way is cut back to the new frame's colours within a frame."""
 
     def __init__(self, scene: Scene, sampler: SeededSampler, max_depth: int, denoiser: Optional["Denoiser"] = None, temporal: Optional[TemporalAccumulator] = None):
         self.scene, self.sampler, self.max_depth = scene, sampler, int(max_depth)
@@ -1204,6 +1235,7 @@ class PreviewSession:
         self.render_stats = None  # (path, aov, temporal, denoise) Stats of the last render()
 
     def reset(self) -> None:
+        """Drops the history.  Not needed after a change of lights when the session's accumulator clips (TemporalAccumulator(clip_gamma=...))."""
         self._prev_matrix = None
 
     def close(self) -> None:

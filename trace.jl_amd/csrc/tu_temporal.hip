@@ -1,15 +1,18 @@
-// tu_temporal.hip — trhip_temporal: the reprojection pass of th_temporal.h on a film, its feature planes and the previous frame's history; and trhip_sensor_world_to_pixel, the
-// host arithmetic that gives the pass its matrix.  No scene, no traversal: an image-space pass.
+// tu_temporal.hip — trhip_temporal: the reprojection pass of th_temporal.h on a film, its feature planes and the previous frame's history; trhip_temporal_clip: the same pass with
+// the history clipped to the new frame's neighbourhood colours (th_temporal_clip.h); and trhip_sensor_world_to_pixel, the host arithmetic that gives the pass its matrix.  No
+// scene, no traversal: image-space passes.
 #include "th_host.h"
-#include "th_temporal.h"
+#include "th_temporal_clip.h"
 
 #include <cmath>
 
 namespace {
 
 static_assert(sizeof(trhip_temporal_params) == 72, "trhip_temporal_params layout");
+static_assert(sizeof(trhip_temporal_clip_params) == 88, "trhip_temporal_clip_params layout");
 
 constexpr size_t kTpHostBytesPerPixel = 160;  // the host entry point's copies: film 16, planes 48, history 48, new history 48
+constexpr size_t kTcHostBytesPerPixel = 176;  // trhip_temporal_clip's: the same and a film of its own for the result (the window reads neighbours' film pixels)
 
 bool positive_finite(float v) { return std::isfinite(v) && v > 0.0f; }
 
@@ -25,16 +28,33 @@ int check_params(trhip_ctx* ctx, const trhip_temporal_params* p) {
     return 0;
 }
 
+// trhip_temporal's checks on base, in its order, then the new fields
+int check_clip_params(trhip_ctx* ctx, const trhip_temporal_clip_params* p) {
+    if (int rc = check_params(ctx, &p->base)) return rc;
+    if (!(p->clip_gamma >= 0.0f)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_clip: clip_gamma must be >= 0 (+Inf: no clipping)");  // false for NaN
+    if (p->clip_radius < 1 || p->clip_radius > 3) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_clip: clip_radius must be 1, 2 or 3, not %u", p->clip_radius);
+    if (p->flags != 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_clip: unknown flag bits 0x%x", p->flags);
+    if (p->reserved != 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_clip: reserved must be 0");
+    return 0;
+}
+
 bool overlap(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a && b && a0 < b0 + nb && b0 < a0 + na;
 }
 
-int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const void* history, uint32_t width, uint32_t height, const trhip_temporal_params* prm, void* out, void* out_history,
-                  bool is_device, trhip_stats* stats) {
+// is_clip false: trhip_temporal with prm; true: trhip_temporal_clip with clip, whose base takes prm's place
+int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const void* history, uint32_t width, uint32_t height, const trhip_temporal_params* prm,
+                  const trhip_temporal_clip_params* clip, bool is_clip, void* out, void* out_history, bool is_device, trhip_stats* stats) {
     // the parameter block first, before any handle is looked at: none of it needs a device
-    if (!prm) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
-    if (int rc = check_params(ctx, prm)) return rc;
+    if (is_clip) {
+        if (!clip) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
+        if (int rc = check_clip_params(ctx, clip)) return rc;
+        prm = &clip->base;
+    } else {
+        if (!prm) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
+        if (int rc = check_params(ctx, prm)) return rc;
+    }
     if (!ctx || !xyzw || !planes || !out || !out_history) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
     if (width == 0 || height == 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: empty film (%u x %u)", width, height);
     const uint64_t npix = (uint64_t)width * height;
@@ -45,15 +65,19 @@ int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const vo
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint32_t bx = (width + kDnTile - 1) / kDnTile, by = (height + kDnTile - 1) / kDnTile;
     const uint64_t lin_blocks = (npix + kDnTile * kDnTile - 1) / (kDnTile * kDnTile);
+    // the clipping kernel reads the film pixels of a whole window, so it cannot write the film it reads: an out_xyzw that is (or overlaps) xyzw is written through a film held
+    // by the context (16 B per pixel, one device-to-device copy more)
+    const bool via_scratch = is_clip && is_device && overlap(out, film_bytes, xyzw, film_bytes);
+    const size_t host_bytes = (size_t)npix * (is_clip ? kTcHostBytesPerPixel : kTpHostBytesPerPixel);
     {
         const size_t held = ctx->tp_in.bytes;  // reused below
-        const double need = is_device ? 0.0 : (double)npix * kTpHostBytesPerPixel;
+        const double need = is_device ? (via_scratch ? (double)film_bytes : 0.0) : (double)host_bytes;
         bool fits;
         double free_gb;
         if (int rc = fits_in_hbm(ctx, need, held, &fits, &free_gb)) return rc;
         if (by > 65535u || lin_blocks > 0x7fffffffull || !fits)
-            return fail(ctx, TRHIP_ERR_UNSUPPORTED, "trhip_temporal: the images of a %u x %u film (%.1f GB, 160 B per pixel) do not fit in free HBM (%.1f GB free); there are no bands here", width,
-                        height, need * 1e-9, free_gb);
+            return fail(ctx, TRHIP_ERR_UNSUPPORTED, "trhip_temporal: the images of a %u x %u film (%.1f GB, %u B per pixel) do not fit in free HBM (%.1f GB free); there are no bands here", width,
+                        height, need * 1e-9, is_clip ? (unsigned)kTcHostBytesPerPixel : (unsigned)kTpHostBytesPerPixel, free_gb);
     }
     const float4* d_beauty = (const float4*)xyzw;
     const float4* d_planes = (const float4*)planes;
@@ -61,7 +85,7 @@ int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const vo
     float4* d_out = (float4*)out;
     float4* d_out_history = (float4*)out_history;
     if (!is_device) {  // the film's copy is accumulated in place
-        if (int rc = ensure(ctx, ctx->tp_in, (size_t)npix * kTpHostBytesPerPixel)) return rc;
+        if (int rc = ensure(ctx, ctx->tp_in, host_bytes)) return rc;
         char* base = (char*)ctx->tp_in.p;
         HIP_TRY(ctx, hipMemcpy(base, xyzw, film_bytes, hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy(base + film_bytes, planes, planes_bytes, hipMemcpyHostToDevice));
@@ -70,6 +94,10 @@ int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const vo
         d_planes = (const float4*)(base + film_bytes);
         d_history = history ? (const float4*)(base + film_bytes + planes_bytes) : nullptr;
         d_out_history = (float4*)(base + film_bytes + 2 * planes_bytes);
+        if (is_clip) d_out = (float4*)(base + film_bytes + 3 * planes_bytes);
+    } else if (via_scratch) {
+        if (int rc = ensure(ctx, ctx->tp_in, film_bytes)) return rc;
+        d_out = (float4*)ctx->tp_in.p;
     }
     TemporalConst k;
     std::memcpy(k.m, prm->prev_world_to_pixel, sizeof k.m);
@@ -83,11 +111,21 @@ int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const vo
     FrameEvents ev;
     HIP_TRY(ctx, ev.begin(st));
     tm.begin(5, st);
-    if (ctx->temporal_patch)  // measured 0.0347 ms against 0.0391 ms at 1024 x 1024 (profiles/r11/temporal.txt)
+    if (is_clip) {  // one mapping, the patch's; the option "temporal_patch" has no effect here
+        const dim3 grid(bx, by), block(kDnTile * kDnTile);
+        const float gamma = clip->clip_gamma;
+        if (clip->clip_radius == 1)
+            hipLaunchKernelGGL((k_temporal_clip<1>), grid, block, 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, gamma, d_out, d_out_history);
+        else if (clip->clip_radius == 2)
+            hipLaunchKernelGGL((k_temporal_clip<2>), grid, block, 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, gamma, d_out, d_out_history);
+        else
+            hipLaunchKernelGGL((k_temporal_clip<3>), grid, block, 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, gamma, d_out, d_out_history);
+    } else if (ctx->temporal_patch)  // measured 0.0347 ms against 0.0391 ms at 1024 x 1024 (profiles/r11/temporal.txt)
         hipLaunchKernelGGL((k_temporal<true>), dim3(bx, by), dim3(kDnTile * kDnTile), 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, d_out, d_out_history);
     else
         hipLaunchKernelGGL((k_temporal<false>), dim3((uint32_t)lin_blocks), dim3(kDnTile * kDnTile), 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, d_out, d_out_history);
     tm.end(5, st);
+    if (via_scratch) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, film_bytes, hipMemcpyDeviceToDevice, st));
     HIP_TRY(ctx, ev.end(st));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -177,11 +215,30 @@ int trhip_temporal_default_params(trhip_temporal_params* out) {
 }
 int trhip_temporal(trhip_ctx* ctx, const float* xyzw, const float* planes, const float* history, uint32_t width, uint32_t height, const trhip_temporal_params* prm, float* out_xyzw,
                    float* out_history, trhip_stats* st) {
-    return temporal_impl(ctx, xyzw, planes, history, width, height, prm, out_xyzw, out_history, false, st);
+    return temporal_impl(ctx, xyzw, planes, history, width, height, prm, nullptr, false, out_xyzw, out_history, false, st);
 }
 int trhip_temporal_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_history, uint32_t width, uint32_t height, const trhip_temporal_params* prm, void* d_out_xyzw,
                           void* d_out_history, trhip_stats* st) {
-    return temporal_impl(ctx, d_xyzw, d_planes, d_history, width, height, prm, d_out_xyzw, d_out_history, true, st);
+    return temporal_impl(ctx, d_xyzw, d_planes, d_history, width, height, prm, nullptr, false, d_out_xyzw, d_out_history, true, st);
+}
+
+int trhip_temporal_clip_default_params(trhip_temporal_clip_params* out) {
+    if (!out) return fail(nullptr, TRHIP_ERR_INVALID, "null argument");
+    std::memset(out, 0, sizeof *out);
+    if (int rc = trhip_temporal_default_params(&out->base)) return rc;
+    // the sweep of profiles/r12/temporal_clip.txt (gamma 0.5, 1, 2, 4 x R 1, 2, 3): of the cells that clip, this one has the lowest geometric mean of the four arc ratios at
+    // max_history 8 (0.1454; not clipping at all has 0.1445).  Smaller windows and gammas relight faster (0.09 against 0.28 of the unclipped error) and cost more on an arc
+    out->clip_gamma = 4.0f;
+    out->clip_radius = 3;
+    return 0;
+}
+int trhip_temporal_clip(trhip_ctx* ctx, const float* xyzw, const float* planes, const float* history, uint32_t width, uint32_t height, const trhip_temporal_clip_params* prm, float* out_xyzw,
+                        float* out_history, trhip_stats* st) {
+    return temporal_impl(ctx, xyzw, planes, history, width, height, nullptr, prm, true, out_xyzw, out_history, false, st);
+}
+int trhip_temporal_clip_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_history, uint32_t width, uint32_t height, const trhip_temporal_clip_params* prm,
+                               void* d_out_xyzw, void* d_out_history, trhip_stats* st) {
+    return temporal_impl(ctx, d_xyzw, d_planes, d_history, width, height, nullptr, prm, true, d_out_xyzw, d_out_history, true, st);
 }
 
 }  // extern "C"

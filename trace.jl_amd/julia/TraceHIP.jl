@@ -397,6 +397,8 @@ end
 include("TraceHIPAO.jl")
 # TemporalAccumulator (trhip_temporal) and world_to_pixel, likewise (tests/golden/julia_shim_temporal_calls.json)
 include("TraceHIPTemporal.jl")
+# ClippedTemporalAccumulator (trhip_temporal_clip), likewise (tests/golden/julia_shim_temporal_clip_calls.json)
+include("TraceHIPTemporalClip.jl")
 
 # SPPMIntegrator (integrators/sppm.jl:132-173) on the device: trhip_render_sppm returns the film after set_image!
 # (film.jl:195-202).  `seed` selects the seeded stream of the camera pass (the reference draws from the global RNG there).
