@@ -450,6 +450,71 @@ int trhip_temporal_clip(trhip_ctx* ctx, const float* xyzw, const float* planes, 
 int trhip_temporal_clip_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_history, uint32_t width, uint32_t height,
                                const trhip_temporal_clip_params* params, void* d_out_xyzw, void* d_out_history, trhip_stats* stats);
 
+/* ---- luminance moments and a variance plane along the reprojection (since ABI 3001, added without a version change: nothing existing moved) ----
+ * The variance estimate of SVGF (Schied et al. 2017, section 4.2), image-space: trhip_temporal with the first two moments of the luminance
+ * the denoiser compares carried along the same reprojection, and a spatial estimate where the history is short.  Specified operation by
+ * operation in docs/design/16-variance.md; bit-reproducible.
+ *
+ * trhip_temporal_moments: xyzw, planes, history, out_xyzw, out_history, the overlap rules and stats as in trhip_temporal; out_xyzw and
+ * out_history are trhip_temporal's BIT FOR BIT for the same inputs, and the history records are interchangeable with that entry point's.
+ *   moments, out_moments   height * width float2 (m1, m2): the accumulated mean of Yd and of Yd * Yd.  moments is NULL exactly when history is
+ *   out_variance           height * width float: the variance of the accumulated luminance, >= 0 and finite; 0 where the pixel is no surface pixel
+ * Per surface pixel: Yd = to_Y(c / a) with the denoiser's clamped base colour a when flags has TRHIP_DENOISE_DEMODULATE, else to_Y(c), c the new
+ * frame's colour.  Over the taps trhip_temporal accepted, with its weights b: s1 += b * m1_q, s2 += b * m2_q.  With sb > 0: m1_h = s1 / sb,
+ * m2_h = s2 / sb, m1' = m1_h + (Yd - m1_h) / N', m2' = m2_h + (Yd * Yd - m2_h) / N', vt = max(m2' - m1' * m1', 0); else, or where trhip_temporal
+ * falls back to c' = c, or where m1' or m2' is not finite: m1' = Yd, m2' = Yd * Yd and there is no vt.  The spatial estimate vs is taken over
+ * trhip_temporal_clip's window at clip_radius 3 — the same order, the same positions count —: S1 += Yd_q, S2 += Yd_q * Yd_q, cnt += 1,
+ * mean = S1 / cnt, vs = max(S2 / cnt - mean * mean, 0).  v = vt where there is one and N' < spatial_below is false, else vs;
+ * out_variance = v / N' (0 if that is not finite): the variance of a mean of N' frames.  It is NOT the variance of the exponential average the
+ * blend becomes at the cap, and it ignores the correlation bilinear resampling puts between neighbours.  history = NULL: every surface pixel
+ * gets the spatial estimate.  out_xyzw may be xyzw: the _device variant then writes through a film held by the context, as trhip_temporal_clip.
+ * TRHIP_ERR_INVALID, in this order, all on the parameter block before any handle: params NULL; trhip_temporal's refusals on base, in its
+ * order; albedo_floor not finite and > 0; spatial_below not finite or < 1; unknown flag bits; reserved != 0.  Then trhip_temporal's refusals of
+ * pointers, sizes and overlaps, moments NULL when history is not (or the reverse), a NULL out_moments or out_variance, and out_history,
+ * out_moments or out_variance overlapping an input or another output.  TRHIP_ERR_UNSUPPORTED: the host variant's device copies (196 bytes
+ * per pixel) do not fit in free HBM.  trhip_temporal_moments_default_params needs no context and no GPU. */
+typedef struct {
+    trhip_temporal_params base;    /* as trhip_temporal takes it; base.flags and base.reserved must be 0 */
+    float albedo_floor;            /* the denoiser's; finite, > 0 */
+    float spatial_below;           /* N' < spatial_below uses the spatial estimate; finite, >= 1 */
+    uint32_t flags;                /* bit 0: TRHIP_DENOISE_DEMODULATE, meaning as in trhip_denoise */
+    uint32_t reserved;             /* 0 */
+} trhip_temporal_moments_params;   /* 88 bytes */
+int trhip_temporal_moments_default_params(trhip_temporal_moments_params* out);
+int trhip_temporal_moments(trhip_ctx* ctx, const float* xyzw, const float* planes, const float* history, const float* moments, uint32_t width, uint32_t height,
+                           const trhip_temporal_moments_params* params, float* out_xyzw, float* out_history, float* out_moments, float* out_variance, trhip_stats* stats);
+int trhip_temporal_moments_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_history, const void* d_moments, uint32_t width, uint32_t height,
+                                  const trhip_temporal_moments_params* params, void* d_out_xyzw, void* d_out_history, void* d_out_moments, void* d_out_variance,
+                                  trhip_stats* stats);
+
+/* ---- variance-guided à-trous filter (since ABI 3001, added without a version change: nothing existing moved) ----
+ * trhip_denoise with the colour edge-stop of SVGF (section 4.3): the colour sigma of a pixel is base.sigma_colour times the standard deviation
+ * of its luminance, from a variance plane (trhip_temporal_moments') that is filtered along with the colour, plus var_eps.  A pixel with a long
+ * history is compared strictly, a pixel disoccluded this frame loosely.  Specified in docs/design/16-variance.md; bit-reproducible.
+ *   xyzw, planes, out_xyzw   as in trhip_denoise; out_xyzw may be xyzw itself
+ *   variance                 height * width float; read as (v > 0) ? v : 0, so NaN, negatives and -Inf count as 0; +Inf removes the colour
+ *                            edge-stop of the pixels whose pre-filter reaches it.  Every output colour is finite whatever the plane holds
+ *   out_variance             height * width float or NULL; may be variance itself: the variance of the filtered colour, 0 off surfaces
+ * Prepare and Finish are trhip_denoise's.  Iteration i (step 2^i), surface pixel p: gv = the 3 x 3 mean of V_i at unit offsets (weights
+ * 0.5 / 0.25 per axis, positions outside the image or off surfaces skipped), sig = base.sigma_colour * sqrt(gv) + var_eps — NOT halved per
+ * iteration —; trhip_denoise's taps and weights with wc = g(|Y_q - Y_p| / sig); vsum += (w * w) * V_i(q); V_{i+1}(p) = vsum / (ws * ws), a NaN
+ * stored as 0.  With iterations = 1 and a variance plane of 1.0, sig = base.sigma_colour + var_eps and out_xyzw is trhip_denoise's bit for bit.
+ * TRHIP_ERR_INVALID, the parameter block first and before any handle: params NULL; trhip_denoise's refusals on base, in its order; var_eps not
+ * finite and > 0; flags != 0; reserved != 0; then a null pointer (out_variance excepted), a zero dimension.  TRHIP_ERR_UNSUPPORTED: the
+ * working set (88 bytes per pixel; the host variant 68 more) does not fit in free HBM.  stats as trhip_denoise: ms_sub [0] prepare and the
+ * variance's seeding, [1] the iterations, [2] finish and the variance's export. */
+typedef struct {
+    trhip_denoise_params base;     /* base.sigma_colour multiplies the standard deviation; it is NOT halved per iteration */
+    float var_eps;                 /* added to the sigma; finite, > 0 */
+    uint32_t flags;                /* 0 */
+    uint32_t reserved[2];          /* 0 */
+} trhip_denoise_var_params;        /* 48 bytes */
+int trhip_denoise_var_default_params(trhip_denoise_var_params* out);
+int trhip_denoise_var(trhip_ctx* ctx, const float* xyzw, const float* planes, const float* variance, uint32_t width, uint32_t height, const trhip_denoise_var_params* params,
+                      float* out_xyzw, float* out_variance, trhip_stats* stats);
+int trhip_denoise_var_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_variance, uint32_t width, uint32_t height,
+                             const trhip_denoise_var_params* params, void* d_out_xyzw, void* d_out_variance, trhip_stats* stats);
+
 /* SPPMIntegrator(camera, initial_search_radius, max_depth, n_iterations, photons_per_iteration)(scene)
  * (integrators/sppm.jl:108-173): per iteration a camera pass to the first diffuse vertex, a hash grid over the visible
  * points, a photon pass (Halton / radical_inverse, sampler/sampling.jl:43-60) and the Float64 pixel update; afterwards
@@ -606,6 +671,7 @@ int trhip_film_allreduce(trhip_ctx* ctx, void* d_xyzw, uint64_t n_pixels);
  * "temporal_patch" (0/1, default 1): which lane of trhip_temporal's kernel computes which pixel — 0 film order (a wave is 64 pixels of a row), 1 the à-trous
  *     kernel's patches of 16 x 4 pixels per wave (measured 11 % faster); same result bit for bit (th_temporal.h).  No effect on
  *     trhip_temporal_clip, whose kernel has the patch mapping only.
+ * "denoise_var_lds" (bit mask 0..3, default 3): as "denoise_lds", for trhip_denoise_var's iterations (measured 17 % and 16 % faster staged; th_denoise_var.h).
  * "film_transpose" (0/1): film pass on pixel-group-major copies of the per-sample radiance / film positions (default 0: no gain).
  * "leaf_kernel" (0/1): one-leaf scenes (tiny_scene_prims) run the dedicated uniform-walk kernel instead of traversal 2 (default 1).
  * "band_tile_rows": PathIntegrator frames whose per-sample buffers (24 B per camera sample) do not fit in HBM are rendered in bands of

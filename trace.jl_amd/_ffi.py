@@ -168,6 +168,27 @@ class TemporalClipParams(C.Structure):
     ]
 
 
+class TemporalMomentsParams(C.Structure):
+    """trhip_temporal_moments_params (88 bytes)"""
+    _fields_ = [
+        ("base", TemporalParams),
+        ("albedo_floor", C.c_float),
+        ("spatial_below", C.c_float),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class DenoiseVarParams(C.Structure):
+    """trhip_denoise_var_params (48 bytes)"""
+    _fields_ = [
+        ("base", DenoiseParams),
+        ("var_eps", C.c_float),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 _F = C.POINTER(C.c_float)
 _U32 = C.POINTER(C.c_uint32)
 _VP = C.c_void_p
@@ -221,6 +242,12 @@ SIGNATURES = {
     "trhip_temporal_clip_default_params": (C.c_int, [C.POINTER(TemporalClipParams)]),
     "trhip_temporal_clip": (C.c_int, [_VP, _F, _F, _F, C.c_uint32, C.c_uint32, C.POINTER(TemporalClipParams), _F, _F, C.POINTER(Stats)]),
     "trhip_temporal_clip_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(TemporalClipParams), _VP, _VP, C.POINTER(Stats)]),
+    "trhip_temporal_moments_default_params": (C.c_int, [C.POINTER(TemporalMomentsParams)]),
+    "trhip_temporal_moments": (C.c_int, [_VP, _F, _F, _F, _F, C.c_uint32, C.c_uint32, C.POINTER(TemporalMomentsParams), _F, _F, _F, _F, C.POINTER(Stats)]),
+    "trhip_temporal_moments_device": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(TemporalMomentsParams), _VP, _VP, _VP, _VP, C.POINTER(Stats)]),
+    "trhip_denoise_var_default_params": (C.c_int, [C.POINTER(DenoiseVarParams)]),
+    "trhip_denoise_var": (C.c_int, [_VP, _F, _F, _F, C.c_uint32, C.c_uint32, C.POINTER(DenoiseVarParams), _F, _F, C.POINTER(Stats)]),
+    "trhip_denoise_var_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(DenoiseVarParams), _VP, _VP, C.POINTER(Stats)]),
     "trhip_render_sppm": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats)]),
     "trhip_render_sppm_ex": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats), C.c_uint32, SPPM_WRITE_FN, _VP]),
     "trhip_sppm_state": (C.c_int, [_VP, _F, _F, _F, C.POINTER(C.c_double), C.POINTER(C.c_int64), _F, _F, _F, C.POINTER(C.c_int64)]),

@@ -1079,10 +1079,15 @@ class AmbientOcclusionIntegrator(_SamplerIntegrator):
 class Denoiser:
     """Edge-avoiding à-trous filter (Dammertz et al. 2010, Tukey's biweight as the edge-stopping function) for the film of a PathIntegrator or WhittedIntegrator render,
     guided by the planes of AOVIntegrator for the same camera and sampler (trhip_denoise; docs/design/12-denoise.md).  Fields left at None come from
-    trhip_denoise_default_params.  Pixels that are no surface pixels — misses, silhouette pixels with less than min_coverage hit weight, NaNs — are returned untouched."""
+    trhip_denoise_default_params.  Pixels that are no surface pixels — misses, silhouette pixels with less than min_coverage hit weight, NaNs — are returned untouched.
+
+    `denoise_variance` is the variance-guided filter (trhip_denoise_var; docs/design/16-variance.md): a pixel's colour sigma is `variance_sigma` times the standard deviation
+    of its luminance, from a variance plane such as TemporalAccumulator(moments=True) returns, plus `var_eps`; both default to trhip_denoise_var_default_params' and have
+    no effect on `denoise`.  Everything else of its parameter block is this denoiser's."""
 
     def __init__(self, iterations: Optional[int] = None, demodulate: bool = True, sigma_colour: Optional[float] = None, sigma_normal: Optional[float] = None,
-                 sigma_plane: Optional[float] = None, albedo_floor: Optional[float] = None, min_coverage: Optional[float] = None):
+                 sigma_plane: Optional[float] = None, albedo_floor: Optional[float] = None, min_coverage: Optional[float] = None, variance_sigma: Optional[float] = None,
+                 var_eps: Optional[float] = None):
         p = _ffi.DenoiseParams()
         rc = _ffi.lib().trhip_denoise_default_params(C.byref(p))
         if rc:
@@ -1093,8 +1098,42 @@ class Denoiser:
                 setattr(p, name, value)
         p.flags = _ffi.DENOISE_DEMODULATE if demodulate else 0
         self.params = p
+        vp = _ffi.DenoiseVarParams()
+        rc = _ffi.lib().trhip_denoise_var_default_params(C.byref(vp))
+        if rc:
+            raise TraceHipError(f"trhip_denoise_var_default_params failed ({rc})")
+        self.variance_sigma = float(vp.base.sigma_colour if variance_sigma is None else variance_sigma)
+        self.var_eps = float(vp.var_eps if var_eps is None else var_eps)
         self.stats: Optional[_ffi.Stats] = None
-        self.render_stats = None  # (path, aov, denoise) Stats of the last render()
+        self.render_stats = None  # (path, aov, denoise) Stats of the last render(); (path, aov, moments, denoise) of a variance-guided one
+
+    def _var_params(self) -> _ffi.DenoiseVarParams:
+        vp = _ffi.DenoiseVarParams()
+        vp.base = _ffi.DenoiseParams.from_buffer_copy(self.params)
+        vp.base.sigma_colour = self.variance_sigma
+        vp.var_eps = self.var_eps
+        return vp
+
+    def denoise_variance(self, xyzw: np.ndarray, planes: np.ndarray, variance: np.ndarray, ctx: Optional[_ffi.Context] = None):
+        """As `denoise`, guided by `variance`, (H, W) as TemporalAccumulator(moments=True).accumulate_moments returns it.  Returns (xyzw, variance of the filtered colour)."""
+        xyzw, planes, variance = _ffi.f32(xyzw), _ffi.f32(planes), _ffi.f32(variance)
+        if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4) or variance.shape != xyzw.shape[:2]:
+            raise TraceHipError(f"denoise_variance: xyzw must be (H, W, 4), planes (H, W, 3, 4) and variance (H, W), not {xyzw.shape}, {planes.shape} and {variance.shape}")
+        ctx = ctx or _ffi.default_context()
+        h, w = xyzw.shape[:2]
+        out, out_var, st, vp = np.empty_like(xyzw), np.empty_like(variance), _ffi.Stats(), self._var_params()
+        ctx.check(_ffi.lib().trhip_denoise_var(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(planes), _ffi.fptr(variance), w, h, C.byref(vp), _ffi.fptr(out), _ffi.fptr(out_var), C.byref(st)))
+        self.stats = st
+        return out, out_var
+
+    def denoise_variance_device(self, d_xyzw: int, d_planes: int, d_variance: int, width: int, height: int, d_out: int, d_out_variance: Optional[int] = None,
+                                ctx: Optional[_ffi.Context] = None) -> None:
+        """The same on device pointers (d_out may equal d_xyzw, d_out_variance may equal d_variance or be None); nothing is copied to the host."""
+        ctx = ctx or _ffi.default_context()
+        st, vp = _ffi.Stats(), self._var_params()
+        ctx.check(_ffi.lib().trhip_denoise_var_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), C.c_void_p(d_variance), int(width), int(height), C.byref(vp), C.c_void_p(d_out),
+                                                      C.c_void_p(d_out_variance) if d_out_variance else None, C.byref(st)))
+        self.stats = st
 
     def denoise(self, xyzw: np.ndarray, planes: np.ndarray, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
         """xyzw: (H, W, 4) as PathIntegrator.render returns it; planes: (H, W, 3, 4) as AOVIntegrator.render(...).planes.  Returns the denoised (H, W, 4)."""
@@ -1115,10 +1154,13 @@ class Denoiser:
         ctx.check(_ffi.lib().trhip_denoise_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), int(width), int(height), C.byref(self.params), C.c_void_p(d_out), C.byref(st)))
         self.stats = st
 
-    def render(self, scene: Scene, camera: PerspectiveCamera, sampler: SeededSampler, max_depth: int, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
-        """Path frame and feature planes with the same sampler settings, both left on the device, denoised there; returns xyzw (H, W, 4), ready for film.set_xyzw / save."""
+    def render(self, scene: Scene, camera: PerspectiveCamera, sampler: SeededSampler, max_depth: int, ctx: Optional[_ffi.Context] = None, variance_guided: bool = False) -> np.ndarray:
+        """Path frame and feature planes with the same sampler settings, both left on the device, denoised there; returns xyzw (H, W, 4), ready for film.set_xyzw / save.
+        `variance_guided`: the frame's own bits through `denoise_variance`, guided by the spatial variance estimate of TemporalAccumulator(moments=True) without history."""
         ctx = scene.flatten(ctx).ctx
         h, w = camera.film.size
+        if variance_guided:
+            return self._render_variance_guided(scene, camera, sampler, max_depth, ctx, h, w)
         d_film, d_planes = _ffi.DeviceBuffer(h * w * 16), _ffi.DeviceBuffer(h * w * 48)
         try:
             path, aov = PathIntegrator(camera, sampler, max_depth), AOVIntegrator(camera, sampler)
@@ -1131,6 +1173,23 @@ class Denoiser:
             d_film.free()
             d_planes.free()
 
+    def _render_variance_guided(self, scene, camera, sampler, max_depth, ctx, h, w) -> np.ndarray:
+        bufs = [_ffi.DeviceBuffer(h * w * n) for n in (16, 48, 16, 48, 8, 4)]
+        d_film, d_planes, d_acc, d_hist, d_mom, d_var = bufs
+        try:
+            path, aov = PathIntegrator(camera, sampler, max_depth), AOVIntegrator(camera, sampler)
+            path.render(scene, ctx, device_out=d_film.ptr)
+            aov.render(scene, ctx, device_out=d_planes.ptr)
+            t = TemporalAccumulator(sigma_normal=self.params.sigma_normal, sigma_plane=self.params.sigma_plane, min_coverage=self.params.min_coverage, moments=True,
+                                    demodulate=bool(self.params.flags & _ffi.DENOISE_DEMODULATE), albedo_floor=self.params.albedo_floor)
+            t.accumulate_moments_device(d_film.ptr, d_planes.ptr, None, None, w, h, None, d_acc.ptr, d_hist.ptr, d_mom.ptr, d_var.ptr, ctx)
+            self.denoise_variance_device(d_film.ptr, d_planes.ptr, d_var.ptr, w, h, d_film.ptr, None, ctx)
+            self.render_stats = (path.stats, aov.stats, t.stats, self.stats)
+            return d_film.to_host(np.float32, (h, w, 4))
+        finally:
+            for b in bufs:
+                b.free()
+
 
 # ---- temporal reprojection (include/tracehip.h, trhip_temporal) ------------------------------------------------------------------------------
 class TemporalAccumulator:
@@ -1141,12 +1200,33 @@ class TemporalAccumulator:
     `clip_gamma` / `clip_radius`: with either given, the reprojected history colour is first confined to mean +- clip_gamma * sd of the new frame's colours in a window of
     (2 clip_radius + 1)^2 pixels (trhip_temporal_clip; docs/design/15-temporal-clip.md), the other coming from trhip_temporal_clip_default_params; a history that no longer
     fits the frame, as after a change of lights, is then cut back within a frame.  clip_gamma = inf gives the unclipped result bit for bit.  With both None nothing changes:
-    `params` is a TemporalParams and the calls go through trhip_temporal."""
+    `params` is a TemporalParams and the calls go through trhip_temporal.
+
+    `moments=True`: `accumulate_moments` / `accumulate_moments_device` also carry the two luminance moments along the reprojection and return a variance plane for
+    Denoiser.denoise_variance (trhip_temporal_moments; docs/design/16-variance.md); their colour and history are `accumulate`'s bit for bit.  `spatial_below`, `albedo_floor`
+    left at None come from trhip_temporal_moments_default_params; `demodulate` must be the denoiser's.  Not combinable with clipping: a clipped moments pass does not exist."""
 
     def __init__(self, max_history: Optional[float] = None, sigma_normal: Optional[float] = None, sigma_plane: Optional[float] = None, min_coverage: Optional[float] = None,
-                 clip_gamma: Optional[float] = None, clip_radius: Optional[int] = None):
+                 clip_gamma: Optional[float] = None, clip_radius: Optional[int] = None, moments: bool = False, spatial_below: Optional[float] = None, demodulate: bool = True,
+                 albedo_floor: Optional[float] = None):
         self.clip_params: Optional[_ffi.TemporalClipParams] = None
-        if clip_gamma is None and clip_radius is None:
+        self.moments_params: Optional[_ffi.TemporalMomentsParams] = None
+        if moments and (clip_gamma is not None or clip_radius is not None):
+            raise TraceHipError("TemporalAccumulator: moments=True cannot be combined with clip_gamma / clip_radius (there is no clipped variant of trhip_temporal_moments)")
+        if not moments and (spatial_below is not None or albedo_floor is not None):
+            raise TraceHipError("TemporalAccumulator: spatial_below and albedo_floor belong to moments=True")
+        if moments:
+            mp = _ffi.TemporalMomentsParams()
+            rc = _ffi.lib().trhip_temporal_moments_default_params(C.byref(mp))
+            if rc:
+                raise TraceHipError(f"trhip_temporal_moments_default_params failed ({rc})")
+            if spatial_below is not None:
+                mp.spatial_below = spatial_below
+            if albedo_floor is not None:
+                mp.albedo_floor = albedo_floor
+            mp.flags = _ffi.DENOISE_DEMODULATE if demodulate else 0
+            self.moments_params, p = mp, mp.base  # a view, as below
+        elif clip_gamma is None and clip_radius is None:
             p = _ffi.TemporalParams()
             rc = _ffi.lib().trhip_temporal_default_params(C.byref(p))
             if rc:
@@ -1204,6 +1284,47 @@ class TemporalAccumulator:
         self.stats = st
         return out, out_history
 
+    def _moments_params_for(self, prev_camera) -> _ffi.TemporalMomentsParams:
+        if self.moments_params is None:
+            raise TraceHipError("TemporalAccumulator: accumulate_moments needs TemporalAccumulator(moments=True)")
+        mp = _ffi.TemporalMomentsParams.from_buffer_copy(self.moments_params)
+        mp.base = self._params_for(prev_camera)
+        return mp
+
+    def accumulate_moments(self, xyzw: np.ndarray, planes: np.ndarray, history: Optional[np.ndarray], moments: Optional[np.ndarray], prev_camera,
+                           ctx: Optional[_ffi.Context] = None):
+        """`accumulate` with the moments: `moments` is (H, W, 2), the third result of the previous frame's call, None exactly when `history` is.  Returns (xyzw, history,
+        moments, variance (H, W)) of this frame; the variance goes into Denoiser.denoise_variance with the returned xyzw and the same planes."""
+        mp = self._moments_params_for(prev_camera)
+        xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
+        if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
+            raise TraceHipError(f"accumulate_moments: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
+        if (history is None) != (moments is None):
+            raise TraceHipError("accumulate_moments: moments must be None exactly when history is")
+        if history is not None:
+            history, moments = _ffi.f32(history), _ffi.f32(moments)
+            if history.shape != planes.shape or moments.shape != xyzw.shape[:2] + (2,):
+                raise TraceHipError(f"accumulate_moments: history must be {planes.shape} and moments {xyzw.shape[:2] + (2,)}, not {history.shape} and {moments.shape}")
+        ctx = ctx or _ffi.default_context()
+        h, w = xyzw.shape[:2]
+        out, out_history, out_moments, out_var, st = np.empty_like(xyzw), np.empty_like(planes), np.empty((h, w, 2), np.float32), np.empty((h, w), np.float32), _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_temporal_moments(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(planes), _ffi.fptr(history) if history is not None else None,
+                                                    _ffi.fptr(moments) if moments is not None else None, w, h, C.byref(mp), _ffi.fptr(out), _ffi.fptr(out_history), _ffi.fptr(out_moments),
+                                                    _ffi.fptr(out_var), C.byref(st)))
+        self.stats = st
+        return out, out_history, out_moments, out_var
+
+    def accumulate_moments_device(self, d_xyzw: int, d_planes: int, d_history: Optional[int], d_moments: Optional[int], width: int, height: int, prev_camera, d_out: int,
+                                  d_out_history: int, d_out_moments: int, d_out_variance: int, ctx: Optional[_ffi.Context] = None) -> None:
+        """The same on device pointers (d_out may equal d_xyzw; d_history and d_moments may both be None); nothing is copied to the host."""
+        mp = self._moments_params_for(prev_camera)
+        ctx = ctx or _ffi.default_context()
+        st = _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_temporal_moments_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), C.c_void_p(d_history) if d_history else None,
+                                                           C.c_void_p(d_moments) if d_moments else None, int(width), int(height), C.byref(mp), C.c_void_p(d_out), C.c_void_p(d_out_history),
+                                                           C.c_void_p(d_out_moments), C.c_void_p(d_out_variance), C.byref(st)))
+        self.stats = st
+
     def accumulate_device(self, d_xyzw: int, d_planes: int, d_history: Optional[int], width: int, height: int, prev_camera, d_out: int, d_out_history: int,
                           ctx: Optional[_ffi.Context] = None) -> None:
         """The same on device pointers (d_out may equal d_xyzw, d_history may be None); nothing is copied to the host."""
@@ -1222,11 +1343,20 @@ class PreviewSession:
     `reset()` drops the history (the frame counter goes on, so the next frame's noise is new): call it after Scene.with_lights, since the unclipped pass does not detect
     lighting changes; a film of another size resets as well.  A frame without history is filtered as Denoiser.render filters it, bit for bit.
     With `temporal=TemporalAccumulator(clip_gamma=...)` the history is clipped to the new frame's neighbourhood colours, and `session.scene = scene.with_lights(...)` between
-    frames needs no reset(): render() flattens `self.scene` every frame, and a history lit the old way is cut back to the new frame's colours within a frame."""
+    frames needs no reset(): render() flattens `self.scene` every frame, and a history lit the old way is cut back to the new frame's colours within a frame.
+    `variance_guided=True`: the accumulator carries the luminance moments (TemporalAccumulator(moments=True), the default then; demodulation and albedo floor the
+    denoiser's) and the filter is Denoiser.denoise_variance with the variance plane of the frame; a frame without history is filtered from its own bits with the spatial
+    estimate, as Denoiser.render(variance_guided=True) filters it.  The default, False, is the session described above, call for call."""
 
-    def __init__(self, scene: Scene, sampler: SeededSampler, max_depth: int, denoiser: Optional["Denoiser"] = None, temporal: Optional[TemporalAccumulator] = None):
+    def __init__(self, scene: Scene, sampler: SeededSampler, max_depth: int, denoiser: Optional["Denoiser"] = None, temporal: Optional[TemporalAccumulator] = None,
+                 variance_guided: bool = False):
         self.scene, self.sampler, self.max_depth = scene, sampler, int(max_depth)
         self.denoiser = denoiser if denoiser is not None else Denoiser()
+        self.variance_guided = bool(variance_guided)
+        if self.variance_guided and temporal is None:
+            temporal = TemporalAccumulator(moments=True, demodulate=bool(self.denoiser.params.flags & _ffi.DENOISE_DEMODULATE), albedo_floor=self.denoiser.params.albedo_floor)
+        if self.variance_guided and temporal.moments_params is None:
+            raise TraceHipError("PreviewSession: variance_guided=True needs a TemporalAccumulator(moments=True)")
         self.temporal = temporal if temporal is not None else TemporalAccumulator()
         self.frame = 0
         self._size = None
@@ -1250,7 +1380,7 @@ class PreviewSession:
         if self._size != (h, w):
             self.close()
             self._size = (h, w)
-            self._buffers = [_ffi.DeviceBuffer(h * w * n) for n in (16, 48, 16, 48, 48)]
+            self._buffers = [_ffi.DeviceBuffer(h * w * n) for n in (16, 48, 16, 48, 48) + ((8, 8, 4) if self.variance_guided else ())]
         d_film, d_planes, d_acc = self._buffers[:3]
         d_prev, d_next = self._buffers[3 + (self.frame & 1)], self._buffers[3 + ((self.frame & 1) ^ 1)]
         spp = self.sampler.samples_per_pixel
@@ -1261,9 +1391,15 @@ class PreviewSession:
         prev_matrix, matrix = self._prev_matrix, camera.world_to_pixel()
         had_history = prev_matrix is not None
         self._prev_matrix = None  # (until this frame's history is complete)
-        self.temporal.accumulate_device(d_film.ptr, d_planes.ptr, d_prev.ptr if had_history else None, w, h, prev_matrix, d_acc.ptr, d_next.ptr, ctx)
-        # without history the accumulated film is the frame itself up to the rounding of XYZ -> RGB -> XYZ: the frame's own bits are filtered then
-        self.denoiser.denoise_device((d_acc if had_history else d_film).ptr, d_planes.ptr, w, h, d_acc.ptr, ctx)
+        if self.variance_guided:
+            m_prev, m_next, d_var = self._buffers[5 + (self.frame & 1)], self._buffers[5 + ((self.frame & 1) ^ 1)], self._buffers[7]
+            self.temporal.accumulate_moments_device(d_film.ptr, d_planes.ptr, d_prev.ptr if had_history else None, m_prev.ptr if had_history else None, w, h, prev_matrix, d_acc.ptr,
+                                                    d_next.ptr, m_next.ptr, d_var.ptr, ctx)
+            self.denoiser.denoise_variance_device((d_acc if had_history else d_film).ptr, d_planes.ptr, d_var.ptr, w, h, d_acc.ptr, None, ctx)
+        else:
+            self.temporal.accumulate_device(d_film.ptr, d_planes.ptr, d_prev.ptr if had_history else None, w, h, prev_matrix, d_acc.ptr, d_next.ptr, ctx)
+            # without history the accumulated film is the frame itself up to the rounding of XYZ -> RGB -> XYZ: the frame's own bits are filtered then
+            self.denoiser.denoise_device((d_acc if had_history else d_film).ptr, d_planes.ptr, w, h, d_acc.ptr, ctx)
         self.render_stats = (path.stats, aov.stats, self.temporal.stats, self.denoiser.stats)
         out = d_acc.to_host(np.float32, (h, w, 4))
         self._prev_matrix = matrix

@@ -253,6 +253,8 @@ int trhip_set_option(trhip_ctx* ctx, const char* name, int64_t value) {
         ctx->denoise_lds = (int)(value & 3);
     else if (!std::strcmp(name, "temporal_patch"))
         ctx->temporal_patch = value != 0;
+    else if (!std::strcmp(name, "denoise_var_lds"))
+        ctx->denoise_var_lds = (int)(value & 3);
     else if (!std::strcmp(name, "pipelines")) {
         if (value < 1 || value > kMaxPipes) return fail(ctx, TRHIP_ERR_INVALID, "pipelines must be in 1..%d", kMaxPipes);
         ctx->pipelines = (int)value;

@@ -1,14 +1,17 @@
 // tu_denoise.hip — trhip_denoise: the edge-avoiding à-trous filter of th_denoise.h on a film and its feature planes.  No scene, no traversal: an image-space pass.
 #include "th_host.h"
 #include "th_denoise.h"
+#include "th_denoise_var.h"
 
 #include <cmath>
 
 namespace {
 
 static_assert(sizeof(trhip_denoise_params) == 32, "trhip_denoise_params layout");
+static_assert(sizeof(trhip_denoise_var_params) == 48, "trhip_denoise_var_params layout");
 
 constexpr uint32_t kDnMaxIterations = 6;
+constexpr size_t kDvBytesPerPixel = 88;  // trhip_denoise_var: the same and V x 2
 constexpr size_t kDnBytesPerPixel = 80;  // {n, flag} {p, 0} {c, Y} x 2 {a, 0}
 
 bool positive_finite(float v) { return std::isfinite(v) && v > 0.0f; }
@@ -105,6 +108,106 @@ int denoise_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, uint32_t 
     return 0;
 }
 
+int denoise_var_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const void* variance, uint32_t width, uint32_t height, const trhip_denoise_var_params* vp, void* out,
+                     void* out_variance, bool is_device, trhip_stats* stats) {
+    // the parameter block first, before any handle is looked at: none of it needs a device
+    if (!vp) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
+    const trhip_denoise_params* prm = &vp->base;
+    if (int rc = check_params(ctx, prm)) return rc;
+    if (!positive_finite(vp->var_eps)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_denoise_var: var_eps must be finite and > 0");
+    if (vp->flags != 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_denoise_var: unknown flag bits 0x%x", vp->flags);
+    if (vp->reserved[0] != 0 || vp->reserved[1] != 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_denoise_var: reserved must be 0");
+    if (!ctx || !xyzw || !planes || !variance || !out) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
+    if (width == 0 || height == 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_denoise: empty film (%u x %u)", width, height);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t npix = (uint64_t)width * height;
+    const size_t film_bytes = (size_t)npix * sizeof(float4), planes_bytes = 3 * film_bytes, var_bytes = (size_t)npix * sizeof(float);
+    const uint32_t bx = (width + kDnTile - 1) / kDnTile, by = (height + kDnTile - 1) / kDnTile;
+    {
+        const size_t held = ctx->dn_work.bytes + ctx->dn_in.bytes;  // reused below
+        const double need = (double)npix * kDvBytesPerPixel + (is_device ? 0.0 : (double)(film_bytes + planes_bytes + var_bytes));
+        bool fits;
+        double free_gb;
+        if (int rc = fits_in_hbm(ctx, need, held, &fits, &free_gb)) return rc;
+        if (by > 65535u || !fits)
+            return fail(ctx, TRHIP_ERR_UNSUPPORTED, "trhip_denoise_var: the working set of a %u x %u film (%.1f GB, 88 B per pixel) does not fit in free HBM (%.1f GB free); there are no bands here",
+                        width, height, need * 1e-9, free_gb);
+    }
+    if (int rc = ensure(ctx, ctx->dn_work, (size_t)npix * kDvBytesPerPixel)) return rc;
+    const float4* d_beauty = (const float4*)xyzw;
+    const float4* d_planes = (const float4*)planes;
+    const float* d_variance = (const float*)variance;
+    float4* d_out = (float4*)out;
+    float* d_out_variance = (float*)out_variance;
+    if (!is_device) {  // the copies of the film and of the variance plane are filtered in place
+        if (int rc = ensure(ctx, ctx->dn_in, film_bytes + planes_bytes + var_bytes)) return rc;
+        char* base = (char*)ctx->dn_in.p;
+        HIP_TRY(ctx, hipMemcpy(base, xyzw, film_bytes, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(base + film_bytes, planes, planes_bytes, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(base + film_bytes + planes_bytes, variance, var_bytes, hipMemcpyHostToDevice));
+        d_beauty = d_out = (float4*)base;
+        d_planes = (const float4*)(base + film_bytes);
+        d_variance = (const float*)(base + film_bytes + planes_bytes);
+        d_out_variance = out_variance ? (float*)(base + film_bytes + planes_bytes) : nullptr;
+    }
+    float4* gn = (float4*)ctx->dn_work.p;
+    float4 *gp = gn + npix, *col[2] = {gn + 2 * npix, gn + 3 * npix}, *alb = gn + 4 * npix;
+    float* var[2] = {(float*)(gn + 5 * npix), (float*)(gn + 5 * npix) + npix};
+    hipStream_t st = ctx->stream;
+    const uint32_t demodulate = prm->flags & TRHIP_DENOISE_DEMODULATE;
+
+    Timer tm(ctx, ctx->timing && stats);
+    FrameEvents ev;
+    HIP_TRY(ctx, ev.begin(st));
+    const int lin_grid = grid_for(ctx, npix, 8);
+    // iterations = 0 copies the film; the variance plane still goes through the seed and the export (clamped, 0 off surfaces), which need the surface flags
+    tm.begin(5, st);
+    hipLaunchKernelGGL(k_denoise_prepare, dim3(lin_grid), dim3(kBlock), 0, st, d_beauty, d_planes, npix, demodulate, prm->albedo_floor, prm->min_coverage, gn, gp, col[0], alb);
+    hipLaunchKernelGGL(k_denoise_var_seed, dim3(lin_grid), dim3(kBlock), 0, st, gn, d_variance, npix, var[0]);
+    tm.end(5, st);
+    const DenoiseWeights sg{prm->sigma_colour, prm->sigma_normal, prm->sigma_plane};  // sigma_colour multiplies the standard deviation and is not halved
+    for (uint32_t i = 0; i < prm->iterations; ++i) {
+        const float4* cin = col[i & 1];
+        float4* cout = col[(i & 1) ^ 1];
+        const float* vin = var[i & 1];
+        float* vout = var[(i & 1) ^ 1];
+        const dim3 grid(bx, by), block(kDnTile * kDnTile);
+        const bool lds = i < 2 && ((ctx->denoise_var_lds >> i) & 1);
+        tm.begin(6, st);
+        if (lds && i == 0)
+            hipLaunchKernelGGL((k_denoise_var_atrous_lds<1>), grid, block, 0, st, gn, gp, cin, vin, cout, vout, (int)width, (int)height, sg, vp->var_eps);
+        else if (lds)
+            hipLaunchKernelGGL((k_denoise_var_atrous_lds<2>), grid, block, 0, st, gn, gp, cin, vin, cout, vout, (int)width, (int)height, sg, vp->var_eps);
+        else
+            hipLaunchKernelGGL(k_denoise_var_atrous, grid, block, 0, st, gn, gp, cin, vin, cout, vout, (int)width, (int)height, 1 << i, sg, vp->var_eps);
+        tm.end(6, st);
+    }
+    tm.begin(7, st);
+    if (prm->iterations == 0) {
+        if (d_out != d_beauty) HIP_TRY(ctx, hipMemcpyAsync(d_out, d_beauty, film_bytes, hipMemcpyDeviceToDevice, st));
+    } else
+        hipLaunchKernelGGL(k_denoise_finish, dim3(lin_grid), dim3(kBlock), 0, st, d_beauty, gn, col[prm->iterations & 1], alb, npix, demodulate, d_out);
+    if (d_out_variance) hipLaunchKernelGGL(k_denoise_var_export, dim3(lin_grid), dim3(kBlock), 0, st, var[prm->iterations & 1], npix, d_out_variance);
+    tm.end(7, st);
+    HIP_TRY(ctx, ev.end(st));
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (!is_device) {
+        HIP_TRY(ctx, hipMemcpy(out, d_out, film_bytes, hipMemcpyDeviceToHost));
+        if (out_variance) HIP_TRY(ctx, hipMemcpy(out_variance, d_out_variance, var_bytes, hipMemcpyDeviceToHost));
+    }
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        stats->ms_total = ev.ms();
+        for (int k = 0; k < 3; ++k) {  // prepare and seed, the iterations, finish and export
+            stats->ms_sub[k] = tm.total(5 + k, &stats->launches_sub[k]);
+            stats->ms_film += stats->ms_sub[k];
+            stats->launches_film += stats->launches_sub[k];
+        }
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -126,6 +229,25 @@ int trhip_denoise(trhip_ctx* ctx, const float* xyzw, const float* planes, uint32
 }
 int trhip_denoise_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, uint32_t width, uint32_t height, const trhip_denoise_params* prm, void* d_out_xyzw, trhip_stats* st) {
     return denoise_impl(ctx, d_xyzw, d_planes, width, height, prm, d_out_xyzw, true, st);
+}
+
+int trhip_denoise_var_default_params(trhip_denoise_var_params* out) {
+    if (!out) return fail(nullptr, TRHIP_ERR_INVALID, "null argument");
+    std::memset(out, 0, sizeof *out);
+    if (int rc = trhip_denoise_default_params(&out->base)) return rc;
+    // sigma_colour (times the standard deviation), var_eps and trhip_temporal_moments' spatial_below = 4: of the 64 swept cells the one with the lowest geometric mean of the
+    // four arc ratios, 0.1461 at max_history 8 (profiles/r13/variance.txt; the unguided session has 0.1445)
+    out->base.sigma_colour = 2.0f;
+    out->var_eps = 1.0f / 64.0f;
+    return 0;
+}
+int trhip_denoise_var(trhip_ctx* ctx, const float* xyzw, const float* planes, const float* variance, uint32_t width, uint32_t height, const trhip_denoise_var_params* prm, float* out_xyzw,
+                      float* out_variance, trhip_stats* st) {
+    return denoise_var_impl(ctx, xyzw, planes, variance, width, height, prm, out_xyzw, out_variance, false, st);
+}
+int trhip_denoise_var_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_variance, uint32_t width, uint32_t height, const trhip_denoise_var_params* prm,
+                             void* d_out_xyzw, void* d_out_variance, trhip_stats* st) {
+    return denoise_var_impl(ctx, d_xyzw, d_planes, d_variance, width, height, prm, d_out_xyzw, d_out_variance, true, st);
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // scene, no traversal: image-space passes.
 #include "th_host.h"
 #include "th_temporal_clip.h"
+#include "th_temporal_moments.h"
 
 #include <cmath>
 
@@ -10,8 +11,10 @@ namespace {
 
 static_assert(sizeof(trhip_temporal_params) == 72, "trhip_temporal_params layout");
 static_assert(sizeof(trhip_temporal_clip_params) == 88, "trhip_temporal_clip_params layout");
+static_assert(sizeof(trhip_temporal_moments_params) == 88, "trhip_temporal_moments_params layout");
 
 constexpr size_t kTpHostBytesPerPixel = 160;  // the host entry point's copies: film 16, planes 48, history 48, new history 48
+constexpr size_t kTmHostBytesPerPixel = 196;  // trhip_temporal_moments': trhip_temporal_clip's and moments 8, new moments 8, variance 4
 constexpr size_t kTcHostBytesPerPixel = 176;  // trhip_temporal_clip's: the same and a film of its own for the result (the window reads neighbours' film pixels)
 
 bool positive_finite(float v) { return std::isfinite(v) && v > 0.0f; }
@@ -142,6 +145,127 @@ int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const vo
     return 0;
 }
 
+// trhip_temporal's checks on base, in its order, then the new fields
+int check_moments_params(trhip_ctx* ctx, const trhip_temporal_moments_params* p) {
+    if (int rc = check_params(ctx, &p->base)) return rc;
+    if (!positive_finite(p->albedo_floor)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_moments: albedo_floor must be finite and > 0");
+    if (!(std::isfinite(p->spatial_below) && p->spatial_below >= 1.0f)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_moments: spatial_below must be finite and >= 1");
+    if (p->flags & ~(uint32_t)TRHIP_DENOISE_DEMODULATE)
+        return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_moments: unknown flag bits 0x%x", p->flags & ~(uint32_t)TRHIP_DENOISE_DEMODULATE);
+    if (p->reserved != 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_moments: reserved must be 0");
+    return 0;
+}
+
+int moments_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const void* history, const void* moments, uint32_t width, uint32_t height,
+                 const trhip_temporal_moments_params* prm, void* out, void* out_history, void* out_moments, void* out_variance, bool is_device, trhip_stats* stats) {
+    // the parameter block first, before any handle is looked at: none of it needs a device
+    if (!prm) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
+    if (int rc = check_moments_params(ctx, prm)) return rc;
+    if (!ctx || !xyzw || !planes || !out || !out_history || !out_moments || !out_variance) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
+    if (width == 0 || height == 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: empty film (%u x %u)", width, height);
+    if ((history == nullptr) != (moments == nullptr)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_moments: moments must be NULL exactly when history is");
+    const uint64_t npix = (uint64_t)width * height;
+    const size_t film_bytes = (size_t)npix * sizeof(float4), planes_bytes = 3 * film_bytes, mom_bytes = (size_t)npix * sizeof(float2), var_bytes = (size_t)npix * sizeof(float);
+    if (overlap(out_history, planes_bytes, history, planes_bytes) || overlap(out_history, planes_bytes, planes, planes_bytes) || overlap(out_history, planes_bytes, xyzw, film_bytes) ||
+        overlap(out_history, planes_bytes, out, film_bytes))
+        return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: out_history overlaps an input or out_xyzw");
+    {
+        const struct { const void* p; size_t n; const char* name; } outs[2] = {{out_moments, mom_bytes, "out_moments"}, {out_variance, var_bytes, "out_variance"}},
+            others[7] = {{xyzw, film_bytes, ""}, {planes, planes_bytes, ""}, {history, planes_bytes, ""}, {moments, mom_bytes, ""}, {out, film_bytes, ""}, {out_history, planes_bytes, ""},
+                         {out_moments, mom_bytes, ""}};
+        for (int o = 0; o < 2; ++o)
+            for (int i = 0; i < 6 + o; ++i)
+                if (overlap(outs[o].p, outs[o].n, others[i].p, others[i].n))
+                    return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_moments: %s overlaps an input or another output", outs[o].name);
+        if (overlap(out, film_bytes, moments, mom_bytes) || overlap(out_history, planes_bytes, moments, mom_bytes))
+            return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_moments: an output overlaps moments");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint32_t bx = (width + kDnTile - 1) / kDnTile, by = (height + kDnTile - 1) / kDnTile;
+    // the staging reads the film pixels of a whole window: an out_xyzw that is (or overlaps) xyzw is written through the context's film, as in trhip_temporal_clip
+    const bool via_scratch = is_device && overlap(out, film_bytes, xyzw, film_bytes);
+    const size_t host_bytes = (size_t)npix * kTmHostBytesPerPixel;
+    {
+        const size_t held = ctx->tp_in.bytes;  // reused below
+        const double need = is_device ? (via_scratch ? (double)film_bytes : 0.0) : (double)host_bytes;
+        bool fits;
+        double free_gb;
+        if (int rc = fits_in_hbm(ctx, need, held, &fits, &free_gb)) return rc;
+        if (by > 65535u || !fits)
+            return fail(ctx, TRHIP_ERR_UNSUPPORTED, "trhip_temporal_moments: the images of a %u x %u film (%.1f GB, %u B per pixel) do not fit in free HBM (%.1f GB free); there are no bands here",
+                        width, height, need * 1e-9, (unsigned)kTmHostBytesPerPixel, free_gb);
+    }
+    const float4* d_beauty = (const float4*)xyzw;
+    const float4* d_planes = (const float4*)planes;
+    const float4* d_history = (const float4*)history;
+    const float2* d_moments = (const float2*)moments;
+    float4* d_out = (float4*)out;
+    float4* d_out_history = (float4*)out_history;
+    float2* d_out_moments = (float2*)out_moments;
+    float* d_out_variance = (float*)out_variance;
+    if (!is_device) {
+        if (int rc = ensure(ctx, ctx->tp_in, host_bytes)) return rc;
+        char* at = (char*)ctx->tp_in.p;
+        auto take = [&at](size_t n) {
+            char* p = at;
+            at += n;
+            return p;
+        };
+        char *b_film = take(film_bytes), *b_planes = take(planes_bytes), *b_hist = take(planes_bytes), *b_out_hist = take(planes_bytes), *b_out = take(film_bytes);
+        char *b_mom = take(mom_bytes), *b_out_mom = take(mom_bytes), *b_var = take(var_bytes);
+        HIP_TRY(ctx, hipMemcpy(b_film, xyzw, film_bytes, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(b_planes, planes, planes_bytes, hipMemcpyHostToDevice));
+        if (history) {
+            HIP_TRY(ctx, hipMemcpy(b_hist, history, planes_bytes, hipMemcpyHostToDevice));
+            HIP_TRY(ctx, hipMemcpy(b_mom, moments, mom_bytes, hipMemcpyHostToDevice));
+        }
+        d_beauty = (const float4*)b_film;
+        d_planes = (const float4*)b_planes;
+        d_history = history ? (const float4*)b_hist : nullptr;
+        d_moments = history ? (const float2*)b_mom : nullptr;
+        d_out = (float4*)b_out;
+        d_out_history = (float4*)b_out_hist;
+        d_out_moments = (float2*)b_out_mom;
+        d_out_variance = (float*)b_var;
+    } else if (via_scratch) {
+        if (int rc = ensure(ctx, ctx->tp_in, film_bytes)) return rc;
+        d_out = (float4*)ctx->tp_in.p;
+    }
+    TemporalConst k;
+    std::memcpy(k.m, prm->base.prev_world_to_pixel, sizeof k.m);
+    k.max_history = prm->base.max_history;
+    k.sigma_normal = prm->base.sigma_normal;
+    k.sigma_plane = prm->base.sigma_plane;
+    k.min_coverage = prm->base.min_coverage;
+    const MomentsConst mk{prm->albedo_floor, prm->spatial_below, prm->flags & TRHIP_DENOISE_DEMODULATE};
+    hipStream_t st = ctx->stream;
+
+    Timer tm(ctx, ctx->timing && stats);
+    FrameEvents ev;
+    HIP_TRY(ctx, ev.begin(st));
+    tm.begin(5, st);
+    const dim3 grid(bx, by), block(kDnTile * kDnTile);
+    hipLaunchKernelGGL(k_temporal_moments, grid, block, 0, st, d_beauty, d_planes, d_history, d_moments, (int)width, (int)height, k, mk, d_out, d_out_history, d_out_moments, d_out_variance);
+    tm.end(5, st);
+    if (via_scratch) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, film_bytes, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(ctx, ev.end(st));
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (!is_device) {
+        HIP_TRY(ctx, hipMemcpy(out, d_out, film_bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out_history, d_out_history, planes_bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out_moments, d_out_moments, mom_bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out_variance, d_out_variance, var_bytes, hipMemcpyDeviceToHost));
+    }
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        stats->ms_total = ev.ms();
+        stats->ms_film = tm.total(5, &stats->launches_film);
+        stats->launches_film = 1;
+    }
+    return 0;
+}
+
 // Gauss-Jordan with partial pivoting on an n x n Float64 matrix (row-major, n <= 4); false when a pivot is zero or not finite.
 bool invert(const double* a, int n, double* inv) {
     double m[4][8];
@@ -239,6 +363,24 @@ int trhip_temporal_clip(trhip_ctx* ctx, const float* xyzw, const float* planes, 
 int trhip_temporal_clip_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_history, uint32_t width, uint32_t height, const trhip_temporal_clip_params* prm,
                                void* d_out_xyzw, void* d_out_history, trhip_stats* st) {
     return temporal_impl(ctx, d_xyzw, d_planes, d_history, width, height, nullptr, prm, true, d_out_xyzw, d_out_history, true, st);
+}
+
+int trhip_temporal_moments_default_params(trhip_temporal_moments_params* out) {
+    if (!out) return fail(nullptr, TRHIP_ERR_INVALID, "null argument");
+    std::memset(out, 0, sizeof *out);
+    if (int rc = trhip_temporal_default_params(&out->base)) return rc;
+    out->albedo_floor = 1.0f / 64.0f;  // trhip_denoise_default_params'
+    out->spatial_below = 4.0f;         // SVGF's: fewer than four frames of history estimate spatially; 2 measured the same to three digits (profiles/r13/variance.txt)
+    out->flags = TRHIP_DENOISE_DEMODULATE;
+    return 0;
+}
+int trhip_temporal_moments(trhip_ctx* ctx, const float* xyzw, const float* planes, const float* history, const float* moments, uint32_t width, uint32_t height,
+                           const trhip_temporal_moments_params* prm, float* out_xyzw, float* out_history, float* out_moments, float* out_variance, trhip_stats* st) {
+    return moments_impl(ctx, xyzw, planes, history, moments, width, height, prm, out_xyzw, out_history, out_moments, out_variance, false, st);
+}
+int trhip_temporal_moments_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_history, const void* d_moments, uint32_t width, uint32_t height,
+                                  const trhip_temporal_moments_params* prm, void* d_out_xyzw, void* d_out_history, void* d_out_moments, void* d_out_variance, trhip_stats* st) {
+    return moments_impl(ctx, d_xyzw, d_planes, d_history, d_moments, width, height, prm, d_out_xyzw, d_out_history, d_out_moments, d_out_variance, true, st);
 }
 
 }  // extern "C"

@@ -399,6 +399,8 @@ include("TraceHIPAO.jl")
 include("TraceHIPTemporal.jl")
 # ClippedTemporalAccumulator (trhip_temporal_clip), likewise (tests/golden/julia_shim_temporal_clip_calls.json)
 include("TraceHIPTemporalClip.jl")
+# MomentsTemporalAccumulator (trhip_temporal_moments) and VarianceDenoiser (trhip_denoise_var), likewise (tests/golden/julia_shim_variance_calls.json)
+include("TraceHIPVariance.jl")
 
 # SPPMIntegrator (integrators/sppm.jl:132-173) on the device: trhip_render_sppm returns the film after set_image!
 # (film.jl:195-202).  `seed` selects the seeded stream of the camera pass (the reference draws from the global RNG there).
