@@ -760,11 +760,6 @@ int orc_sppm_ex(void* sp, const orc_sensor* sn, float initial_radius, int max_de
         g_err = "scene not committed";
         return -1;
     }
-    for (const Light& l : s->scene.lights)
-        if (l.kind == Light::DIRECTIONAL) {
-            g_err = "orc_sppm: sample_le of a DirectionalLight is not restated";
-            return -1;
-        }
     const Film film = make_film(sn);
     const PerspectiveCamera cam = make_camera(sn);
     SPPMParams prm;
@@ -782,6 +777,10 @@ int orc_sppm_ex(void* sp, const orc_sensor* sn, float initial_radius, int max_de
     if (!sppm_render(s->scene, cam, film, prm, st, image)) {
         g_err = "SPPM needs a film whose crop starts at pixel (1, 1) (sppm.jl:203 indexes pixels[y, x] with raster coordinates)";
         return -2;
+    }
+    if (st.directional_pick >= 0) {  // raised at the pick, as the reference raises: a DirectionalLight that no photon picks is no obstacle
+        g_err = "orc_sppm: photon " + std::to_string(st.directional_pick) + " picked a DirectionalLight, whose sample_le is not restated (sppm.jl:361 raises a MethodError)";
+        return -1;
     }
     const size_t n = st.pixels.size();
     for (size_t i = 0; i < n; ++i) {

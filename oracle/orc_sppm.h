@@ -201,6 +201,7 @@ struct SPPMState {
     bool grid_valid = false;
     uint64_t photon_hits = 0, grid_entries = 0;
     Counters totals;  // rays / visits of all threads
+    int64_t directional_pick = -1;  // first photon index found whose light is a DirectionalLight: no sample_le (sppm.jl:361 raises a MethodError), the render fails
     SPPMPixel& at(int x1, int y1) { return pixels[(size_t)(y1 - 1) * width + (size_t)(x1 - 1)]; }  // pixels[y, x], 1-based
 };
 
@@ -352,6 +353,11 @@ inline void sppm_trace_photons(Scene& scene, const SPPMParams& prm, SPPMState& s
         dim += 1;
         const DiscreteSample ds = sample_discrete(light_distr, light_sample);
         const Light& light = scene.lights[(size_t)ds.offset - 1];
+        if (light.kind == Light::DIRECTIONAL) {  // the reference stops here; a DirectionalLight that no photon picks (zero power) is rendered
+#pragma omp critical(orc_sppm_pick)
+            if (st.directional_pick < 0) st.directional_pick = (int64_t)hi;
+            continue;
+        }
         const V2 u_light_0{radical_inverse(dim, hi), radical_inverse(dim + 1, hi)};
         dim += 5;  // u_light_1 (2) and the time (1) are drawn and ignored by the δ-lights
         const LeSample ls = sample_le(light, u_light_0);
@@ -465,6 +471,7 @@ inline bool sppm_render(Scene& scene, const PerspectiveCamera& cam, const Film& 
         sppm_camera_pass(scene, cam, film, prm, st, it);
         sppm_populate_grid(st, grid, n_pixels);
         if (!scene.lights.empty()) sppm_trace_photons(scene, prm, st, grid, light_distr, it, n_pixels);
+        if (st.directional_pick >= 0) return true;  // the caller reports it
         if (prm.exchange) {  // multi-process job: ϕ and M summed over the processes before _update_pixels!
             const size_t n = st.pixels.size();
             x_phi.resize(3 * n);

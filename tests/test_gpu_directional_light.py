@@ -1,5 +1,5 @@
 """DirectionalLight on the MI355X: per-sample radiance against the composite model (tests/directional_model.py), the zero-direction
-shadow rays of an un-preprocessed light against the oracle, full-depth renders against the reference's tree alone, and SPPM."""
+shadow rays of an un-preprocessed light against the oracle, full-depth renders against the oracle and the reference's tree alone, and SPPM."""
 
 import numpy as np
 import pytest
@@ -75,9 +75,19 @@ def _film(T, ctx, scene, integrator, depth, spp=4):
 @pytest.mark.parametrize("special", [False, True])
 @pytest.mark.parametrize("lights,preprocessed", CONFIGS)
 @pytest.mark.parametrize("integrator,depth", [("path", 8), ("whitted", 5)])
-def test_full_depth_film_equals_the_reference_tree_walk(T, ctx, integrator, depth, lights, preprocessed, special):
+def test_full_depth_film_equals_the_reference_tree_walk(T, ob, ctx, integrator, depth, lights, preprocessed, special):
     make = lambda: dm.floor_scene(T, "plastic" if special else "matte", lights, preprocessed, special)  # noqa: E731
     a = _film(T, ctx, make(), integrator, depth)
+    # ... and the oracle on the committed tree: every vertex of every path under the sun, not the library against itself
+    scene = make()
+    integ = (T.WhittedIntegrator if integrator == "whitted" else T.PathIntegrator)(T.scenes.shadows_camera(48), T.SeededSampler(4, seed=SEED), depth)
+    film = integ.render(scene, ctx).copy()
+    osc = ob.OracleScene.from_scene(scene, bvh=scene.flatten(ctx).bvh())
+    ref_film, ref_L, ref_st = osc.render(T.scenes.shadows_camera(48), integrator, 4, depth, seed=SEED, want_samples=True)
+    assert_bits_equal(integ.sample_radiance(scene), ref_L, f"{integrator} depth {depth}: per-sample radiance vs the oracle")
+    assert_bits_equal(film, ref_film, f"{integrator} depth {depth}: film vs the oracle")
+    assert_bits_equal(a, ref_film, f"{integrator} depth {depth}: the first run's film vs the oracle")
+    assert integ.stats.closest_rays == ref_st.closest_rays and integ.stats.shadow_rays == ref_st.shadow_rays
     b = _film(T, ctx, make(), integrator, depth)
     assert np.isfinite(a).all()
     assert_bits_equal(a, b, "two runs")
@@ -127,6 +137,10 @@ def test_sppm_accepted_scene_camera_pass_direct_term(T, ob, ctx):
     a = integ3.render(scene, ctx).copy()
     b = integ3.render(scene, ctx).copy()
     assert np.isfinite(a).all() and np.array_equal(a, b)
+    # three iterations at depth 4 against the oracle, which renders a sun that no photon picks (tests/test_gpu_sppm.py's comparison and tolerances)
+    from test_gpu_sppm import check_pair, run_pair
+    _, xyzw, got, ref = run_pair(T, ob, ctx, scene, cam, 0.05, 4, 3, -1, seed=SEED)
+    check_pair(T, xyzw, got, ref, 3)
 
 
 @pytest.mark.parametrize("lights,preprocessed,photons", [("sun", True, 100), ("sun", False, 100), ("point_after", True, 100), ("point_first", False, 1 << 25)])
