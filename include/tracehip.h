@@ -515,6 +515,56 @@ int trhip_denoise_var(trhip_ctx* ctx, const float* xyzw, const float* planes, co
 int trhip_denoise_var_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_variance, uint32_t width, uint32_t height,
                              const trhip_denoise_var_params* params, void* d_out_xyzw, void* d_out_variance, trhip_stats* stats);
 
+/* ---- edge-aware upscaling of a low-resolution film (since ABI 3001, added without a version change: nothing existing moved) ----
+ * Joint bilateral upsampling (Kopf et al. 2007): the path frame is rendered through a sensor of lower resolution, the feature planes through
+ * both sensors, and the full-size film is reconstructed from the low one with the normal and plane-distance edge tests of trhip_denoise
+ * between a full-size pixel and its low-resolution neighbours.  Base-colour demodulation puts material edges back at full resolution; a miss
+ * carries exactly zero radiance (the library has no environment light), so silhouettes are put back by coverage.  Specified operation by
+ * operation in docs/design/17-upscale.md; bit-reproducible.
+ *   lo_xyzw, lo_planes   lo_height * lo_width float4 and * 3 float4: what trhip_render_path (or trhip_denoise, trhip_temporal*) and
+ *                        trhip_render_aov wrote for the low-resolution sensor
+ *   hi_planes            height * width * 3 float4: what trhip_render_aov wrote for the full-size sensor, at any spp
+ *   out_xyzw             height * width float4, a full-size film state: into film.set_xyzw / save, and into trhip_denoise with hi_planes.  Its .w
+ *                        lane is plane 0's weight of hi_planes BIT FOR BIT: the filter_weight_sum of a native frame with the guides' sampler
+ *   out_mask             height * width bytes or NULL: 0 nothing (no weight, or no usable low pixel: colour 0), 1 guided, 2 unguided (no surface
+ *                        pixel: bilinear over the plain low colours), 3 orphan — a full-size surface pixel that no low-resolution tap agreed
+ *                        with, a feature the low frame missed: filled like 2, flagged, the caller's to re-render
+ * lo_from_hi = (ax, bx, ay, by): full-size ARRAY pixel x lies at low-resolution array coordinate x * ax + bx (integers at pixel centres), likewise
+ * y.  For two sensors of one camera with the optical axis at raster position o (o = -m03 / m00 of raster_to_camera): ax = res_lo.x / res_hi.x,
+ * bx = (crop_min_hi.x + 0.5 - o_hi.x) * ax + o_lo.x - 0.5 - crop_min_lo.x (docs/design/17-upscale.md).
+ * Low pixel q: trhip_denoise's Prepare gives (s, n, p, c), c demodulated with TRHIP_UPSCALE_DEMODULATE and, with TRHIP_UPSCALE_COVERAGE, divided by
+ * v = H / A; plain colour u = xyz_to_rgb(xyz / w), valid iff w > 0 and u finite.  Full-size pixel with A = plane 0's weight, H = plane 1's:
+ * A > 0 false gives (0, 0, 0, A).  A surface pixel (H > 0, H >= min_coverage * A, finite n, p, a, v) sums the (2 radius)^2 low pixels around its
+ * position, j outer and i inner, with w = (k * wn) * wp: k the tent 1 - d / radius per axis, wn = g((1 - n.n_q) / sigma_normal),
+ * wp = g(|n.(p_q - p)| / sigma_plane), g Tukey's biweight; taps off the image or with s false are skipped; c' = sum / ws, times a, times v.  Any
+ * other pixel, and a surface pixel with ws = 0 or c' not finite, takes the bilinear mean of u over the valid ones of its four low pixels.
+ * out = (rgb_to_xyz(c') * A, A).
+ * TRHIP_ERR_INVALID, in this order, the parameter block before any handle: params NULL; an entry of lo_from_hi not finite, ax or ay outside
+ * [1/4, 1], |bx| or |by| >= 2^20; radius not 1 or 2; sigma_normal, sigma_plane or albedo_floor not finite and > 0; min_coverage outside [0, 1];
+ * unknown flag bits; reserved != 0; then a null pointer (out_mask and stats excepted); a zero dimension; out_xyzw or out_mask overlapping an
+ * input or each other.  TRHIP_ERR_UNSUPPORTED: the host variant's device copies (64 bytes per low pixel, 65 per full-size pixel) do not fit in free
+ * HBM, or an image of more than 2^20 pixels on a side.  stats (may be NULL): ms_total, ms_film and launches_film over the call's kernels.  The
+ * _device variant takes DEVICE pointers for the five images and allocates nothing beyond the context's scratch.  The default parameters need no
+ * context and no GPU: radius 2, flags 0, sigma_normal 0.25 (the denoiser's), sigma_plane 0.4 — of the swept cells the one with the lowest error against the
+ * native frame (profiles/r14/upscale.txt) —, albedo_floor 1/64, min_coverage 0.5; they leave lo_from_hi zero, which is refused: the map has to be given. */
+#define TRHIP_UPSCALE_DEMODULATE 1u
+#define TRHIP_UPSCALE_COVERAGE 2u
+typedef struct {
+    float lo_from_hi[4];           /* ax, bx, ay, by: low-res array coordinate of high-res array pixel x is x * ax + bx */
+    uint32_t radius;               /* 1 or 2: guided footprint of (2 radius)^2 low-res taps */
+    uint32_t flags;                /* TRHIP_UPSCALE_DEMODULATE | TRHIP_UPSCALE_COVERAGE, or 0 (the default) */
+    float sigma_normal;            /* the denoiser's edge tests, between a full-size pixel and a low one */
+    float sigma_plane;
+    float albedo_floor;            /* the denoiser's; finite, > 0 */
+    float min_coverage;            /* the denoiser's surface-pixel rule, [0, 1] */
+    uint32_t reserved[2];          /* 0 */
+} trhip_upscale_params;            /* 48 bytes */
+int trhip_upscale_default_params(trhip_upscale_params* out);
+int trhip_upscale(trhip_ctx* ctx, const float* lo_xyzw, const float* lo_planes, uint32_t lo_width, uint32_t lo_height, const float* hi_planes, uint32_t width, uint32_t height,
+                  const trhip_upscale_params* params, float* out_xyzw, uint8_t* out_mask, trhip_stats* stats);
+int trhip_upscale_device(trhip_ctx* ctx, const void* d_lo_xyzw, const void* d_lo_planes, uint32_t lo_width, uint32_t lo_height, const void* d_hi_planes, uint32_t width,
+                         uint32_t height, const trhip_upscale_params* params, void* d_out_xyzw, void* d_out_mask, trhip_stats* stats);
+
 /* SPPMIntegrator(camera, initial_search_radius, max_depth, n_iterations, photons_per_iteration)(scene)
  * (integrators/sppm.jl:108-173): per iteration a camera pass to the first diffuse vertex, a hash grid over the visible
  * points, a photon pass (Halton / radical_inverse, sampler/sampling.jl:43-60) and the Float64 pixel update; afterwards

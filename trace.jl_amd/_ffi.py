@@ -189,6 +189,23 @@ class DenoiseVarParams(C.Structure):
     ]
 
 
+class UpscaleParams(C.Structure):
+    """trhip_upscale_params (48 bytes)"""
+    _fields_ = [
+        ("lo_from_hi", C.c_float * 4),
+        ("radius", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("sigma_normal", C.c_float),
+        ("sigma_plane", C.c_float),
+        ("albedo_floor", C.c_float),
+        ("min_coverage", C.c_float),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+UPSCALE_DEMODULATE = 1  # TRHIP_UPSCALE_DEMODULATE
+UPSCALE_COVERAGE = 2    # TRHIP_UPSCALE_COVERAGE
+
 _F = C.POINTER(C.c_float)
 _U32 = C.POINTER(C.c_uint32)
 _VP = C.c_void_p
@@ -248,6 +265,9 @@ SIGNATURES = {
     "trhip_denoise_var_default_params": (C.c_int, [C.POINTER(DenoiseVarParams)]),
     "trhip_denoise_var": (C.c_int, [_VP, _F, _F, _F, C.c_uint32, C.c_uint32, C.POINTER(DenoiseVarParams), _F, _F, C.POINTER(Stats)]),
     "trhip_denoise_var_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(DenoiseVarParams), _VP, _VP, C.POINTER(Stats)]),
+    "trhip_upscale_default_params": (C.c_int, [C.POINTER(UpscaleParams)]),
+    "trhip_upscale": (C.c_int, [_VP, _F, _F, C.c_uint32, C.c_uint32, _F, C.c_uint32, C.c_uint32, C.POINTER(UpscaleParams), _F, C.POINTER(C.c_uint8), C.POINTER(Stats)]),
+    "trhip_upscale_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP, C.c_uint32, C.c_uint32, C.POINTER(UpscaleParams), _VP, _VP, C.POINTER(Stats)]),
     "trhip_render_sppm": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats)]),
     "trhip_render_sppm_ex": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats), C.c_uint32, SPPM_WRITE_FN, _VP]),
     "trhip_sppm_state": (C.c_int, [_VP, _F, _F, _F, C.POINTER(C.c_double), C.POINTER(C.c_int64), _F, _F, _F, C.POINTER(C.c_int64)]),

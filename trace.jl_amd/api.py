@@ -518,6 +518,7 @@ class Film:  # film.jl:7-62
         self.crop_window = (float(cmin[0]), float(cmin[1]), float(cmax[0]), float(cmax[1]))  # the constructor's fractional window (kept for hosts / tests)
         self.crop_bounds = Bounds2(np.ceil(res * cmin) + f32(1.0), np.ceil(res * cmax))  # :41-44
         self.filter = filter
+        self.diagonal_mm = diagonal  # the constructor's argument (PerspectiveCamera.with_resolution)
         self.diagonal = f32(diagonal) * f32(0.001)
         self.scale = f32(scale)
         self.filename = filename
@@ -570,6 +571,7 @@ class PerspectiveCamera:  # camera/perspective.jl:11-40, 58-80
         self.shutter_open, self.shutter_close = f32(shutter_open), f32(shutter_close)
         self.lens_radius, self.focal_distance = f32(lens_radius), f32(focal_distance)
         self.film = film
+        self.fov, self.screen_window = fov, screen_window
         self.camera_to_screen = perspective(fov, 0.01, 1000.0)  # near / far hard-coded at :65
         smin = np.asarray(screen_window.p_min, dtype=np.float32)
         smax = np.asarray(screen_window.p_max, dtype=np.float32)
@@ -592,6 +594,13 @@ class PerspectiveCamera:  # camera/perspective.jl:11-40, 58-80
         s.filter_table[:] = f.filter_table.reshape(-1).tolist()
         s.scale = float(f.scale)
         return s
+
+    def with_resolution(self, resolution) -> "PerspectiveCamera":
+        """The same camera on a Film of another resolution: the fractional crop window, the filter, the diagonal, the scale and the filename are the film's (the pixel bounds
+        of the crop are derived again, as Film derives them)."""
+        f = self.film
+        film = Film(resolution, Bounds2(f.crop_window[:2], f.crop_window[2:]), f.filter, f.diagonal_mm, f.scale, f.filename)
+        return PerspectiveCamera(self.camera_to_world, self.screen_window, self.shutter_open, self.shutter_close, self.lens_radius, self.focal_distance, self.fov, film)
 
     def world_to_pixel(self) -> np.ndarray:
         """The 3 x 4 Float32 matrix M of trhip_sensor_world_to_pixel: with h = M (p, 1) for a world point p, (h.x / h.z, h.y / h.z) is p's position in film-array pixel
@@ -1191,6 +1200,127 @@ class Denoiser:
                 b.free()
 
 
+# ---- edge-aware upscaling (include/tracehip.h, trhip_upscale) ----------------------------------------------------------------------------------
+class Upscaler:
+    """Joint bilateral upsampling of a low-resolution path film onto the feature planes of the full-size sensor (trhip_upscale; docs/design/17-upscale.md): the path frame
+    is traced at 1 / factor of the resolution per axis, the cheap first-hit planes at both sizes, and the full-size film is reconstructed with the denoiser's normal and
+    plane-distance edge tests.  Fields left at None come from trhip_upscale_default_params.  `upscale` returns (xyzw, mask): mask 1 guided, 2 unguided (no surface
+    pixel), 3 orphan (a full-size surface no low pixel agreed with: filled bilinearly, the caller's to re-render), 0 nothing."""
+
+    def __init__(self, radius: Optional[int] = None, demodulate: Optional[bool] = None, coverage: Optional[bool] = None, sigma_normal: Optional[float] = None, sigma_plane: Optional[float] = None,
+                 albedo_floor: Optional[float] = None, min_coverage: Optional[float] = None):
+        p = _ffi.UpscaleParams()
+        rc = _ffi.lib().trhip_upscale_default_params(C.byref(p))
+        if rc:
+            raise TraceHipError(f"trhip_upscale_default_params failed ({rc})")
+        if radius is not None:
+            if int(radius) != radius or not 0 <= radius < 2 ** 32:
+                raise TraceHipError(f"Upscaler: radius must be 1 or 2, not {radius!r}")
+            p.radius = int(radius)
+        for name, value in (("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane), ("albedo_floor", albedo_floor), ("min_coverage", min_coverage)):
+            if value is not None:
+                setattr(p, name, value)
+        for flag, value in ((_ffi.UPSCALE_DEMODULATE, demodulate), (_ffi.UPSCALE_COVERAGE, coverage)):
+            if value is not None:
+                p.flags = (p.flags | flag) if value else (p.flags & ~flag)
+        self.params = p
+        self.stats: Optional[_ffi.Stats] = None
+        self.render_stats = None  # (path, low planes, full planes, denoise or None, upscale) Stats of the last render()
+
+    @staticmethod
+    def pixel_map(hi_camera: PerspectiveCamera, lo_camera: PerspectiveCamera):
+        """(ax, bx, ay, by) of trhip_upscale_params.lo_from_hi for two films of one camera: array pixel x of the full-size film lies at x * ax + bx in the low film's array
+        coordinates.  Film pixel X (1-based) has its centre at raster position X + 0.5 and array index X - crop_min (docs/design/14-temporal.md); the two rasters share the
+        optical axis, which pierces them at o = -m03 / m00 of raster_to_camera (y: -m13 / m11), and differ by the ratio of the resolutions about it:
+        ax = res_lo.x / res_hi.x, bx = (crop_min_hi.x + 0.5 - o_hi.x) * ax + o_lo.x - 0.5 - crop_min_lo.x.  Float64, rounded once (docs/design/17-upscale.md derives it)."""
+        out = []
+        for k in (0, 1):
+            o = []
+            for cam in (hi_camera, lo_camera):
+                m = np.asarray(cam.raster_to_camera.m, np.float64)
+                if m[k, 1 - k] != 0.0 or m[k, k] == 0.0:
+                    raise TraceHipError("Upscaler.pixel_map: raster_to_camera must be axis-aligned (maps that are not axis-aligned affine are out of scope)")
+                o.append(-m[k, 3] / m[k, k])
+            a = float(lo_camera.film.resolution[k]) / float(hi_camera.film.resolution[k])
+            b = (float(hi_camera.film.crop_bounds.p_min[k]) + 0.5 - o[0]) * a + o[1] - 0.5 - float(lo_camera.film.crop_bounds.p_min[k])
+            out += [float(np.float32(a)), float(np.float32(b))]
+        return tuple(out)
+
+    @staticmethod
+    def low_camera(camera: PerspectiveCamera, factor) -> PerspectiveCamera:
+        """`camera` at 1 / factor of its resolution per axis (rounded to whole pixels, at least one)."""
+        if not 1.0 <= float(factor) <= 4.0:
+            raise TraceHipError(f"Upscaler: factor must lie in [1, 4], not {factor!r}")
+        res = [max(1, int(round(float(r) / float(factor)))) for r in camera.film.resolution]
+        return camera.with_resolution(res)
+
+    def _params_for(self, pixel_map) -> _ffi.UpscaleParams:
+        p = _ffi.UpscaleParams.from_buffer_copy(self.params)
+        m = [float(v) for v in pixel_map]
+        if len(m) != 4:
+            raise TraceHipError(f"Upscaler: pixel_map must be (ax, bx, ay, by), not {pixel_map!r}")
+        p.lo_from_hi[:] = m
+        return p
+
+    def upscale(self, lo_xyzw: np.ndarray, lo_planes: np.ndarray, hi_planes: np.ndarray, pixel_map, ctx: Optional[_ffi.Context] = None):
+        """lo_xyzw (h, w, 4) and lo_planes (h, w, 3, 4) of the low-resolution camera, hi_planes (H, W, 3, 4) of the full-size one, pixel_map as `pixel_map` returns it.
+        Returns (xyzw (H, W, 4), mask (H, W) uint8)."""
+        lo_xyzw, lo_planes, hi_planes = _ffi.f32(lo_xyzw), _ffi.f32(lo_planes), _ffi.f32(hi_planes)
+        if lo_xyzw.ndim != 3 or lo_xyzw.shape[2] != 4 or lo_planes.shape != lo_xyzw.shape[:2] + (3, 4) or hi_planes.ndim != 4 or hi_planes.shape[2:] != (3, 4):
+            raise TraceHipError(f"upscale: lo_xyzw must be (h, w, 4), lo_planes (h, w, 3, 4) and hi_planes (H, W, 3, 4), not {lo_xyzw.shape}, {lo_planes.shape} and {hi_planes.shape}")
+        p = self._params_for(pixel_map)
+        ctx = ctx or _ffi.default_context()
+        (lh, lw), (h, w) = lo_xyzw.shape[:2], hi_planes.shape[:2]
+        out, mask, st = np.empty((h, w, 4), np.float32), np.empty((h, w), np.uint8), _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_upscale(ctx._h, _ffi.fptr(lo_xyzw), _ffi.fptr(lo_planes), lw, lh, _ffi.fptr(hi_planes), w, h, C.byref(p), _ffi.fptr(out),
+                                           mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st)))
+        self.stats = st
+        return out, mask
+
+    def upscale_device(self, d_lo_xyzw: int, d_lo_planes: int, lo_width: int, lo_height: int, d_hi_planes: int, width: int, height: int, pixel_map, d_out: int,
+                       d_out_mask: Optional[int] = None, ctx: Optional[_ffi.Context] = None) -> None:
+        """The same on device pointers (d_out_mask may be None); nothing is copied to the host."""
+        p = self._params_for(pixel_map)
+        ctx = ctx or _ffi.default_context()
+        st = _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_upscale_device(ctx._h, C.c_void_p(d_lo_xyzw), C.c_void_p(d_lo_planes), int(lo_width), int(lo_height), C.c_void_p(d_hi_planes), int(width), int(height),
+                                                  C.byref(p), C.c_void_p(d_out), C.c_void_p(d_out_mask) if d_out_mask else None, C.byref(st)))
+        self.stats = st
+
+    def render(self, scene: Scene, camera: PerspectiveCamera, sampler: SeededSampler, max_depth: int, factor=2, guide_spp: Optional[int] = None,
+               denoiser: Optional["Denoiser"] = None, denoise_at: Optional[str] = "high", ctx: Optional[_ffi.Context] = None, want_mask: bool = False):
+        """The one-shot frame, everything on the device: the path frame and its planes through `camera` at 1 / factor of the resolution with `sampler`, the full-size planes
+        with `guide_spp` samples per pixel (default: the sampler's; same seed and offset), `denoiser` on the upscaled frame with the full-size planes (denoise_at "high", the
+        default: it measured better in every swept cell, profiles/r14/upscale.txt), on the low frame ("low") or not at all (None, or no denoiser).  Returns xyzw (H, W, 4), ready for film.set_xyzw / save; with want_mask (xyzw, mask)."""
+        if denoise_at not in ("low", "high", None):
+            raise TraceHipError(f"Upscaler.render: denoise_at must be 'low', 'high' or None, not {denoise_at!r}")
+        ctx = scene.flatten(ctx).ctx
+        lo_cam = self.low_camera(camera, factor)
+        (h, w), (lh, lw) = camera.film.size, lo_cam.film.size
+        guide = SeededSampler(sampler.samples_per_pixel if guide_spp is None else int(guide_spp), seed=sampler.seed, sample_offset=sampler.sample_offset)
+        bufs = [_ffi.DeviceBuffer(n) for n in (lh * lw * 16, lh * lw * 48, h * w * 48, h * w * 16, h * w)]
+        d_lo, d_lo_planes, d_hi_planes, d_out, d_mask = bufs
+        try:
+            path, aov_lo, aov_hi = PathIntegrator(lo_cam, sampler, max_depth), AOVIntegrator(lo_cam, sampler), AOVIntegrator(camera, guide)
+            path.render(scene, ctx, device_out=d_lo.ptr)
+            aov_lo.render(scene, ctx, device_out=d_lo_planes.ptr)
+            aov_hi.render(scene, ctx, device_out=d_hi_planes.ptr)
+            dn_stats = None
+            if denoiser is not None and denoise_at == "low":
+                denoiser.denoise_device(d_lo.ptr, d_lo_planes.ptr, lw, lh, d_lo.ptr, ctx)
+                dn_stats = denoiser.stats
+            self.upscale_device(d_lo.ptr, d_lo_planes.ptr, lw, lh, d_hi_planes.ptr, w, h, self.pixel_map(camera, lo_cam), d_out.ptr, d_mask.ptr if want_mask else None, ctx)
+            if denoiser is not None and denoise_at == "high":
+                denoiser.denoise_device(d_out.ptr, d_hi_planes.ptr, w, h, d_out.ptr, ctx)
+                dn_stats = denoiser.stats
+            self.render_stats = (path.stats, aov_lo.stats, aov_hi.stats, dn_stats, self.stats)
+            out = d_out.to_host(np.float32, (h, w, 4))
+            return (out, d_mask.to_host(np.uint8, (h, w))) if want_mask else out
+        finally:
+            for b in bufs:
+                b.free()
+
+
 # ---- temporal reprojection (include/tracehip.h, trhip_temporal) ------------------------------------------------------------------------------
 class TemporalAccumulator:
     """Blends a path frame with the previous frame's accumulated colour, fetched through the previous camera and validated against the feature planes (trhip_temporal;
@@ -1346,11 +1476,16 @@ class PreviewSession:
     frames needs no reset(): render() flattens `self.scene` every frame, and a history lit the old way is cut back to the new frame's colours within a frame.
     `variance_guided=True`: the accumulator carries the luminance moments (TemporalAccumulator(moments=True), the default then; demodulation and albedo floor the
     denoiser's) and the filter is Denoiser.denoise_variance with the variance plane of the frame; a frame without history is filtered from its own bits with the spatial
-    estimate, as Denoiser.render(variance_guided=True) filters it.  The default, False, is the session described above, call for call."""
+    estimate, as Denoiser.render(variance_guided=True) filters it.  The default, False, is the session described above, call for call.
+    `upscaler=Upscaler(...)`: path frame, planes, temporal pass and filter run through `camera.with_resolution(resolution / factor)` and the history is held at that size;
+    the full-size planes are drawn with `guide_spp` samples per pixel (default: the sampler's) and the filtered frame is upscaled last (trhip_upscale;
+    docs/design/17-upscale.md).  With None, the default, the session is the one described above, call for call."""
 
     def __init__(self, scene: Scene, sampler: SeededSampler, max_depth: int, denoiser: Optional["Denoiser"] = None, temporal: Optional[TemporalAccumulator] = None,
-                 variance_guided: bool = False):
+                 variance_guided: bool = False, upscaler: Optional["Upscaler"] = None, factor=2, guide_spp: Optional[int] = None):
         self.scene, self.sampler, self.max_depth = scene, sampler, int(max_depth)
+        self.upscaler, self.factor, self.guide_spp = upscaler, factor, guide_spp
+        self._up_buffers, self._up_size = None, None  # full-size planes and the upscaled film
         self.denoiser = denoiser if denoiser is not None else Denoiser()
         self.variance_guided = bool(variance_guided)
         if self.variance_guided and temporal is None:
@@ -1372,10 +1507,16 @@ class PreviewSession:
         for b in self._buffers or ():
             b.free()
         self._buffers, self._size, self._prev_matrix = None, None, None
+        for b in self._up_buffers or ():
+            b.free()
+        self._up_buffers, self._up_size = None, None
 
     def render(self, camera: PerspectiveCamera, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
         """The next frame through `camera`; returns xyzw (H, W, 4), ready for film.set_xyzw / save."""
         ctx = self.scene.flatten(ctx).ctx
+        hi_camera = camera
+        if self.upscaler is not None:
+            camera = Upscaler.low_camera(hi_camera, self.factor)
         h, w = camera.film.size
         if self._size != (h, w):
             self.close()
@@ -1401,13 +1542,32 @@ class PreviewSession:
             # without history the accumulated film is the frame itself up to the rounding of XYZ -> RGB -> XYZ: the frame's own bits are filtered then
             self.denoiser.denoise_device((d_acc if had_history else d_film).ptr, d_planes.ptr, w, h, d_acc.ptr, ctx)
         self.render_stats = (path.stats, aov.stats, self.temporal.stats, self.denoiser.stats)
-        out = d_acc.to_host(np.float32, (h, w, 4))
+        if self.upscaler is not None:
+            out = self._upscale(hi_camera, camera, sampler, d_acc, d_planes, ctx)
+        else:
+            out = d_acc.to_host(np.float32, (h, w, 4))
         self._prev_matrix = matrix
         self.frame += 1
         return out
 
 
 # ---- SPPM and the DirectionalLight -------------------------------------------------------------------------------------------------
+    def _upscale(self, hi_camera, lo_camera, sampler, d_lo, d_lo_planes, ctx) -> np.ndarray:
+        """The session's filtered low-resolution frame onto the full-size planes of this frame."""
+        (hh, hw), (lh, lw) = hi_camera.film.size, lo_camera.film.size
+        if self._up_size != (hh, hw):
+            for b in self._up_buffers or ():
+                b.free()
+            self._up_size, self._up_buffers = (hh, hw), [_ffi.DeviceBuffer(hh * hw * n) for n in (48, 16)]
+        d_hi_planes, d_out = self._up_buffers
+        guide = SeededSampler(sampler.samples_per_pixel if self.guide_spp is None else int(self.guide_spp), seed=sampler.seed, sample_offset=sampler.sample_offset)
+        aov = AOVIntegrator(hi_camera, guide)
+        aov.render(self.scene, ctx, device_out=d_hi_planes.ptr)
+        self.upscaler.upscale_device(d_lo.ptr, d_lo_planes.ptr, lw, lh, d_hi_planes.ptr, hw, hh, Upscaler.pixel_map(hi_camera, lo_camera), d_out.ptr, None, ctx)
+        self.render_stats = self.render_stats + (aov.stats, self.upscaler.stats)
+        return d_out.to_host(np.float32, (hh, hw, 4))
+
+
 def _to_Y(c) -> np.float32:  # spectrum.jl:64-66
     c = np.asarray(c, np.float32)
     return f32(f32(f32(0.212671) * c[0]) + f32(f32(0.715160) * c[1])) + f32(f32(0.072169) * c[2])

@@ -143,6 +143,7 @@ struct trhip_ctx {
                             // the result's film (176 B); trhip_temporal_clip_device's film for a result that aliases its input (16 B); trhip_temporal_moments likewise (196 B; 16 B)
     int temporal_patch = 1; // trhip_temporal's lane-to-pixel mapping: 0 film order, 1 patches of 16 x 4 per wave, measured 11 % faster (option "temporal_patch", profiles/r11/temporal.txt)
     int denoise_var_lds = 3;  // bit i: iteration i (step 2^i, i < 2) of trhip_denoise_var runs the LDS-staged kernel (option "denoise_var_lds", profiles/r13/variance.txt)
+    DevBuf up_in;      // trhip_upscale's host entry point: its copies of the five images (th_upscale.h; 64 B per low pixel, 65 per full-size pixel)
     DevBuf cb_rc;      // one word: a host callback's return code, max-reduced over the ranks of a job (tu_sppm.hip)
     DevBuf ov8[2], fb_list[2], fb_counts[2];  // k_trace8: global stack levels, fallback lists + their counters / work cursors ([closest | any])
     Comm comm;  // multi-GPU job this context belongs to (trhip_comm_init); n_ranks == 1 without one

@@ -52,6 +52,7 @@ void trhip_shutdown(trhip_ctx* ctx) {
     release(ctx->dn_work);
     release(ctx->dn_in);
     release(ctx->tp_in);
+    release(ctx->up_in);
     release(ctx->cb_rc);
     for (auto& pp : ctx->pipes) {
         for (auto& a : pp.q)

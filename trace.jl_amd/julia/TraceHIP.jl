@@ -401,6 +401,8 @@ include("TraceHIPTemporal.jl")
 include("TraceHIPTemporalClip.jl")
 # MomentsTemporalAccumulator (trhip_temporal_moments) and VarianceDenoiser (trhip_denoise_var), likewise (tests/golden/julia_shim_variance_calls.json)
 include("TraceHIPVariance.jl")
+# Upscaler (trhip_upscale) and pixel_map, likewise (tests/golden/julia_shim_upscale_calls.json)
+include("TraceHIPUpscale.jl")
 
 # SPPMIntegrator (integrators/sppm.jl:132-173) on the device: trhip_render_sppm returns the film after set_image!
 # (film.jl:195-202).  `seed` selects the seeded stream of the camera pass (the reference draws from the global RNG there).
