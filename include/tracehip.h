@@ -565,6 +565,68 @@ int trhip_upscale(trhip_ctx* ctx, const float* lo_xyzw, const float* lo_planes, 
 int trhip_upscale_device(trhip_ctx* ctx, const void* d_lo_xyzw, const void* d_lo_planes, uint32_t lo_width, uint32_t lo_height, const void* d_hi_planes, uint32_t width,
                          uint32_t height, const trhip_upscale_params* params, void* d_out_xyzw, void* d_out_mask, trhip_stats* stats);
 
+/* ---- display pass: metered exposure, tone curve and 8-bit encode of a film (since ABI 3001, added without a version change: nothing existing moved) ----
+ * The last stage of a preview: the Float32 film state is metered, exposed, tone-mapped and encoded to 8-bit RGBA on the device, 4 bytes per pixel
+ * instead of 16 for the host to fetch.  Specified operation by operation in docs/design/18-display.md; no transcendental function is evaluated, and the
+ * result is bit-reproducible from run to run (the metering histogram is integer).
+ *   xyzw               height * width float4: a film state, what trhip_render_path, trhip_denoise, trhip_temporal*, trhip_upscale wrote
+ *   scale              the film's scale (film.jl: the factor of save)
+ *   out_rgba           height * width * 4 bytes: R, G, B, A per pixel, A = 255 where the pixel's weight is not 0 and 0 elsewhere; row r of the output is row
+ *                      height - 1 - r of the film with TRHIP_DISPLAY_FLIP_ROWS (the order save writes), row r otherwise
+ *   out_histogram256   256 uint32 or NULL: the metered counts (all zero without TRHIP_DISPLAY_AUTO_EXPOSURE)
+ *   state              16 bytes the CALLER owns, carried from frame to frame; all zero = no state.  trhip_display takes it in HOST memory (in and out),
+ *                      trhip_display_device in DEVICE memory.  NULL: no state is read, none is kept.  Written only with AUTO_EXPOSURE.
+ * Metering (AUTO_EXPOSURE only): a pixel counts iff w > 0 and Y = ((y / w as y * (1 / w)) * scale) satisfies 2^-20 <= Y < +Inf; its bin is
+ * min((bits(Y) >> 20) - 856, 255): 256 bins, eight per octave from 2^-20 to 2^12, the lower edge of bin b being the float with bits (b + 856) << 20.
+ * Resolve: total = sum of the counts.  total == 0: E = state.valid ? state.exposure : exposure, state = {E, state.valid, 0, 0}.  Otherwise b = the smallest
+ * bin with cum(b) * 1000 >= total * percentile_permille, need = ceil(total * permille / 1000), Lm = L(b) + (float(need - cum(b - 1)) / float(hist[b])) *
+ * (L(b + 1) - L(b)), Et = clamp(key / Lm, min_exposure, max_exposure), E = state.exposure + (Et - state.exposure) * adapt_rate when a valid state is given
+ * and adapt_rate < 1, else Et; state = {E, 1, total, b}.  Without AUTO_EXPOSURE E = exposure.
+ * Encode: c = what trhip_film_to_rgb computes before its clamp (XYZ -> RGB, divided by w and floored at 0 where w != 0, times scale), times E, capped at
+ * 2^40; per channel t = c (CLAMP), (c * (1 + c / white^2)) / (1 + c) (REINHARD, extended), (c * (2.51 c + 0.03)) / (c * (2.43 c + 0.59) + 0.14) (ACES,
+ * Narkowicz's fit); t clamped to [0, 1], NaN to 0; the byte is rint(t * 255), ties to even (LINEAR), or the number of k in 1..255 with t >= T[k] (SRGB),
+ * T the table trhip_display_srgb_table returns: T[k] the smallest Float32 not below the sRGB EOTF of (k - 0.5) / 255.  Every byte is defined whatever the
+ * film holds.  With CLAMP, LINEAR, no AUTO_EXPOSURE, exposure 1 and FLIP_ROWS the RGB bytes are the ones save writes for every pixel free of NaN.
+ * TRHIP_ERR_INVALID, in this order, the parameter block before any handle: params NULL; curve > 2; transfer > 1; unknown flag bits; exposure, key,
+ * min_exposure or max_exposure not finite and > 0; min_exposure > max_exposure; percentile_permille outside 1..1000; adapt_rate outside (0, 1]; white outside
+ * [2^-10, 2^20]; scale not finite; reserved != 0; then a null pointer (state, histogram and stats excepted); a zero dimension; width * height >= 2^31;
+ * out_rgba overlapping the input.  TRHIP_ERR_UNSUPPORTED: more than 65535 blocks of 16 pixels on a side, or the host variant's device copies (20 bytes
+ * per pixel) do not fit in free HBM.  stats (may be NULL): ms_total, ms_film and launches_film over the call's kernels: 3 with AUTO_EXPOSURE (meter,
+ * resolve, encode), 1 without; their parts in ms_sub / launches_sub: [0] meter, [1] resolve, [2] encode; the 1 KiB histogram is cleared by a memset,
+ * which is not counted.  The _device variant takes DEVICE pointers and allocates
+ * nothing beyond a 1 KiB histogram and a 16-byte state slot kept on the context.  The default parameters need no context and no GPU: REINHARD, SRGB, both
+ * flags, exposure 1, key 0.18, the median (500), adapt_rate 1, exposures within [2^-8, 2^8], white 4 — conventional values, not swept. */
+#define TRHIP_DISPLAY_AUTO_EXPOSURE 1u
+#define TRHIP_DISPLAY_FLIP_ROWS 2u
+#define TRHIP_DISPLAY_CURVE_CLAMP 0u
+#define TRHIP_DISPLAY_CURVE_REINHARD 1u
+#define TRHIP_DISPLAY_CURVE_ACES 2u
+#define TRHIP_DISPLAY_TRANSFER_LINEAR 0u
+#define TRHIP_DISPLAY_TRANSFER_SRGB 1u
+typedef struct {
+    uint32_t curve;                /* 0 CLAMP, 1 REINHARD (extended), 2 ACES (Narkowicz's rational fit) */
+    uint32_t transfer;             /* 0 LINEAR, 1 SRGB */
+    uint32_t flags;                /* TRHIP_DISPLAY_AUTO_EXPOSURE | TRHIP_DISPLAY_FLIP_ROWS */
+    float exposure;                /* the exposure when AUTO is off; the fallback when nothing could be metered */
+    float key;                     /* luminance the metered percentile is mapped to */
+    uint32_t percentile_permille;  /* 1..1000 */
+    float adapt_rate;              /* (0, 1]; 1 = no smoothing */
+    float min_exposure, max_exposure;
+    float white;                   /* REINHARD's white point, in exposed units */
+    uint32_t reserved[2];          /* 0 */
+} trhip_display_params;            /* 48 bytes */
+typedef struct {
+    float exposure;
+    uint32_t valid, counted, key_bin;
+} trhip_display_state;             /* 16 bytes; all zero = no state */
+int trhip_display_default_params(trhip_display_params* out);
+/* out256[0] = 0, out256[k] = T[k]; no context, no GPU */
+int trhip_display_srgb_table(float* out256);
+int trhip_display(trhip_ctx* ctx, const float* xyzw, uint32_t width, uint32_t height, float scale, const trhip_display_params* params, trhip_display_state* host_state_inout,
+                  uint8_t* out_rgba, uint32_t* out_histogram256, trhip_stats* stats);
+int trhip_display_device(trhip_ctx* ctx, const void* d_xyzw, uint32_t width, uint32_t height, float scale, const trhip_display_params* params, void* d_state, void* d_out_rgba,
+                         void* d_histogram256, trhip_stats* stats);
+
 /* SPPMIntegrator(camera, initial_search_radius, max_depth, n_iterations, photons_per_iteration)(scene)
  * (integrators/sppm.jl:108-173): per iteration a camera pass to the first diffuse vertex, a hash grid over the visible
  * points, a photon pass (Halton / radical_inverse, sampler/sampling.jl:43-60) and the Float64 pixel update; afterwards

@@ -206,6 +206,34 @@ class UpscaleParams(C.Structure):
 UPSCALE_DEMODULATE = 1  # TRHIP_UPSCALE_DEMODULATE
 UPSCALE_COVERAGE = 2    # TRHIP_UPSCALE_COVERAGE
 
+
+class DisplayParams(C.Structure):
+    """trhip_display_params (48 bytes)"""
+    _fields_ = [
+        ("curve", C.c_uint32),
+        ("transfer", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("exposure", C.c_float),
+        ("key", C.c_float),
+        ("percentile_permille", C.c_uint32),
+        ("adapt_rate", C.c_float),
+        ("min_exposure", C.c_float),
+        ("max_exposure", C.c_float),
+        ("white", C.c_float),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class DisplayState(C.Structure):
+    """trhip_display_state (16 bytes); all zero = no state"""
+    _fields_ = [("exposure", C.c_float), ("valid", C.c_uint32), ("counted", C.c_uint32), ("key_bin", C.c_uint32)]
+
+
+DISPLAY_AUTO_EXPOSURE = 1  # TRHIP_DISPLAY_AUTO_EXPOSURE
+DISPLAY_FLIP_ROWS = 2      # TRHIP_DISPLAY_FLIP_ROWS
+DISPLAY_CURVES = {"clamp": 0, "reinhard": 1, "aces": 2}  # TRHIP_DISPLAY_CURVE_*
+DISPLAY_TRANSFERS = {"linear": 0, "srgb": 1}             # TRHIP_DISPLAY_TRANSFER_*
+
 _F = C.POINTER(C.c_float)
 _U32 = C.POINTER(C.c_uint32)
 _VP = C.c_void_p
@@ -268,6 +296,10 @@ SIGNATURES = {
     "trhip_upscale_default_params": (C.c_int, [C.POINTER(UpscaleParams)]),
     "trhip_upscale": (C.c_int, [_VP, _F, _F, C.c_uint32, C.c_uint32, _F, C.c_uint32, C.c_uint32, C.POINTER(UpscaleParams), _F, C.POINTER(C.c_uint8), C.POINTER(Stats)]),
     "trhip_upscale_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP, C.c_uint32, C.c_uint32, C.POINTER(UpscaleParams), _VP, _VP, C.POINTER(Stats)]),
+    "trhip_display_default_params": (C.c_int, [C.POINTER(DisplayParams)]),
+    "trhip_display_srgb_table": (C.c_int, [_F]),
+    "trhip_display": (C.c_int, [_VP, _F, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(DisplayParams), C.POINTER(DisplayState), C.POINTER(C.c_uint8), _U32, C.POINTER(Stats)]),
+    "trhip_display_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(DisplayParams), _VP, _VP, _VP, C.POINTER(Stats)]),
     "trhip_render_sppm": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats)]),
     "trhip_render_sppm_ex": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats), C.c_uint32, SPPM_WRITE_FN, _VP]),
     "trhip_sppm_state": (C.c_int, [_VP, _F, _F, _F, C.POINTER(C.c_double), C.POINTER(C.c_int64), _F, _F, _F, C.POINTER(C.c_int64)]),

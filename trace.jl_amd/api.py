@@ -1321,6 +1321,92 @@ class Upscaler:
                 b.free()
 
 
+# ---- display pass (include/tracehip.h, trhip_display) ---------------------------------------------------------------------------------------
+class Display:
+    """The last stage of a preview, on the device: meter the film's luminance, expose, apply a tone curve and encode to 8-bit RGBA (trhip_display;
+    docs/design/18-display.md).  curve "clamp" | "reinhard" | "aces", transfer "linear" | "srgb" (or the header's numbers); `percentile` in (0, 1] is the metered quantile that
+    is mapped to `key`.  Fields left at None come from trhip_display_default_params.  `state` is the 16-byte exposure state carried from frame to frame: a
+    _ffi.DisplayState for `encode` (host), a device address for `encode_device`."""
+
+    def __init__(self, curve=None, transfer=None, auto_exposure: Optional[bool] = None, flip_rows: Optional[bool] = None, exposure: Optional[float] = None, key: Optional[float] = None,
+                 percentile: Optional[float] = None, adapt_rate: Optional[float] = None, min_exposure: Optional[float] = None, max_exposure: Optional[float] = None,
+                 white: Optional[float] = None):
+        p = _ffi.DisplayParams()
+        rc = _ffi.lib().trhip_display_default_params(C.byref(p))
+        if rc:
+            raise TraceHipError(f"trhip_display_default_params failed ({rc})")
+        for name, value, names in (("curve", curve, _ffi.DISPLAY_CURVES), ("transfer", transfer, _ffi.DISPLAY_TRANSFERS)):
+            if value is not None:
+                number = names.get(value.lower()) if isinstance(value, str) else value
+                if number is None or int(number) != number or not 0 <= number < 2 ** 32:
+                    raise TraceHipError(f"Display: {name} must be one of {sorted(names)}, not {value!r}")
+                setattr(p, name, int(number))
+        if percentile is not None:
+            permille = int(round(float(percentile) * 1000.0)) if math.isfinite(percentile) else -1
+            if not 0 <= permille < 2 ** 32:
+                raise TraceHipError(f"Display: percentile must lie in (0, 1], not {percentile!r}")
+            p.percentile_permille = permille
+        for name, value in (("exposure", exposure), ("key", key), ("adapt_rate", adapt_rate), ("min_exposure", min_exposure), ("max_exposure", max_exposure), ("white", white)):
+            if value is not None:
+                setattr(p, name, value)
+        for flag, value in ((_ffi.DISPLAY_AUTO_EXPOSURE, auto_exposure), (_ffi.DISPLAY_FLIP_ROWS, flip_rows)):
+            if value is not None:
+                p.flags = (p.flags | flag) if value else (p.flags & ~flag)
+        self.params = p
+        self.stats: Optional[_ffi.Stats] = None
+
+    @staticmethod
+    def reference() -> "Display":
+        """The look of `save`: linear clamp, no transfer function, exposure 1, rows flipped.  Its RGB bytes are the ones save(film) writes for every pixel free of NaN."""
+        return Display(curve="clamp", transfer="linear", auto_exposure=False, flip_rows=True, exposure=1.0)
+
+    @staticmethod
+    def srgb_table() -> np.ndarray:
+        """(256,) Float32: [0] = 0, [k] = T[k], the sRGB encode's thresholds (trhip_display_srgb_table; no GPU)."""
+        out = np.empty(256, np.float32)
+        rc = _ffi.lib().trhip_display_srgb_table(_ffi.fptr(out))
+        if rc:
+            raise TraceHipError(f"trhip_display_srgb_table failed ({rc})")
+        return out
+
+    def encode(self, xyzw: np.ndarray, scale=1.0, state: Optional[_ffi.DisplayState] = None, ctx: Optional[_ffi.Context] = None, want_histogram: bool = False):
+        """xyzw (H, W, 4) -> uint8 (H, W, 4).  With a `state` (a _ffi.DisplayState; DisplayState() = none yet) returns (rgba, state), the state a new object; with
+        want_histogram (rgba, state, histogram (256,) uint32), the state None when none was given."""
+        xyzw = _ffi.f32(xyzw)
+        if xyzw.ndim != 3 or xyzw.shape[2] != 4:
+            raise TraceHipError(f"Display.encode: xyzw must be (H, W, 4), not {xyzw.shape}")
+        ctx = ctx or _ffi.default_context()
+        h, w = xyzw.shape[:2]
+        out, st = np.empty((h, w, 4), np.uint8), _ffi.Stats()
+        hist = np.empty(256, np.uint32) if want_histogram else None
+        new_state = _ffi.DisplayState.from_buffer_copy(state) if state is not None else None
+        ctx.check(_ffi.lib().trhip_display(ctx._h, _ffi.fptr(xyzw), w, h, float(scale), C.byref(self.params), C.byref(new_state) if new_state is not None else None,
+                                           out.ctypes.data_as(C.POINTER(C.c_uint8)), _ffi.u32ptr(hist) if hist is not None else None, C.byref(st)))
+        self.stats = st
+        if want_histogram:
+            return out, new_state, hist
+        return (out, new_state) if state is not None else out
+
+    def encode_device(self, d_xyzw: int, width: int, height: int, scale, d_out_rgba: int, d_state: Optional[int] = None, d_histogram: Optional[int] = None,
+                      ctx: Optional[_ffi.Context] = None) -> None:
+        """The same on device pointers: d_out_rgba height * width * 4 bytes, d_state 16 bytes (zeroed = no state yet) or None, d_histogram 1024 bytes or None; nothing is
+        copied to the host."""
+        ctx = ctx or _ffi.default_context()
+        st = _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_display_device(ctx._h, C.c_void_p(d_xyzw), int(width), int(height), float(scale), C.byref(self.params), C.c_void_p(d_state) if d_state else None,
+                                                  C.c_void_p(d_out_rgba), C.c_void_p(d_histogram) if d_histogram else None, C.byref(st)))
+        self.stats = st
+
+    def save(self, film: "Film", ctx: Optional[_ffi.Context] = None) -> str:
+        """Writes film.filename (8-bit PNG) through the pass: the rows come out in the order the parameters say (flipped by default, as `save` writes them) and the bytes are
+        the device's; nothing is flipped or rounded on the host."""
+        from PIL import Image
+        xyzw = np.concatenate([film.xyz, film.filter_weight_sum[..., None]], axis=-1)
+        rgba = self.encode(xyzw, film.scale, ctx=ctx)
+        Image.fromarray(np.ascontiguousarray(rgba[..., :3]), "RGB").save(film.filename)
+        return film.filename
+
+
 # ---- temporal reprojection (include/tracehip.h, trhip_temporal) ------------------------------------------------------------------------------
 class TemporalAccumulator:
     """Blends a path frame with the previous frame's accumulated colour, fetched through the previous camera and validated against the feature planes (trhip_temporal;
@@ -1479,11 +1565,16 @@ class PreviewSession:
     estimate, as Denoiser.render(variance_guided=True) filters it.  The default, False, is the session described above, call for call.
     `upscaler=Upscaler(...)`: path frame, planes, temporal pass and filter run through `camera.with_resolution(resolution / factor)` and the history is held at that size;
     the full-size planes are drawn with `guide_spp` samples per pixel (default: the sampler's) and the filtered frame is upscaled last (trhip_upscale;
-    docs/design/17-upscale.md).  With None, the default, the session is the one described above, call for call."""
+    docs/design/17-upscale.md).  With None, the default, the session is the one described above, call for call.
+    `display=Display(...)`: `render_display(camera)` renders the frame as `render` does and encodes the final device buffer to 8-bit RGBA (trhip_display;
+    docs/design/18-display.md): only the bytes are downloaded, and the exposure state stays on the device from frame to frame (reset() and a film of another size clear it).
+    `render` itself makes the calls it always made, with or without a display."""
 
     def __init__(self, scene: Scene, sampler: SeededSampler, max_depth: int, denoiser: Optional["Denoiser"] = None, temporal: Optional[TemporalAccumulator] = None,
-                 variance_guided: bool = False, upscaler: Optional["Upscaler"] = None, factor=2, guide_spp: Optional[int] = None):
+                 variance_guided: bool = False, upscaler: Optional["Upscaler"] = None, factor=2, guide_spp: Optional[int] = None, display: Optional["Display"] = None):
         self.scene, self.sampler, self.max_depth = scene, sampler, int(max_depth)
+        self.display = display
+        self._display_buffers, self._display_size = None, None  # RGBA bytes and the 16-byte exposure state
         self.upscaler, self.factor, self.guide_spp = upscaler, factor, guide_spp
         self._up_buffers, self._up_size = None, None  # full-size planes and the upscaled film
         self.denoiser = denoiser if denoiser is not None else Denoiser()
@@ -1502,6 +1593,8 @@ class PreviewSession:
     def reset(self) -> None:
         """Drops the history.  Not needed after a change of lights when the session's accumulator clips (TemporalAccumulator(clip_gamma=...))."""
         self._prev_matrix = None
+        if self._display_buffers:
+            self._display_buffers[1].zero()
 
     def close(self) -> None:
         for b in self._buffers or ():
@@ -1510,9 +1603,32 @@ class PreviewSession:
         for b in self._up_buffers or ():
             b.free()
         self._up_buffers, self._up_size = None, None
+        for b in self._display_buffers or ():
+            b.free()
+        self._display_buffers, self._display_size = None, None
 
     def render(self, camera: PerspectiveCamera, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
         """The next frame through `camera`; returns xyzw (H, W, 4), ready for film.set_xyzw / save."""
+        d_out, (h, w), _ = self._render_device(camera, ctx)
+        return d_out.to_host(np.float32, (h, w, 4))
+
+    def render_display(self, camera: PerspectiveCamera, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
+        """The next frame through `camera`, rendered exactly as `render` renders it and encoded by the session's Display with scale = camera.film.scale; returns uint8
+        (H, W, 4).  Only these bytes leave the device."""
+        if self.display is None:
+            raise TraceHipError("PreviewSession.render_display: the session was constructed without display=Display(...)")
+        d_out, (h, w), ctx = self._render_device(camera, ctx)
+        if self._display_size != (h, w):
+            for b in self._display_buffers or ():
+                b.free()
+            self._display_size, self._display_buffers = (h, w), [_ffi.DeviceBuffer(h * w * 4), _ffi.DeviceBuffer(16).zero()]
+        d_rgba, d_state = self._display_buffers
+        self.display.encode_device(d_out.ptr, w, h, camera.film.scale, d_rgba.ptr, d_state.ptr, None, ctx)
+        self.render_stats = self.render_stats + (self.display.stats,)
+        return d_rgba.to_host(np.uint8, (h, w, 4))
+
+    def _render_device(self, camera: PerspectiveCamera, ctx: Optional[_ffi.Context]):
+        """The frame of `render`, left on the device: (buffer, (H, W), context)."""
         ctx = self.scene.flatten(ctx).ctx
         hi_camera = camera
         if self.upscaler is not None:
@@ -1543,17 +1659,17 @@ class PreviewSession:
             self.denoiser.denoise_device((d_acc if had_history else d_film).ptr, d_planes.ptr, w, h, d_acc.ptr, ctx)
         self.render_stats = (path.stats, aov.stats, self.temporal.stats, self.denoiser.stats)
         if self.upscaler is not None:
-            out = self._upscale(hi_camera, camera, sampler, d_acc, d_planes, ctx)
+            out = self._upscale(hi_camera, camera, sampler, d_acc, d_planes, ctx), hi_camera.film.size, ctx
         else:
-            out = d_acc.to_host(np.float32, (h, w, 4))
+            out = d_acc, (h, w), ctx
         self._prev_matrix = matrix
         self.frame += 1
         return out
 
 
 # ---- SPPM and the DirectionalLight -------------------------------------------------------------------------------------------------
-    def _upscale(self, hi_camera, lo_camera, sampler, d_lo, d_lo_planes, ctx) -> np.ndarray:
-        """The session's filtered low-resolution frame onto the full-size planes of this frame."""
+    def _upscale(self, hi_camera, lo_camera, sampler, d_lo, d_lo_planes, ctx) -> "_ffi.DeviceBuffer":
+        """The session's filtered low-resolution frame onto the full-size planes of this frame (left on the device)."""
         (hh, hw), (lh, lw) = hi_camera.film.size, lo_camera.film.size
         if self._up_size != (hh, hw):
             for b in self._up_buffers or ():
@@ -1565,7 +1681,7 @@ class PreviewSession:
         aov.render(self.scene, ctx, device_out=d_hi_planes.ptr)
         self.upscaler.upscale_device(d_lo.ptr, d_lo_planes.ptr, lw, lh, d_hi_planes.ptr, hw, hh, Upscaler.pixel_map(hi_camera, lo_camera), d_out.ptr, None, ctx)
         self.render_stats = self.render_stats + (aov.stats, self.upscaler.stats)
-        return d_out.to_host(np.float32, (hh, hw, 4))
+        return d_out
 
 
 def _to_Y(c) -> np.float32:  # spectrum.jl:64-66

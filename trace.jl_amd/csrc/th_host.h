@@ -3,7 +3,7 @@
 // and linked into the one shared object): tu_api.hip (context, options, communicator), tu_scene.hip (scene flattening, commit, upload),
 // tu_lbvh.hip (BVH build on the device), tu_trace.hip / tu_trace3.hip / tu_trace3c.hip / tu_trace7.hip / tu_trace8.hip (traversal launches and entry points),
 // tu_path.hip (PathIntegrator frames, film, and the out-of-line part of the frame scaffold below: the stats functions), tu_aov.hip (first-hit feature buffers),
-// tu_ao.hip (ambient occlusion; the two share their camera-ray front half, th_camera.h), tu_denoise.hip (the à-trous filter), tu_temporal.hip (temporal reprojection), tu_whitted.hip, tu_sppm.hip.
+// tu_ao.hip (ambient occlusion; the two share their camera-ray front half, th_camera.h), tu_denoise.hip (the à-trous filter), tu_temporal.hip (temporal reprojection), tu_upscale.hip, tu_display.hip (the 8-bit display pass), tu_whitted.hip, tu_sppm.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -144,6 +144,7 @@ struct trhip_ctx {
     int temporal_patch = 1; // trhip_temporal's lane-to-pixel mapping: 0 film order, 1 patches of 16 x 4 per wave, measured 11 % faster (option "temporal_patch", profiles/r11/temporal.txt)
     int denoise_var_lds = 3;  // bit i: iteration i (step 2^i, i < 2) of trhip_denoise_var runs the LDS-staged kernel (option "denoise_var_lds", profiles/r13/variance.txt)
     DevBuf up_in;      // trhip_upscale's host entry point: its copies of the five images (th_upscale.h; 64 B per low pixel, 65 per full-size pixel)
+    DevBuf dp_work, dp_in;  // trhip_display: the 1 KiB metering histogram and a 16-byte state slot (th_display.h); the host entry point's copy of the film and its bytes (20 B per pixel)
     DevBuf cb_rc;      // one word: a host callback's return code, max-reduced over the ranks of a job (tu_sppm.hip)
     DevBuf ov8[2], fb_list[2], fb_counts[2];  // k_trace8: global stack levels, fallback lists + their counters / work cursors ([closest | any])
     Comm comm;  // multi-GPU job this context belongs to (trhip_comm_init); n_ranks == 1 without one

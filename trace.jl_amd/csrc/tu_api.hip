@@ -53,6 +53,8 @@ void trhip_shutdown(trhip_ctx* ctx) {
     release(ctx->dn_in);
     release(ctx->tp_in);
     release(ctx->up_in);
+    release(ctx->dp_work);
+    release(ctx->dp_in);
     release(ctx->cb_rc);
     for (auto& pp : ctx->pipes) {
         for (auto& a : pp.q)

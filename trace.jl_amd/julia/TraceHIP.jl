@@ -403,6 +403,8 @@ include("TraceHIPTemporalClip.jl")
 include("TraceHIPVariance.jl")
 # Upscaler (trhip_upscale) and pixel_map, likewise (tests/golden/julia_shim_upscale_calls.json)
 include("TraceHIPUpscale.jl")
+# Display (trhip_display), likewise (tests/golden/julia_shim_display_calls.json)
+include("TraceHIPDisplay.jl")
 
 # SPPMIntegrator (integrators/sppm.jl:132-173) on the device: trhip_render_sppm returns the film after set_image!
 # (film.jl:195-202).  `seed` selects the seeded stream of the camera pass (the reference draws from the global RNG there).
