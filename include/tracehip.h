@@ -627,6 +627,56 @@ int trhip_display(trhip_ctx* ctx, const float* xyzw, uint32_t width, uint32_t he
 int trhip_display_device(trhip_ctx* ctx, const void* d_xyzw, uint32_t width, uint32_t height, float scale, const trhip_display_params* params, void* d_state, void* d_out_rgba,
                          void* d_histogram256, trhip_stats* stats);
 
+/* ---- temporal upsampling of jittered low-resolution path frames (since ABI 3001, added without a version change: nothing existing moved) ----
+ * trhip_upscale rebuilds every full-size frame from one low-resolution estimate; with a low camera that is shifted by a sub-pixel offset every frame and a history
+ * held at FULL size, detail below the low grid accumulates instead.  One fused pass: the low film is upscaled onto the full-size planes as trhip_upscale
+ * does it (flags off), and blended into the previous frame's history, fetched through the previous full-size camera as trhip_temporal fetches it, with a
+ * weight kappa in [0, 1] that says how directly a low sample observed the pixel.  Specified operation by operation in docs/design/19-temporal-upsample.md; bit-reproducible.
+ *   lo_xyzw, lo_planes   what trhip_render_path and trhip_render_aov wrote for the (jittered) low-resolution sensor
+ *   hi_planes            what trhip_render_aov wrote for the full-size sensor (any spp)
+ *   history              height * width * 3 float4 in trhip_temporal's layout, or NULL: word 0 = (c.rgb, Omega), Omega an accumulated WEIGHT, not a frame count;
+ *                        word 1 = (n, 1.0 if surface else 0.0); word 2 = (p, 0).  The out_history of the previous call.
+ *   out_xyzw             height * width float4: a film state; .w is plane 0's weight of hi_planes bit for bit
+ *   out_history          this frame's history
+ *   out_mask             height * width bytes or NULL: trhip_upscale's class (0 nothing, 1 guided, 2 unguided, 3 orphan) + 4 where history was found
+ * lo_from_hi as in trhip_upscale_params, for THIS frame's jittered low sensor; prev_world_to_pixel: trhip_sensor_world_to_pixel of the previous FULL-SIZE sensor.
+ * Per full-size pixel: steps H1-H5 of trhip_upscale with guide_sigma_normal, guide_sigma_plane, min_coverage, radius and no flags give its colour c and class m; every
+ * accepted guided tap also gives e = ((gy * gx) * wn) * wp, gx = max(1 - d_x * confidence_sharpness, 0) with d_x the tap's distance in low pixels, and kmax is the largest
+ * e.  kappa = max(kmax, confidence_floor) for a guided pixel, confidence_floor for an orphan, 0 for a surface pixel nothing was found for.  A pixel that is no surface
+ * pixel gets trhip_upscale's value and a zero history.  A surface pixel gathers four history taps as trhip_temporal does (a tap needs Omega > 0) and blends
+ * Omega' = min(Omega_h + kappa, max_history), c' = c_h + (kappa / Omega') * (c - c_h); without history, or when the blend is not finite, c' = c and Omega' = kappa.
+ * With history NULL out_xyzw and out_mask are trhip_upscale's bit for bit.
+ * TRHIP_ERR_INVALID, in this order, the parameter block before any handle: params NULL; trhip_upscale's checks of lo_from_hi, radius, guide_sigma_normal,
+ * guide_sigma_plane, min_coverage; flags != 0; reserved != 0; trhip_temporal's checks of prev_world_to_pixel, max_history, sigma_normal, sigma_plane;
+ * confidence_floor outside (0, 1]; confidence_sharpness outside [0, 4]; then a null pointer (history, out_mask and stats excepted); a zero dimension; out_history
+ * overlapping an input; out_xyzw or out_mask overlapping an input, out_history or each other.  TRHIP_ERR_UNSUPPORTED as trhip_upscale (the host variant's copies are
+ * 64 bytes per low pixel and 161 per full-size pixel).  stats (may be NULL): ms_total, ms_film, launches_film = 1.  The _device variant takes DEVICE pointers and
+ * allocates nothing.  The default parameters need no context and no GPU: radius 1, max_history 8, confidence_sharpness 2, confidence_floor 1/16 — of the swept cells
+ * the one with the lowest error against the upscaled session (profiles/r16/temporal_upsample.txt) —, the sigmas of trhip_temporal and trhip_upscale, min_coverage 0.5;
+ * they leave lo_from_hi and prev_world_to_pixel zero. */
+typedef struct {
+    float lo_from_hi[4];           /* ax, bx, ay, by of this frame's (jittered) low sensor, as in trhip_upscale_params */
+    float prev_world_to_pixel[12]; /* trhip_sensor_world_to_pixel of the previous frame's FULL-SIZE sensor */
+    float max_history;             /* cap of the accumulated weight, >= 1 */
+    float sigma_normal;            /* the history taps: strict thresholds as in trhip_temporal_params: 0.25, 0.1 */
+    float sigma_plane;
+    float min_coverage;            /* the surface-pixel rule of both sizes, [0, 1] */
+    float guide_sigma_normal;      /* the low taps: Tukey widths as in trhip_upscale_params: 0.25, 0.4 */
+    float guide_sigma_plane;
+    float confidence_floor;        /* kappa_0 in (0, 1]: the least weight of a guided pixel, and an orphan's */
+    float confidence_sharpness;    /* rho in [0, 4]: the confidence falls to 0 at 1 / rho low pixels from a low pixel centre; 0: geometry alone decides */
+    uint32_t radius;               /* 1 or 2 */
+    uint32_t flags;                /* 0 */
+    uint32_t reserved[2];          /* 0 */
+} trhip_temporal_upsample_params;  /* 112 bytes */
+int trhip_temporal_upsample_default_params(trhip_temporal_upsample_params* out);
+int trhip_temporal_upsample(trhip_ctx* ctx, const float* lo_xyzw, const float* lo_planes, uint32_t lo_width, uint32_t lo_height, const float* hi_planes, const float* history,
+                            uint32_t width, uint32_t height, const trhip_temporal_upsample_params* params, float* out_xyzw, float* out_history, uint8_t* out_mask,
+                            trhip_stats* stats);
+int trhip_temporal_upsample_device(trhip_ctx* ctx, const void* d_lo_xyzw, const void* d_lo_planes, uint32_t lo_width, uint32_t lo_height, const void* d_hi_planes,
+                                   const void* d_history, uint32_t width, uint32_t height, const trhip_temporal_upsample_params* params, void* d_out_xyzw, void* d_out_history,
+                                   void* d_out_mask, trhip_stats* stats);
+
 /* SPPMIntegrator(camera, initial_search_radius, max_depth, n_iterations, photons_per_iteration)(scene)
  * (integrators/sppm.jl:108-173): per iteration a camera pass to the first diffuse vertex, a hash grid over the visible
  * points, a photon pass (Halton / radical_inverse, sampler/sampling.jl:43-60) and the Float64 pixel update; afterwards

@@ -207,6 +207,25 @@ UPSCALE_DEMODULATE = 1  # TRHIP_UPSCALE_DEMODULATE
 UPSCALE_COVERAGE = 2    # TRHIP_UPSCALE_COVERAGE
 
 
+class TemporalUpsampleParams(C.Structure):
+    """trhip_temporal_upsample_params (112 bytes)"""
+    _fields_ = [
+        ("lo_from_hi", C.c_float * 4),
+        ("prev_world_to_pixel", C.c_float * 12),
+        ("max_history", C.c_float),
+        ("sigma_normal", C.c_float),
+        ("sigma_plane", C.c_float),
+        ("min_coverage", C.c_float),
+        ("guide_sigma_normal", C.c_float),
+        ("guide_sigma_plane", C.c_float),
+        ("confidence_floor", C.c_float),
+        ("confidence_sharpness", C.c_float),
+        ("radius", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 class DisplayParams(C.Structure):
     """trhip_display_params (48 bytes)"""
     _fields_ = [
@@ -300,6 +319,11 @@ SIGNATURES = {
     "trhip_display_srgb_table": (C.c_int, [_F]),
     "trhip_display": (C.c_int, [_VP, _F, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(DisplayParams), C.POINTER(DisplayState), C.POINTER(C.c_uint8), _U32, C.POINTER(Stats)]),
     "trhip_display_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(DisplayParams), _VP, _VP, _VP, C.POINTER(Stats)]),
+    "trhip_temporal_upsample_default_params": (C.c_int, [C.POINTER(TemporalUpsampleParams)]),
+    "trhip_temporal_upsample": (C.c_int, [_VP, _F, _F, C.c_uint32, C.c_uint32, _F, _F, C.c_uint32, C.c_uint32, C.POINTER(TemporalUpsampleParams), _F, _F, C.POINTER(C.c_uint8),
+                                          C.POINTER(Stats)]),
+    "trhip_temporal_upsample_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(TemporalUpsampleParams), _VP, _VP, _VP,
+                                                 C.POINTER(Stats)]),
     "trhip_render_sppm": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats)]),
     "trhip_render_sppm_ex": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats), C.c_uint32, SPPM_WRITE_FN, _VP]),
     "trhip_sppm_state": (C.c_int, [_VP, _F, _F, _F, C.POINTER(C.c_double), C.POINTER(C.c_int64), _F, _F, _F, C.POINTER(C.c_int64)]),

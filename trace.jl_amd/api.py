@@ -1247,12 +1247,23 @@ class Upscaler:
         return tuple(out)
 
     @staticmethod
-    def low_camera(camera: PerspectiveCamera, factor) -> PerspectiveCamera:
-        """`camera` at 1 / factor of its resolution per axis (rounded to whole pixels, at least one)."""
+    def low_camera(camera: PerspectiveCamera, factor, jitter=(0.0, 0.0)) -> PerspectiveCamera:
+        """`camera` at 1 / factor of its resolution per axis (rounded to whole pixels, at least one).  `jitter` = (jx, jy), in LOW-pixel units, is defined by its effect:
+        pixel_map(camera, low_camera(camera, factor, jitter)) is the unjittered map with bx + jx and by + jy.  The optical axis pierces every raster of these cameras at
+        (-screen_window.p_min.x, -screen_window.p_max.y) raster pixels, whatever the resolution (docs/design/17-upscale.md), so the jittered camera is the same camera with
+        both corners of its screen window moved by (-jx, -jy): the extent, hence the field of view, stays (docs/design/19-temporal-upsample.md)."""
         if not 1.0 <= float(factor) <= 4.0:
             raise TraceHipError(f"Upscaler: factor must lie in [1, 4], not {factor!r}")
         res = [max(1, int(round(float(r) / float(factor)))) for r in camera.film.resolution]
-        return camera.with_resolution(res)
+        lo = camera.with_resolution(res)
+        jx, jy = (float(v) for v in jitter)
+        if jx == 0.0 and jy == 0.0:
+            return lo
+        if not (math.isfinite(jx) and math.isfinite(jy)):
+            raise TraceHipError(f"Upscaler.low_camera: jitter must be finite, not {jitter!r}")
+        sw = camera.screen_window
+        window = Bounds2([f32(sw.p_min[0]) - f32(jx), f32(sw.p_min[1]) - f32(jy)], [f32(sw.p_max[0]) - f32(jx), f32(sw.p_max[1]) - f32(jy)])
+        return PerspectiveCamera(lo.camera_to_world, window, lo.shutter_open, lo.shutter_close, lo.lens_radius, lo.focal_distance, lo.fov, lo.film)
 
     def _params_for(self, pixel_map) -> _ffi.UpscaleParams:
         p = _ffi.UpscaleParams.from_buffer_copy(self.params)
@@ -1553,6 +1564,104 @@ class TemporalAccumulator:
         self.stats = st
 
 
+# ---- temporal upsampling (include/tracehip.h, trhip_temporal_upsample) -------------------------------------------------------------------------
+class TemporalUpsampler:
+    """Upscales a jittered low-resolution path film onto the full-size planes and blends it into a full-size history in one pass (trhip_temporal_upsample;
+    docs/design/19-temporal-upsample.md): each full-size pixel trusts the new frame in proportion to how directly a low sample observed it.  Fields left at None come from
+    trhip_temporal_upsample_default_params.  The history is a (H, W, 3, 4) array in TemporalAccumulator's layout whose word 0 holds (c.rgb, Omega), Omega an accumulated
+    weight.  `jitter`: "grid" (factor 2 only: four offsets of a quarter low pixel that put every full-size pixel centre on a low pixel centre once in four frames),
+    "halton" (bases 2 and 3, any factor) or None.  `accumulate` returns (xyzw, history, mask): mask is Upscaler's class + 4 where history was found."""
+
+    GRID = ((0.25, 0.25), (-0.25, -0.25), (-0.25, 0.25), (0.25, -0.25))
+
+    def __init__(self, radius: Optional[int] = None, max_history: Optional[float] = None, sigma_normal: Optional[float] = None, sigma_plane: Optional[float] = None,
+                 guide_sigma_normal: Optional[float] = None, guide_sigma_plane: Optional[float] = None, confidence_floor: Optional[float] = None,
+                 confidence_sharpness: Optional[float] = None, min_coverage: Optional[float] = None, jitter: Optional[str] = "grid"):
+        if jitter not in ("grid", "halton", None):
+            raise TraceHipError(f"TemporalUpsampler: jitter must be 'grid', 'halton' or None, not {jitter!r}")
+        p = _ffi.TemporalUpsampleParams()
+        rc = _ffi.lib().trhip_temporal_upsample_default_params(C.byref(p))
+        if rc:
+            raise TraceHipError(f"trhip_temporal_upsample_default_params failed ({rc})")
+        if radius is not None:
+            if int(radius) != radius or not 0 <= radius < 2 ** 32:
+                raise TraceHipError(f"TemporalUpsampler: radius must be 1 or 2, not {radius!r}")
+            p.radius = int(radius)
+        for name, value in (("max_history", max_history), ("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane), ("guide_sigma_normal", guide_sigma_normal),
+                            ("guide_sigma_plane", guide_sigma_plane), ("confidence_floor", confidence_floor), ("confidence_sharpness", confidence_sharpness),
+                            ("min_coverage", min_coverage)):
+            if value is not None:
+                setattr(p, name, value)
+        self.params, self.jitter = p, jitter
+        self.stats: Optional[_ffi.Stats] = None
+
+    def jitter_for(self, frame: int, factor=2):
+        """(jx, jy) of frame `frame`, in low-pixel units, for Upscaler.low_camera."""
+        frame = int(frame)
+        if frame < 0:
+            raise TraceHipError(f"TemporalUpsampler.jitter_for: frame must be >= 0, not {frame}")
+        if self.jitter is None:
+            return (0.0, 0.0)
+        if self.jitter == "grid":
+            if float(factor) != 2.0:
+                raise TraceHipError(f"TemporalUpsampler: jitter 'grid' needs factor 2, not {factor!r} (use 'halton')")
+            return self.GRID[frame % 4]
+
+        def radical_inverse(base, i):
+            f, r = 1.0, 0.0
+            while i > 0:
+                f /= base
+                r += f * (i % base)
+                i //= base
+            return r
+        return (radical_inverse(2, frame + 1) - 0.5, radical_inverse(3, frame + 1) - 0.5)
+
+    def _params_for(self, pixel_map, prev_camera) -> _ffi.TemporalUpsampleParams:
+        """`pixel_map`: Upscaler.pixel_map of this frame's cameras; `prev_camera`: the previous frame's FULL-SIZE PerspectiveCamera, its world_to_pixel() matrix, or None."""
+        p = _ffi.TemporalUpsampleParams.from_buffer_copy(self.params)
+        m = [float(v) for v in pixel_map]
+        if len(m) != 4:
+            raise TraceHipError(f"TemporalUpsampler: pixel_map must be (ax, bx, ay, by), not {pixel_map!r}")
+        p.lo_from_hi[:] = m
+        if prev_camera is not None:
+            w2p = prev_camera.world_to_pixel() if hasattr(prev_camera, "world_to_pixel") else _ffi.f32(prev_camera)
+            if w2p.size != 12:
+                raise TraceHipError(f"TemporalUpsampler: the previous camera's matrix must be 3 x 4, not {w2p.shape}")
+            p.prev_world_to_pixel[:] = w2p.reshape(-1).tolist()
+        return p
+
+    def accumulate(self, lo_xyzw: np.ndarray, lo_planes: np.ndarray, hi_planes: np.ndarray, history: Optional[np.ndarray], pixel_map, prev_camera,
+                   ctx: Optional[_ffi.Context] = None):
+        """lo_xyzw (h, w, 4) and lo_planes (h, w, 3, 4) of this frame's jittered low camera, hi_planes (H, W, 3, 4) of the full-size one, history the second result of the
+        previous frame's call, or None.  Returns (xyzw (H, W, 4), history (H, W, 3, 4), mask (H, W) uint8)."""
+        lo_xyzw, lo_planes, hi_planes = _ffi.f32(lo_xyzw), _ffi.f32(lo_planes), _ffi.f32(hi_planes)
+        if lo_xyzw.ndim != 3 or lo_xyzw.shape[2] != 4 or lo_planes.shape != lo_xyzw.shape[:2] + (3, 4) or hi_planes.ndim != 4 or hi_planes.shape[2:] != (3, 4):
+            raise TraceHipError(f"accumulate: lo_xyzw must be (h, w, 4), lo_planes (h, w, 3, 4) and hi_planes (H, W, 3, 4), not {lo_xyzw.shape}, {lo_planes.shape} and {hi_planes.shape}")
+        if history is not None:
+            history = _ffi.f32(history)
+            if history.shape != hi_planes.shape:
+                raise TraceHipError(f"accumulate: history must be {hi_planes.shape} like hi_planes, not {history.shape}")
+        p = self._params_for(pixel_map, prev_camera)
+        ctx = ctx or _ffi.default_context()
+        (lh, lw), (h, w) = lo_xyzw.shape[:2], hi_planes.shape[:2]
+        out, out_history, mask, st = np.empty((h, w, 4), np.float32), np.empty((h, w, 3, 4), np.float32), np.empty((h, w), np.uint8), _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_temporal_upsample(ctx._h, _ffi.fptr(lo_xyzw), _ffi.fptr(lo_planes), lw, lh, _ffi.fptr(hi_planes), _ffi.fptr(history) if history is not None else None,
+                                                     w, h, C.byref(p), _ffi.fptr(out), _ffi.fptr(out_history), mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st)))
+        self.stats = st
+        return out, out_history, mask
+
+    def accumulate_device(self, d_lo_xyzw: int, d_lo_planes: int, lo_width: int, lo_height: int, d_hi_planes: int, d_history: Optional[int], width: int, height: int, pixel_map,
+                          prev_camera, d_out: int, d_out_history: int, d_out_mask: Optional[int] = None, ctx: Optional[_ffi.Context] = None) -> None:
+        """The same on device pointers (d_history and d_out_mask may be None); nothing is copied to the host."""
+        p = self._params_for(pixel_map, prev_camera)
+        ctx = ctx or _ffi.default_context()
+        st = _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_temporal_upsample_device(ctx._h, C.c_void_p(d_lo_xyzw), C.c_void_p(d_lo_planes), int(lo_width), int(lo_height), C.c_void_p(d_hi_planes),
+                                                            C.c_void_p(d_history) if d_history else None, int(width), int(height), C.byref(p), C.c_void_p(d_out),
+                                                            C.c_void_p(d_out_history), C.c_void_p(d_out_mask) if d_out_mask else None, C.byref(st)))
+        self.stats = st
+
+
 class PreviewSession:
     """A moving-camera preview of a static scene: frame k is the path film and the feature planes at sample_offset = sampler.sample_offset + k * spp, temporal accumulation
     against the previous frame's history and camera, then the à-trous filter with this frame's planes — all on the device, the buffers kept between frames.
@@ -1568,10 +1677,26 @@ class PreviewSession:
     docs/design/17-upscale.md).  With None, the default, the session is the one described above, call for call.
     `display=Display(...)`: `render_display(camera)` renders the frame as `render` does and encodes the final device buffer to 8-bit RGBA (trhip_display;
     docs/design/18-display.md): only the bytes are downloaded, and the exposure state stays on the device from frame to frame (reset() and a film of another size clear it).
-    `render` itself makes the calls it always made, with or without a display."""
+    `render` itself makes the calls it always made, with or without a display.
+    `temporal_upsample=TemporalUpsampler(...)`, with an `upscaler` (whose presence, `factor` and `guide_spp` select the low camera and the guides; its own parameters are
+    not consulted, the TemporalUpsampler's are): frame k traces the path frame and its planes through the low camera shifted by `jitter_for(k, factor)`, the full-size
+    planes with `guide_spp`, upscales and blends into a FULL-SIZE history through the previous full-size camera in one pass (trhip_temporal_upsample;
+    docs/design/19-temporal-upsample.md) and filters the result with the full-size planes.  Not combinable with variance_guided=True or a clipping / moments accumulator.
+    With None, the default, the session makes the calls described above."""
 
     def __init__(self, scene: Scene, sampler: SeededSampler, max_depth: int, denoiser: Optional["Denoiser"] = None, temporal: Optional[TemporalAccumulator] = None,
-                 variance_guided: bool = False, upscaler: Optional["Upscaler"] = None, factor=2, guide_spp: Optional[int] = None, display: Optional["Display"] = None):
+                 variance_guided: bool = False, upscaler: Optional["Upscaler"] = None, factor=2, guide_spp: Optional[int] = None, display: Optional["Display"] = None,
+                 temporal_upsample: Optional["TemporalUpsampler"] = None):
+        if temporal_upsample is not None:
+            if upscaler is None:
+                raise TraceHipError("PreviewSession: temporal_upsample needs an upscaler (upscaler=Upscaler(), with factor and guide_spp)")
+            if variance_guided:
+                raise TraceHipError("PreviewSession: temporal_upsample cannot be combined with variance_guided=True (there are no moments on the full-size history)")
+            if temporal is not None and (temporal.clip_params is not None or temporal.moments_params is not None):
+                raise TraceHipError("PreviewSession: temporal_upsample cannot be combined with a clipping or moments TemporalAccumulator")
+            temporal_upsample.jitter_for(0, factor)  # 'grid' with another factor is refused here, not at the first frame
+        self.temporal_upsample = temporal_upsample
+        self._tu_buffers, self._tu_size = None, None  # low film, low planes; full planes, film, history x 2
         self.scene, self.sampler, self.max_depth = scene, sampler, int(max_depth)
         self.display = display
         self._display_buffers, self._display_size = None, None  # RGBA bytes and the 16-byte exposure state
@@ -1603,6 +1728,9 @@ class PreviewSession:
         for b in self._up_buffers or ():
             b.free()
         self._up_buffers, self._up_size = None, None
+        for b in self._tu_buffers or ():
+            b.free()
+        self._tu_buffers, self._tu_size = None, None
         for b in self._display_buffers or ():
             b.free()
         self._display_buffers, self._display_size = None, None
@@ -1630,6 +1758,8 @@ class PreviewSession:
     def _render_device(self, camera: PerspectiveCamera, ctx: Optional[_ffi.Context]):
         """The frame of `render`, left on the device: (buffer, (H, W), context)."""
         ctx = self.scene.flatten(ctx).ctx
+        if self.temporal_upsample is not None:
+            return self._render_temporal_upsample(camera, ctx)
         hi_camera = camera
         if self.upscaler is not None:
             camera = Upscaler.low_camera(hi_camera, self.factor)
@@ -1682,6 +1812,34 @@ class PreviewSession:
         self.upscaler.upscale_device(d_lo.ptr, d_lo_planes.ptr, lw, lh, d_hi_planes.ptr, hw, hh, Upscaler.pixel_map(hi_camera, lo_camera), d_out.ptr, None, ctx)
         self.render_stats = self.render_stats + (aov.stats, self.upscaler.stats)
         return d_out
+
+    def _render_temporal_upsample(self, hi_camera: PerspectiveCamera, ctx):
+        """The frame of the temporal-upsampling mode, left on the device: (buffer, (H, W), context)."""
+        tu = self.temporal_upsample
+        lo_camera = Upscaler.low_camera(hi_camera, self.factor, jitter=tu.jitter_for(self.frame, self.factor))
+        (hh, hw), (lh, lw) = hi_camera.film.size, lo_camera.film.size
+        if self._tu_size != ((hh, hw), (lh, lw)):
+            self.close()
+            self._tu_size = ((hh, hw), (lh, lw))
+            self._tu_buffers = [_ffi.DeviceBuffer(n) for n in (lh * lw * 16, lh * lw * 48, hh * hw * 48, hh * hw * 16, hh * hw * 48, hh * hw * 48)]
+        d_lo, d_lo_planes, d_hi_planes, d_out = self._tu_buffers[:4]
+        d_prev, d_next = self._tu_buffers[4 + (self.frame & 1)], self._tu_buffers[4 + ((self.frame & 1) ^ 1)]
+        spp = self.sampler.samples_per_pixel
+        sampler = SeededSampler(spp, seed=self.sampler.seed, sample_offset=self.sampler.sample_offset + self.frame * spp)
+        guide = SeededSampler(spp if self.guide_spp is None else int(self.guide_spp), seed=sampler.seed, sample_offset=sampler.sample_offset)
+        path, aov_lo, aov_hi = PathIntegrator(lo_camera, sampler, self.max_depth), AOVIntegrator(lo_camera, sampler), AOVIntegrator(hi_camera, guide)
+        path.render(self.scene, ctx, device_out=d_lo.ptr)
+        aov_lo.render(self.scene, ctx, device_out=d_lo_planes.ptr)
+        aov_hi.render(self.scene, ctx, device_out=d_hi_planes.ptr)
+        prev_matrix, matrix = self._prev_matrix, hi_camera.world_to_pixel()
+        self._prev_matrix = None  # (until this frame's history is complete)
+        tu.accumulate_device(d_lo.ptr, d_lo_planes.ptr, lw, lh, d_hi_planes.ptr, d_prev.ptr if prev_matrix is not None else None, hw, hh, Upscaler.pixel_map(hi_camera, lo_camera),
+                             prev_matrix, d_out.ptr, d_next.ptr, None, ctx)
+        self.denoiser.denoise_device(d_out.ptr, d_hi_planes.ptr, hw, hh, d_out.ptr, ctx)
+        self.render_stats = (path.stats, aov_lo.stats, aov_hi.stats, tu.stats, self.denoiser.stats)
+        self._prev_matrix = matrix
+        self.frame += 1
+        return d_out, (hh, hw), ctx
 
 
 def _to_Y(c) -> np.float32:  # spectrum.jl:64-66

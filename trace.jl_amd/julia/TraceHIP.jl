@@ -405,6 +405,8 @@ include("TraceHIPVariance.jl")
 include("TraceHIPUpscale.jl")
 # Display (trhip_display), likewise (tests/golden/julia_shim_display_calls.json)
 include("TraceHIPDisplay.jl")
+# TemporalUpsampler (trhip_temporal_upsample) and jitter_for, likewise (tests/golden/julia_shim_temporal_upsample_calls.json)
+include("TraceHIPTemporalUpsample.jl")
 
 # SPPMIntegrator (integrators/sppm.jl:132-173) on the device: trhip_render_sppm returns the film after set_image!
 # (film.jl:195-202).  `seed` selects the seeded stream of the camera pass (the reference draws from the global RNG there).
