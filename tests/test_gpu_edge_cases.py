@@ -312,3 +312,61 @@ def assert_counters_equal(banded, whole, n_bands, what):
     assert got == want, f"{what}: {got} != {want}"
     assert list(banded.count_sub) == list(whole.count_sub), f"{what}: count_sub {list(banded.count_sub)} != {list(whole.count_sub)}"
     assert banded.n_batches == n_bands and whole.n_batches == 1, f"{what}: n_batches {banded.n_batches}, {whole.n_batches}"
+
+
+def _image_pass_calls(T):
+    """entry point -> (the family its refusal names, call(ctx, w, h) on zero images of that size; the upscaling passes from a low image of (w + 1) // 2 x (h + 1) // 2, at most 8 x 8)"""
+    def images(w, h):
+        return np.zeros((h, w, 4), np.float32), np.zeros((h, w, 3, 4), np.float32)
+
+    def low(w, h):
+        lw, lh = min(8, (w + 1) // 2), min(8, (h + 1) // 2)
+        return images(lw, lh) + ((0.5, 0.0, 0.5, 0.0),)
+
+    def denoise(ctx, w, h):
+        T.Denoiser().denoise(*images(w, h), ctx)
+
+    def denoise_var(ctx, w, h):
+        T.Denoiser().denoise_variance(*images(w, h), np.zeros((h, w), np.float32), ctx)
+
+    def temporal(ctx, w, h):
+        T.TemporalAccumulator().accumulate(*images(w, h), None, None, ctx)
+
+    def temporal_clip(ctx, w, h):
+        T.TemporalAccumulator(clip_gamma=1.0).accumulate(*images(w, h), None, None, ctx)
+
+    def temporal_moments(ctx, w, h):
+        T.TemporalAccumulator(moments=True).accumulate_moments(*images(w, h), None, None, None, ctx)
+
+    def upscale(ctx, w, h):
+        lo_xyzw, lo_planes, pixel_map = low(w, h)
+        T.Upscaler().upscale(lo_xyzw, lo_planes, images(w, h)[1], pixel_map, ctx)
+
+    def display(ctx, w, h):
+        T.Display().encode(images(w, h)[0], ctx=ctx)
+
+    def temporal_upsample(ctx, w, h):
+        lo_xyzw, lo_planes, pixel_map = low(w, h)
+        hi_planes = images(w, h)[1]
+        T.TemporalUpsampler().accumulate(lo_xyzw, lo_planes, hi_planes, np.zeros_like(hi_planes), pixel_map, None, ctx)
+
+    return {"denoise": ("trhip_denoise:", denoise, False), "denoise_var": ("trhip_denoise_var:", denoise_var, False), "temporal": ("trhip_temporal:", temporal, False),
+            "temporal_clip": ("trhip_temporal:", temporal_clip, False), "temporal_moments": ("trhip_temporal_moments:", temporal_moments, False),
+            "upscale": ("trhip_upscale:", upscale, True), "display": ("trhip_display:", display, True), "temporal_upsample": ("trhip_temporal_upsample:", temporal_upsample, True)}
+
+
+@pytest.mark.parametrize("entry", ["denoise", "denoise_var", "temporal", "temporal_clip", "temporal_moments", "upscale", "display", "temporal_upsample"])
+def test_image_pass_refuses_a_tile_grid_past_the_launch_limit(T, ctx, entry):
+    """The host entry points of the image-space passes launch one block per 16 x 16 tile and refuse an image whose tile grid has more than 65535 blocks along an axis they
+    check (1048561 pixels: 65536 tiles) with TRHIP_ERR_UNSUPPORTED and their "fit in free HBM" sentence, on the host, before anything is allocated, copied or launched; the
+    context goes on working.  The upscaling passes and the display pass check both axes and get the row of 1048561 pixels, the others check the rows alone and get the
+    column.  The images are real arrays of the true sizes, so the overlap checks that come first see true ranges.  (trhip_temporal_clip's sentence names trhip_temporal.)"""
+    family, call, checks_columns = _image_pass_calls(T)[entry]
+    w, h = (1048561, 1) if checks_columns else (1, 1048561)
+    with pytest.raises(T.TraceHipError) as e:
+        call(ctx, w, h)
+    message = str(e.value)
+    print(message)
+    assert message.startswith("libtracehip error -3: " + family), message
+    assert "fit in free HBM" in message and (f"{w} x {h}" in message), message
+    call(ctx, 17, 5)  # raises unless the entry point returns 0

@@ -3,7 +3,8 @@
 // and linked into the one shared object): tu_api.hip (context, options, communicator), tu_scene.hip (scene flattening, commit, upload),
 // tu_lbvh.hip (BVH build on the device), tu_trace.hip / tu_trace3.hip / tu_trace3c.hip / tu_trace7.hip / tu_trace8.hip (traversal launches and entry points),
 // tu_path.hip (PathIntegrator frames, film, and the out-of-line part of the frame scaffold below: the stats functions), tu_aov.hip (first-hit feature buffers),
-// tu_ao.hip (ambient occlusion; the two share their camera-ray front half, th_camera.h), tu_denoise.hip (the à-trous filter), tu_temporal.hip (temporal reprojection), tu_upscale.hip, tu_display.hip (the 8-bit display pass), tu_whitted.hip, tu_sppm.hip.
+// tu_ao.hip (ambient occlusion; the two share their camera-ray front half, th_camera.h), tu_denoise.hip (the à-trous filters), tu_temporal.hip (temporal reprojection), tu_upscale.hip, tu_display.hip (the 8-bit display pass), tu_temporal_upsample.hip — these five, the
+// image-space passes, share their host side through th_image_pass.h —, tu_whitted.hip, tu_sppm.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -137,6 +138,7 @@ struct trhip_ctx {
     DevBuf cert_cold;  // k_trace3c's CertCold (th_trace3c.h)
     DevBuf aov_rec;    // trhip_render_aov: the frame's per-sample records (th_aov.h, 80 B per camera sample)
     DevBuf ao_tmax;    // trhip_render_ao: the reach of every occlusion ray, beside the any-hit queue sq (th_ao.h, 4 B per queue entry)
+    // dn_in, tp_in, up_in, dp_in: where the host entry points of the image-space passes stage their images, laid out by ImageStaging (th_image_pass.h) in the order a pass declares them
     DevBuf dn_work, dn_in;  // trhip_denoise: guides, two colour buffers and the base colour (th_denoise.h, 80 B per pixel); the host entry point's copy of film and planes
     int denoise_lds = 3;    // bit i: iteration i (step 2^i, i < 2) of trhip_denoise runs the LDS-staged kernel (option "denoise_lds")
     DevBuf tp_in;           // trhip_temporal's host entry point: its copy of film, planes, history and the new history (th_temporal.h, 160 B per pixel); trhip_temporal_clip's: the same and
@@ -438,7 +440,7 @@ inline size_t held_in_pipes(const trhip_ctx* ctx) {
     }
     return held;
 }
-// The one-batch entry points (aov, ao, denoise, temporal) refuse a frame that needs more than 0.9 of what is free plus what the context already holds for it (`held`, reused).
+// The one-batch entry points (aov, ao, and the image-space passes: denoise, denoise_var, temporal and temporal_clip, temporal_moments, upscale, display, temporal_upsample) refuse a frame that needs more than 0.9 of what is free plus what the context already holds for it (`held`, reused).
 // *free_gb is that sum, for the caller's sentence.
 inline int fits_in_hbm(trhip_ctx* ctx, double need, size_t held, bool* fits, double* free_gb) {
     size_t free_b = 0, total_b = 0;

@@ -2,6 +2,7 @@
 #include "th_host.h"
 #include "th_denoise.h"
 #include "th_denoise_var.h"
+#include "th_image_pass.h"
 
 #include <cmath>
 
@@ -13,8 +14,6 @@ static_assert(sizeof(trhip_denoise_var_params) == 48, "trhip_denoise_var_params 
 constexpr uint32_t kDnMaxIterations = 6;
 constexpr size_t kDvBytesPerPixel = 88;  // trhip_denoise_var: the same and V x 2
 constexpr size_t kDnBytesPerPixel = 80;  // {n, flag} {p, 0} {c, Y} x 2 {a, 0}
-
-bool positive_finite(float v) { return std::isfinite(v) && v > 0.0f; }
 
 int check_params(trhip_ctx* ctx, const trhip_denoise_params* p) {
     if (p->iterations > kDnMaxIterations) return fail(ctx, TRHIP_ERR_INVALID, "trhip_denoise: iterations = %u, at most %u", p->iterations, kDnMaxIterations);
@@ -36,9 +35,12 @@ int denoise_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, uint32_t 
     const uint64_t npix = (uint64_t)width * height;
     const size_t film_bytes = (size_t)npix * sizeof(float4), planes_bytes = 3 * film_bytes;
     const uint32_t bx = (width + kDnTile - 1) / kDnTile, by = (height + kDnTile - 1) / kDnTile;
+    ImageStaging images(ctx, ctx->dn_in, is_device);
+    const ImageStaging::Image& film = images.inout(xyzw, out, film_bytes);  // the film's copy is denoised in place
+    const ImageStaging::Image& guides = images.input(planes, planes_bytes);
     {
         const size_t held = ctx->dn_work.bytes + ctx->dn_in.bytes;  // reused below
-        const double need = (double)npix * kDnBytesPerPixel + (is_device ? 0.0 : (double)(film_bytes + planes_bytes));
+        const double need = (double)npix * kDnBytesPerPixel + (double)images.bytes();
         bool fits;
         double free_gb;
         if (int rc = fits_in_hbm(ctx, need, held, &fits, &free_gb)) return rc;
@@ -47,65 +49,44 @@ int denoise_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, uint32_t 
                         height, need * 1e-9, free_gb);
     }
     if (int rc = ensure(ctx, ctx->dn_work, (size_t)npix * kDnBytesPerPixel)) return rc;
-    const float4* d_beauty = (const float4*)xyzw;
-    const float4* d_planes = (const float4*)planes;
-    float4* d_out = (float4*)out;
-    if (!is_device) {  // the film's copy is denoised in place
-        if (int rc = ensure(ctx, ctx->dn_in, film_bytes + planes_bytes)) return rc;
-        HIP_TRY(ctx, hipMemcpy(ctx->dn_in.p, xyzw, film_bytes, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy((char*)ctx->dn_in.p + film_bytes, planes, planes_bytes, hipMemcpyHostToDevice));
-        d_beauty = d_out = (float4*)ctx->dn_in.p;
-        d_planes = (const float4*)((char*)ctx->dn_in.p + film_bytes);
-    }
+    if (int rc = images.upload()) return rc;
+    const float4 *d_beauty = film.in<float4>(), *d_planes = guides.in<float4>();
+    float4* d_out = film.out<float4>();
     float4* gn = (float4*)ctx->dn_work.p;
     float4 *gp = gn + npix, *col[2] = {gn + 2 * npix, gn + 3 * npix}, *alb = gn + 4 * npix;
     hipStream_t st = ctx->stream;
     const uint32_t demodulate = prm->flags & TRHIP_DENOISE_DEMODULATE;
 
-    Timer tm(ctx, ctx->timing && stats);
-    FrameEvents ev;
-    HIP_TRY(ctx, ev.begin(st));
+    PassWindow w(ctx, stats);
+    HIP_TRY(ctx, w.open());
     if (prm->iterations == 0) {
         if (d_out != d_beauty) HIP_TRY(ctx, hipMemcpyAsync(d_out, d_beauty, film_bytes, hipMemcpyDeviceToDevice, st));
     } else {
         const int lin_grid = grid_for(ctx, npix, 8);
-        tm.begin(5, st);
+        w.begin(5);
         hipLaunchKernelGGL(k_denoise_prepare, dim3(lin_grid), dim3(kBlock), 0, st, d_beauty, d_planes, npix, demodulate, prm->albedo_floor, prm->min_coverage, gn, gp, col[0], alb);
-        tm.end(5, st);
+        w.end(5);
         DenoiseWeights sg{prm->sigma_colour, prm->sigma_normal, prm->sigma_plane};
         for (uint32_t i = 0; i < prm->iterations; ++i) {
             const float4* cin = col[i & 1];
             float4* cout = col[(i & 1) ^ 1];
             const dim3 grid(bx, by), block(kDnTile * kDnTile);
             const bool lds = i < 2 && ((ctx->denoise_lds >> i) & 1);  // steps 1 and 2: measured faster staged, step 4 slower (profiles/r9/denoise.txt)
-            tm.begin(6, st);
+            w.begin(6);
             if (lds && i == 0)
                 hipLaunchKernelGGL((k_denoise_atrous_lds<1>), grid, block, 0, st, gn, gp, cin, cout, (int)width, (int)height, sg);
             else if (lds)
                 hipLaunchKernelGGL((k_denoise_atrous_lds<2>), grid, block, 0, st, gn, gp, cin, cout, (int)width, (int)height, sg);
             else
                 hipLaunchKernelGGL(k_denoise_atrous, grid, block, 0, st, gn, gp, cin, cout, (int)width, (int)height, 1 << i, sg);
-            tm.end(6, st);
+            w.end(6);
             sg.sigma_colour *= 0.5f;
         }
-        tm.begin(7, st);
+        w.begin(7);
         hipLaunchKernelGGL(k_denoise_finish, dim3(lin_grid), dim3(kBlock), 0, st, d_beauty, gn, col[prm->iterations & 1], alb, npix, demodulate, d_out);
-        tm.end(7, st);
+        w.end(7);
     }
-    HIP_TRY(ctx, ev.end(st));
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (!is_device) HIP_TRY(ctx, hipMemcpy(out, d_out, film_bytes, hipMemcpyDeviceToHost));
-    if (stats) {
-        std::memset(stats, 0, sizeof *stats);
-        stats->ms_total = ev.ms();
-        for (int k = 0; k < 3; ++k) {  // prepare, the iterations, finish
-            stats->ms_sub[k] = tm.total(5 + k, &stats->launches_sub[k]);
-            stats->ms_film += stats->ms_sub[k];
-            stats->launches_film += stats->launches_sub[k];
-        }
-    }
-    return 0;
+    return close_pass(ctx, w, images, stats, 3, kCountedLaunches);  // prepare, the iterations, finish
 }
 
 int denoise_var_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const void* variance, uint32_t width, uint32_t height, const trhip_denoise_var_params* vp, void* out,
@@ -123,9 +104,13 @@ int denoise_var_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const
     const uint64_t npix = (uint64_t)width * height;
     const size_t film_bytes = (size_t)npix * sizeof(float4), planes_bytes = 3 * film_bytes, var_bytes = (size_t)npix * sizeof(float);
     const uint32_t bx = (width + kDnTile - 1) / kDnTile, by = (height + kDnTile - 1) / kDnTile;
+    ImageStaging images(ctx, ctx->dn_in, is_device);
+    const ImageStaging::Image& film = images.inout(xyzw, out, film_bytes);  // the copies of the film and of the variance plane are filtered in place
+    const ImageStaging::Image& guides = images.input(planes, planes_bytes);
+    const ImageStaging::Image& var_plane = images.inout(variance, out_variance, var_bytes);
     {
         const size_t held = ctx->dn_work.bytes + ctx->dn_in.bytes;  // reused below
-        const double need = (double)npix * kDvBytesPerPixel + (is_device ? 0.0 : (double)(film_bytes + planes_bytes + var_bytes));
+        const double need = (double)npix * kDvBytesPerPixel + (double)images.bytes();
         bool fits;
         double free_gb;
         if (int rc = fits_in_hbm(ctx, need, held, &fits, &free_gb)) return rc;
@@ -134,37 +119,25 @@ int denoise_var_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const
                         width, height, need * 1e-9, free_gb);
     }
     if (int rc = ensure(ctx, ctx->dn_work, (size_t)npix * kDvBytesPerPixel)) return rc;
-    const float4* d_beauty = (const float4*)xyzw;
-    const float4* d_planes = (const float4*)planes;
-    const float* d_variance = (const float*)variance;
-    float4* d_out = (float4*)out;
-    float* d_out_variance = (float*)out_variance;
-    if (!is_device) {  // the copies of the film and of the variance plane are filtered in place
-        if (int rc = ensure(ctx, ctx->dn_in, film_bytes + planes_bytes + var_bytes)) return rc;
-        char* base = (char*)ctx->dn_in.p;
-        HIP_TRY(ctx, hipMemcpy(base, xyzw, film_bytes, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(base + film_bytes, planes, planes_bytes, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(base + film_bytes + planes_bytes, variance, var_bytes, hipMemcpyHostToDevice));
-        d_beauty = d_out = (float4*)base;
-        d_planes = (const float4*)(base + film_bytes);
-        d_variance = (const float*)(base + film_bytes + planes_bytes);
-        d_out_variance = out_variance ? (float*)(base + film_bytes + planes_bytes) : nullptr;
-    }
+    if (int rc = images.upload()) return rc;
+    const float4 *d_beauty = film.in<float4>(), *d_planes = guides.in<float4>();
+    const float* d_variance = var_plane.in<float>();
+    float4* d_out = film.out<float4>();
+    float* d_out_variance = var_plane.out<float>();  // NULL when the caller wants none
     float4* gn = (float4*)ctx->dn_work.p;
     float4 *gp = gn + npix, *col[2] = {gn + 2 * npix, gn + 3 * npix}, *alb = gn + 4 * npix;
     float* var[2] = {(float*)(gn + 5 * npix), (float*)(gn + 5 * npix) + npix};
     hipStream_t st = ctx->stream;
     const uint32_t demodulate = prm->flags & TRHIP_DENOISE_DEMODULATE;
 
-    Timer tm(ctx, ctx->timing && stats);
-    FrameEvents ev;
-    HIP_TRY(ctx, ev.begin(st));
+    PassWindow w(ctx, stats);
+    HIP_TRY(ctx, w.open());
     const int lin_grid = grid_for(ctx, npix, 8);
     // iterations = 0 copies the film; the variance plane still goes through the seed and the export (clamped, 0 off surfaces), which need the surface flags
-    tm.begin(5, st);
+    w.begin(5);
     hipLaunchKernelGGL(k_denoise_prepare, dim3(lin_grid), dim3(kBlock), 0, st, d_beauty, d_planes, npix, demodulate, prm->albedo_floor, prm->min_coverage, gn, gp, col[0], alb);
     hipLaunchKernelGGL(k_denoise_var_seed, dim3(lin_grid), dim3(kBlock), 0, st, gn, d_variance, npix, var[0]);
-    tm.end(5, st);
+    w.end(5);
     const DenoiseWeights sg{prm->sigma_colour, prm->sigma_normal, prm->sigma_plane};  // sigma_colour multiplies the standard deviation and is not halved
     for (uint32_t i = 0; i < prm->iterations; ++i) {
         const float4* cin = col[i & 1];
@@ -173,39 +146,23 @@ int denoise_var_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const
         float* vout = var[(i & 1) ^ 1];
         const dim3 grid(bx, by), block(kDnTile * kDnTile);
         const bool lds = i < 2 && ((ctx->denoise_var_lds >> i) & 1);
-        tm.begin(6, st);
+        w.begin(6);
         if (lds && i == 0)
             hipLaunchKernelGGL((k_denoise_var_atrous_lds<1>), grid, block, 0, st, gn, gp, cin, vin, cout, vout, (int)width, (int)height, sg, vp->var_eps);
         else if (lds)
             hipLaunchKernelGGL((k_denoise_var_atrous_lds<2>), grid, block, 0, st, gn, gp, cin, vin, cout, vout, (int)width, (int)height, sg, vp->var_eps);
         else
             hipLaunchKernelGGL(k_denoise_var_atrous, grid, block, 0, st, gn, gp, cin, vin, cout, vout, (int)width, (int)height, 1 << i, sg, vp->var_eps);
-        tm.end(6, st);
+        w.end(6);
     }
-    tm.begin(7, st);
+    w.begin(7);
     if (prm->iterations == 0) {
         if (d_out != d_beauty) HIP_TRY(ctx, hipMemcpyAsync(d_out, d_beauty, film_bytes, hipMemcpyDeviceToDevice, st));
     } else
         hipLaunchKernelGGL(k_denoise_finish, dim3(lin_grid), dim3(kBlock), 0, st, d_beauty, gn, col[prm->iterations & 1], alb, npix, demodulate, d_out);
     if (d_out_variance) hipLaunchKernelGGL(k_denoise_var_export, dim3(lin_grid), dim3(kBlock), 0, st, var[prm->iterations & 1], npix, d_out_variance);
-    tm.end(7, st);
-    HIP_TRY(ctx, ev.end(st));
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (!is_device) {
-        HIP_TRY(ctx, hipMemcpy(out, d_out, film_bytes, hipMemcpyDeviceToHost));
-        if (out_variance) HIP_TRY(ctx, hipMemcpy(out_variance, d_out_variance, var_bytes, hipMemcpyDeviceToHost));
-    }
-    if (stats) {
-        std::memset(stats, 0, sizeof *stats);
-        stats->ms_total = ev.ms();
-        for (int k = 0; k < 3; ++k) {  // prepare and seed, the iterations, finish and export
-            stats->ms_sub[k] = tm.total(5 + k, &stats->launches_sub[k]);
-            stats->ms_film += stats->ms_sub[k];
-            stats->launches_film += stats->launches_sub[k];
-        }
-    }
-    return 0;
+    w.end(7);
+    return close_pass(ctx, w, images, stats, 3, kCountedLaunches);  // prepare and seed, the iterations, finish and export
 }
 
 }  // namespace

@@ -2,6 +2,7 @@
 // image-space pass, the last of a preview.
 #include "th_host.h"
 #include "th_display.h"
+#include "th_image_pass.h"
 
 #include <cmath>
 
@@ -13,13 +14,6 @@ static_assert(sizeof(trhip_display_state) == 16 && sizeof(DisplayState) == 16, "
 const float h_srgb_thresholds[256] = {TH_SRGB_THRESHOLDS};
 constexpr size_t kHistBytes = kDisplayBins * sizeof(uint32_t);  // ctx->dp_work: the histogram, then a state slot for a caller who keeps none
 constexpr size_t kWorkBytes = kHistBytes + sizeof(DisplayState);
-
-bool positive_finite(float v) { return std::isfinite(v) && v > 0.0f; }
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
 
 int check_params(trhip_ctx* ctx, const trhip_display_params* p, float scale) {
     if (p->curve > TRHIP_DISPLAY_CURVE_ACES) return fail(ctx, TRHIP_ERR_INVALID, "trhip_display: curve must be 0 (clamp), 1 (Reinhard) or 2 (ACES), not %u", p->curve);
@@ -61,9 +55,12 @@ int display_impl(trhip_ctx* ctx, const void* xyzw, uint32_t width, uint32_t heig
     if (overlap(out_rgba, rgba_bytes, xyzw, film_bytes)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_display: out_rgba overlaps the input");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint32_t bx = (width + kDnTile - 1) / kDnTile, by = (height + kDnTile - 1) / kDnTile;
+    ImageStaging images(ctx, ctx->dp_in, is_device);
+    const ImageStaging::Image& film = images.input(xyzw, film_bytes);
+    const ImageStaging::Image& rgba = images.output(out_rgba, rgba_bytes);
     {
         const size_t held = ctx->dp_in.bytes;  // reused below
-        const double need = is_device ? 0.0 : (double)(film_bytes + rgba_bytes);
+        const double need = (double)images.bytes();
         bool fits;
         double free_gb;
         if (int rc = fits_in_hbm(ctx, need, held, &fits, &free_gb)) return rc;
@@ -75,16 +72,13 @@ int display_impl(trhip_ctx* ctx, const void* xyzw, uint32_t width, uint32_t heig
     if (int rc = ensure(ctx, ctx->dp_work, kWorkBytes)) return rc;
     uint32_t* d_hist = (uint32_t*)ctx->dp_work.p;
     DisplayState* d_slot = (DisplayState*)((char*)ctx->dp_work.p + kHistBytes);
-    const float4* d_in = (const float4*)xyzw;
-    uint32_t* d_out = (uint32_t*)out_rgba;
+    if (int rc = images.upload()) return rc;
+    const float4* d_in = film.in<float4>();
+    uint32_t* d_out = rgba.out<uint32_t>();
     DisplayState* d_state = (DisplayState*)state;  // the device variant's, or null
     uint32_t* d_out_hist = (uint32_t*)out_hist;    // likewise
     hipStream_t st = ctx->stream;
-    if (!is_device) {
-        if (int rc = ensure(ctx, ctx->dp_in, film_bytes + rgba_bytes)) return rc;
-        HIP_TRY(ctx, hipMemcpy(ctx->dp_in.p, xyzw, film_bytes, hipMemcpyHostToDevice));
-        d_in = (const float4*)ctx->dp_in.p;
-        d_out = (uint32_t*)((char*)ctx->dp_in.p + film_bytes);
+    if (!is_device) {  // the 16-byte state and the histogram are not images: they live in dp_work
         d_state = nullptr;
         d_out_hist = nullptr;  // the host reads the context's histogram itself
         if (automatic && state) HIP_TRY(ctx, hipMemcpy(d_slot, state, sizeof(DisplayState), hipMemcpyHostToDevice));
@@ -106,35 +100,31 @@ int display_impl(trhip_ctx* ctx, const void* xyzw, uint32_t width, uint32_t heig
     // 0.013 ms at 1024^2 against 0.044 at eight blocks per CU (th_display.h, profiles/r15/display.txt)
     const uint32_t meter_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((npix + 255) / 256, (uint64_t)ctx->num_cu));
 
-    Timer tm(ctx, ctx->timing && stats);
-    FrameEvents ev;
-    HIP_TRY(ctx, ev.begin(st));
+    PassWindow w(ctx, stats);
+    HIP_TRY(ctx, w.open());
     if (automatic) {
         // histogram, and the slot when it stands for "no state"
         HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, own_slot && !slot_filled ? kWorkBytes : kHistBytes, st));
-        tm.begin(5, st);
+        w.begin(5);
         hipLaunchKernelGGL(k_display_meter, dim3(meter_blocks), dim3(256), 0, st, d_in, (uint32_t)npix, scale, d_hist);
-        tm.end(5, st);
-        tm.begin(6, st);
+        w.end(5);
+        w.begin(6);
         hipLaunchKernelGGL(k_display_resolve, dim3(1), dim3(64), 0, st, d_hist, rk, d_state, d_out_hist);
-        tm.end(6, st);
+        w.end(6);
     } else if (d_out_hist) {
         HIP_TRY(ctx, hipMemsetAsync(d_out_hist, 0, kHistBytes, st));
     }
     const DisplayState* e_state = automatic ? d_state : nullptr;
-    tm.begin(7, st);
+    w.begin(7);
     if (prm->curve == TRHIP_DISPLAY_CURVE_CLAMP)
         launch_encode<0>(prm->transfer, grid, block, st, d_in, (int)width, (int)height, ek, e_state, d_out);
     else if (prm->curve == TRHIP_DISPLAY_CURVE_REINHARD)
         launch_encode<1>(prm->transfer, grid, block, st, d_in, (int)width, (int)height, ek, e_state, d_out);
     else
         launch_encode<2>(prm->transfer, grid, block, st, d_in, (int)width, (int)height, ek, e_state, d_out);
-    tm.end(7, st);
-    HIP_TRY(ctx, ev.end(st));
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(st));
+    w.end(7);
+    if (int rc = close_pass(ctx, w, images, stats, 3, automatic ? 3 : 1)) return rc;  // meter, resolve, encode
     if (!is_device) {
-        HIP_TRY(ctx, hipMemcpy(out_rgba, d_out, rgba_bytes, hipMemcpyDeviceToHost));
         if (automatic && state) HIP_TRY(ctx, hipMemcpy(state, d_slot, sizeof(DisplayState), hipMemcpyDeviceToHost));
         if (out_hist) {
             if (automatic)
@@ -142,13 +132,6 @@ int display_impl(trhip_ctx* ctx, const void* xyzw, uint32_t width, uint32_t heig
             else
                 std::memset(out_hist, 0, kHistBytes);
         }
-    }
-    if (stats) {
-        std::memset(stats, 0, sizeof *stats);
-        stats->ms_total = ev.ms();
-        for (int part = 0; part < 3; ++part) stats->ms_sub[part] = tm.total(5 + part, &stats->launches_sub[part]);  // meter, resolve, encode
-        stats->ms_film = stats->ms_sub[0] + stats->ms_sub[1] + stats->ms_sub[2];
-        stats->launches_film = automatic ? 3u : 1u;  // (the Timer counts nothing when timing is off)
     }
     return 0;
 }

@@ -4,6 +4,7 @@
 #include "th_host.h"
 #include "th_temporal_clip.h"
 #include "th_temporal_moments.h"
+#include "th_image_pass.h"
 
 #include <cmath>
 
@@ -16,8 +17,6 @@ static_assert(sizeof(trhip_temporal_moments_params) == 88, "trhip_temporal_momen
 constexpr size_t kTpHostBytesPerPixel = 160;  // the host entry point's copies: film 16, planes 48, history 48, new history 48
 constexpr size_t kTmHostBytesPerPixel = 196;  // trhip_temporal_moments': trhip_temporal_clip's and moments 8, new moments 8, variance 4
 constexpr size_t kTcHostBytesPerPixel = 176;  // trhip_temporal_clip's: the same and a film of its own for the result (the window reads neighbours' film pixels)
-
-bool positive_finite(float v) { return std::isfinite(v) && v > 0.0f; }
 
 int check_params(trhip_ctx* ctx, const trhip_temporal_params* p) {
     for (int i = 0; i < 12; ++i)
@@ -41,11 +40,6 @@ int check_clip_params(trhip_ctx* ctx, const trhip_temporal_clip_params* p) {
     return 0;
 }
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
-
 // is_clip false: trhip_temporal with prm; true: trhip_temporal_clip with clip, whose base takes prm's place
 int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const void* history, uint32_t width, uint32_t height, const trhip_temporal_params* prm,
                   const trhip_temporal_clip_params* clip, bool is_clip, void* out, void* out_history, bool is_device, trhip_stats* stats) {
@@ -62,19 +56,23 @@ int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const vo
     if (width == 0 || height == 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: empty film (%u x %u)", width, height);
     const uint64_t npix = (uint64_t)width * height;
     const size_t film_bytes = (size_t)npix * sizeof(float4), planes_bytes = 3 * film_bytes;
-    if (overlap(out_history, planes_bytes, history, planes_bytes) || overlap(out_history, planes_bytes, planes, planes_bytes) || overlap(out_history, planes_bytes, xyzw, film_bytes) ||
-        overlap(out_history, planes_bytes, out, film_bytes))
-        return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: out_history overlaps an input or out_xyzw");
+    const ByteRange frame[4] = {{xyzw, film_bytes}, {planes, planes_bytes}, {history, planes_bytes}, {out, film_bytes}};
+    if (overlaps_any(out_history, planes_bytes, frame, 4)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: out_history overlaps an input or out_xyzw");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint32_t bx = (width + kDnTile - 1) / kDnTile, by = (height + kDnTile - 1) / kDnTile;
     const uint64_t lin_blocks = (npix + kDnTile * kDnTile - 1) / (kDnTile * kDnTile);
-    // the clipping kernel reads the film pixels of a whole window, so it cannot write the film it reads: an out_xyzw that is (or overlaps) xyzw is written through a film held
-    // by the context (16 B per pixel, one device-to-device copy more)
-    const bool via_scratch = is_clip && is_device && overlap(out, film_bytes, xyzw, film_bytes);
-    const size_t host_bytes = (size_t)npix * (is_clip ? kTcHostBytesPerPixel : kTpHostBytesPerPixel);
+    // trhip_temporal accumulates the film where it is: the host variant's copy in place.  The clipping kernel reads the film pixels of a whole window, so it cannot write the film
+    // it reads: the host variant has a film of its own for the result, and a device out_xyzw that is (or overlaps) xyzw is written through a film held by the context (16 B per
+    // pixel, one device-to-device copy more)
+    ImageStaging images(ctx, ctx->tp_in, is_device);
+    const ImageStaging::Image& film = is_clip ? images.input(xyzw, film_bytes) : images.inout(xyzw, out, film_bytes);
+    const ImageStaging::Image& guides = images.input(planes, planes_bytes);
+    const ImageStaging::Image& old_history = images.input(history, planes_bytes);
+    const ImageStaging::Image& new_history = images.output(out_history, planes_bytes);
+    const ImageStaging::Image& result = is_clip ? images.output_apart(out, film_bytes, film) : film;
     {
         const size_t held = ctx->tp_in.bytes;  // reused below
-        const double need = is_device ? (via_scratch ? (double)film_bytes : 0.0) : (double)host_bytes;
+        const double need = (double)images.bytes();
         bool fits;
         double free_gb;
         if (int rc = fits_in_hbm(ctx, need, held, &fits, &free_gb)) return rc;
@@ -82,38 +80,16 @@ int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const vo
             return fail(ctx, TRHIP_ERR_UNSUPPORTED, "trhip_temporal: the images of a %u x %u film (%.1f GB, %u B per pixel) do not fit in free HBM (%.1f GB free); there are no bands here", width,
                         height, need * 1e-9, is_clip ? (unsigned)kTcHostBytesPerPixel : (unsigned)kTpHostBytesPerPixel, free_gb);
     }
-    const float4* d_beauty = (const float4*)xyzw;
-    const float4* d_planes = (const float4*)planes;
-    const float4* d_history = (const float4*)history;
-    float4* d_out = (float4*)out;
-    float4* d_out_history = (float4*)out_history;
-    if (!is_device) {  // the film's copy is accumulated in place
-        if (int rc = ensure(ctx, ctx->tp_in, host_bytes)) return rc;
-        char* base = (char*)ctx->tp_in.p;
-        HIP_TRY(ctx, hipMemcpy(base, xyzw, film_bytes, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(base + film_bytes, planes, planes_bytes, hipMemcpyHostToDevice));
-        if (history) HIP_TRY(ctx, hipMemcpy(base + film_bytes + planes_bytes, history, planes_bytes, hipMemcpyHostToDevice));
-        d_beauty = d_out = (float4*)base;
-        d_planes = (const float4*)(base + film_bytes);
-        d_history = history ? (const float4*)(base + film_bytes + planes_bytes) : nullptr;
-        d_out_history = (float4*)(base + film_bytes + 2 * planes_bytes);
-        if (is_clip) d_out = (float4*)(base + film_bytes + 3 * planes_bytes);
-    } else if (via_scratch) {
-        if (int rc = ensure(ctx, ctx->tp_in, film_bytes)) return rc;
-        d_out = (float4*)ctx->tp_in.p;
-    }
-    TemporalConst k;
-    std::memcpy(k.m, prm->prev_world_to_pixel, sizeof k.m);
-    k.max_history = prm->max_history;
-    k.sigma_normal = prm->sigma_normal;
-    k.sigma_plane = prm->sigma_plane;
-    k.min_coverage = prm->min_coverage;
+    if (int rc = images.upload()) return rc;
+    const float4 *d_beauty = film.in<float4>(), *d_planes = guides.in<float4>(), *d_history = old_history.in<float4>();
+    float4 *d_out = result.out<float4>(), *d_out_history = new_history.out<float4>();
+    const TemporalConst k = temporal_const<TemporalConst>(*prm);
+
     hipStream_t st = ctx->stream;
 
-    Timer tm(ctx, ctx->timing && stats);
-    FrameEvents ev;
-    HIP_TRY(ctx, ev.begin(st));
-    tm.begin(5, st);
+    PassWindow w(ctx, stats);
+    HIP_TRY(ctx, w.open());
+    w.begin(5);
     if (is_clip) {  // one mapping, the patch's; the option "temporal_patch" has no effect here
         const dim3 grid(bx, by), block(kDnTile * kDnTile);
         const float gamma = clip->clip_gamma;
@@ -127,22 +103,8 @@ int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const vo
         hipLaunchKernelGGL((k_temporal<true>), dim3(bx, by), dim3(kDnTile * kDnTile), 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, d_out, d_out_history);
     else
         hipLaunchKernelGGL((k_temporal<false>), dim3((uint32_t)lin_blocks), dim3(kDnTile * kDnTile), 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, d_out, d_out_history);
-    tm.end(5, st);
-    if (via_scratch) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, film_bytes, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(ctx, ev.end(st));
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (!is_device) {
-        HIP_TRY(ctx, hipMemcpy(out, d_out, film_bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(out_history, d_out_history, planes_bytes, hipMemcpyDeviceToHost));
-    }
-    if (stats) {
-        std::memset(stats, 0, sizeof *stats);
-        stats->ms_total = ev.ms();
-        stats->ms_film = tm.total(5, &stats->launches_film);
-        stats->launches_film = 1;
-    }
-    return 0;
+    w.end(5);
+    return close_pass(ctx, w, images, stats, 1, 1);
 }
 
 // trhip_temporal's checks on base, in its order, then the new fields
@@ -166,28 +128,29 @@ int moments_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const voi
     if ((history == nullptr) != (moments == nullptr)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_moments: moments must be NULL exactly when history is");
     const uint64_t npix = (uint64_t)width * height;
     const size_t film_bytes = (size_t)npix * sizeof(float4), planes_bytes = 3 * film_bytes, mom_bytes = (size_t)npix * sizeof(float2), var_bytes = (size_t)npix * sizeof(float);
-    if (overlap(out_history, planes_bytes, history, planes_bytes) || overlap(out_history, planes_bytes, planes, planes_bytes) || overlap(out_history, planes_bytes, xyzw, film_bytes) ||
-        overlap(out_history, planes_bytes, out, film_bytes))
-        return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: out_history overlaps an input or out_xyzw");
-    {
-        const struct { const void* p; size_t n; const char* name; } outs[2] = {{out_moments, mom_bytes, "out_moments"}, {out_variance, var_bytes, "out_variance"}},
-            others[7] = {{xyzw, film_bytes, ""}, {planes, planes_bytes, ""}, {history, planes_bytes, ""}, {moments, mom_bytes, ""}, {out, film_bytes, ""}, {out_history, planes_bytes, ""},
-                         {out_moments, mom_bytes, ""}};
-        for (int o = 0; o < 2; ++o)
-            for (int i = 0; i < 6 + o; ++i)
-                if (overlap(outs[o].p, outs[o].n, others[i].p, others[i].n))
-                    return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_moments: %s overlaps an input or another output", outs[o].name);
-        if (overlap(out, film_bytes, moments, mom_bytes) || overlap(out_history, planes_bytes, moments, mom_bytes))
-            return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_moments: an output overlaps moments");
-    }
+    // trhip_temporal's four, then what each further output may not overlap either: out_moments the first six, out_variance all seven
+    const ByteRange others[7] = {{xyzw, film_bytes}, {planes, planes_bytes}, {history, planes_bytes}, {out, film_bytes}, {moments, mom_bytes}, {out_history, planes_bytes},
+                                 {out_moments, mom_bytes}};
+    if (overlaps_any(out_history, planes_bytes, others, 4)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal: out_history overlaps an input or out_xyzw");
+    if (overlaps_any(out_moments, mom_bytes, others, 6)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_moments: %s overlaps an input or another output", "out_moments");
+    if (overlaps_any(out_variance, var_bytes, others, 7)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_moments: %s overlaps an input or another output", "out_variance");
+    if (overlap(out, film_bytes, moments, mom_bytes) || overlap(out_history, planes_bytes, moments, mom_bytes))
+        return fail(ctx, TRHIP_ERR_INVALID, "trhip_temporal_moments: an output overlaps moments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint32_t bx = (width + kDnTile - 1) / kDnTile, by = (height + kDnTile - 1) / kDnTile;
-    // the staging reads the film pixels of a whole window: an out_xyzw that is (or overlaps) xyzw is written through the context's film, as in trhip_temporal_clip
-    const bool via_scratch = is_device && overlap(out, film_bytes, xyzw, film_bytes);
-    const size_t host_bytes = (size_t)npix * kTmHostBytesPerPixel;
+    // trhip_temporal_clip's images in its layout (the kernel's staging reads the film pixels of a whole window, so out_xyzw is kept apart from xyzw in the same way), then the moments'
+    ImageStaging images(ctx, ctx->tp_in, is_device);
+    const ImageStaging::Image& film = images.input(xyzw, film_bytes);
+    const ImageStaging::Image& guides = images.input(planes, planes_bytes);
+    const ImageStaging::Image& old_history = images.input(history, planes_bytes);
+    const ImageStaging::Image& new_history = images.output(out_history, planes_bytes);
+    const ImageStaging::Image& result = images.output_apart(out, film_bytes, film);
+    const ImageStaging::Image& old_moments = images.input(moments, mom_bytes);
+    const ImageStaging::Image& new_moments = images.output(out_moments, mom_bytes);
+    const ImageStaging::Image& var = images.output(out_variance, var_bytes);
     {
         const size_t held = ctx->tp_in.bytes;  // reused below
-        const double need = is_device ? (via_scratch ? (double)film_bytes : 0.0) : (double)host_bytes;
+        const double need = (double)images.bytes();
         bool fits;
         double free_gb;
         if (int rc = fits_in_hbm(ctx, need, held, &fits, &free_gb)) return rc;
@@ -195,75 +158,18 @@ int moments_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const voi
             return fail(ctx, TRHIP_ERR_UNSUPPORTED, "trhip_temporal_moments: the images of a %u x %u film (%.1f GB, %u B per pixel) do not fit in free HBM (%.1f GB free); there are no bands here",
                         width, height, need * 1e-9, (unsigned)kTmHostBytesPerPixel, free_gb);
     }
-    const float4* d_beauty = (const float4*)xyzw;
-    const float4* d_planes = (const float4*)planes;
-    const float4* d_history = (const float4*)history;
-    const float2* d_moments = (const float2*)moments;
-    float4* d_out = (float4*)out;
-    float4* d_out_history = (float4*)out_history;
-    float2* d_out_moments = (float2*)out_moments;
-    float* d_out_variance = (float*)out_variance;
-    if (!is_device) {
-        if (int rc = ensure(ctx, ctx->tp_in, host_bytes)) return rc;
-        char* at = (char*)ctx->tp_in.p;
-        auto take = [&at](size_t n) {
-            char* p = at;
-            at += n;
-            return p;
-        };
-        char *b_film = take(film_bytes), *b_planes = take(planes_bytes), *b_hist = take(planes_bytes), *b_out_hist = take(planes_bytes), *b_out = take(film_bytes);
-        char *b_mom = take(mom_bytes), *b_out_mom = take(mom_bytes), *b_var = take(var_bytes);
-        HIP_TRY(ctx, hipMemcpy(b_film, xyzw, film_bytes, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(b_planes, planes, planes_bytes, hipMemcpyHostToDevice));
-        if (history) {
-            HIP_TRY(ctx, hipMemcpy(b_hist, history, planes_bytes, hipMemcpyHostToDevice));
-            HIP_TRY(ctx, hipMemcpy(b_mom, moments, mom_bytes, hipMemcpyHostToDevice));
-        }
-        d_beauty = (const float4*)b_film;
-        d_planes = (const float4*)b_planes;
-        d_history = history ? (const float4*)b_hist : nullptr;
-        d_moments = history ? (const float2*)b_mom : nullptr;
-        d_out = (float4*)b_out;
-        d_out_history = (float4*)b_out_hist;
-        d_out_moments = (float2*)b_out_mom;
-        d_out_variance = (float*)b_var;
-    } else if (via_scratch) {
-        if (int rc = ensure(ctx, ctx->tp_in, film_bytes)) return rc;
-        d_out = (float4*)ctx->tp_in.p;
-    }
-    TemporalConst k;
-    std::memcpy(k.m, prm->base.prev_world_to_pixel, sizeof k.m);
-    k.max_history = prm->base.max_history;
-    k.sigma_normal = prm->base.sigma_normal;
-    k.sigma_plane = prm->base.sigma_plane;
-    k.min_coverage = prm->base.min_coverage;
+    if (int rc = images.upload()) return rc;
+    const TemporalConst k = temporal_const<TemporalConst>(prm->base);
     const MomentsConst mk{prm->albedo_floor, prm->spatial_below, prm->flags & TRHIP_DENOISE_DEMODULATE};
-    hipStream_t st = ctx->stream;
 
-    Timer tm(ctx, ctx->timing && stats);
-    FrameEvents ev;
-    HIP_TRY(ctx, ev.begin(st));
-    tm.begin(5, st);
+    PassWindow w(ctx, stats);
+    HIP_TRY(ctx, w.open());
+    w.begin(5);
     const dim3 grid(bx, by), block(kDnTile * kDnTile);
-    hipLaunchKernelGGL(k_temporal_moments, grid, block, 0, st, d_beauty, d_planes, d_history, d_moments, (int)width, (int)height, k, mk, d_out, d_out_history, d_out_moments, d_out_variance);
-    tm.end(5, st);
-    if (via_scratch) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, film_bytes, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(ctx, ev.end(st));
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (!is_device) {
-        HIP_TRY(ctx, hipMemcpy(out, d_out, film_bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(out_history, d_out_history, planes_bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(out_moments, d_out_moments, mom_bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(out_variance, d_out_variance, var_bytes, hipMemcpyDeviceToHost));
-    }
-    if (stats) {
-        std::memset(stats, 0, sizeof *stats);
-        stats->ms_total = ev.ms();
-        stats->ms_film = tm.total(5, &stats->launches_film);
-        stats->launches_film = 1;
-    }
-    return 0;
+    hipLaunchKernelGGL(k_temporal_moments, grid, block, 0, w.st, film.in<float4>(), guides.in<float4>(), old_history.in<float4>(), old_moments.in<float2>(), (int)width, (int)height, k, mk,
+                       result.out<float4>(), new_history.out<float4>(), new_moments.out<float2>(), var.out<float>());
+    w.end(5);
+    return close_pass(ctx, w, images, stats, 1, 1);
 }
 
 // Gauss-Jordan with partial pivoting on an n x n Float64 matrix (row-major, n <= 4); false when a pivot is zero or not finite.

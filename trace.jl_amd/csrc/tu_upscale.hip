@@ -2,6 +2,7 @@
 // traversal: an image-space pass.
 #include "th_host.h"
 #include "th_upscale.h"
+#include "th_image_pass.h"
 
 #include <cmath>
 
@@ -9,23 +10,8 @@ namespace {
 
 static_assert(sizeof(trhip_upscale_params) == 48, "trhip_upscale_params layout");
 
-constexpr uint32_t kUpMaxLowDim = 1u << 24;  // low-image indices are ints; positions stay below 2^21 (th_upscale.h)
-
-bool positive_finite(float v) { return std::isfinite(v) && v > 0.0f; }
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
-
 int check_params(trhip_ctx* ctx, const trhip_upscale_params* p) {
-    for (int i = 0; i < 4; ++i)
-        if (!std::isfinite(p->lo_from_hi[i])) return fail(ctx, TRHIP_ERR_INVALID, "trhip_upscale: lo_from_hi[%d] is not finite", i);
-    for (int i = 0; i < 4; i += 2) {
-        if (!(p->lo_from_hi[i] >= 0.25f && p->lo_from_hi[i] <= 1.0f))
-            return fail(ctx, TRHIP_ERR_INVALID, "trhip_upscale: lo_from_hi[%d] = %g, the scale must lie in [1/4, 1]", i, (double)p->lo_from_hi[i]);
-        if (!(std::fabs(p->lo_from_hi[i + 1]) < 1048576.0f)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_upscale: lo_from_hi[%d], the offset, must be below 2^20 in magnitude", i + 1);
-    }
+    if (int rc = check_lo_from_hi(ctx, "trhip_upscale", p->lo_from_hi)) return rc;
     if (p->radius != 1 && p->radius != 2) return fail(ctx, TRHIP_ERR_INVALID, "trhip_upscale: radius must be 1 or 2, not %u", p->radius);
     if (!positive_finite(p->sigma_normal)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_upscale: sigma_normal must be finite and > 0");
     if (!positive_finite(p->sigma_plane)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_upscale: sigma_plane must be finite and > 0");
@@ -48,25 +34,24 @@ int upscale_impl(trhip_ctx* ctx, const void* lo_xyzw, const void* lo_planes, uin
     const uint64_t npix = (uint64_t)width * height, nlo = (uint64_t)lo_width * lo_height;
     const size_t film_bytes = (size_t)npix * sizeof(float4), planes_bytes = 3 * film_bytes, lo_film_bytes = (size_t)nlo * sizeof(float4), lo_planes_bytes = 3 * lo_film_bytes;
     const size_t mask_bytes = (size_t)npix;
-    {
-        const struct { const void* p; size_t n; } ins[3] = {{lo_xyzw, lo_film_bytes}, {lo_planes, lo_planes_bytes}, {hi_planes, planes_bytes}};
-        for (auto& in : ins) {
-            if (overlap(out, film_bytes, in.p, in.n)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_upscale: out_xyzw overlaps an input");
-            if (overlap(out_mask, mask_bytes, in.p, in.n)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_upscale: out_mask overlaps an input");
-        }
-        if (overlap(out_mask, mask_bytes, out, film_bytes)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_upscale: out_mask overlaps out_xyzw");
-    }
+    const ByteRange ins[3] = {{lo_xyzw, lo_film_bytes}, {lo_planes, lo_planes_bytes}, {hi_planes, planes_bytes}};
+    if (overlaps_any(out, film_bytes, ins, 3)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_upscale: out_xyzw overlaps an input");
+    if (overlaps_any(out_mask, mask_bytes, ins, 3)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_upscale: out_mask overlaps an input");
+    if (overlap(out_mask, mask_bytes, out, film_bytes)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_upscale: out_mask overlaps out_xyzw");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint32_t bx = (width + kDnTile - 1) / kDnTile, by = (height + kDnTile - 1) / kDnTile;
     const int R = (int)prm->radius;
-    // the staged square (th_upscale.h): ceil(15 a) + 1 + 2 R positions per axis, the larger axis deciding
-    const float amax = std::fmax(prm->lo_from_hi[0], prm->lo_from_hi[2]);
-    const int tw = (int)std::ceil(15.0 * (double)amax) + 1 + 2 * R, stride = tw <= 16 ? 16 : 32;
-    const size_t lds_bytes = (size_t)4 * tw * stride * sizeof(float4);  // at most 40960
-    const size_t host_bytes = lo_film_bytes + lo_planes_bytes + planes_bytes + film_bytes + mask_bytes;
+    const StagedSquare sq = staged_square(prm->lo_from_hi, R);
+    // the host variant's copies: 64 B per low pixel, 65 per full-size pixel
+    ImageStaging images(ctx, ctx->up_in, is_device);
+    const ImageStaging::Image& lo_film = images.input(lo_xyzw, lo_film_bytes);
+    const ImageStaging::Image& lo_guides = images.input(lo_planes, lo_planes_bytes);
+    const ImageStaging::Image& hi_guides = images.input(hi_planes, planes_bytes);
+    const ImageStaging::Image& result = images.output(out, film_bytes);
+    const ImageStaging::Image& mask = images.output(out_mask, mask_bytes);
     {
         const size_t held = ctx->up_in.bytes;  // reused below
-        const double need = is_device ? 0.0 : (double)host_bytes;
+        const double need = (double)images.bytes();
         bool fits;
         double free_gb;
         if (int rc = fits_in_hbm(ctx, need, held, &fits, &free_gb)) return rc;
@@ -74,62 +59,27 @@ int upscale_impl(trhip_ctx* ctx, const void* lo_xyzw, const void* lo_planes, uin
             return fail(ctx, TRHIP_ERR_UNSUPPORTED, "trhip_upscale: the images of a %u x %u film from %u x %u (%.1f GB) do not fit in free HBM (%.1f GB free); there are no bands here", width,
                         height, lo_width, lo_height, need * 1e-9, free_gb);
     }
-    const float4* d_lo = (const float4*)lo_xyzw;
-    const float4* d_lo_planes = (const float4*)lo_planes;
-    const float4* d_hi_planes = (const float4*)hi_planes;
-    float4* d_out = (float4*)out;
-    uint8_t* d_mask = (uint8_t*)out_mask;
-    if (!is_device) {
-        if (int rc = ensure(ctx, ctx->up_in, host_bytes)) return rc;
-        char* at = (char*)ctx->up_in.p;
-        auto take = [&at](size_t n) {
-            char* p = at;
-            at += n;
-            return p;
-        };
-        char *b_lo = take(lo_film_bytes), *b_lo_planes = take(lo_planes_bytes), *b_hi = take(planes_bytes), *b_out = take(film_bytes), *b_mask = take(mask_bytes);
-        HIP_TRY(ctx, hipMemcpy(b_lo, lo_xyzw, lo_film_bytes, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(b_lo_planes, lo_planes, lo_planes_bytes, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(b_hi, hi_planes, planes_bytes, hipMemcpyHostToDevice));
-        d_lo = (const float4*)b_lo;
-        d_lo_planes = (const float4*)b_lo_planes;
-        d_hi_planes = (const float4*)b_hi;
-        d_out = (float4*)b_out;
-        d_mask = out_mask ? (uint8_t*)b_mask : nullptr;
-    }
-    UpscaleConst k;
-    k.ax = prm->lo_from_hi[0], k.bx = prm->lo_from_hi[1], k.ay = prm->lo_from_hi[2], k.by = prm->lo_from_hi[3];
-    k.inv_r = 1.0f / (float)R;
+    if (int rc = images.upload()) return rc;
+    const float4 *d_lo = lo_film.in<float4>(), *d_lo_planes = lo_guides.in<float4>(), *d_hi_planes = hi_guides.in<float4>();
+    float4* d_out = result.out<float4>();
+    uint8_t* d_mask = mask.out<uint8_t>();  // NULL when the caller wants none
+    UpscaleConst k = upscale_const<UpscaleConst>(prm->lo_from_hi, R, prm->sigma_normal, prm->sigma_plane, prm->min_coverage);
     k.demodulate = prm->flags & TRHIP_UPSCALE_DEMODULATE;
     k.coverage = prm->flags & TRHIP_UPSCALE_COVERAGE;
-    k.sigma_normal = prm->sigma_normal, k.sigma_plane = prm->sigma_plane, k.albedo_floor = prm->albedo_floor, k.min_coverage = prm->min_coverage;
+    k.albedo_floor = prm->albedo_floor;
     hipStream_t st = ctx->stream;
     const dim3 grid(bx, by), block(kDnTile * kDnTile);
     const int lw = (int)lo_width, lh = (int)lo_height;
 
-    Timer tm(ctx, ctx->timing && stats);
-    FrameEvents ev;
-    HIP_TRY(ctx, ev.begin(st));
-    tm.begin(5, st);
+    PassWindow w(ctx, stats);
+    HIP_TRY(ctx, w.open());
+    w.begin(5);
     if (R == 1)
-        hipLaunchKernelGGL((k_upscale<1>), grid, block, lds_bytes, st, d_lo, d_lo_planes, lw, lh, d_hi_planes, (int)width, (int)height, k, tw, stride, d_out, d_mask);
+        hipLaunchKernelGGL((k_upscale<1>), grid, block, sq.lds_bytes, st, d_lo, d_lo_planes, lw, lh, d_hi_planes, (int)width, (int)height, k, sq.tw, sq.stride, d_out, d_mask);
     else
-        hipLaunchKernelGGL((k_upscale<2>), grid, block, lds_bytes, st, d_lo, d_lo_planes, lw, lh, d_hi_planes, (int)width, (int)height, k, tw, stride, d_out, d_mask);
-    tm.end(5, st);
-    HIP_TRY(ctx, ev.end(st));
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (!is_device) {
-        HIP_TRY(ctx, hipMemcpy(out, d_out, film_bytes, hipMemcpyDeviceToHost));
-        if (out_mask) HIP_TRY(ctx, hipMemcpy(out_mask, d_mask, mask_bytes, hipMemcpyDeviceToHost));
-    }
-    if (stats) {
-        std::memset(stats, 0, sizeof *stats);
-        stats->ms_total = ev.ms();
-        stats->ms_film = tm.total(5, &stats->launches_film);
-        stats->launches_film = 1;
-    }
-    return 0;
+        hipLaunchKernelGGL((k_upscale<2>), grid, block, sq.lds_bytes, st, d_lo, d_lo_planes, lw, lh, d_hi_planes, (int)width, (int)height, k, sq.tw, sq.stride, d_out, d_mask);
+    w.end(5);
+    return close_pass(ctx, w, images, stats, 1, 1);
 }
 
 }  // namespace
