@@ -392,8 +392,8 @@ int trhip_denoise_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_plane
  * tap counting when it lies inside the image, was a surface pixel with N > 0, 1 - n.n_q < sigma_normal and |n.(p_q - p)| < sigma_plane.  With
  * c_h, N_h the weighted means over the counting taps: N' = min(N_h + 1, max_history), c' = c_h + (c - c_h) / N'; without any (or h.z <= 0, a
  * position that is not finite or beyond 2^20, a result that is not finite): c' = c, N' = 1.  out_xyzw = (rgb_to_xyz(c') * w, w): the .w lane
- * is returned as given, so the output goes into trhip_denoise, film.set_xyzw and save.  Scenes are static; lighting changes are NOT detected:
- * pass history = NULL after one.
+ * is returned as given, so the output goes into trhip_denoise, film.set_xyzw and save.  Scenes are static (rigid bodies that move between frames:
+ * trhip_temporal_motion, below); lighting changes are NOT detected: pass history = NULL after one.
  * TRHIP_ERR_INVALID: params NULL, an entry of prev_world_to_pixel not finite, max_history not finite or < 1, flags != 0, a sigma not finite
  * and > 0, min_coverage outside [0, 1], reserved != 0 (the parameter block is checked first, before any handle); then a null pointer (history
  * excepted), a zero dimension, out_history overlapping history, planes, xyzw or out_xyzw.  TRHIP_ERR_UNSUPPORTED: the host variant's device
@@ -676,6 +676,63 @@ int trhip_temporal_upsample(trhip_ctx* ctx, const float* lo_xyzw, const float* l
 int trhip_temporal_upsample_device(trhip_ctx* ctx, const void* d_lo_xyzw, const void* d_lo_planes, uint32_t lo_width, uint32_t lo_height, const void* d_hi_planes,
                                    const void* d_history, uint32_t width, uint32_t height, const trhip_temporal_upsample_params* params, void* d_out_xyzw, void* d_out_history,
                                    void* d_out_mask, trhip_stats* stats);
+
+/* ---- moving geometry in a preview: the id plane and motion-aware reprojection (since ABI 3001, added without a version change: nothing existing moved) ----
+ * trhip_temporal looks for a pixel's history where its surface point lies NOW; on a rigid body that moved between the frames the point was elsewhere, and the
+ * taps found there fail the plane test.  Two entry points close the gap: a per-pixel id plane that says which primitive a pixel shows, and trhip_temporal with a
+ * per-body matrix that carries the pixel's surface back to where its body was.  Specified operation by operation in docs/design/20-motion.md; bit-reproducible.
+ *
+ * trhip_render_aov_ids: trhip_render_aov with a third, optional output.  out_planes and out_samples are trhip_render_aov's BIT FOR BIT for the same arguments.
+ * Any output may be NULL (all three: TRHIP_ERR_INVALID).  out_ids: (crop height) * (crop width) trhip_aov_id records in [y][x] order, like out_planes.  Film pixel
+ * (x, y) looks at its OWN spp records, [s][y - sb.min.y][x - sb.min.x], s = 0 .. spp-1 — not at the neighbours that reach it through the filter —: n_hit is the number
+ * of them with prim >= 0, and among those whose t is not NaN the one with the smallest t gives prim, material and t (ties: the lowest s).  Without one:
+ * prim = material = -1, t = +Inf (n_hit = 0 unless every hitting record's t is NaN).  prim is trhip_hit.prim: the ordered-primitive slot, prim_order[prim] the
+ * caller's index.  One more launch (stats.ms_film includes it when out_planes is drawn; launches_film counts it); 16 bytes per film pixel beside trhip_render_aov's buffers. */
+typedef struct {
+    int32_t prim;      /* ordered-primitive slot of the nearest of the pixel's own camera samples, -1: none hit */
+    int32_t material;  /* its material id as trhip_aov_sample.material, -1: none */
+    float t;           /* its ray parameter, +Inf: none hit */
+    uint32_t n_hit;    /* how many of the pixel's spp camera samples hit anything */
+} trhip_aov_id;        /* 16 bytes */
+int trhip_render_aov_ids(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset, float* out_planes,
+                         trhip_aov_sample* out_samples, trhip_aov_id* out_ids, trhip_stats* stats);
+int trhip_render_aov_ids_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset,
+                                void* d_out_planes, void* d_out_samples, void* d_out_ids, trhip_stats* stats);
+
+/* trhip_temporal_motion: trhip_temporal — its images, layouts, overlap rules and stats — with
+ *   ids            height * width trhip_aov_id of the CURRENT frame (only prim is read)
+ *   body_of_prim   n_prims uint32, indexed by ids.prim: the rigid body of the primitive; a value >= n_bodies (by convention 0xFFFFFFFF) means static.  May be NULL.
+ *   bodies         n_bodies * 12 floats: per body a row-major 3 x 4 matrix prev_from_cur that maps a point of the body in THIS frame's world to where that point was
+ *                  in the PREVIOUS frame's world.  The caller promises a rigid motion; nothing about the matrix is checked.  May be NULL.
+ * A pixel is static when ids.prim < 0 or >= n_prims, when body_of_prim or bodies is NULL, or when its body index is >= n_bodies: it gets trhip_temporal's arithmetic
+ * on its n and p untouched, bit for bit (no multiplication by an identity).  Otherwise p' = A (p, 1), component i = ((A[i][0]*p.x + A[i][1]*p.y) + A[i][2]*p.z) + A[i][3],
+ * and n' the same without the last column, not renormalised; p' or n' not finite: no history.  p' is projected through prev_world_to_pixel, and n', p' stand for n, p in both
+ * tap tests.  Blend, cap, the non-finite fallback and out_xyzw as in trhip_temporal.  out_history stores the CURRENT n and p: the next frame's previous world.
+ * For ANY bit content of ids and body_of_prim the kernel reads only inside the three arrays: every index is range-checked before it addresses anything.
+ * Shadows and reflections that a moving body drags over other surfaces are not re-projected: they lag by the history length (docs/design/20-motion.md).
+ * TRHIP_ERR_INVALID, in this order: params NULL; trhip_temporal's checks of the fields it shares, in its order; flags != 0; reserved != 0 (the parameter block first,
+ * before any handle); then a null pointer (history, body_of_prim, bodies and stats excepted); a zero dimension; n_prims > 0 with body_of_prim NULL; n_bodies > 0 with
+ * bodies NULL; out_history overlapping any input or out_xyzw.  out_xyzw may be xyzw.  TRHIP_ERR_UNSUPPORTED: the host variant's device copies (176 bytes per pixel, 4 per
+ * primitive, 48 per body) do not fit in free HBM.  stats (may be NULL): ms_total, ms_film, launches_film = 1.  The _device variant takes DEVICE pointers for all eight
+ * arrays and allocates nothing.  trhip_temporal_motion_default_params needs no context and no GPU: trhip_temporal_default_params' values, n_prims = n_bodies = 0. */
+typedef struct {
+    float prev_world_to_pixel[12]; /* as in trhip_temporal_params, and the four below */
+    float max_history;
+    float sigma_normal;
+    float sigma_plane;
+    float min_coverage;
+    uint32_t n_prims;              /* entries of body_of_prim */
+    uint32_t n_bodies;             /* matrices in bodies */
+    uint32_t flags;                /* 0 */
+    uint32_t reserved;             /* 0 */
+} trhip_temporal_motion_params;    /* 80 bytes */
+int trhip_temporal_motion_default_params(trhip_temporal_motion_params* out);
+int trhip_temporal_motion(trhip_ctx* ctx, const float* xyzw, const float* planes, const float* history, const trhip_aov_id* ids, const uint32_t* body_of_prim,
+                          const float* bodies, uint32_t width, uint32_t height, const trhip_temporal_motion_params* params, float* out_xyzw, float* out_history,
+                          trhip_stats* stats);
+int trhip_temporal_motion_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_history, const void* d_ids, const void* d_body_of_prim,
+                                 const void* d_bodies, uint32_t width, uint32_t height, const trhip_temporal_motion_params* params, void* d_out_xyzw, void* d_out_history,
+                                 trhip_stats* stats);
 
 /* SPPMIntegrator(camera, initial_search_radius, max_depth, n_iterations, photons_per_iteration)(scene)
  * (integrators/sppm.jl:108-173): per iteration a camera pass to the first diffuse vertex, a hash grid over the visible

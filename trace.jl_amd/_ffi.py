@@ -226,6 +226,26 @@ class TemporalUpsampleParams(C.Structure):
     ]
 
 
+class TemporalMotionParams(C.Structure):
+    """trhip_temporal_motion_params (80 bytes)"""
+    _fields_ = [
+        ("prev_world_to_pixel", C.c_float * 12),
+        ("max_history", C.c_float),
+        ("sigma_normal", C.c_float),
+        ("sigma_plane", C.c_float),
+        ("min_coverage", C.c_float),
+        ("n_prims", C.c_uint32),
+        ("n_bodies", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+# trhip_aov_id, the record of the id plane (AOVIntegrator.ids)
+AOV_ID_DTYPE = np.dtype([("prim", np.int32), ("material", np.int32), ("t", np.float32), ("n_hit", np.uint32)])
+STATIC_BODY = 0xFFFFFFFF  # the conventional "no body" word of body_of_prim
+
+
 class DisplayParams(C.Structure):
     """trhip_display_params (48 bytes)"""
     _fields_ = [
@@ -324,6 +344,11 @@ SIGNATURES = {
                                           C.POINTER(Stats)]),
     "trhip_temporal_upsample_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(TemporalUpsampleParams), _VP, _VP, _VP,
                                                  C.POINTER(Stats)]),
+    "trhip_render_aov_ids": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _F, _VP, _VP, C.POINTER(Stats)]),
+    "trhip_render_aov_ids_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, _VP, _VP, C.POINTER(Stats)]),
+    "trhip_temporal_motion_default_params": (C.c_int, [C.POINTER(TemporalMotionParams)]),
+    "trhip_temporal_motion": (C.c_int, [_VP, _F, _F, _F, _VP, _U32, _F, C.c_uint32, C.c_uint32, C.POINTER(TemporalMotionParams), _F, _F, C.POINTER(Stats)]),
+    "trhip_temporal_motion_device": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(TemporalMotionParams), _VP, _VP, C.POINTER(Stats)]),
     "trhip_render_sppm": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats)]),
     "trhip_render_sppm_ex": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats), C.c_uint32, SPPM_WRITE_FN, _VP]),
     "trhip_sppm_state": (C.c_int, [_VP, _F, _F, _F, C.POINTER(C.c_double), C.POINTER(C.c_int64), _F, _F, _F, C.POINTER(C.c_int64)]),

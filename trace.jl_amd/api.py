@@ -460,6 +460,53 @@ class Scene:  # Trace.jl:176-187
         s._base = self
         return s
 
+    def moved(self, motion) -> "Scene":
+        """The scene with some of its bodies carried to a new pose: `motion` is {index into self.aggregate.primitives: Transformation}, each the rigid motion of that
+        top-level entry from its pose in this scene to the new one (a nested BVHAccel or a MeshPrimitives entry moves as a whole).  Returns a new Scene with the same lights,
+        the same structure and the same material objects; entries without a motion are shared.  Host arithmetic only; the new scene commits in full when first rendered.
+        A sphere gets the composed object_to_world (m = T.m o2w.m, inv_m = o2w.inv_m T.inv_m — the true inverse, not Transformation.__mul__'s).  A mesh's world-space
+        vertices go through transform_points(T, .), its normals and tangents through T's linear part (the reference leaves both as the caller gave them, TriangleMesh above,
+        so turning them is this helper's job); the moved mesh holds its vertices as given, under an identity object_to_world with the same effective orientation."""
+        top = self.aggregate.primitives
+        for k in motion:
+            if not (isinstance(k, (int, np.integer)) and 0 <= k < len(top)):
+                raise TraceHipError(f"Scene.moved: {k!r} is no index into the {len(top)} top-level primitives")
+        meshes = {}
+
+        def linear(T, v):
+            m = T.m
+            return np.ascontiguousarray(np.stack([(m[i, 0] * v[:, 0] + m[i, 1] * v[:, 1]) + m[i, 2] * v[:, 2] for i in range(3)], axis=1), dtype=np.float32)
+
+        def moved_mesh(mesh, T):
+            key = (id(mesh), id(T))
+            if key not in meshes:
+                new = TriangleMesh.__new__(TriangleMesh)
+                new.core = ShapeCore(Transformation(), mesh.core.reverse_orientation != mesh.core.transform_swaps_handedness)
+                new.indices, new.n_triangles, new.uv = mesh.indices, mesh.n_triangles, getattr(mesh, "uv", None)
+                new.vertices = transform_points(T, mesh.vertices)
+                new.object_vertices = new.vertices
+                new.normals = None if mesh.normals is None else linear(T, mesh.normals)
+                tangents = getattr(mesh, "tangents", None)
+                new.tangents = None if tangents is None else linear(T, tangents)
+                meshes[key] = new
+            return meshes[key]
+
+        def moved_primitive(p, T):
+            if isinstance(p, BVHAccel):
+                return BVHAccel([moved_primitive(q, T) for q in p.primitives], p.max_node_primitives)
+            if isinstance(p, MeshPrimitives):
+                return MeshPrimitives(moved_mesh(p.mesh, T), p.material)
+            if isinstance(p.shape, Sphere):
+                s, o2w = p.shape, p.shape.core.object_to_world
+                core = ShapeCore(Transformation(_mat_mul(T.m, o2w.m), _mat_mul(o2w.inv_m, T.inv_m)), s.core.reverse_orientation)
+                return GeometricPrimitive(Sphere(core, s.radius, s.z_min, s.z_max, s.phi_max_deg), p.material)
+            if isinstance(p.shape, Triangle):
+                return GeometricPrimitive(Triangle(moved_mesh(p.shape.mesh, T), p.shape.k), p.material)
+            raise TraceHipError(f"Scene.moved: unsupported shape {type(p.shape).__name__}")
+
+        prims = [moved_primitive(p, motion[i]) if i in motion else p for i, p in enumerate(top)]
+        return Scene(self.lights, BVHAccel(prims, self.aggregate.max_node_primitives))
+
     @property
     def bound(self) -> np.ndarray:
         """scene.bound = world_bound(aggregate) (Trace.jl:183, accel/bvh.jl:208-210), as 6 Float32s p_min, p_max: the root box of the reference's BVH, i.e.
@@ -685,6 +732,16 @@ def splice_nested(prims):
     return out
 
 
+def top_level_counts(scene: "Scene"):
+    """How many primitives of the flat list each top-level entry of scene.aggregate.primitives stands for (a MeshPrimitives its triangles, a nested BVHAccel everything
+    in it): the scene's structure as FlatScene.body_table and PreviewSession's motion frames see it."""
+    def count(p):
+        if isinstance(p, BVHAccel):
+            return sum(count(q) for q in p.primitives)
+        return p.mesh.n_triangles if isinstance(p, MeshPrimitives) else 1
+    return [count(p) for p in scene.aggregate.primitives]
+
+
 class FlatScene:
     """Walk Scene -> BVHAccel -> GeometricPrimitive -> shape/material and push everything through the C ABI."""
 
@@ -708,6 +765,7 @@ class FlatScene:
 
         prims = splice_nested(scene.aggregate.primitives)
         self.n_prims = len(prims)
+        self.top_counts = top_level_counts(scene)
         i = 0
         while i < len(prims):
             p = prims[i]
@@ -754,6 +812,7 @@ class FlatScene:
         self.ctx = base.ctx
         self._h = C.c_void_p()
         self.n_prims = base.n_prims
+        self.top_counts = base.top_counts
         self.ctx.check(L.trhip_scene_relight(base._h, C.byref(self._h)))
         self._add_lights(scene)
         self.ctx.check(L.trhip_scene_commit(self._h, scene.aggregate.max_node_primitives))
@@ -799,6 +858,28 @@ class FlatScene:
         order = np.empty(npr.value, dtype=np.uint32)
         self.ctx.check(L.trhip_scene_get_bvh(self._h, _ffi.fptr(bounds), _ffi.u32ptr(a), _ffi.u32ptr(flags), _ffi.u32ptr(order)))
         return bounds, a, flags, order
+
+    def prim_order(self) -> np.ndarray:
+        """prim_order of bvh() alone (prim_order[slot] = caller primitive index), without copying the nodes."""
+        nn, npr = C.c_uint32(), C.c_uint32()
+        self.ctx.check(_ffi.lib().trhip_scene_bvh_size(self._h, C.byref(nn), C.byref(npr)))
+        order = np.empty(npr.value, dtype=np.uint32)
+        self.ctx.check(_ffi.lib().trhip_scene_get_bvh(self._h, None, None, None, _ffi.u32ptr(order)))
+        return order
+
+    def body_table(self, bodies) -> np.ndarray:
+        """body_of_prim of trhip_temporal_motion, in ordered-primitive slot order (what trhip_hit.prim and the id plane's prim index): `bodies` gives the rigid-body index
+        of every TOP-LEVEL entry of scene.aggregate.primitives — a MeshPrimitives entry or a nested BVHAccel is one body for everything in it —, None meaning static
+        (the word 0xFFFFFFFF).  The caller-order table goes through this scene's prim_order (FlatScene.bvh()'s fourth array)."""
+        bodies = list(bodies)
+        if len(bodies) != len(self.top_counts):
+            raise TraceHipError(f"FlatScene.body_table: {len(bodies)} entries for {len(self.top_counts)} top-level primitives")
+        words = np.array([_ffi.STATIC_BODY if b is None else int(b) for b in bodies], dtype=np.uint32)
+        per_prim = np.repeat(words, self.top_counts)
+        order = self.prim_order()
+        if order.size != per_prim.size:
+            raise TraceHipError(f"FlatScene.body_table: the scene holds {order.size} primitives, its top-level entries {per_prim.size}")
+        return np.ascontiguousarray(per_prim[order], dtype=np.uint32)
 
     @property
     def geometry_id(self) -> int:
@@ -1003,19 +1084,38 @@ class AOVIntegrator:
         sb = self.camera.film.get_sample_bounds()
         return int(sb.p_max[1] - sb.p_min[1]) + 1, int(sb.p_max[0] - sb.p_min[0]) + 1
 
-    def _call(self, scene, ctx, planes, samples, device):
+    def _call(self, scene, ctx, planes, samples, device, ids=None):
+        """One frame through trhip_render_aov(_device), or, with an id plane asked for, through trhip_render_aov_ids(_device)."""
         flat = scene.flatten(ctx)
         ctx = flat.ctx
         sn, st, smp = self.camera.sensor(), _ffi.Stats(), self.sampler
-        entry = _ffi.lib().trhip_render_aov_device if device else _ffi.lib().trhip_render_aov
-        ctx.check(entry(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, planes, samples, C.byref(st)))
+        L = _ffi.lib()
+        if ids is None:
+            entry, outputs = (L.trhip_render_aov_device if device else L.trhip_render_aov), (planes, samples)
+        else:
+            entry, outputs = (L.trhip_render_aov_ids_device if device else L.trhip_render_aov_ids), (planes, samples, ids)
+        ctx.check(entry(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, *outputs, C.byref(st)))
         self.stats = st
 
-    def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None):
+    def ids(self, scene: Scene, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
+        """The id plane, (H, W) of _ffi.AOV_ID_DTYPE (trhip_render_aov_ids): per film pixel the nearest of its own spp camera samples — `prim` (the ordered-primitive
+        slot, as in trhip_hit; FlatScene.bvh()'s prim_order[prim] is the caller's index), `material`, `t` — and `n_hit`, how many of them hit.  No hit: (-1, -1, inf, 0)."""
+        h, w = self.camera.film.size
+        out = np.empty((h, w), dtype=_ffi.AOV_ID_DTYPE)
+        self._call(scene, ctx, None, None, False, ids=out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None, device_ids: Optional[int] = None):
         """The filtered planes.  Returns an AOVResult with `planes` (H, W, 3, 4: the raw, un-normalised sums of include/tracehip.h) and, each divided by its own
         weight where that weight is not zero (zero elsewhere), `albedo` (H, W, 3; by the weight of all samples), `normal`, `position` (H, W, 3) and `depth` (H, W)
         (by the weight of the hitting samples), and `alpha` = hit weight / total weight.  With ``device_out`` (a device pointer to H * W * 12 floats) the planes are
-        written there, nothing is copied to the host and None is returned."""
+        written there, nothing is copied to the host and None is returned.  With ``device_ids`` (a device pointer to H * W 16-byte records; needs ``device_out``) the
+        same call also writes the id plane there (trhip_render_aov_ids_device)."""
+        if device_ids is not None:
+            if device_out is None:
+                raise TraceHipError("AOVIntegrator.render: device_ids needs device_out (for the id plane on the host use ids())")
+            self._call(scene, ctx, C.c_void_p(device_out), None, True, ids=C.c_void_p(device_ids))
+            return None
         if device_out is not None:
             self._call(scene, ctx, C.c_void_p(device_out), None, True)
             return None
@@ -1431,7 +1531,11 @@ class TemporalAccumulator:
 
     `moments=True`: `accumulate_moments` / `accumulate_moments_device` also carry the two luminance moments along the reprojection and return a variance plane for
     Denoiser.denoise_variance (trhip_temporal_moments; docs/design/16-variance.md); their colour and history are `accumulate`'s bit for bit.  `spatial_below`, `albedo_floor`
-    left at None come from trhip_temporal_moments_default_params; `demodulate` must be the denoiser's.  Not combinable with clipping: a clipped moments pass does not exist."""
+    left at None come from trhip_temporal_moments_default_params; `demodulate` must be the denoiser's.  Not combinable with clipping: a clipped moments pass does not exist.
+
+    `accumulate_motion` / `accumulate_motion_device` (a plain accumulator only): `accumulate` for a scene whose rigid bodies moved between the frames — with the frame's id
+    plane, a body per primitive and a prev_from_cur matrix per body each pixel's surface is carried back to where its body was before the history is looked up
+    (trhip_temporal_motion; docs/design/20-motion.md).  The history arrays are `accumulate`'s; with no table and no matrices the result is `accumulate`'s bit for bit."""
 
     def __init__(self, max_history: Optional[float] = None, sigma_normal: Optional[float] = None, sigma_plane: Optional[float] = None, min_coverage: Optional[float] = None,
                  clip_gamma: Optional[float] = None, clip_radius: Optional[int] = None, moments: bool = False, spatial_below: Optional[float] = None, demodulate: bool = True,
@@ -1550,6 +1654,58 @@ class TemporalAccumulator:
         ctx.check(_ffi.lib().trhip_temporal_moments_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), C.c_void_p(d_history) if d_history else None,
                                                            C.c_void_p(d_moments) if d_moments else None, int(width), int(height), C.byref(mp), C.c_void_p(d_out), C.c_void_p(d_out_history),
                                                            C.c_void_p(d_out_moments), C.c_void_p(d_out_variance), C.byref(st)))
+        self.stats = st
+
+    def _motion_params_for(self, prev_camera, n_prims: int, n_bodies: int) -> _ffi.TemporalMotionParams:
+        if self.clip_params is not None or self.moments_params is not None:
+            raise TraceHipError("TemporalAccumulator: accumulate_motion needs a plain accumulator (there is no clipped or moments variant of trhip_temporal_motion)")
+        base, mp = self._params_for(prev_camera), _ffi.TemporalMotionParams()
+        mp.prev_world_to_pixel[:] = list(base.prev_world_to_pixel)
+        mp.max_history, mp.sigma_normal, mp.sigma_plane, mp.min_coverage = base.max_history, base.sigma_normal, base.sigma_plane, base.min_coverage
+        mp.n_prims, mp.n_bodies = int(n_prims), int(n_bodies)
+        return mp
+
+    @staticmethod
+    def prev_from_cur(motion) -> np.ndarray:
+        """The (3, 4) Float32 matrix trhip_temporal_motion wants for a body that `motion` (a Transformation) carried from the previous frame's pose to this one: the first
+        three rows of its inv_m, each entry rounded to Float32 once."""
+        return np.ascontiguousarray(np.asarray(motion.inv_m, np.float64)[:3, :4], dtype=np.float32)
+
+    def accumulate_motion(self, xyzw: np.ndarray, planes: np.ndarray, history: Optional[np.ndarray], ids: np.ndarray, body_of_prim: Optional[np.ndarray],
+                          bodies: Optional[np.ndarray], prev_camera, ctx: Optional[_ffi.Context] = None):
+        """`accumulate` for a scene with moving rigid bodies (trhip_temporal_motion; docs/design/20-motion.md).  ids: (H, W) of _ffi.AOV_ID_DTYPE, this frame's
+        AOVIntegrator.ids; body_of_prim: uint32 per ordered-primitive slot (FlatScene.body_table) or None; bodies: (n_bodies, 3, 4) prev_from_cur matrices or None.
+        Returns (xyzw, history) of this frame."""
+        xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
+        if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
+            raise TraceHipError(f"accumulate_motion: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
+        if history is not None:
+            history = _ffi.f32(history)
+            if history.shape != planes.shape:
+                raise TraceHipError(f"accumulate_motion: history must be {planes.shape} like planes, not {history.shape}")
+        ids = np.ascontiguousarray(ids)
+        h, w = xyzw.shape[:2]
+        if ids.nbytes != h * w * 16:
+            raise TraceHipError(f"accumulate_motion: ids must hold one 16-byte record per pixel, not {ids.nbytes} bytes for {h} x {w}")
+        table = None if body_of_prim is None else np.ascontiguousarray(body_of_prim, dtype=np.uint32).reshape(-1)
+        mats = None if bodies is None else _ffi.f32(bodies).reshape(-1, 12)
+        ctx = ctx or _ffi.default_context()
+        out, out_history, st = np.empty_like(xyzw), np.empty_like(planes), _ffi.Stats()
+        p = self._motion_params_for(prev_camera, 0 if table is None else table.size, 0 if mats is None else mats.shape[0])
+        ctx.check(_ffi.lib().trhip_temporal_motion(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(planes), _ffi.fptr(history) if history is not None else None, ids.ctypes.data_as(C.c_void_p),
+                                                   _ffi.u32ptr(table) if table is not None else None, _ffi.fptr(mats) if mats is not None else None, w, h, C.byref(p), _ffi.fptr(out),
+                                                   _ffi.fptr(out_history), C.byref(st)))
+        self.stats = st
+        return out, out_history
+
+    def accumulate_motion_device(self, d_xyzw: int, d_planes: int, d_history: Optional[int], d_ids: int, d_body_of_prim: Optional[int], n_prims: int, d_bodies: Optional[int],
+                                 n_bodies: int, width: int, height: int, prev_camera, d_out: int, d_out_history: int, ctx: Optional[_ffi.Context] = None) -> None:
+        """The same on device pointers (d_out may equal d_xyzw; d_history, d_body_of_prim and d_bodies may be None); nothing is copied to the host."""
+        ctx = ctx or _ffi.default_context()
+        st, p = _ffi.Stats(), self._motion_params_for(prev_camera, n_prims if d_body_of_prim else 0, n_bodies if d_bodies else 0)
+        ctx.check(_ffi.lib().trhip_temporal_motion_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), C.c_void_p(d_history) if d_history else None, C.c_void_p(d_ids),
+                                                          C.c_void_p(d_body_of_prim) if d_body_of_prim else None, C.c_void_p(d_bodies) if d_bodies else None, int(width), int(height),
+                                                          C.byref(p), C.c_void_p(d_out), C.c_void_p(d_out_history), C.byref(st)))
         self.stats = st
 
     def accumulate_device(self, d_xyzw: int, d_planes: int, d_history: Optional[int], width: int, height: int, prev_camera, d_out: int, d_out_history: int,
@@ -1682,7 +1838,13 @@ class PreviewSession:
     not consulted, the TemporalUpsampler's are): frame k traces the path frame and its planes through the low camera shifted by `jitter_for(k, factor)`, the full-size
     planes with `guide_spp`, upscales and blends into a FULL-SIZE history through the previous full-size camera in one pass (trhip_temporal_upsample;
     docs/design/19-temporal-upsample.md) and filters the result with the full-size planes.  Not combinable with variance_guided=True or a clipping / moments accumulator.
-    With None, the default, the session makes the calls described above."""
+    With None, the default, the session makes the calls described above.
+    `render(camera, motion={...})` / `render_display(camera, motion={...})`: a frame of a scene whose rigid bodies moved (docs/design/20-motion.md).  The caller has
+    assigned the moved scene (Scene.moved) to `session.scene`; the dict maps top-level indices of scene.aggregate.primitives to the Transformation that carried that body
+    from the previous frame's pose to this one.  The frame then also draws the id plane (trhip_render_aov_ids) and reprojects through trhip_temporal_motion, so a moving
+    body keeps its history; an empty dict runs the same two calls with every pixel static.  With motion=None, the default, the session makes exactly the calls described
+    above and draws no id plane — a body that moved then restarts its history every frame.  A motion frame needs the plain session: no upscaler, variance_guided,
+    temporal_upsample, and no clipping or moments accumulator.  The scene's top-level structure and primitive count must be the previous frame's (else: reset())."""
 
     def __init__(self, scene: Scene, sampler: SeededSampler, max_depth: int, denoiser: Optional["Denoiser"] = None, temporal: Optional[TemporalAccumulator] = None,
                  variance_guided: bool = False, upscaler: Optional["Upscaler"] = None, factor=2, guide_spp: Optional[int] = None, display: Optional["Display"] = None,
@@ -1713,6 +1875,8 @@ class PreviewSession:
         self._size = None
         self._buffers = None     # film, planes, accumulated film, history x 2
         self._prev_matrix = None  # world_to_pixel of the camera whose history is held; None: no history
+        self._prev_structure = None  # top_level_counts of the scene whose history is held (motion frames compare it)
+        self._motion_buffers = None  # motion frames: the id plane, the body table, the body matrices
         self.render_stats = None  # (path, aov, temporal, denoise) Stats of the last render()
 
     def reset(self) -> None:
@@ -1725,6 +1889,9 @@ class PreviewSession:
         for b in self._buffers or ():
             b.free()
         self._buffers, self._size, self._prev_matrix = None, None, None
+        for b in self._motion_buffers or ():
+            b.free()
+        self._motion_buffers = None
         for b in self._up_buffers or ():
             b.free()
         self._up_buffers, self._up_size = None, None
@@ -1735,17 +1902,17 @@ class PreviewSession:
             b.free()
         self._display_buffers, self._display_size = None, None
 
-    def render(self, camera: PerspectiveCamera, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
-        """The next frame through `camera`; returns xyzw (H, W, 4), ready for film.set_xyzw / save."""
-        d_out, (h, w), _ = self._render_device(camera, ctx)
+    def render(self, camera: PerspectiveCamera, ctx: Optional[_ffi.Context] = None, motion=None) -> np.ndarray:
+        """The next frame through `camera`; returns xyzw (H, W, 4), ready for film.set_xyzw / save.  `motion`: see the class text."""
+        d_out, (h, w), _ = self._render_device(camera, ctx, motion)
         return d_out.to_host(np.float32, (h, w, 4))
 
-    def render_display(self, camera: PerspectiveCamera, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
+    def render_display(self, camera: PerspectiveCamera, ctx: Optional[_ffi.Context] = None, motion=None) -> np.ndarray:
         """The next frame through `camera`, rendered exactly as `render` renders it and encoded by the session's Display with scale = camera.film.scale; returns uint8
         (H, W, 4).  Only these bytes leave the device."""
         if self.display is None:
             raise TraceHipError("PreviewSession.render_display: the session was constructed without display=Display(...)")
-        d_out, (h, w), ctx = self._render_device(camera, ctx)
+        d_out, (h, w), ctx = self._render_device(camera, ctx, motion)
         if self._display_size != (h, w):
             for b in self._display_buffers or ():
                 b.free()
@@ -1755,9 +1922,45 @@ class PreviewSession:
         self.render_stats = self.render_stats + (self.display.stats,)
         return d_rgba.to_host(np.uint8, (h, w, 4))
 
-    def _render_device(self, camera: PerspectiveCamera, ctx: Optional[_ffi.Context]):
+    def _check_motion(self, motion) -> None:
+        if not isinstance(motion, dict):
+            raise TraceHipError("PreviewSession: motion must be a dict {top-level primitive index: Transformation} or None")
+        if self.upscaler is not None and self.temporal_upsample is None:
+            raise TraceHipError("PreviewSession: motion cannot be combined with an upscaler (the low-resolution history has no motion-aware pass)")
+        if self.variance_guided:
+            raise TraceHipError("PreviewSession: motion cannot be combined with variance_guided=True (trhip_temporal_moments does not carry bodies back)")
+        if self.temporal_upsample is not None:
+            raise TraceHipError("PreviewSession: motion cannot be combined with temporal_upsample (trhip_temporal_upsample does not carry bodies back)")
+        if self.temporal.clip_params is not None or self.temporal.moments_params is not None:
+            raise TraceHipError("PreviewSession: motion cannot be combined with a clipping or moments TemporalAccumulator (the clipped variant with motion does not exist)")
+
+    def _motion_tables(self, flat, motion, h, w):
+        """(id plane, body table or None, matrices or None, n_prims, n_bodies) on the device for this frame's motion dict."""
+        keys = sorted(motion)
+        for k in keys:
+            if not (isinstance(k, (int, np.integer)) and 0 <= k < len(flat.top_counts)):
+                raise TraceHipError(f"PreviewSession: motion key {k!r} is no index into the {len(flat.top_counts)} top-level primitives of the scene")
+        old = self._motion_buffers or []
+        keep = bool(old) and old[0].nbytes == h * w * 16  # the id plane's buffer stays from frame to frame; the tables are this frame's
+        for b in old[1 if keep else 0:]:
+            b.free()
+        self._motion_buffers = [old[0] if keep else _ffi.DeviceBuffer(h * w * 16)]
+        if not keys:
+            return self._motion_buffers[0], None, None, 0, 0
+        body_of_top = [None] * len(flat.top_counts)
+        for i, k in enumerate(keys):
+            body_of_top[k] = i
+        table = flat.body_table(body_of_top)
+        mats = np.ascontiguousarray(np.stack([TemporalAccumulator.prev_from_cur(motion[k]) for k in keys]), dtype=np.float32)
+        self._motion_buffers += [_ffi.DeviceBuffer(table.nbytes).from_host(table), _ffi.DeviceBuffer(mats.nbytes).from_host(mats)]
+        return self._motion_buffers[0], self._motion_buffers[1], self._motion_buffers[2], table.size, len(keys)
+
+    def _render_device(self, camera: PerspectiveCamera, ctx: Optional[_ffi.Context], motion=None):
         """The frame of `render`, left on the device: (buffer, (H, W), context)."""
-        ctx = self.scene.flatten(ctx).ctx
+        if motion is not None:
+            self._check_motion(motion)
+        flat = self.scene.flatten(ctx)
+        ctx = flat.ctx
         if self.temporal_upsample is not None:
             return self._render_temporal_upsample(camera, ctx)
         hi_camera = camera
@@ -1773,12 +1976,25 @@ class PreviewSession:
         spp = self.sampler.samples_per_pixel
         sampler = SeededSampler(spp, seed=self.sampler.seed, sample_offset=self.sampler.sample_offset + self.frame * spp)
         path, aov = PathIntegrator(camera, sampler, self.max_depth), AOVIntegrator(camera, sampler)
+        structure = list(flat.top_counts)
+        if motion is not None:
+            if self._prev_matrix is not None and self._prev_structure is not None and structure != self._prev_structure:
+                raise TraceHipError("PreviewSession: the scene's top-level structure or primitive count differs from the previous frame's, so its bodies cannot be "
+                                    "matched with the history: call reset() before rendering it")
+            d_ids, d_table, d_bodies, n_prims, n_bodies = self._motion_tables(flat, motion, h, w)
         path.render(self.scene, ctx, device_out=d_film.ptr)
-        aov.render(self.scene, ctx, device_out=d_planes.ptr)
+        if motion is not None:
+            aov.render(self.scene, ctx, device_out=d_planes.ptr, device_ids=d_ids.ptr)
+        else:
+            aov.render(self.scene, ctx, device_out=d_planes.ptr)
         prev_matrix, matrix = self._prev_matrix, camera.world_to_pixel()
         had_history = prev_matrix is not None
         self._prev_matrix = None  # (until this frame's history is complete)
-        if self.variance_guided:
+        if motion is not None:
+            self.temporal.accumulate_motion_device(d_film.ptr, d_planes.ptr, d_prev.ptr if had_history else None, d_ids.ptr, d_table.ptr if d_table else None, n_prims,
+                                                   d_bodies.ptr if d_bodies else None, n_bodies, w, h, prev_matrix, d_acc.ptr, d_next.ptr, ctx)
+            self.denoiser.denoise_device((d_acc if had_history else d_film).ptr, d_planes.ptr, w, h, d_acc.ptr, ctx)
+        elif self.variance_guided:
             m_prev, m_next, d_var = self._buffers[5 + (self.frame & 1)], self._buffers[5 + ((self.frame & 1) ^ 1)], self._buffers[7]
             self.temporal.accumulate_moments_device(d_film.ptr, d_planes.ptr, d_prev.ptr if had_history else None, m_prev.ptr if had_history else None, w, h, prev_matrix, d_acc.ptr,
                                                     d_next.ptr, m_next.ptr, d_var.ptr, ctx)
@@ -1793,6 +2009,7 @@ class PreviewSession:
         else:
             out = d_acc, (h, w), ctx
         self._prev_matrix = matrix
+        self._prev_structure = structure
         self.frame += 1
         return out
 

@@ -407,6 +407,8 @@ include("TraceHIPUpscale.jl")
 include("TraceHIPDisplay.jl")
 # TemporalUpsampler (trhip_temporal_upsample) and jitter_for, likewise (tests/golden/julia_shim_temporal_upsample_calls.json)
 include("TraceHIPTemporalUpsample.jl")
+# aov_ids (trhip_render_aov_ids) and accumulate_motion (trhip_temporal_motion), likewise (tests/golden/julia_shim_motion_calls.json)
+include("TraceHIPMotion.jl")
 
 # SPPMIntegrator (integrators/sppm.jl:132-173) on the device: trhip_render_sppm returns the film after set_image!
 # (film.jl:195-202).  `seed` selects the seeded stream of the camera pass (the reference draws from the global RNG there).
