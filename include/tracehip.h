@@ -709,7 +709,8 @@ int trhip_render_aov_ids_device(trhip_ctx* ctx, const trhip_scene* scene, const 
  * and n' the same without the last column, not renormalised; p' or n' not finite: no history.  p' is projected through prev_world_to_pixel, and n', p' stand for n, p in both
  * tap tests.  Blend, cap, the non-finite fallback and out_xyzw as in trhip_temporal.  out_history stores the CURRENT n and p: the next frame's previous world.
  * For ANY bit content of ids and body_of_prim the kernel reads only inside the three arrays: every index is range-checked before it addresses anything.
- * Shadows and reflections that a moving body drags over other surfaces are not re-projected: they lag by the history length (docs/design/20-motion.md).
+ * Shadows and reflections that a moving body drags over other surfaces are not re-projected: they lag by the history length (docs/design/20-motion.md);
+ * trhip_temporal_clip_motion, below, clips them.
  * TRHIP_ERR_INVALID, in this order: params NULL; trhip_temporal's checks of the fields it shares, in its order; flags != 0; reserved != 0 (the parameter block first,
  * before any handle); then a null pointer (history, body_of_prim, bodies and stats excepted); a zero dimension; n_prims > 0 with body_of_prim NULL; n_bodies > 0 with
  * bodies NULL; out_history overlapping any input or out_xyzw.  out_xyzw may be xyzw.  TRHIP_ERR_UNSUPPORTED: the host variant's device copies (176 bytes per pixel, 4 per
@@ -733,6 +734,38 @@ int trhip_temporal_motion(trhip_ctx* ctx, const float* xyzw, const float* planes
 int trhip_temporal_motion_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_history, const void* d_ids, const void* d_body_of_prim,
                                  const void* d_bodies, uint32_t width, uint32_t height, const trhip_temporal_motion_params* params, void* d_out_xyzw, void* d_out_history,
                                  trhip_stats* stats);
+
+/* trhip_temporal_clip_motion: trhip_temporal_motion — its arguments in its order, its body carry, its memory-safety promise — with trhip_temporal_clip's variance clipping of
+ * the reprojected history colour, and a history length that is cut when a clip fires (docs/design/21-clip-motion.md is the specification).
+ *   The window statistics are trhip_temporal_clip's on the CURRENT frame's n, p, c (same visiting order, counting rule, lo and hi): no motion enters them.
+ *   p' and n' of trhip_temporal_motion project and validate the four taps.
+ *   After c_h = sc / sb: per channel c_h = (c_h < lo) ? lo : ((c_h > hi) ? hi : c_h); clipped = any of the six comparisons held; N_h = sN / sb;
+ *   if (clipped && clip_max_history < N_h) N_h = clip_max_history; then N1 = N_h + 1, the cap, the blend and the non-finite fallback of trhip_temporal.
+ *   out_history stores the CURRENT n and p.
+ * ids may be NULL when n_prims == 0: every pixel is then static, and the pass serves a static scene for its history shortening alone.
+ * Every pixel static and clip_max_history = +Inf: trhip_temporal_clip's output bit for bit.  clip_gamma = +Inf: trhip_temporal_motion's bit for bit, whatever
+ * clip_max_history is.  A NaN c_h is never "clipped".  clip_max_history = 0: a clipped pixel restarts (blend weight 1, N' = 1).
+ * TRHIP_ERR_INVALID, in this order: params NULL; trhip_temporal_motion's block checks on base, in its order; clip_gamma NaN or < 0; clip_radius not 1, 2 or 3;
+ * clip_max_history NaN or < 0; reserved2 != 0 (the parameter block first, before any handle); then trhip_temporal_motion's pointer, size and overlap checks, with ids
+ * NULL-able only when n_prims == 0.  out_xyzw may be xyzw: the window reads neighbours' film pixels, so the host variant gives the result a film of its own and the device
+ * variant writes through a film held by the context and copies, as trhip_temporal_clip does.  TRHIP_ERR_UNSUPPORTED: the host variant's device copies (192 bytes per
+ * pixel, 4 per primitive, 48 per body) do not fit in free HBM.  stats (may be NULL): ms_total, ms_film, launches_film = 1.
+ * trhip_temporal_clip_motion_default_params needs no context and no GPU: trhip_temporal_motion_default_params' base, clip_gamma 4, clip_radius 3 and the
+ * clip_max_history chosen by the sweep of profiles/r18/clip_motion.txt. */
+typedef struct {
+    trhip_temporal_motion_params base;
+    float clip_gamma;         /* >= 0; +Inf: no clipping */
+    uint32_t clip_radius;     /* 1, 2 or 3 */
+    float clip_max_history;   /* >= 0; +Inf: the history length is never cut */
+    uint32_t reserved2;       /* 0 */
+} trhip_temporal_clip_motion_params; /* 96 bytes */
+int trhip_temporal_clip_motion_default_params(trhip_temporal_clip_motion_params* out);
+int trhip_temporal_clip_motion(trhip_ctx* ctx, const float* xyzw, const float* planes, const float* history, const trhip_aov_id* ids, const uint32_t* body_of_prim,
+                               const float* bodies, uint32_t width, uint32_t height, const trhip_temporal_clip_motion_params* params, float* out_xyzw, float* out_history,
+                               trhip_stats* stats);
+int trhip_temporal_clip_motion_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_planes, const void* d_history, const void* d_ids, const void* d_body_of_prim,
+                                      const void* d_bodies, uint32_t width, uint32_t height, const trhip_temporal_clip_motion_params* params, void* d_out_xyzw,
+                                      void* d_out_history, trhip_stats* stats);
 
 /* SPPMIntegrator(camera, initial_search_radius, max_depth, n_iterations, photons_per_iteration)(scene)
  * (integrators/sppm.jl:108-173): per iteration a camera pass to the first diffuse vertex, a hash grid over the visible

@@ -241,6 +241,17 @@ class TemporalMotionParams(C.Structure):
     ]
 
 
+class TemporalClipMotionParams(C.Structure):
+    """trhip_temporal_clip_motion_params (96 bytes)"""
+    _fields_ = [
+        ("base", TemporalMotionParams),
+        ("clip_gamma", C.c_float),
+        ("clip_radius", C.c_uint32),
+        ("clip_max_history", C.c_float),
+        ("reserved2", C.c_uint32),
+    ]
+
+
 # trhip_aov_id, the record of the id plane (AOVIntegrator.ids)
 AOV_ID_DTYPE = np.dtype([("prim", np.int32), ("material", np.int32), ("t", np.float32), ("n_hit", np.uint32)])
 STATIC_BODY = 0xFFFFFFFF  # the conventional "no body" word of body_of_prim
@@ -349,6 +360,9 @@ SIGNATURES = {
     "trhip_temporal_motion_default_params": (C.c_int, [C.POINTER(TemporalMotionParams)]),
     "trhip_temporal_motion": (C.c_int, [_VP, _F, _F, _F, _VP, _U32, _F, C.c_uint32, C.c_uint32, C.POINTER(TemporalMotionParams), _F, _F, C.POINTER(Stats)]),
     "trhip_temporal_motion_device": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(TemporalMotionParams), _VP, _VP, C.POINTER(Stats)]),
+    "trhip_temporal_clip_motion_default_params": (C.c_int, [C.POINTER(TemporalClipMotionParams)]),
+    "trhip_temporal_clip_motion": (C.c_int, [_VP, _F, _F, _F, _VP, _U32, _F, C.c_uint32, C.c_uint32, C.POINTER(TemporalClipMotionParams), _F, _F, C.POINTER(Stats)]),
+    "trhip_temporal_clip_motion_device": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(TemporalClipMotionParams), _VP, _VP, C.POINTER(Stats)]),
     "trhip_render_sppm": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats)]),
     "trhip_render_sppm_ex": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats), C.c_uint32, SPPM_WRITE_FN, _VP]),
     "trhip_sppm_state": (C.c_int, [_VP, _F, _F, _F, C.POINTER(C.c_double), C.POINTER(C.c_int64), _F, _F, _F, C.POINTER(C.c_int64)]),

@@ -1535,13 +1535,27 @@ class TemporalAccumulator:
 
     `accumulate_motion` / `accumulate_motion_device` (a plain accumulator only): `accumulate` for a scene whose rigid bodies moved between the frames — with the frame's id
     plane, a body per primitive and a prev_from_cur matrix per body each pixel's surface is carried back to where its body was before the history is looked up
-    (trhip_temporal_motion; docs/design/20-motion.md).  The history arrays are `accumulate`'s; with no table and no matrices the result is `accumulate`'s bit for bit."""
+    (trhip_temporal_motion; docs/design/20-motion.md).  The history arrays are `accumulate`'s; with no table and no matrices the result is `accumulate`'s bit for bit.
+
+    `carry_bodies=True` (needs `clip_gamma`): the clipping accumulator whose every call goes through trhip_temporal_clip_motion (docs/design/21-clip-motion.md) —
+    `accumulate` / `accumulate_device` without an id plane (every pixel static), `accumulate_motion` / `accumulate_motion_device` with the tables —, so that a moving body
+    keeps its history AND the shadow it drags over static surfaces is cut back to the new frame's colours.  `clip_max_history` (default:
+    trhip_temporal_clip_motion_default_params'): a pixel whose history colour was clipped has its history length cut to this before the blend; inf never cuts it, and with
+    inf and no moving pixel the result is the clipping accumulator's bit for bit.  Not combinable with moments=True: a moments pass that carries bodies does not exist."""
 
     def __init__(self, max_history: Optional[float] = None, sigma_normal: Optional[float] = None, sigma_plane: Optional[float] = None, min_coverage: Optional[float] = None,
                  clip_gamma: Optional[float] = None, clip_radius: Optional[int] = None, moments: bool = False, spatial_below: Optional[float] = None, demodulate: bool = True,
-                 albedo_floor: Optional[float] = None):
+                 albedo_floor: Optional[float] = None, carry_bodies: bool = False, clip_max_history: Optional[float] = None):
         self.clip_params: Optional[_ffi.TemporalClipParams] = None
         self.moments_params: Optional[_ffi.TemporalMomentsParams] = None
+        self.clip_motion_params: Optional[_ffi.TemporalClipMotionParams] = None
+        if carry_bodies and moments:
+            raise TraceHipError("TemporalAccumulator: moments=True cannot be combined with carry_bodies=True (trhip_temporal_moments does not carry bodies back)")
+        if carry_bodies and clip_gamma is None:
+            raise TraceHipError("TemporalAccumulator: carry_bodies=True needs clip_gamma (it selects trhip_temporal_clip_motion; without clipping, accumulate_motion of a "
+                                "plain accumulator carries the bodies)")
+        if clip_max_history is not None and not carry_bodies:
+            raise TraceHipError("TemporalAccumulator: clip_max_history belongs to carry_bodies=True (trhip_temporal_clip_motion alone shortens the history)")
         if moments and (clip_gamma is not None or clip_radius is not None):
             raise TraceHipError("TemporalAccumulator: moments=True cannot be combined with clip_gamma / clip_radius (there is no clipped variant of trhip_temporal_moments)")
         if not moments and (spatial_below is not None or albedo_floor is not None):
@@ -1574,6 +1588,14 @@ class TemporalAccumulator:
                     raise TraceHipError(f"TemporalAccumulator: clip_radius must be 1, 2 or 3, not {clip_radius!r}")
                 cp.clip_radius = int(clip_radius)
             self.clip_params, p = cp, cp.base  # p is a view of cp.base: the fields set below land in the block that is passed
+            if carry_bodies:
+                cm = _ffi.TemporalClipMotionParams()
+                rc = _ffi.lib().trhip_temporal_clip_motion_default_params(C.byref(cm))
+                if rc:
+                    raise TraceHipError(f"trhip_temporal_clip_motion_default_params failed ({rc})")
+                if clip_max_history is not None:
+                    cm.clip_max_history = clip_max_history
+                self.clip_motion_params = cm  # gamma, radius and the base are taken from clip_params / params when a call is made
         for name, value in (("max_history", max_history), ("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane), ("min_coverage", min_coverage)):
             if value is not None:
                 setattr(p, name, value)
@@ -1595,9 +1617,20 @@ class TemporalAccumulator:
         cp.base = self._params_for(prev_camera)
         return cp
 
+    def _clip_motion_params_for(self, prev_camera, n_prims: int, n_bodies: int) -> _ffi.TemporalClipMotionParams:
+        base, cm = self._params_for(prev_camera), _ffi.TemporalClipMotionParams.from_buffer_copy(self.clip_motion_params)
+        mp = cm.base
+        mp.prev_world_to_pixel[:] = list(base.prev_world_to_pixel)
+        mp.max_history, mp.sigma_normal, mp.sigma_plane, mp.min_coverage = base.max_history, base.sigma_normal, base.sigma_plane, base.min_coverage
+        mp.n_prims, mp.n_bodies = int(n_prims), int(n_bodies)
+        cm.clip_gamma, cm.clip_radius = self.clip_params.clip_gamma, self.clip_params.clip_radius
+        return cm
+
     def accumulate(self, xyzw: np.ndarray, planes: np.ndarray, history: Optional[np.ndarray], prev_camera, ctx: Optional[_ffi.Context] = None):
         """xyzw: (H, W, 4) as PathIntegrator.render returns it; planes: (H, W, 3, 4) as AOVIntegrator.render(...).planes; history: the second result of the previous
         frame's call, or None.  Returns (xyzw, history) of this frame; the xyzw goes into Denoiser.denoise with the same planes."""
+        if self.clip_motion_params is not None:  # no id plane: every pixel is static
+            return self._accumulate_clip_motion("accumulate", xyzw, planes, history, None, None, None, prev_camera, ctx)
         xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
         if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
             raise TraceHipError(f"accumulate: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
@@ -1658,7 +1691,8 @@ class TemporalAccumulator:
 
     def _motion_params_for(self, prev_camera, n_prims: int, n_bodies: int) -> _ffi.TemporalMotionParams:
         if self.clip_params is not None or self.moments_params is not None:
-            raise TraceHipError("TemporalAccumulator: accumulate_motion needs a plain accumulator (there is no clipped or moments variant of trhip_temporal_motion)")
+            raise TraceHipError("TemporalAccumulator: accumulate_motion needs a plain accumulator, or a clipping one built with carry_bodies=True (there is no moments "
+                                "variant of trhip_temporal_motion, and a clipping accumulator without carry_bodies goes through trhip_temporal_clip)")
         base, mp = self._params_for(prev_camera), _ffi.TemporalMotionParams()
         mp.prev_world_to_pixel[:] = list(base.prev_world_to_pixel)
         mp.max_history, mp.sigma_normal, mp.sigma_plane, mp.min_coverage = base.max_history, base.sigma_normal, base.sigma_plane, base.min_coverage
@@ -1675,7 +1709,9 @@ class TemporalAccumulator:
                           bodies: Optional[np.ndarray], prev_camera, ctx: Optional[_ffi.Context] = None):
         """`accumulate` for a scene with moving rigid bodies (trhip_temporal_motion; docs/design/20-motion.md).  ids: (H, W) of _ffi.AOV_ID_DTYPE, this frame's
         AOVIntegrator.ids; body_of_prim: uint32 per ordered-primitive slot (FlatScene.body_table) or None; bodies: (n_bodies, 3, 4) prev_from_cur matrices or None.
-        Returns (xyzw, history) of this frame."""
+        Returns (xyzw, history) of this frame.  An accumulator built with carry_bodies=True makes the same call through trhip_temporal_clip_motion."""
+        if self.clip_motion_params is not None:
+            return self._accumulate_clip_motion("accumulate_motion", xyzw, planes, history, ids, body_of_prim, bodies, prev_camera, ctx)
         xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
         if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
             raise TraceHipError(f"accumulate_motion: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
@@ -1698,10 +1734,43 @@ class TemporalAccumulator:
         self.stats = st
         return out, out_history
 
+    def _accumulate_clip_motion(self, who, xyzw, planes, history, ids, body_of_prim, bodies, prev_camera, ctx):
+        """The host call of an accumulator built with carry_bodies=True (trhip_temporal_clip_motion); ids None: every pixel is static."""
+        xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
+        if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
+            raise TraceHipError(f"{who}: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
+        if history is not None:
+            history = _ffi.f32(history)
+            if history.shape != planes.shape:
+                raise TraceHipError(f"{who}: history must be {planes.shape} like planes, not {history.shape}")
+        h, w = xyzw.shape[:2]
+        if ids is not None:
+            ids = np.ascontiguousarray(ids)
+            if ids.nbytes != h * w * 16:
+                raise TraceHipError(f"{who}: ids must hold one 16-byte record per pixel, not {ids.nbytes} bytes for {h} x {w}")
+        table = None if body_of_prim is None or ids is None else np.ascontiguousarray(body_of_prim, dtype=np.uint32).reshape(-1)
+        mats = None if bodies is None or ids is None else _ffi.f32(bodies).reshape(-1, 12)
+        ctx = ctx or _ffi.default_context()
+        out, out_history, st = np.empty_like(xyzw), np.empty_like(planes), _ffi.Stats()
+        p = self._clip_motion_params_for(prev_camera, 0 if table is None else table.size, 0 if mats is None else mats.shape[0])
+        ctx.check(_ffi.lib().trhip_temporal_clip_motion(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(planes), _ffi.fptr(history) if history is not None else None,
+                                                        ids.ctypes.data_as(C.c_void_p) if ids is not None else None, _ffi.u32ptr(table) if table is not None else None,
+                                                        _ffi.fptr(mats) if mats is not None else None, w, h, C.byref(p), _ffi.fptr(out), _ffi.fptr(out_history), C.byref(st)))
+        self.stats = st
+        return out, out_history
+
     def accumulate_motion_device(self, d_xyzw: int, d_planes: int, d_history: Optional[int], d_ids: int, d_body_of_prim: Optional[int], n_prims: int, d_bodies: Optional[int],
                                  n_bodies: int, width: int, height: int, prev_camera, d_out: int, d_out_history: int, ctx: Optional[_ffi.Context] = None) -> None:
         """The same on device pointers (d_out may equal d_xyzw; d_history, d_body_of_prim and d_bodies may be None); nothing is copied to the host."""
         ctx = ctx or _ffi.default_context()
+        if self.clip_motion_params is not None:
+            st, p = _ffi.Stats(), self._clip_motion_params_for(prev_camera, n_prims if d_body_of_prim else 0, n_bodies if d_bodies else 0)
+            ctx.check(_ffi.lib().trhip_temporal_clip_motion_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), C.c_void_p(d_history) if d_history else None,
+                                                                   C.c_void_p(d_ids) if d_ids else None, C.c_void_p(d_body_of_prim) if d_body_of_prim else None,
+                                                                   C.c_void_p(d_bodies) if d_bodies else None, int(width), int(height), C.byref(p), C.c_void_p(d_out),
+                                                                   C.c_void_p(d_out_history), C.byref(st)))
+            self.stats = st
+            return
         st, p = _ffi.Stats(), self._motion_params_for(prev_camera, n_prims if d_body_of_prim else 0, n_bodies if d_bodies else 0)
         ctx.check(_ffi.lib().trhip_temporal_motion_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), C.c_void_p(d_history) if d_history else None, C.c_void_p(d_ids),
                                                           C.c_void_p(d_body_of_prim) if d_body_of_prim else None, C.c_void_p(d_bodies) if d_bodies else None, int(width), int(height),
@@ -1711,6 +1780,8 @@ class TemporalAccumulator:
     def accumulate_device(self, d_xyzw: int, d_planes: int, d_history: Optional[int], width: int, height: int, prev_camera, d_out: int, d_out_history: int,
                           ctx: Optional[_ffi.Context] = None) -> None:
         """The same on device pointers (d_out may equal d_xyzw, d_history may be None); nothing is copied to the host."""
+        if self.clip_motion_params is not None:  # no id plane: every pixel is static
+            return self.accumulate_motion_device(d_xyzw, d_planes, d_history, None, None, 0, None, 0, width, height, prev_camera, d_out, d_out_history, ctx)
         ctx = ctx or _ffi.default_context()
         st, clipped = _ffi.Stats(), self.clip_params is not None
         p = self._clip_params_for(prev_camera) if clipped else self._params_for(prev_camera)
@@ -1844,7 +1915,8 @@ class PreviewSession:
     from the previous frame's pose to this one.  The frame then also draws the id plane (trhip_render_aov_ids) and reprojects through trhip_temporal_motion, so a moving
     body keeps its history; an empty dict runs the same two calls with every pixel static.  With motion=None, the default, the session makes exactly the calls described
     above and draws no id plane — a body that moved then restarts its history every frame.  A motion frame needs the plain session: no upscaler, variance_guided,
-    temporal_upsample, and no clipping or moments accumulator.  The scene's top-level structure and primitive count must be the previous frame's (else: reset())."""
+    temporal_upsample, and no moments accumulator; a clipping accumulator serves when it was built with carry_bodies=True (trhip_temporal_clip_motion; docs/design/21-clip-motion.md:
+    the shadow a moving body drags over static surfaces is then cut back within a frame, buffers passed apart, no copy paid).  The scene's top-level structure and primitive count must be the previous frame's (else: reset())."""
 
     def __init__(self, scene: Scene, sampler: SeededSampler, max_depth: int, denoiser: Optional["Denoiser"] = None, temporal: Optional[TemporalAccumulator] = None,
                  variance_guided: bool = False, upscaler: Optional["Upscaler"] = None, factor=2, guide_spp: Optional[int] = None, display: Optional["Display"] = None,
@@ -1931,8 +2003,9 @@ class PreviewSession:
             raise TraceHipError("PreviewSession: motion cannot be combined with variance_guided=True (trhip_temporal_moments does not carry bodies back)")
         if self.temporal_upsample is not None:
             raise TraceHipError("PreviewSession: motion cannot be combined with temporal_upsample (trhip_temporal_upsample does not carry bodies back)")
-        if self.temporal.clip_params is not None or self.temporal.moments_params is not None:
-            raise TraceHipError("PreviewSession: motion cannot be combined with a clipping or moments TemporalAccumulator (the clipped variant with motion does not exist)")
+        if (self.temporal.clip_params is not None and self.temporal.clip_motion_params is None) or self.temporal.moments_params is not None:
+            raise TraceHipError("PreviewSession: motion cannot be combined with a clipping or moments TemporalAccumulator, unless the clipping one was built with "
+                                "carry_bodies=True (trhip_temporal_clip and trhip_temporal_moments do not carry bodies back)")
 
     def _motion_tables(self, flat, motion, h, w):
         """(id plane, body table or None, matrices or None, n_prims, n_bodies) on the device for this frame's motion dict."""

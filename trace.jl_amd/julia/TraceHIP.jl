@@ -409,6 +409,8 @@ include("TraceHIPDisplay.jl")
 include("TraceHIPTemporalUpsample.jl")
 # aov_ids (trhip_render_aov_ids) and accumulate_motion (trhip_temporal_motion), likewise (tests/golden/julia_shim_motion_calls.json)
 include("TraceHIPMotion.jl")
+# accumulate_clip_motion (trhip_temporal_clip_motion), likewise (tests/golden/julia_shim_clip_motion_calls.json)
+include("TraceHIPClipMotion.jl")
 
 # SPPMIntegrator (integrators/sppm.jl:132-173) on the device: trhip_render_sppm returns the film after set_image!
 # (film.jl:195-202).  `seed` selects the seeded stream of the camera pass (the reference draws from the global RNG there).
