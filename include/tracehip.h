@@ -767,6 +767,40 @@ int trhip_temporal_clip_motion_device(trhip_ctx* ctx, const void* d_xyzw, const 
                                       const void* d_bodies, uint32_t width, uint32_t height, const trhip_temporal_clip_motion_params* params, void* d_out_xyzw,
                                       void* d_out_history, trhip_stats* stats);
 
+/* trhip_temporal_upsample_motion: trhip_temporal_upsample — its arguments in its order, its images, layouts and stats — for a scene whose rigid bodies moved between the
+ * frames, with ids, body_of_prim, bodies of trhip_temporal_motion directly after history (docs/design/22-upsample-motion.md is the specification).
+ *   ids            height * width trhip_aov_id of the FULL-SIZE frame (only prim is read); may be NULL when n_prims == 0: every pixel is then static
+ *   body_of_prim   n_prims uint32 as in trhip_temporal_motion; may be NULL
+ *   bodies         n_bodies * 12 floats, prev_from_cur per body as in trhip_temporal_motion; may be NULL
+ * Step U of trhip_temporal_upsample (the upscale onto the full-size planes, the class m, the confidence kappa) is unchanged: the low frame and the full-size planes are this
+ * frame's.  A pixel that is no surface pixel is trhip_temporal_upsample's, and its id is not looked at.  A surface pixel is static or moving by trhip_temporal_motion's rule
+ * (each test before the next one's memory is touched); a static pixel keeps the bits of p and n, a moving one gets p' = A (p, 1) and n' = A n (no last column) by
+ * trhip_temporal_motion's two three-line products, and a non-finite component of either means no history.  p' is projected through prev_world_to_pixel, and n', p' stand
+ * for n, p in both tap tests; the Omega > 0 rule, the sums, the blend, the cap and the non-finite fallback are trhip_temporal_upsample's.  out_history stores the CURRENT
+ * n and p; out_mask is m + 4 where history was found.
+ * Every pixel static: trhip_temporal_upsample's three outputs bit for bit.  history NULL: trhip_upscale's film and mask bit for bit, whatever the bodies are.  Words 1 and 2
+ * of out_history and out_xyzw's .w never depend on the bodies.  For ANY bit content of ids and body_of_prim the kernel reads only inside its arrays.
+ * TRHIP_ERR_INVALID, in this order: params NULL; trhip_temporal_upsample's block checks on base, in its order; motion_flags != 0; reserved2 != 0 (the parameter block first,
+ * before any handle); then trhip_temporal_upsample's pointer, size and overlap checks with ids, body_of_prim and bodies counted among the inputs; n_prims > 0 with
+ * body_of_prim or ids NULL; n_bodies > 0 with bodies NULL.  TRHIP_ERR_UNSUPPORTED: the host variant's device copies (64 bytes per low pixel, 177 per full-size pixel, 4 per
+ * primitive, 48 per body) do not fit in free HBM.  stats (may be NULL): ms_total, ms_film, launches_film = 1.  The _device variant takes DEVICE pointers for all ten arrays
+ * and allocates nothing.  trhip_temporal_upsample_motion_default_params needs no context and no GPU: trhip_temporal_upsample_default_params' base, both counts 0. */
+typedef struct {
+    trhip_temporal_upsample_params base;
+    uint32_t n_prims;       /* entries of body_of_prim */
+    uint32_t n_bodies;      /* matrices in bodies */
+    uint32_t motion_flags;  /* 0 */
+    uint32_t reserved2;     /* 0 */
+} trhip_temporal_upsample_motion_params; /* 128 bytes */
+int trhip_temporal_upsample_motion_default_params(trhip_temporal_upsample_motion_params* out);
+int trhip_temporal_upsample_motion(trhip_ctx* ctx, const float* lo_xyzw, const float* lo_planes, uint32_t lo_width, uint32_t lo_height, const float* hi_planes,
+                                   const float* history, const trhip_aov_id* ids, const uint32_t* body_of_prim, const float* bodies, uint32_t width, uint32_t height,
+                                   const trhip_temporal_upsample_motion_params* params, float* out_xyzw, float* out_history, uint8_t* out_mask, trhip_stats* stats);
+int trhip_temporal_upsample_motion_device(trhip_ctx* ctx, const void* d_lo_xyzw, const void* d_lo_planes, uint32_t lo_width, uint32_t lo_height, const void* d_hi_planes,
+                                          const void* d_history, const void* d_ids, const void* d_body_of_prim, const void* d_bodies, uint32_t width, uint32_t height,
+                                          const trhip_temporal_upsample_motion_params* params, void* d_out_xyzw, void* d_out_history, void* d_out_mask,
+                                          trhip_stats* stats);
+
 /* SPPMIntegrator(camera, initial_search_radius, max_depth, n_iterations, photons_per_iteration)(scene)
  * (integrators/sppm.jl:108-173): per iteration a camera pass to the first diffuse vertex, a hash grid over the visible
  * points, a photon pass (Halton / radical_inverse, sampler/sampling.jl:43-60) and the Float64 pixel update; afterwards

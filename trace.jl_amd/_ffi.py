@@ -241,6 +241,17 @@ class TemporalMotionParams(C.Structure):
     ]
 
 
+class TemporalUpsampleMotionParams(C.Structure):
+    """trhip_temporal_upsample_motion_params (128 bytes)"""
+    _fields_ = [
+        ("base", TemporalUpsampleParams),
+        ("n_prims", C.c_uint32),
+        ("n_bodies", C.c_uint32),
+        ("motion_flags", C.c_uint32),
+        ("reserved2", C.c_uint32),
+    ]
+
+
 class TemporalClipMotionParams(C.Structure):
     """trhip_temporal_clip_motion_params (96 bytes)"""
     _fields_ = [
@@ -363,6 +374,11 @@ SIGNATURES = {
     "trhip_temporal_clip_motion_default_params": (C.c_int, [C.POINTER(TemporalClipMotionParams)]),
     "trhip_temporal_clip_motion": (C.c_int, [_VP, _F, _F, _F, _VP, _U32, _F, C.c_uint32, C.c_uint32, C.POINTER(TemporalClipMotionParams), _F, _F, C.POINTER(Stats)]),
     "trhip_temporal_clip_motion_device": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(TemporalClipMotionParams), _VP, _VP, C.POINTER(Stats)]),
+    "trhip_temporal_upsample_motion_default_params": (C.c_int, [C.POINTER(TemporalUpsampleMotionParams)]),
+    "trhip_temporal_upsample_motion": (C.c_int, [_VP, _F, _F, C.c_uint32, C.c_uint32, _F, _F, _VP, _U32, _F, C.c_uint32, C.c_uint32, C.POINTER(TemporalUpsampleMotionParams), _F, _F,
+                                                 C.POINTER(C.c_uint8), C.POINTER(Stats)]),
+    "trhip_temporal_upsample_motion_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32,
+                                                        C.POINTER(TemporalUpsampleMotionParams), _VP, _VP, _VP, C.POINTER(Stats)]),
     "trhip_render_sppm": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats)]),
     "trhip_render_sppm_ex": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats), C.c_uint32, SPPM_WRITE_FN, _VP]),
     "trhip_sppm_state": (C.c_int, [_VP, _F, _F, _F, C.POINTER(C.c_double), C.POINTER(C.c_int64), _F, _F, _F, C.POINTER(C.c_int64)]),

@@ -1797,13 +1797,17 @@ class TemporalUpsampler:
     docs/design/19-temporal-upsample.md): each full-size pixel trusts the new frame in proportion to how directly a low sample observed it.  Fields left at None come from
     trhip_temporal_upsample_default_params.  The history is a (H, W, 3, 4) array in TemporalAccumulator's layout whose word 0 holds (c.rgb, Omega), Omega an accumulated
     weight.  `jitter`: "grid" (factor 2 only: four offsets of a quarter low pixel that put every full-size pixel centre on a low pixel centre once in four frames),
-    "halton" (bases 2 and 3, any factor) or None.  `accumulate` returns (xyzw, history, mask): mask is Upscaler's class + 4 where history was found."""
+    "halton" (bases 2 and 3, any factor) or None.  `accumulate` returns (xyzw, history, mask): mask is Upscaler's class + 4 where history was found.
+
+    `carry_bodies=True`: every call goes through trhip_temporal_upsample_motion (docs/design/22-upsample-motion.md) — `accumulate` / `accumulate_device` without an id
+    plane (every pixel static: trhip_temporal_upsample's bits), `accumulate_motion` / `accumulate_motion_device` with the FULL-SIZE frame's id plane, a body per primitive
+    and a prev_from_cur matrix per body, so that a moving body's surface is carried back to where it was before the full-size history is looked up."""
 
     GRID = ((0.25, 0.25), (-0.25, -0.25), (-0.25, 0.25), (0.25, -0.25))
 
     def __init__(self, radius: Optional[int] = None, max_history: Optional[float] = None, sigma_normal: Optional[float] = None, sigma_plane: Optional[float] = None,
                  guide_sigma_normal: Optional[float] = None, guide_sigma_plane: Optional[float] = None, confidence_floor: Optional[float] = None,
-                 confidence_sharpness: Optional[float] = None, min_coverage: Optional[float] = None, jitter: Optional[str] = "grid"):
+                 confidence_sharpness: Optional[float] = None, min_coverage: Optional[float] = None, jitter: Optional[str] = "grid", carry_bodies: bool = False):
         if jitter not in ("grid", "halton", None):
             raise TraceHipError(f"TemporalUpsampler: jitter must be 'grid', 'halton' or None, not {jitter!r}")
         p = _ffi.TemporalUpsampleParams()
@@ -1820,6 +1824,7 @@ class TemporalUpsampler:
             if value is not None:
                 setattr(p, name, value)
         self.params, self.jitter = p, jitter
+        self.carry_bodies = bool(carry_bodies)
         self.stats: Optional[_ffi.Stats] = None
 
     def jitter_for(self, frame: int, factor=2):
@@ -1857,10 +1862,68 @@ class TemporalUpsampler:
             p.prev_world_to_pixel[:] = w2p.reshape(-1).tolist()
         return p
 
+    def _require_carry_bodies(self) -> None:
+        if not self.carry_bodies:
+            raise TraceHipError("TemporalUpsampler: accumulate_motion needs an upsampler built with carry_bodies=True (trhip_temporal_upsample does not carry bodies back)")
+
+    def _motion_params_for(self, pixel_map, prev_camera, n_prims: int, n_bodies: int) -> _ffi.TemporalUpsampleMotionParams:
+        self._require_carry_bodies()
+        mp = _ffi.TemporalUpsampleMotionParams()
+        mp.base = self._params_for(pixel_map, prev_camera)
+        mp.n_prims, mp.n_bodies = int(n_prims), int(n_bodies)
+        return mp
+
+    def accumulate_motion(self, lo_xyzw: np.ndarray, lo_planes: np.ndarray, hi_planes: np.ndarray, history: Optional[np.ndarray], ids: Optional[np.ndarray],
+                          body_of_prim: Optional[np.ndarray], bodies: Optional[np.ndarray], pixel_map, prev_camera, ctx: Optional[_ffi.Context] = None):
+        """`accumulate` for a scene with moving rigid bodies (trhip_temporal_upsample_motion; docs/design/22-upsample-motion.md).  ids: (H, W) of _ffi.AOV_ID_DTYPE, the
+        FULL-SIZE frame's AOVIntegrator.ids, or None (every pixel static); body_of_prim: uint32 per ordered-primitive slot (FlatScene.body_table) or None; bodies:
+        (n_bodies, 3, 4) prev_from_cur matrices or None.  Returns (xyzw, history, mask) of this frame."""
+        self._require_carry_bodies()
+        lo_xyzw, lo_planes, hi_planes = _ffi.f32(lo_xyzw), _ffi.f32(lo_planes), _ffi.f32(hi_planes)
+        if lo_xyzw.ndim != 3 or lo_xyzw.shape[2] != 4 or lo_planes.shape != lo_xyzw.shape[:2] + (3, 4) or hi_planes.ndim != 4 or hi_planes.shape[2:] != (3, 4):
+            raise TraceHipError(f"accumulate_motion: lo_xyzw must be (h, w, 4), lo_planes (h, w, 3, 4) and hi_planes (H, W, 3, 4), not {lo_xyzw.shape}, {lo_planes.shape} and "
+                                f"{hi_planes.shape}")
+        if history is not None:
+            history = _ffi.f32(history)
+            if history.shape != hi_planes.shape:
+                raise TraceHipError(f"accumulate_motion: history must be {hi_planes.shape} like hi_planes, not {history.shape}")
+        (lh, lw), (h, w) = lo_xyzw.shape[:2], hi_planes.shape[:2]
+        if ids is not None:
+            ids = np.ascontiguousarray(ids)
+            if ids.nbytes != h * w * 16:
+                raise TraceHipError(f"accumulate_motion: ids must hold one 16-byte record per FULL-SIZE pixel, not {ids.nbytes} bytes for {h} x {w}")
+        table = None if body_of_prim is None or ids is None else np.ascontiguousarray(body_of_prim, dtype=np.uint32).reshape(-1)
+        mats = None if bodies is None or ids is None else _ffi.f32(bodies).reshape(-1, 12)
+        p = self._motion_params_for(pixel_map, prev_camera, 0 if table is None else table.size, 0 if mats is None else mats.shape[0])
+        ctx = ctx or _ffi.default_context()
+        out, out_history, mask, st = np.empty((h, w, 4), np.float32), np.empty((h, w, 3, 4), np.float32), np.empty((h, w), np.uint8), _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_temporal_upsample_motion(ctx._h, _ffi.fptr(lo_xyzw), _ffi.fptr(lo_planes), lw, lh, _ffi.fptr(hi_planes),
+                                                            _ffi.fptr(history) if history is not None else None, ids.ctypes.data_as(C.c_void_p) if ids is not None else None,
+                                                            _ffi.u32ptr(table) if table is not None else None, _ffi.fptr(mats) if mats is not None else None, w, h, C.byref(p),
+                                                            _ffi.fptr(out), _ffi.fptr(out_history), mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st)))
+        self.stats = st
+        return out, out_history, mask
+
+    def accumulate_motion_device(self, d_lo_xyzw: int, d_lo_planes: int, lo_width: int, lo_height: int, d_hi_planes: int, d_history: Optional[int], d_ids: Optional[int],
+                                 d_body_of_prim: Optional[int], n_prims: int, d_bodies: Optional[int], n_bodies: int, width: int, height: int, pixel_map, prev_camera,
+                                 d_out: int, d_out_history: int, d_out_mask: Optional[int] = None, ctx: Optional[_ffi.Context] = None) -> None:
+        """The same on device pointers (d_history, d_ids, d_body_of_prim, d_bodies and d_out_mask may be None); nothing is copied to the host."""
+        p = self._motion_params_for(pixel_map, prev_camera, n_prims if d_body_of_prim and d_ids else 0, n_bodies if d_bodies and d_ids else 0)
+        ctx = ctx or _ffi.default_context()
+        st = _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_temporal_upsample_motion_device(ctx._h, C.c_void_p(d_lo_xyzw), C.c_void_p(d_lo_planes), int(lo_width), int(lo_height), C.c_void_p(d_hi_planes),
+                                                                   C.c_void_p(d_history) if d_history else None, C.c_void_p(d_ids) if d_ids else None,
+                                                                   C.c_void_p(d_body_of_prim) if d_body_of_prim else None, C.c_void_p(d_bodies) if d_bodies else None, int(width),
+                                                                   int(height), C.byref(p), C.c_void_p(d_out), C.c_void_p(d_out_history),
+                                                                   C.c_void_p(d_out_mask) if d_out_mask else None, C.byref(st)))
+        self.stats = st
+
     def accumulate(self, lo_xyzw: np.ndarray, lo_planes: np.ndarray, hi_planes: np.ndarray, history: Optional[np.ndarray], pixel_map, prev_camera,
                    ctx: Optional[_ffi.Context] = None):
         """lo_xyzw (h, w, 4) and lo_planes (h, w, 3, 4) of this frame's jittered low camera, hi_planes (H, W, 3, 4) of the full-size one, history the second result of the
         previous frame's call, or None.  Returns (xyzw (H, W, 4), history (H, W, 3, 4), mask (H, W) uint8)."""
+        if self.carry_bodies:  # no id plane: every pixel is static
+            return self.accumulate_motion(lo_xyzw, lo_planes, hi_planes, history, None, None, None, pixel_map, prev_camera, ctx)
         lo_xyzw, lo_planes, hi_planes = _ffi.f32(lo_xyzw), _ffi.f32(lo_planes), _ffi.f32(hi_planes)
         if lo_xyzw.ndim != 3 or lo_xyzw.shape[2] != 4 or lo_planes.shape != lo_xyzw.shape[:2] + (3, 4) or hi_planes.ndim != 4 or hi_planes.shape[2:] != (3, 4):
             raise TraceHipError(f"accumulate: lo_xyzw must be (h, w, 4), lo_planes (h, w, 3, 4) and hi_planes (H, W, 3, 4), not {lo_xyzw.shape}, {lo_planes.shape} and {hi_planes.shape}")
@@ -1880,6 +1943,9 @@ class TemporalUpsampler:
     def accumulate_device(self, d_lo_xyzw: int, d_lo_planes: int, lo_width: int, lo_height: int, d_hi_planes: int, d_history: Optional[int], width: int, height: int, pixel_map,
                           prev_camera, d_out: int, d_out_history: int, d_out_mask: Optional[int] = None, ctx: Optional[_ffi.Context] = None) -> None:
         """The same on device pointers (d_history and d_out_mask may be None); nothing is copied to the host."""
+        if self.carry_bodies:  # no id plane: every pixel is static
+            return self.accumulate_motion_device(d_lo_xyzw, d_lo_planes, lo_width, lo_height, d_hi_planes, d_history, None, None, 0, None, 0, width, height, pixel_map,
+                                                 prev_camera, d_out, d_out_history, d_out_mask, ctx)
         p = self._params_for(pixel_map, prev_camera)
         ctx = ctx or _ffi.default_context()
         st = _ffi.Stats()
@@ -1915,7 +1981,8 @@ class PreviewSession:
     from the previous frame's pose to this one.  The frame then also draws the id plane (trhip_render_aov_ids) and reprojects through trhip_temporal_motion, so a moving
     body keeps its history; an empty dict runs the same two calls with every pixel static.  With motion=None, the default, the session makes exactly the calls described
     above and draws no id plane — a body that moved then restarts its history every frame.  A motion frame needs the plain session: no upscaler, variance_guided,
-    temporal_upsample, and no moments accumulator; a clipping accumulator serves when it was built with carry_bodies=True (trhip_temporal_clip_motion; docs/design/21-clip-motion.md:
+    and no moments accumulator; `temporal_upsample` serves when the TemporalUpsampler was built with carry_bodies=True (trhip_temporal_upsample_motion;
+    docs/design/22-upsample-motion.md: the id plane is drawn at full size with the guide sampler); a clipping accumulator serves when it was built with carry_bodies=True (trhip_temporal_clip_motion; docs/design/21-clip-motion.md:
     the shadow a moving body drags over static surfaces is then cut back within a frame, buffers passed apart, no copy paid).  The scene's top-level structure and primitive count must be the previous frame's (else: reset())."""
 
     def __init__(self, scene: Scene, sampler: SeededSampler, max_depth: int, denoiser: Optional["Denoiser"] = None, temporal: Optional[TemporalAccumulator] = None,
@@ -2002,7 +2069,10 @@ class PreviewSession:
         if self.variance_guided:
             raise TraceHipError("PreviewSession: motion cannot be combined with variance_guided=True (trhip_temporal_moments does not carry bodies back)")
         if self.temporal_upsample is not None:
-            raise TraceHipError("PreviewSession: motion cannot be combined with temporal_upsample (trhip_temporal_upsample does not carry bodies back)")
+            if not self.temporal_upsample.carry_bodies:
+                raise TraceHipError("PreviewSession: motion cannot be combined with temporal_upsample unless the TemporalUpsampler was built with carry_bodies=True "
+                                    "(trhip_temporal_upsample does not carry bodies back)")
+            return  # the accumulator is not used in this mode
         if (self.temporal.clip_params is not None and self.temporal.clip_motion_params is None) or self.temporal.moments_params is not None:
             raise TraceHipError("PreviewSession: motion cannot be combined with a clipping or moments TemporalAccumulator, unless the clipping one was built with "
                                 "carry_bodies=True (trhip_temporal_clip and trhip_temporal_moments do not carry bodies back)")
@@ -2035,7 +2105,7 @@ class PreviewSession:
         flat = self.scene.flatten(ctx)
         ctx = flat.ctx
         if self.temporal_upsample is not None:
-            return self._render_temporal_upsample(camera, ctx)
+            return self._render_temporal_upsample(camera, ctx, motion, flat)
         hi_camera = camera
         if self.upscaler is not None:
             camera = Upscaler.low_camera(hi_camera, self.factor)
@@ -2103,8 +2173,9 @@ class PreviewSession:
         self.render_stats = self.render_stats + (aov.stats, self.upscaler.stats)
         return d_out
 
-    def _render_temporal_upsample(self, hi_camera: PerspectiveCamera, ctx):
-        """The frame of the temporal-upsampling mode, left on the device: (buffer, (H, W), context)."""
+    def _render_temporal_upsample(self, hi_camera: PerspectiveCamera, ctx, motion=None, flat=None):
+        """The frame of the temporal-upsampling mode, left on the device: (buffer, (H, W), context).  With a motion dict (an upsampler built with carry_bodies=True) the
+        full-size planes and the full-size id plane are drawn in one call and the pass is trhip_temporal_upsample_motion; with None the calls are what they were."""
         tu = self.temporal_upsample
         lo_camera = Upscaler.low_camera(hi_camera, self.factor, jitter=tu.jitter_for(self.frame, self.factor))
         (hh, hw), (lh, lw) = hi_camera.film.size, lo_camera.film.size
@@ -2118,16 +2189,31 @@ class PreviewSession:
         sampler = SeededSampler(spp, seed=self.sampler.seed, sample_offset=self.sampler.sample_offset + self.frame * spp)
         guide = SeededSampler(spp if self.guide_spp is None else int(self.guide_spp), seed=sampler.seed, sample_offset=sampler.sample_offset)
         path, aov_lo, aov_hi = PathIntegrator(lo_camera, sampler, self.max_depth), AOVIntegrator(lo_camera, sampler), AOVIntegrator(hi_camera, guide)
+        structure = list(flat.top_counts) if flat is not None else None
+        if motion is not None:
+            if self._prev_matrix is not None and self._prev_structure is not None and structure != self._prev_structure:
+                raise TraceHipError("PreviewSession: the scene's top-level structure or primitive count differs from the previous frame's, so its bodies cannot be "
+                                    "matched with the history: call reset() before rendering it")
+            d_ids, d_table, d_bodies, n_prims, n_bodies = self._motion_tables(flat, motion, hh, hw)
         path.render(self.scene, ctx, device_out=d_lo.ptr)
         aov_lo.render(self.scene, ctx, device_out=d_lo_planes.ptr)
-        aov_hi.render(self.scene, ctx, device_out=d_hi_planes.ptr)
+        if motion is not None:
+            aov_hi.render(self.scene, ctx, device_out=d_hi_planes.ptr, device_ids=d_ids.ptr)
+        else:
+            aov_hi.render(self.scene, ctx, device_out=d_hi_planes.ptr)
         prev_matrix, matrix = self._prev_matrix, hi_camera.world_to_pixel()
         self._prev_matrix = None  # (until this frame's history is complete)
-        tu.accumulate_device(d_lo.ptr, d_lo_planes.ptr, lw, lh, d_hi_planes.ptr, d_prev.ptr if prev_matrix is not None else None, hw, hh, Upscaler.pixel_map(hi_camera, lo_camera),
-                             prev_matrix, d_out.ptr, d_next.ptr, None, ctx)
+        if motion is not None:
+            tu.accumulate_motion_device(d_lo.ptr, d_lo_planes.ptr, lw, lh, d_hi_planes.ptr, d_prev.ptr if prev_matrix is not None else None, d_ids.ptr,
+                                        d_table.ptr if d_table else None, n_prims, d_bodies.ptr if d_bodies else None, n_bodies, hw, hh,
+                                        Upscaler.pixel_map(hi_camera, lo_camera), prev_matrix, d_out.ptr, d_next.ptr, None, ctx)
+        else:
+            tu.accumulate_device(d_lo.ptr, d_lo_planes.ptr, lw, lh, d_hi_planes.ptr, d_prev.ptr if prev_matrix is not None else None, hw, hh,
+                                 Upscaler.pixel_map(hi_camera, lo_camera), prev_matrix, d_out.ptr, d_next.ptr, None, ctx)
         self.denoiser.denoise_device(d_out.ptr, d_hi_planes.ptr, hw, hh, d_out.ptr, ctx)
         self.render_stats = (path.stats, aov_lo.stats, aov_hi.stats, tu.stats, self.denoiser.stats)
         self._prev_matrix = matrix
+        self._prev_structure = structure
         self.frame += 1
         return d_out, (hh, hw), ctx
 

@@ -148,7 +148,8 @@ struct trhip_ctx {
     int temporal_patch = 1; // trhip_temporal's lane-to-pixel mapping: 0 film order, 1 patches of 16 x 4 per wave, measured 11 % faster (option "temporal_patch", profiles/r11/temporal.txt)
     int denoise_var_lds = 3;  // bit i: iteration i (step 2^i, i < 2) of trhip_denoise_var runs the LDS-staged kernel (option "denoise_var_lds", profiles/r13/variance.txt)
     DevBuf up_in;      // trhip_upscale's host entry point: its copies of the five images (th_upscale.h; 64 B per low pixel, 65 per full-size pixel);
-                       // trhip_temporal_upsample's likewise (th_temporal_upsample.h; 64 B per low pixel, 161 per full-size pixel)
+                       // trhip_temporal_upsample's likewise (th_temporal_upsample.h; 64 B per low pixel, 161 per full-size pixel); trhip_temporal_upsample_motion's: the same and
+                       // the id plane, the body matrices and the body table (177 B per full-size pixel, 48 per body, 4 per primitive)
     DevBuf dp_work, dp_in;  // trhip_display: the 1 KiB metering histogram and a 16-byte state slot (th_display.h); the host entry point's copy of the film and its bytes (20 B per pixel)
     DevBuf cb_rc;      // one word: a host callback's return code, max-reduced over the ranks of a job (tu_sppm.hip)
     DevBuf ov8[2], fb_list[2], fb_counts[2];  // k_trace8: global stack levels, fallback lists + their counters / work cursors ([closest | any])

@@ -411,6 +411,8 @@ include("TraceHIPTemporalUpsample.jl")
 include("TraceHIPMotion.jl")
 # accumulate_clip_motion (trhip_temporal_clip_motion), likewise (tests/golden/julia_shim_clip_motion_calls.json)
 include("TraceHIPClipMotion.jl")
+# accumulate_upsample_motion (trhip_temporal_upsample_motion), likewise (tests/golden/julia_shim_upsample_motion_calls.json)
+include("TraceHIPUpsampleMotion.jl")
 
 # SPPMIntegrator (integrators/sppm.jl:132-173) on the device: trhip_render_sppm returns the film after set_image!
 # (film.jl:195-202).  `seed` selects the seeded stream of the camera pass (the reference draws from the global RNG there).
