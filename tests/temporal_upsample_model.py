@@ -48,15 +48,16 @@ def sharp(d, rho):
     return np.where(g > 0, g, F(0.0)).astype(F)
 
 
-def surface_and_confidence(lo_xyzw, lo_planes, hi_planes, prm):
-    """(surface, n, p, kmax) of every full-size pixel: H2 of 17-upscale.md with the flags off, and the largest e = ((gy gx) wn) wp over the accepted guided taps."""
+def surface_and_confidence(lo_xyzw, lo_planes, hi_planes, prm, records=None):
+    """(surface, n, p, kmax) of every full-size pixel: H2 of 17-upscale.md with the flags off, and the largest e = ((gy gx) wn) wp over the accepted guided taps.
+    `records`: what um.low_records returns for these frames and upscale_params(prm), given instead of computed."""
     up = upscale_params(prm)
     PH = np.ascontiguousarray(hi_planes, F)
     h, w = PH.shape[:2]
     lh, lw = lo_xyzw.shape[:2]
     R, rho = prm.radius, F(prm.confidence_sharpness)
     with np.errstate(all="ignore"):
-        s_q, n_q, p_q, _, _, _ = um.low_records(np.ascontiguousarray(lo_xyzw, F), np.ascontiguousarray(lo_planes, F), up)
+        s_q, n_q, p_q, _, _, _ = um.low_records(np.ascontiguousarray(lo_xyzw, F), np.ascontiguousarray(lo_planes, F), up) if records is None else records
         A, H = PH[..., 0, 3], PH[..., 1, 3]
         surface = (H > 0) & (H >= F(prm.min_coverage) * A)
         iH = F(1.0) / H
@@ -96,8 +97,9 @@ def accumulate(lo_xyzw, lo_planes, hi_planes, history, M, prm, tally=None):
     h, w = PH.shape[:2]
     A = PH[..., 0, 3]
     # U: colour and class are the upscaler's
-    up_out, m, c = um.upscale(lo_xyzw, lo_planes, PH, upscale_params(prm), want_colour=True)
-    surface, n, p, kmax = surface_and_confidence(lo_xyzw, lo_planes, PH, prm)
+    records = um.low_records(np.ascontiguousarray(lo_xyzw, F), np.ascontiguousarray(lo_planes, F), upscale_params(prm))  # once for both halves of part U
+    up_out, m, c = um.upscale(lo_xyzw, lo_planes, PH, upscale_params(prm), want_colour=True, records=records)
+    surface, n, p, kmax = surface_and_confidence(lo_xyzw, lo_planes, PH, prm, records)
     assert not (np.isin(m, (1, 3)) & ~surface).any() and not ((m == 2) & surface).any(), "H2 here is not the upscaler's"
     assert not ((m == 1) & ~(kmax >= 0)).any()
     k0 = F(prm.confidence_floor)
@@ -191,17 +193,20 @@ def synthetic_matrix(hh, hw, lo_from_hi):
     return np.array([[m00, 0.0, 0.0, m03], [0.0, m11, 0.0, -1.0], [0.0, 0.0, 0.0625, 1.0]], F)
 
 
-def synthetic(hh, hw, lh, lw, seed):
-    """(lo_xyzw, lo_planes, hi_planes, lo_from_hi, history, M): um.synthetic_pair's frames with a block of 4 x 4 low pixels of weight 0 (full-size surface pixels nothing
+def synthetic(hh, hw, lh, lw, seed, lo_from_hi=None):
+    """`lo_from_hi`: an explicit map, handed to um.synthetic_pair (the block of weight 0 then lies in um.low_window); without it, today's arrays bit for bit.
+    (lo_xyzw, lo_planes, hi_planes, lo_from_hi, history, M): um.synthetic_pair's frames with a block of 4 x 4 low pixels of weight 0 (full-size surface pixels nothing
     is found for), groups of full-size pixels of exactly known position — behind the previous camera, on its plane, at positions that overflow, at exact integer positions —
     and as history what the pass makes of the pair of the next seed, given weights of 0.25 .. 12 (the cap of the tests is 8) and poisoned: NaN, +Inf and -Inf colours, weights
     of 0, -1, NaN and +Inf, a flag that is not 1."""
-    lo_xyzw, lo_planes, hi_planes, lo_from_hi = um.synthetic_pair(hh, hw, lh, lw, seed)
+    wy, wx, wh, ww = um.low_window(hh, hw, lh, lw, lo_from_hi)
+    given = lo_from_hi
+    lo_xyzw, lo_planes, hi_planes, lo_from_hi = um.synthetic_pair(hh, hw, lh, lw, seed, given)
     M = synthetic_matrix(hh, hw, lo_from_hi)
     rng = np.random.default_rng(seed + 77)
-    big = lh >= 12 and lw >= 16 and hh >= 16 and hw >= 16
+    big = wh >= 12 and ww >= 16 and hh >= 16 and hw >= 16
     if big:
-        y0, x0 = lh - 7, lw // 2 + 2
+        y0, x0 = wy + wh - 7, wx + ww // 2 + 2
         lo_xyzw[y0:y0 + 4, x0:x0 + 4, 3] = F(0.0)
         cells = [(y, x) for y in range(2, hh - 2) for x in range(2, hw - 2)]
         picks = [cells[k] for k in rng.choice(len(cells), 40, replace=False)]
@@ -218,7 +223,7 @@ def synthetic(hh, hw, lh, lw, seed):
             else:
                 p = [float(1 + r % 3), float(1 + r % 2), 0.0]        # ... and y position m11 (1 + r % 2) - 1
             set_exact_pixel(hi_planes, y, x, p)
-    lo2, lp2, hp2, _ = um.synthetic_pair(hh, hw, lh, lw, seed + 1)
+    lo2, lp2, hp2, _ = um.synthetic_pair(hh, hw, lh, lw, seed + 1, given)
     _, Hs, _ = accumulate(lo2, lp2, hp2, None, None, Params(lo_from_hi))
     was_surface = Hs[..., 1, 3] == 1
     Hs[..., 0, 3] = np.where(was_surface, rng.integers(1, 49, (hh, hw)).astype(F) * F(0.25), F(0.0))

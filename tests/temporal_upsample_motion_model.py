@@ -33,8 +33,9 @@ def accumulate(lo_xyzw, lo_planes, hi_planes, history, M, ids, body_of_prim, bod
     h, w = PH.shape[:2]
     A = PH[..., 0, 3]
     # U: colour and class are the upscaler's, surface, n, p and the confidence temporal_upsample_model's
-    up_out, m, c = um.upscale(lo_xyzw, lo_planes, PH, tum.upscale_params(prm), want_colour=True)
-    surface, n, p, kmax = tum.surface_and_confidence(lo_xyzw, lo_planes, PH, prm)
+    records = um.low_records(np.ascontiguousarray(lo_xyzw, F), np.ascontiguousarray(lo_planes, F), tum.upscale_params(prm))  # once for both halves of part U
+    up_out, m, c = um.upscale(lo_xyzw, lo_planes, PH, tum.upscale_params(prm), want_colour=True, records=records)
+    surface, n, p, kmax = tum.surface_and_confidence(lo_xyzw, lo_planes, PH, prm, records)
     k0 = F(prm.confidence_floor)
     kappa = np.where(m == 1, np.where(kmax > k0, kmax, k0), np.where(m == 3, k0, F(0.0))).astype(F)
     count("guided", m == 1), count("orphan", m == 3), count("unguided", m == 2), count("nothing", (m == 0) & ~surface), count("nothing_on_surface", (m == 0) & surface)
@@ -52,7 +53,7 @@ def accumulate(lo_xyzw, lo_planes, hi_planes, history, M, ids, body_of_prim, bod
             count("static_no_table" if body_of_prim is None or bodies is None else "static_by_index", surface & rest)
         count("moving", surface & moving)
         pr, nr, carried = p, n, np.ones((h, w), bool)
-        if moving.any():
+        if moving.any() and (history is not None or tally is not None):  # (without history p', n' are used by nothing but the tally)
             Ab = np.ascontiguousarray(bodies, F).reshape(-1, 3, 4)[body]
             pm, nm = mm.carry(Ab, p), mm.carry(Ab, n, point=False)
             pr = np.where(moving[..., None], pm, p).astype(F)  # a static pixel keeps its bits: no identity is applied
@@ -139,16 +140,21 @@ def synthetic_bodies():
     return mm.synthetic_bodies()
 
 
-def synthetic(hh, hw, lh, lw, seed):
-    """(lo_xyzw, lo_planes, hi_planes, lo_from_hi, history, M, ids, body_of_prim, bodies): temporal_upsample_model.synthetic's frames, history and matrix with
+def synthetic(hh, hw, lh, lw, seed, lo_from_hi=None):
+    """`lo_from_hi`: an explicit map, handed to temporal_upsample_model.synthetic; without it, today's arrays bit for bit.
+    (lo_xyzw, lo_planes, hi_planes, lo_from_hi, history, M, ids, body_of_prim, bodies): temporal_upsample_model.synthetic's frames, history and matrix with
     20-motion.md's garbage laid over them at FULL size — motion_model.synthetic's id plane and body table (prims from INT32_MIN to INT32_MAX, body words of every magnitude
     between n_bodies and 0xFFFFFFFF, random bits in the id words the pass does not read) and its six matrices, one of them infinite.  temporal_upsample_model's pixels of
     exactly known position stay static, so that its own branches (behind, overflow, integer positions) are taken as often as there.  Added here: NaN and +-Inf in the low
     film and in the history's colours, every 31st pixel in turn."""
-    lo_xyzw, lo_planes, hi_planes, lo_from_hi, Hs, M = tum.synthetic(hh, hw, lh, lw, seed)
+    lo_xyzw, lo_planes, hi_planes, lo_from_hi, Hs, M = tum.synthetic(hh, hw, lh, lw, seed, lo_from_hi)
     small = hh < 16 or hw < 16  # motion_model's generator is made for frames of some size: a small frame takes the window [8:8+hh, 8:8+hw] of its 37 x 29 id plane
     src = mm.synthetic(29, 37, seed) if small else mm.synthetic(hh, hw, seed)
-    ids, table, bodies = np.ascontiguousarray(src[3][8:8 + hh, 8:8 + hw] if small else src[3]).copy(), src[4], synthetic_bodies()
+    if small and (hh > 21 or hw > 29):  # a strip: the 37 x 29 id plane laid side by side
+        plane = np.tile(src[3], (-(-hh // 29), -(-hw // 37)))[:hh, :hw]
+    else:
+        plane = src[3][8:8 + hh, 8:8 + hw] if small else src[3]
+    ids, table, bodies = np.ascontiguousarray(plane).copy(), src[4], synthetic_bodies()
     exact = np.all(hi_planes[..., 0, :] == F([0.5, 0.5, 0.5, 1.0]), axis=-1) & np.all(hi_planes[..., 1, :] == F([0.0, 0.0, 1.0, 1.0]), axis=-1)
     prim = ids["prim"].astype(np.int64)
     to_static = exact & (prim >= 0) & (prim < N_MOVING_PRIMS)

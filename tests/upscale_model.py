@@ -186,21 +186,46 @@ def geometry(hh, hw, ys, xs):
     return n, p, albedo
 
 
-def synthetic_pair(hh, hw, lh, lw, seed):
+def low_window(hh, hw, lh, lw, lo_from_hi):
+    """(y0, x0, rows, columns): the part of the low image that the full-size image's positions fall on (H3 in Float64, clipped to the low image; rows or columns may be 0).
+    Without a map: the whole low image."""
+    if lo_from_hi is None:
+        return 0, 0, lh, lw
+    ax, bx, ay, by = (float(F(v)) for v in lo_from_hi)
+    x0, x1 = max(0, int(np.floor(bx))), min(lw, int(np.floor((hw - 1) * ax + bx)) + 2)
+    y0, y1 = max(0, int(np.floor(by))), min(lh, int(np.floor((hh - 1) * ay + by)) + 2)
+    return y0, x0, max(0, y1 - y0), max(0, x1 - x0)
+
+
+def synthetic_pair(hh, hw, lh, lw, seed, lo_from_hi=None):
     """(lo_xyzw, lo_planes, hi_planes, lo_from_hi): the analytic geometry of `geometry` evaluated at the pixel centres of both resolutions (full frames of one camera, so the
     guides agree), a noisy low colour, and the cases that drive every branch: a stripe one full-size pixel wide that falls between low pixel centres (orphans), misses, pixels
     under min_coverage = 0.5, non-positive W and A, NaN and +-Inf in a low colour, a low normal, a low position and a full-size plane, and two neighbouring low colours near
-    FLT_MAX whose guided sum overflows."""
+    FLT_MAX whose guided sum overflows.  `lo_from_hi` = (ax, bx, ay, by): an explicit map instead of the one the sizes give (tests/upsample_maps.py); the low guides are then
+    the geometry at (q - b) / a, and the planted low pixels sit in the part of the low image the full-size image falls on (`low_window`).  Without it the arrays are what
+    they always were, bit for bit."""
     rng = np.random.default_rng(seed)
-    ax, ay = lw / hw, lh / hh
-    lo_from_hi = (F(ax), F(1.5 * ax - 1.5), F(ay), F(1.5 * ay - 1.5))  # full frames whose 1-based pixels start at 1 (docs/design/17-upscale.md): -0.75 at 2 x, 0 at ratio 1
+    explicit = lo_from_hi is not None
+    wy, wx, wh, ww = low_window(hh, hw, lh, lw, lo_from_hi)
+    if explicit:
+        lo_from_hi = tuple(F(v) for v in lo_from_hi)
+        ax, bx, ay, by = (float(v) for v in lo_from_hi)
+    else:
+        ax, ay = lw / hw, lh / hh
+        bx, by = 1.5 * ax - 1.5, 1.5 * ay - 1.5
+        lo_from_hi = (F(ax), F(bx), F(ay), F(by))  # full frames whose 1-based pixels start at 1 (docs/design/17-upscale.md): -0.75 at 2 x, 0 at ratio 1
     ys, xs = np.mgrid[0:hh, 0:hw].astype(F)
     n_h, p_h, alb_h = geometry(hh, hw, ys, xs)
     lys, lxs = np.mgrid[0:lh, 0:lw].astype(F)
-    n_l, p_l, alb_l = geometry(hh, hw, ((lys + F(1.5)) / F(ay) - F(1.5)).astype(F), ((lxs + F(1.5)) / F(ax) - F(1.5)).astype(F))
+    if explicit:
+        n_l, p_l, alb_l = geometry(hh, hw, ((lys - F(by)) / F(ay)).astype(F), ((lxs - F(bx)) / F(ax)).astype(F))
+    else:
+        n_l, p_l, alb_l = geometry(hh, hw, ((lys + F(1.5)) / F(ay) - F(1.5)).astype(F), ((lxs + F(1.5)) / F(ax) - F(1.5)).astype(F))
     # the stripe: one full-size column on a plane of its own, between two low pixel centres (at ratio 1 there is no such column: any column then)
-    sx = next((x for x in range(hw // 5, hw) if 0.3 < ((x * ax + 1.5 * ax - 1.5) % 1.0) < 0.7), hw // 5)
-    n_h[:, sx], p_h[:, sx, 2] = np.array([0.0, 0.8, 0.6], F), p_h[:, sx, 2] - F(0.5)
+    between = (lambda x: x * ax + bx) if explicit else (lambda x: x * ax + 1.5 * ax - 1.5)
+    sx = next((x for x in range(hw // 5, hw) if 0.3 < (between(x) % 1.0) < 0.7), hw // 5)
+    if not explicit or hw >= 8:  # (a column image with a map keeps its guided pixels: the stripe would be all of it)
+        n_h[:, sx], p_h[:, sx, 2] = np.array([0.0, 0.8, 0.6], F), p_h[:, sx, 2] - F(0.5)
     A_h = rng.uniform(0.6, 1.4, (hh, hw)).astype(F)
     cover_h = np.ones((hh, hw), F)
     cover_h[rng.random((hh, hw)) < 0.06] = F(0.3)
@@ -215,26 +240,27 @@ def synthetic_pair(hh, hw, lh, lw, seed):
     cover_l[rng.random((lh, lw)) < 0.06] = F(0.3)
     cover_l[rng.random((lh, lw)) < 0.05] = F(0.75)
     miss_l = np.zeros((lh, lw), bool)
-    miss_l[int(hh // 2 * ay):int((hh // 2 + 4) * ay) + 1, int(hw // 3 * ax):int((hw // 3 + 5) * ax) + 1] = True
+    my, mx = (max(0, int(np.floor(by))), max(0, int(np.floor(bx)))) if explicit else (0, 0)  # the low pixels under the full-size block of misses
+    miss_l[my + int(hh // 2 * ay):my + int((hh // 2 + 4) * ay) + 1, mx + int(hw // 3 * ax):mx + int((hw // 3 + 5) * ax) + 1] = True
     cover_l[miss_l] = F(0.0)
     lo_planes = dm.planes_of(n_l, p_l, alb_l, A_l, (A_l * cover_l).astype(F))
     rgb = alb_l * (F(0.5) + rng.exponential(0.25, (lh, lw, 3)).astype(F)) * cover_l[..., None]
     rgb_to = np.array([[0.412453, 0.357580, 0.180423], [0.212671, 0.715160, 0.072169], [0.019334, 0.119193, 0.950227]], F)
     W_l = rng.uniform(0.6, 1.4, (lh, lw)).astype(F)
     lo_xyzw = np.concatenate([(rgb @ rgb_to.T) * W_l[..., None], W_l[..., None]], -1).astype(F)
-    if lh >= 8 and lw >= 8:  # the poisoned pixels, away from each other
-        lo_xyzw[1, 2, 3] = F(0.0)               # W = 0
-        lo_xyzw[2, lw - 2, 3] = F(-1.0)         # W < 0
-        lo_xyzw[lh // 3, lw // 2, 0] = F(np.nan)   # NaN colour
-        lo_xyzw[lh // 3 + 2, 1, 1] = F(np.inf)     # +Inf colour
-        lo_xyzw[lh - 2, 3, 2] = F(-np.inf)         # -Inf colour
-        lo_planes[lh // 2, 1, 1, 0] = F(np.nan)    # NaN normal
-        lo_planes[lh // 2 + 2, lw - 3, 2, 1] = F(np.inf)  # Inf position
-        lo_planes[3, lw // 2, 0, 3] = F(0.0)       # A = 0 in the low planes
+    if wh >= 8 and ww >= 8 and hh >= 3 and hw >= 4:  # the poisoned pixels, away from each other
+        lo_xyzw[wy + 1, wx + 2, 3] = F(0.0)               # W = 0
+        lo_xyzw[wy + 2, wx + ww - 2, 3] = F(-1.0)         # W < 0
+        lo_xyzw[wy + wh // 3, wx + ww // 2, 0] = F(np.nan)   # NaN colour
+        lo_xyzw[wy + wh // 3 + 2, wx + 1, 1] = F(np.inf)     # +Inf colour
+        lo_xyzw[wy + wh - 2, wx + 3, 2] = F(-np.inf)         # -Inf colour
+        lo_planes[wy + wh // 2, wx + 1, 1, 0] = F(np.nan)    # NaN normal
+        lo_planes[wy + wh // 2 + 2, wx + ww - 3, 2, 1] = F(np.inf)  # Inf position
+        lo_planes[wy + 3, wx + ww // 2, 0, 3] = F(0.0)       # A = 0 in the low planes
         # two neighbours near FLT_MAX: grey 1e38 (every product of xyz_to_rgb stays finite) over a base colour of 0.3, so c = 3.3e38 is finite after Prepare and the guided
         # sum of the two, whose tent weights add up to 1.5 at radius 2, is not
-        g, yb = F(1.0e38), lh // 4
-        for x in (1, 2):
+        g, yb = F(1.0e38), wy + wh // 4
+        for x in (wx + 1, wx + 2):
             lo_xyzw[yb, x] = np.array([F(0.412453) * g + F(0.357580) * g + F(0.180423) * g, g, F(0.019334) * g + F(0.119193) * g + F(0.950227) * g, F(1.0)], F)
             one = np.ones((1, 1), F)
             lo_planes[yb, x] = dm.planes_of(n_l[yb:yb + 1, x:x + 1], p_l[yb:yb + 1, x:x + 1], np.full((1, 1, 3), 0.3, F), one, one)[0, 0]
