@@ -801,6 +801,30 @@ int trhip_temporal_upsample_motion_device(trhip_ctx* ctx, const void* d_lo_xyzw,
                                           const trhip_temporal_upsample_motion_params* params, void* d_out_xyzw, void* d_out_history, void* d_out_mask,
                                           trhip_stats* stats);
 
+/* trhip_temporal_split: trhip_temporal_motion — its arguments, its parameter block, its body carry, its memory-safety promise — for a preview that keeps the first-hit direct
+ * light out of the history (docs/design/23-direct-split.md is the specification), with
+ *   direct         height * width * 4 floats, directly after xyzw: the film of the frame's direct light (xyz, w; w is not read).  May be NULL.
+ * Step 0: B' = (B.x - D.x, B.y - D.y, B.z - D.z, B.w) with D = direct[pixel]; direct NULL: B' = B, the same bits.  Everything after it is trhip_temporal_motion on B': the
+ * surface test, the body carry, the four taps, the blend, the fallback; a pixel that is no surface pixel gets out_xyzw = B' and twelve zero history words.  The history
+ * then holds the indirect remainder alone; trhip_film_add puts the direct film back after the filter.
+ * direct NULL, or all +0: trhip_temporal_motion's outputs bit for bit; with no table and no matrices as well, trhip_temporal's.  direct is read at the pixel's own place only.
+ * ids may be NULL when n_prims == 0, as in trhip_temporal_clip_motion: every pixel is then static, and a static scene needs no id plane.
+ * TRHIP_ERR_INVALID: trhip_temporal_motion's refusals in its order (ids NULL-able only when n_prims == 0), then out_history overlapping direct, then out_xyzw overlapping
+ * direct.  out_xyzw may be xyzw.  TRHIP_ERR_UNSUPPORTED: the host variant's device copies (192 bytes per pixel, 4 per primitive, 48 per body) do not fit in free HBM.
+ * stats (may be NULL): ms_total, ms_film, launches_film = 1.  The _device variant takes DEVICE pointers for all nine arrays and allocates nothing. */
+int trhip_temporal_split(trhip_ctx* ctx, const float* xyzw, const float* direct, const float* planes, const float* history, const trhip_aov_id* ids, const uint32_t* body_of_prim,
+                         const float* bodies, uint32_t width, uint32_t height, const trhip_temporal_motion_params* params, float* out_xyzw, float* out_history,
+                         trhip_stats* stats);
+int trhip_temporal_split_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_direct, const void* d_planes, const void* d_history, const void* d_ids,
+                                const void* d_body_of_prim, const void* d_bodies, uint32_t width, uint32_t height, const trhip_temporal_motion_params* params,
+                                void* d_out_xyzw, void* d_out_history, trhip_stats* stats);
+
+/* trhip_film_add: out.xyz = a.xyz + b.xyz, one Float32 addition per lane, and out.w = a.w, for two films of height * width * 4 floats.  out may be a.
+ * TRHIP_ERR_INVALID, in this order: a null pointer (stats excepted); a zero dimension; out overlapping b.  TRHIP_ERR_UNSUPPORTED: the host variant's device copies (32 bytes
+ * per pixel) do not fit in free HBM.  stats (may be NULL): ms_total, ms_film, launches_film = 1.  The _device variant takes DEVICE pointers and allocates nothing. */
+int trhip_film_add(trhip_ctx* ctx, const float* a, const float* b, uint32_t width, uint32_t height, float* out, trhip_stats* stats);
+int trhip_film_add_device(trhip_ctx* ctx, const void* d_a, const void* d_b, uint32_t width, uint32_t height, void* d_out, trhip_stats* stats);
+
 /* SPPMIntegrator(camera, initial_search_radius, max_depth, n_iterations, photons_per_iteration)(scene)
  * (integrators/sppm.jl:108-173): per iteration a camera pass to the first diffuse vertex, a hash grid over the visible
  * points, a photon pass (Halton / radical_inverse, sampler/sampling.jl:43-60) and the Float64 pixel update; afterwards

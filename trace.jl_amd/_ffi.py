@@ -379,6 +379,10 @@ SIGNATURES = {
                                                  C.POINTER(C.c_uint8), C.POINTER(Stats)]),
     "trhip_temporal_upsample_motion_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32,
                                                         C.POINTER(TemporalUpsampleMotionParams), _VP, _VP, _VP, C.POINTER(Stats)]),
+    "trhip_temporal_split": (C.c_int, [_VP, _F, _F, _F, _F, _VP, _U32, _F, C.c_uint32, C.c_uint32, C.POINTER(TemporalMotionParams), _F, _F, C.POINTER(Stats)]),
+    "trhip_temporal_split_device": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(TemporalMotionParams), _VP, _VP, C.POINTER(Stats)]),
+    "trhip_film_add": (C.c_int, [_VP, _F, _F, C.c_uint32, C.c_uint32, _F, C.POINTER(Stats)]),
+    "trhip_film_add_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP, C.POINTER(Stats)]),
     "trhip_render_sppm": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats)]),
     "trhip_render_sppm_ex": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_float, C.c_int, C.c_uint32, C.c_int64, C.c_uint64, _F, C.POINTER(Stats), C.c_uint32, SPPM_WRITE_FN, _VP]),
     "trhip_sppm_state": (C.c_int, [_VP, _F, _F, _F, C.POINTER(C.c_double), C.POINTER(C.c_int64), _F, _F, _F, C.POINTER(C.c_int64)]),

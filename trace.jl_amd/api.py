@@ -602,6 +602,26 @@ class Film:  # film.jl:7-62
         ctx.check(_ffi.lib().trhip_film_to_rgb(ctx._h, _ffi.fptr(xyzw), w, h, float(self.scale), _ffi.fptr(out)))
         return out
 
+    @staticmethod
+    def add(a: np.ndarray, b: np.ndarray, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
+        """a.xyz + b.xyz with a's weight lane, for two (H, W, 4) films (trhip_film_add; docs/design/23-direct-split.md): how a direct film goes back onto a filtered
+        remainder."""
+        a, b = _ffi.f32(a), _ffi.f32(b)
+        if a.ndim != 3 or a.shape[2] != 4 or b.shape != a.shape:
+            raise TraceHipError(f"Film.add: both films must be (H, W, 4), not {a.shape} and {b.shape}")
+        ctx = ctx or _ffi.default_context()
+        out = np.empty_like(a)
+        ctx.check(_ffi.lib().trhip_film_add(ctx._h, _ffi.fptr(a), _ffi.fptr(b), a.shape[1], a.shape[0], _ffi.fptr(out), None))
+        return out
+
+    @staticmethod
+    def add_device(d_a: int, d_b: int, width: int, height: int, d_out: int, ctx: Optional[_ffi.Context] = None) -> "_ffi.Stats":
+        """The same on device pointers (d_out may equal d_a); nothing is copied to the host.  Returns the call's Stats."""
+        ctx = ctx or _ffi.default_context()
+        st = _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_film_add_device(ctx._h, C.c_void_p(d_a), C.c_void_p(d_b), int(width), int(height), C.c_void_p(d_out), C.byref(st)))
+        return st
+
 
 def save(film: Film, ctx: Optional[_ffi.Context] = None) -> str:
     """film.jl:204-222: writes film.filename (8-bit PNG, rows flipped, no gamma)."""
@@ -1541,7 +1561,10 @@ class TemporalAccumulator:
     `accumulate` / `accumulate_device` without an id plane (every pixel static), `accumulate_motion` / `accumulate_motion_device` with the tables —, so that a moving body
     keeps its history AND the shadow it drags over static surfaces is cut back to the new frame's colours.  `clip_max_history` (default:
     trhip_temporal_clip_motion_default_params'): a pixel whose history colour was clipped has its history length cut to this before the blend; inf never cuts it, and with
-    inf and no moving pixel the result is the clipping accumulator's bit for bit.  Not combinable with moments=True: a moments pass that carries bodies does not exist."""
+    inf and no moving pixel the result is the clipping accumulator's bit for bit.  Not combinable with moments=True: a moments pass that carries bodies does not exist.
+
+    `accumulate_split` / `accumulate_split_device` (a plain accumulator only): `accumulate_motion` on the film minus a direct film, so that the history holds the indirect
+    light alone (trhip_temporal_split; docs/design/23-direct-split.md).  With direct=None the result is `accumulate_motion`'s bit for bit."""
 
     def __init__(self, max_history: Optional[float] = None, sigma_normal: Optional[float] = None, sigma_plane: Optional[float] = None, min_coverage: Optional[float] = None,
                  clip_gamma: Optional[float] = None, clip_radius: Optional[int] = None, moments: bool = False, spatial_below: Optional[float] = None, demodulate: bool = True,
@@ -1733,6 +1756,57 @@ class TemporalAccumulator:
                                                    _ffi.fptr(out_history), C.byref(st)))
         self.stats = st
         return out, out_history
+
+    def _split_params_for(self, prev_camera, n_prims: int, n_bodies: int) -> _ffi.TemporalMotionParams:
+        if self.clip_params is not None or self.moments_params is not None:
+            raise TraceHipError("TemporalAccumulator: accumulate_split needs a plain accumulator (trhip_temporal_split neither clips nor carries moments)")
+        return self._motion_params_for(prev_camera, n_prims, n_bodies)
+
+    def accumulate_split(self, xyzw: np.ndarray, direct: Optional[np.ndarray], planes: np.ndarray, history: Optional[np.ndarray], ids: Optional[np.ndarray],
+                         body_of_prim: Optional[np.ndarray], bodies: Optional[np.ndarray], prev_camera, ctx: Optional[_ffi.Context] = None):
+        """`accumulate_motion` on xyzw.xyz - direct.xyz (a plain accumulator only; trhip_temporal_split, docs/design/23-direct-split.md): `direct` is the (H, W, 4) film of the
+        frame's first-hit direct light, or None (then `accumulate_motion`'s result bit for bit).  ids may be None when there is no table: every pixel is static.  The returned
+        film and history hold the indirect remainder; Film.add puts `direct` back after the filter."""
+        xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
+        if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
+            raise TraceHipError(f"accumulate_split: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
+        if direct is not None:
+            direct = _ffi.f32(direct)
+            if direct.shape != xyzw.shape:
+                raise TraceHipError(f"accumulate_split: direct must be {xyzw.shape} like xyzw, not {direct.shape}")
+        if history is not None:
+            history = _ffi.f32(history)
+            if history.shape != planes.shape:
+                raise TraceHipError(f"accumulate_split: history must be {planes.shape} like planes, not {history.shape}")
+        h, w = xyzw.shape[:2]
+        if ids is not None:
+            ids = np.ascontiguousarray(ids)
+            if ids.nbytes != h * w * 16:
+                raise TraceHipError(f"accumulate_split: ids must hold one 16-byte record per pixel, not {ids.nbytes} bytes for {h} x {w}")
+        table = None if body_of_prim is None or ids is None else np.ascontiguousarray(body_of_prim, dtype=np.uint32).reshape(-1)
+        mats = None if bodies is None or ids is None else _ffi.f32(bodies).reshape(-1, 12)
+        p = self._split_params_for(prev_camera, 0 if table is None else table.size, 0 if mats is None else mats.shape[0])
+        ctx = ctx or _ffi.default_context()
+        out, out_history, st = np.empty_like(xyzw), np.empty_like(planes), _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_temporal_split(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(direct) if direct is not None else None, _ffi.fptr(planes),
+                                                  _ffi.fptr(history) if history is not None else None, ids.ctypes.data_as(C.c_void_p) if ids is not None else None,
+                                                  _ffi.u32ptr(table) if table is not None else None, _ffi.fptr(mats) if mats is not None else None, w, h, C.byref(p), _ffi.fptr(out),
+                                                  _ffi.fptr(out_history), C.byref(st)))
+        self.stats = st
+        return out, out_history
+
+    def accumulate_split_device(self, d_xyzw: int, d_direct: Optional[int], d_planes: int, d_history: Optional[int], d_ids: Optional[int], d_body_of_prim: Optional[int], n_prims: int,
+                                d_bodies: Optional[int], n_bodies: int, width: int, height: int, prev_camera, d_out: int, d_out_history: int,
+                                ctx: Optional[_ffi.Context] = None) -> None:
+        """The same on device pointers (d_out may equal d_xyzw; d_direct, d_history, d_body_of_prim, d_bodies and, without a table, d_ids may be None); nothing is copied to
+        the host."""
+        st, p = _ffi.Stats(), self._split_params_for(prev_camera, n_prims if d_body_of_prim and d_ids else 0, n_bodies if d_bodies and d_ids else 0)
+        ctx = ctx or _ffi.default_context()
+        ctx.check(_ffi.lib().trhip_temporal_split_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_direct) if d_direct else None, C.c_void_p(d_planes),
+                                                         C.c_void_p(d_history) if d_history else None, C.c_void_p(d_ids) if d_ids else None,
+                                                         C.c_void_p(d_body_of_prim) if d_body_of_prim else None, C.c_void_p(d_bodies) if d_bodies else None, int(width), int(height),
+                                                         C.byref(p), C.c_void_p(d_out), C.c_void_p(d_out_history), C.byref(st)))
+        self.stats = st
 
     def _accumulate_clip_motion(self, who, xyzw, planes, history, ids, body_of_prim, bodies, prev_camera, ctx):
         """The host call of an accumulator built with carry_bodies=True (trhip_temporal_clip_motion); ids None: every pixel is static."""
@@ -1983,11 +2057,31 @@ class PreviewSession:
     above and draws no id plane — a body that moved then restarts its history every frame.  A motion frame needs the plain session: no upscaler, variance_guided,
     and no moments accumulator; `temporal_upsample` serves when the TemporalUpsampler was built with carry_bodies=True (trhip_temporal_upsample_motion;
     docs/design/22-upsample-motion.md: the id plane is drawn at full size with the guide sampler); a clipping accumulator serves when it was built with carry_bodies=True (trhip_temporal_clip_motion; docs/design/21-clip-motion.md:
-    the shadow a moving body drags over static surfaces is then cut back within a frame, buffers passed apart, no copy paid).  The scene's top-level structure and primitive count must be the previous frame's (else: reset())."""
+    the shadow a moving body drags over static surfaces is then cut back within a frame, buffers passed apart, no copy paid).  The scene's top-level structure and primitive count must be the previous frame's (else: reset()).
+    `split_direct=True` (docs/design/23-direct-split.md): the first-hit direct light stays out of the history.  Every light is a delta light, so that term has no noise
+    to average and, kept apart, cannot lag: each frame also renders PathIntegrator(camera, sampler, 1) — path_li's first vertex with the frame's own samples —, the
+    temporal pass is trhip_temporal_split on frame - direct (with a `motion` dict the bodies are carried, without one every pixel is static), the filter runs on the pass's
+    output on every frame, and trhip_film_add puts the direct film back last: with one light the depth-1 path film, with more WhittedIntegrator(camera, sampler, 1), which
+    sums every light instead of picking one.  A scene without lights renders no direct film.  render_stats then ends with the direct renders' and the addition's Stats.
+    Not combinable with an upscaler, temporal_upsample, variance_guided=True or a clipping / moments accumulator.  The default, False, makes exactly the calls described
+    above."""
 
     def __init__(self, scene: Scene, sampler: SeededSampler, max_depth: int, denoiser: Optional["Denoiser"] = None, temporal: Optional[TemporalAccumulator] = None,
                  variance_guided: bool = False, upscaler: Optional["Upscaler"] = None, factor=2, guide_spp: Optional[int] = None, display: Optional["Display"] = None,
-                 temporal_upsample: Optional["TemporalUpsampler"] = None):
+                 temporal_upsample: Optional["TemporalUpsampler"] = None, split_direct: bool = False):
+        if split_direct:
+            if upscaler is not None and temporal_upsample is None:
+                raise TraceHipError("PreviewSession: split_direct cannot be combined with an upscaler (the direct film would have to be upscaled beside the remainder)")
+            if temporal_upsample is not None:
+                raise TraceHipError("PreviewSession: split_direct cannot be combined with temporal_upsample (trhip_temporal_upsample takes no direct film)")
+            if variance_guided:
+                raise TraceHipError("PreviewSession: split_direct cannot be combined with variance_guided=True (trhip_temporal_moments takes no direct film)")
+            if temporal is not None and (temporal.clip_params is not None or temporal.moments_params is not None):
+                raise TraceHipError("PreviewSession: split_direct cannot be combined with a clipping or moments TemporalAccumulator (trhip_temporal_split neither clips "
+                                    "nor carries moments)")
+        self.split_direct = bool(split_direct)
+        self._split_buffers = None  # split_direct: the depth-1 path film and the depth-1 Whitted film
+        self._split_whitted = True  # with more than one light the film added back is Whitted's; False adds the depth-1 path film back (docs/design/23-direct-split.md)
         if temporal_upsample is not None:
             if upscaler is None:
                 raise TraceHipError("PreviewSession: temporal_upsample needs an upscaler (upscaler=Upscaler(), with factor and guide_spp)")
@@ -2031,6 +2125,9 @@ class PreviewSession:
         for b in self._motion_buffers or ():
             b.free()
         self._motion_buffers = None
+        for b in self._split_buffers or ():
+            b.free()
+        self._split_buffers = None
         for b in self._up_buffers or ():
             b.free()
         self._up_buffers, self._up_size = None, None
@@ -2126,6 +2223,20 @@ class PreviewSession:
                                     "matched with the history: call reset() before rendering it")
             d_ids, d_table, d_bodies, n_prims, n_bodies = self._motion_tables(flat, motion, h, w)
         path.render(self.scene, ctx, device_out=d_film.ptr)
+        d_direct = d_direct_all = None  # split_direct: the film taken out before the history, the film put back after the filter
+        direct_stats = ()
+        if self.split_direct and self.scene.lights:
+            if self._split_buffers is None:
+                self._split_buffers = [_ffi.DeviceBuffer(h * w * 16) for _ in range(2)]
+            d_direct, d_direct_all = self._split_buffers[0], self._split_buffers[0]
+            first = PathIntegrator(camera, sampler, 1)  # path_li's first vertex: the same samples, film weights and light picks as `path`
+            first.render(self.scene, ctx, device_out=d_direct.ptr)
+            direct_stats = (first.stats,)
+            if len(self.scene.lights) > 1 and self._split_whitted:  # every light summed at the first hit: no light-picking noise comes back
+                every = WhittedIntegrator(camera, sampler, 1)
+                d_direct_all = self._split_buffers[1]
+                every.render(self.scene, ctx, device_out=d_direct_all.ptr)
+                direct_stats += (every.stats,)
         if motion is not None:
             aov.render(self.scene, ctx, device_out=d_planes.ptr, device_ids=d_ids.ptr)
         else:
@@ -2133,7 +2244,16 @@ class PreviewSession:
         prev_matrix, matrix = self._prev_matrix, camera.world_to_pixel()
         had_history = prev_matrix is not None
         self._prev_matrix = None  # (until this frame's history is complete)
-        if motion is not None:
+        if self.split_direct:
+            if motion is None:
+                d_ids, d_table, d_bodies, n_prims, n_bodies = None, None, None, 0, 0
+            self.temporal.accumulate_split_device(d_film.ptr, d_direct.ptr if d_direct else None, d_planes.ptr, d_prev.ptr if had_history else None, d_ids.ptr if d_ids else None,
+                                                  d_table.ptr if d_table else None, n_prims, d_bodies.ptr if d_bodies else None, n_bodies, w, h, prev_matrix, d_acc.ptr, d_next.ptr, ctx)
+            # always the pass's output, the first frame too: the filter's input is the remainder, not the frame
+            self.denoiser.denoise_device(d_acc.ptr, d_planes.ptr, w, h, d_acc.ptr, ctx)
+            if d_direct_all:
+                direct_stats += (Film.add_device(d_acc.ptr, d_direct_all.ptr, w, h, d_acc.ptr, ctx),)
+        elif motion is not None:
             self.temporal.accumulate_motion_device(d_film.ptr, d_planes.ptr, d_prev.ptr if had_history else None, d_ids.ptr, d_table.ptr if d_table else None, n_prims,
                                                    d_bodies.ptr if d_bodies else None, n_bodies, w, h, prev_matrix, d_acc.ptr, d_next.ptr, ctx)
             self.denoiser.denoise_device((d_acc if had_history else d_film).ptr, d_planes.ptr, w, h, d_acc.ptr, ctx)
@@ -2146,7 +2266,7 @@ class PreviewSession:
             self.temporal.accumulate_device(d_film.ptr, d_planes.ptr, d_prev.ptr if had_history else None, w, h, prev_matrix, d_acc.ptr, d_next.ptr, ctx)
             # without history the accumulated film is the frame itself up to the rounding of XYZ -> RGB -> XYZ: the frame's own bits are filtered then
             self.denoiser.denoise_device((d_acc if had_history else d_film).ptr, d_planes.ptr, w, h, d_acc.ptr, ctx)
-        self.render_stats = (path.stats, aov.stats, self.temporal.stats, self.denoiser.stats)
+        self.render_stats = (path.stats, aov.stats, self.temporal.stats, self.denoiser.stats) + direct_stats
         if self.upscaler is not None:
             out = self._upscale(hi_camera, camera, sampler, d_acc, d_planes, ctx), hi_camera.film.size, ctx
         else:

@@ -144,7 +144,8 @@ struct trhip_ctx {
     DevBuf tp_in;           // trhip_temporal's host entry point: its copy of film, planes, history and the new history (th_temporal.h, 160 B per pixel); trhip_temporal_clip's: the same and
                             // the result's film (176 B); trhip_temporal_clip_device's film for a result that aliases its input (16 B); trhip_temporal_moments likewise (196 B; 16 B);
                             // trhip_temporal_motion's: trhip_temporal's and the id plane, the body matrices and the body table (176 B per pixel, 48 per body, 4 per primitive);
-                            // trhip_temporal_clip_motion's: the same and the result's film (192 B per pixel); its _device variant's film for a result that aliases its input (16 B)
+                            // trhip_temporal_clip_motion's: the same and the result's film (192 B per pixel); its _device variant's film for a result that aliases its input (16 B);
+                            // trhip_temporal_split's: trhip_temporal_motion's and the direct film (192 B per pixel); trhip_film_add's two films (32 B per pixel)
     int temporal_patch = 1; // trhip_temporal's lane-to-pixel mapping: 0 film order, 1 patches of 16 x 4 per wave, measured 11 % faster (option "temporal_patch", profiles/r11/temporal.txt)
     int denoise_var_lds = 3;  // bit i: iteration i (step 2^i, i < 2) of trhip_denoise_var runs the LDS-staged kernel (option "denoise_var_lds", profiles/r13/variance.txt)
     DevBuf up_in;      // trhip_upscale's host entry point: its copies of the five images (th_upscale.h; 64 B per low pixel, 65 per full-size pixel);

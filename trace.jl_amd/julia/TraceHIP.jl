@@ -413,6 +413,8 @@ include("TraceHIPMotion.jl")
 include("TraceHIPClipMotion.jl")
 # accumulate_upsample_motion (trhip_temporal_upsample_motion), likewise (tests/golden/julia_shim_upsample_motion_calls.json)
 include("TraceHIPUpsampleMotion.jl")
+# accumulate_split (trhip_temporal_split) and film_add (trhip_film_add), likewise (tests/golden/julia_shim_direct_split_calls.json)
+include("TraceHIPDirectSplit.jl")
 
 # SPPMIntegrator (integrators/sppm.jl:132-173) on the device: trhip_render_sppm returns the film after set_image!
 # (film.jl:195-202).  `seed` selects the seeded stream of the camera pass (the reference draws from the global RNG there).
