@@ -1,5 +1,6 @@
-// th_image_pass.h — the host scaffold of the image-space passes of a preview: tu_denoise.hip, tu_temporal.hip, tu_upscale.hip, tu_display.hip, tu_temporal_upsample.hip, tu_temporal_motion.hip, tu_temporal_clip_motion.hip, tu_temporal_upsample_motion.hip and tu_temporal_split.hip, and
-// nobody else.  Host code only: no kernel lives here and no kernel header is included, so the units instantiate what they instantiated before.  What a pass keeps to itself: its
+// th_image_pass.h — the host scaffold of the image-space passes of a preview: tu_denoise.hip, tu_temporal.hip, tu_upscale.hip, tu_display.hip, tu_temporal_upsample.hip,
+// tu_temporal_motion.hip, tu_temporal_clip_motion.hip, tu_temporal_upsample_motion.hip and tu_temporal_split.hip, and nobody else.  Host code only: no kernel lives here and
+// no kernel header is included, so the units instantiate what they instantiated before.  What a pass keeps to itself: its
 // parameter checks, its refusal sentences, its launches.  What it gets from here: where its images live (ImageStaging), whether two of them overlap, the timed window around
 // its launches and the block that closes it (PassWindow, close_pass), and the derivations two passes share.  Everything above "the timed window" is arithmetic on the
 // arguments and needs no device.
