@@ -242,6 +242,74 @@ int trhip_render_whitted_device(trhip_ctx* ctx, const trhip_scene* scene, const 
  * (film.jl:68-73).  Parity tests compare this with the oracle bit-for-bit. */
 int trhip_last_sample_radiance(trhip_ctx* ctx, float* out_rgb, uint64_t n_floats);
 
+/* ---- adaptive sampling (added without a version change: nothing existing moved; docs/design/24-adaptive.md is the specification) -------
+ * trhip_render_path_map: trhip_render_path with a per-pixel sample count instead of one spp.
+ *   counts     one uint32 per SAMPLE pixel — the film's sample bounds, filter border included — indexed like trhip_last_sample_radiance:
+ *              (y - sb.min.y) * sb_width + (x - sb.min.x); every entry in 0 .. max_spp.
+ * Sample pixel p draws the sample indices sample_offset + s for s < counts[p] and no others.  ts_stream_key (trace_sampler.h) does not depend on
+ * the sample count, so each drawn sample's radiance is trhip_render_path's for that (pixel, index) bit for bit.  The film is the reference loop
+ * (integrators/sampler.jl:24-52, film.jl:134-193) with samples_per_pixel replaced by counts[p]: tiles in k order, sample pixels in Bounds2
+ * order, samples in index order, one partial sum per tile, the NaN rule; a sample that is not drawn is SKIPPED, not added with weight 0.
+ * counts == spp everywhere is trhip_render_path(spp) bit for bit, and films stay additive over sample_offset.
+ * Work: stats.camera_samples = sum of counts; no ray is generated for a sample that is not drawn and the film pass reads no record of one.
+ * The frame's camera samples are a job list (an exclusive sum over counts, then one word per drawn sample, 4 bytes each); wavefront batches are
+ * ranges of that list.  The sum of counts plans the batches on the host: the host variant adds the counts up on the host, the _device variant
+ * reads 8 bytes back after a reduction over the map on the device.
+ * Film passes: a filter radius in (0, 1] on both axes takes the pixel-group-major records with packed splat descriptors and the 2 x 4 gather;
+ * any other radius takes sample-major records, film positions for the drawn samples and the 1 x 4 block gather.  The options that select other
+ * film passes ("film_block", "film_tiled", "film_transpose", "film_fused", "film_relayout", "film_swizzle"), "streaming" and "pipelines" are
+ * IGNORED by map frames; "batch_paths" (rounded down to whole waves of 64) and "overlap" hold.
+ * trhip_last_sample_radiance after a map frame: the dense max_spp * n_sample_pixels * 3 array, +0.0 in every entry with s >= counts[p].
+ * TRHIP_ERR_INVALID, in this order: a null pointer (stats excepted); max_spp == 0; an empty film; a count above max_spp (looked for on the host
+ * by the host variant, on the device beside the sum by the _device variant); a sum of counts of 0; then trhip_render_path's refusals in its
+ * order (an uncommitted scene, max_depth).  TRHIP_ERR_UNSUPPORTED: 2^31 sample pixels or 2^32 camera samples at max_spp (after the empty
+ * film); a scene with a material-less primitive, where trhip_render_path refuses it; a frame whose per-sample buffers — dense at max_spp, 17 or
+ * 25 bytes per slot, and 4 bytes per drawn sample — do not fit in half of free HBM: there are no bands here, as in trhip_render_aov.
+ * The _device variant takes DEVICE pointers for counts and the film. */
+int trhip_render_path_map(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, const uint32_t* counts, uint32_t max_spp, int max_depth, uint64_t seed,
+                          uint32_t sample_offset, float* out_xyzw, trhip_stats* stats);
+int trhip_render_path_map_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, const void* d_counts, uint32_t max_spp, int max_depth, uint64_t seed,
+                                 uint32_t sample_offset, void* d_out_xyzw, trhip_stats* stats);
+
+/* trhip_film_sum: out = a + b on all FOUR lanes, one Float32 addition each, for two films of height * width * 4 floats: the film of sample indices [o, o + n0)
+ * plus a map frame's film at sample_offset o + n0 is the film of their union up to the order of the two partial sums, weight lane included.  (trhip_film_add keeps
+ * a's weight lane and is not the call for this.)  out may be a or b.  TRHIP_ERR_INVALID: a null pointer; a zero dimension.  The _device variant takes DEVICE pointers
+ * and allocates nothing. */
+int trhip_film_sum(trhip_ctx* ctx, const float* a, const float* b, uint32_t width, uint32_t height, float* out);
+int trhip_film_sum_device(trhip_ctx* ctx, const void* d_a, const void* d_b, uint32_t width, uint32_t height, void* d_out);
+
+/* trhip_last_sample_stats: mean and variance of the luminance of every sample pixel over the n = spp radiance records of the context's last
+ * one-band trhip_render_path frame (either record layout), or over the records the last trhip_film_accumulate was given.  out_mv: n_sample_pixels * 2 floats, (m, v) per sample pixel in
+ * trhip_last_sample_radiance's pixel order.  Per sample, in index order: the NaN rule (a record with a NaN lane counts as black),
+ * Y = 0.212671 r + 0.715160 g + 0.072169 b evaluated left to right, S1 += Y, S2 += Y * Y, both from +0; then m = S1 / n,
+ * x = S2 / n - m * m, v = x < 0 ? +0 : x (a NaN x stays NaN).  All Float32, no contraction.
+ * TRHIP_ERR_INVALID: a null pointer; a last frame that is neither (none yet, a banded, Whitted, AO or map frame). */
+int trhip_last_sample_stats(trhip_ctx* ctx, float* out_mv);
+int trhip_last_sample_stats_device(trhip_ctx* ctx, void* d_out_mv);
+
+/* trhip_sample_map: the extra samples per sample pixel that bring the relative standard error of a pilot frame's own estimate under tau.
+ *   mv           sb_height * sb_width * 2 floats: what trhip_last_sample_stats wrote for a pilot frame of `pilot` samples per pixel
+ *   out_counts   sb_height * sb_width uint32;  out_total: one uint64, the sum of out_counts (an integer sum: no order in it)
+ * e[q] = v / ((|m| + eps) * (|m| + eps)), +Inf when that is NaN or not finite;  E[p] = the largest e over the 3 x 3 sample pixels around p
+ * that lie inside the sample bounds;  x = E / (tau * tau);  counts[p] = max_extra when !(x < float(pilot + max_extra)), otherwise
+ * max(0, int(ceilf(x)) - pilot).  A relative-error target measured on the pilot's own samples is biased, like every such scheme
+ * (docs/design/24-adaptive.md); adding the map frame to the pilot frame keeps every pixel's pilot samples.
+ * TRHIP_ERR_INVALID, in this order, the parameter block before any handle: params NULL; tau not > 0 (+Inf is allowed: no extra sample where
+ * E is finite); eps not finite or < 0; pilot + max_extra > 2^24; flags != 0; reserved != 0; then a null pointer; a zero dimension or 2^31
+ * sample pixels.  The _device variant takes DEVICE pointers for mv, out_counts and out_total and allocates nothing.
+ * trhip_sample_map_default_params needs no context and no GPU. */
+typedef struct {
+    float tau;          /* target relative standard error of a pixel's mean luminance; default 0.25 */
+    float eps;          /* added to |m|: keeps black pixels from asking for samples; default 0.01 */
+    uint32_t pilot;     /* samples per pixel of the frame mv came from; default 8 */
+    uint32_t max_extra; /* cap of a count; default 56 */
+    uint32_t flags;     /* 0 */
+    uint32_t reserved;  /* 0 */
+} trhip_sample_map_params;         /* 24 bytes */
+int trhip_sample_map_default_params(trhip_sample_map_params* params);
+int trhip_sample_map(trhip_ctx* ctx, const float* mv, uint32_t sb_width, uint32_t sb_height, const trhip_sample_map_params* params, uint32_t* out_counts, uint64_t* out_total);
+int trhip_sample_map_device(trhip_ctx* ctx, const void* d_mv, uint32_t sb_width, uint32_t sb_height, const trhip_sample_map_params* params, void* d_out_counts, void* d_out_total);
+
 /* ---- first-hit feature buffers (since ABI 3001, added without a version change: nothing existing moved) -------------------
  * What a denoiser, a compositor, an object picker or an edge-aware upscaler wants beside the beauty frame: for every camera
  * sample of a frame the closest hit of its camera ray — depth, position, geometric and shading normal, base colour, primitive

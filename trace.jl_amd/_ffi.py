@@ -131,6 +131,18 @@ class DenoiseParams(C.Structure):
 DENOISE_DEMODULATE = 1  # TRHIP_DENOISE_DEMODULATE
 
 
+class SampleMapParams(C.Structure):
+    """trhip_sample_map_params (24 bytes)"""
+    _fields_ = [
+        ("tau", C.c_float),
+        ("eps", C.c_float),
+        ("pilot", C.c_uint32),
+        ("max_extra", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class AoParams(C.Structure):
     """trhip_ao_params (16 bytes)"""
     _fields_ = [
@@ -333,6 +345,15 @@ SIGNATURES = {
     "trhip_render_path_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(Stats)]),
     "trhip_render_whitted_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(Stats)]),
     "trhip_last_sample_radiance": (C.c_int, [_VP, _F, C.c_uint64]),
+    "trhip_render_path_map": (C.c_int, [_VP, _VP, C.POINTER(Sensor), _U32, C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _F, C.POINTER(Stats)]),
+    "trhip_render_path_map_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), _VP, C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(Stats)]),
+    "trhip_film_sum": (C.c_int, [_VP, _F, _F, C.c_uint32, C.c_uint32, _F]),
+    "trhip_film_sum_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP]),
+    "trhip_last_sample_stats": (C.c_int, [_VP, _F]),
+    "trhip_last_sample_stats_device": (C.c_int, [_VP, _VP]),
+    "trhip_sample_map_default_params": (C.c_int, [C.POINTER(SampleMapParams)]),
+    "trhip_sample_map": (C.c_int, [_VP, _F, C.c_uint32, C.c_uint32, C.POINTER(SampleMapParams), _U32, C.POINTER(C.c_uint64)]),
+    "trhip_sample_map_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(SampleMapParams), _VP, _VP]),
     "trhip_render_aov": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _F, _VP, C.POINTER(Stats)]),
     "trhip_render_aov_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, _VP, C.POINTER(Stats)]),
     "trhip_ao_default_params": (C.c_int, [C.POINTER(AoParams)]),

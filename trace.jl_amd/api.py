@@ -1053,6 +1053,192 @@ class PathIntegrator(_SamplerIntegrator):
     _entry = "trhip_render_path"
     _entry_device = "trhip_render_path_device"
 
+    def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None, sample_map: Optional["SampleMap"] = None) -> np.ndarray:
+        """_SamplerIntegrator.render; with ``sample_map`` a map frame (trhip_render_path_map): sample pixel p draws ``sample_map.counts[p]`` samples from the sampler's
+        sample_offset on, and ``sampler.samples_per_pixel`` is not read."""
+        if sample_map is None:
+            return super().render(scene, ctx, device_out)
+        flat = scene.flatten(ctx)
+        ctx = flat.ctx
+        sn = self.camera.sensor()
+        st = _ffi.Stats()
+        film = self.camera.film
+        h, w = film.size
+        smp = self.sampler
+        counts = sample_map.for_film(film)
+        L = _ffi.lib()
+        if device_out is not None:
+            d_counts = _ffi.DeviceBuffer(counts.nbytes).from_host(counts)
+            try:
+                ctx.check(L.trhip_render_path_map_device(ctx._h, flat._h, C.byref(sn), C.c_void_p(d_counts.ptr), sample_map.max_spp, self.max_depth, smp.seed, smp.sample_offset,
+                                                         C.c_void_p(device_out), C.byref(st)))
+            finally:
+                d_counts.free()
+            self.stats = st
+            return None
+        out = np.empty((h, w, 4), dtype=np.float32)
+        ctx.check(L.trhip_render_path_map(ctx._h, flat._h, C.byref(sn), _ffi.u32ptr(counts), sample_map.max_spp, self.max_depth, smp.seed, smp.sample_offset, _ffi.fptr(out), C.byref(st)))
+        self.stats = st
+        film.set_xyzw(out)
+        return out
+
+
+# ---- adaptive sampling (include/tracehip.h, trhip_render_path_map; docs/design/24-adaptive.md) ---------------------------------------------
+def sample_bounds_shape(film: "Film"):
+    """(sb_h, sb_w, x0, y0): the film's sample bounds — filter border included — as a shape and the raster pixel of its first entry."""
+    sb = film.get_sample_bounds()
+    return int(sb.p_max[1] - sb.p_min[1]) + 1, int(sb.p_max[0] - sb.p_min[0]) + 1, int(sb.p_min[0]), int(sb.p_min[1])
+
+
+class SampleMap:
+    """A per-pixel sample count for PathIntegrator.render(sample_map=...): ``counts`` is (sb_h, sb_w) uint32 over the film's SAMPLE pixels (get_sample_bounds, filter
+    border included), every entry in 0 .. max_spp."""
+
+    def __init__(self, counts, max_spp: int):
+        c = np.asarray(counts)
+        if c.ndim != 2 or c.size == 0:
+            raise TraceHipError(f"SampleMap: counts must be (sb_h, sb_w), not {c.shape}")
+        if np.any(c < 0) or np.any(c > int(max_spp)):
+            raise TraceHipError(f"SampleMap: counts must lie in 0 .. max_spp = {int(max_spp)}")
+        self.counts = np.ascontiguousarray(c, dtype=np.uint32)
+        self.max_spp = int(max_spp)
+
+    @property
+    def total(self) -> int:
+        return int(self.counts.sum(dtype=np.uint64))
+
+    def for_film(self, film: "Film") -> np.ndarray:
+        sbh, sbw, _, _ = sample_bounds_shape(film)
+        if self.counts.shape != (sbh, sbw):
+            raise TraceHipError(f"SampleMap: counts are {self.counts.shape}, the film's sample bounds {(sbh, sbw)}")
+        return self.counts
+
+    @classmethod
+    def from_film(cls, film: "Film", counts_hw, max_spp: Optional[int] = None) -> "SampleMap":
+        """From a count per FILM pixel, (H, W) in film.pixels order: every sample pixel takes the count of the nearest film pixel, clamped at the border."""
+        c = np.asarray(counts_hw)
+        h, w = film.size
+        if c.shape != (h, w):
+            raise TraceHipError(f"SampleMap.from_film: counts are {c.shape}, the film {(h, w)}")
+        sbh, sbw, x0, y0 = sample_bounds_shape(film)
+        fx0, fy0 = int(film.crop_bounds.p_min[0]), int(film.crop_bounds.p_min[1])  # raster pixel of film.pixels[0, 0]
+        xs = np.clip(np.arange(sbw) + x0 - fx0, 0, w - 1)
+        ys = np.clip(np.arange(sbh) + y0 - fy0, 0, h - 1)
+        out = c[np.ix_(ys, xs)]
+        return cls(out, int(out.max()) if max_spp is None else max_spp)
+
+    @classmethod
+    def region(cls, film: "Film", box, inside: int, outside: int) -> "SampleMap":
+        """Region of interest: ``inside`` samples for the film pixels of box = (x0, y0, x1, y1) (film.pixels indices, x1 and y1 exclusive), ``outside`` elsewhere."""
+        h, w = film.size
+        x0, y0, x1, y1 = (int(v) for v in box)
+        c = np.full((h, w), int(outside), dtype=np.int64)
+        c[max(y0, 0):max(y1, 0), max(x0, 0):max(x1, 0)] = int(inside)
+        return cls.from_film(film, c, max(int(inside), int(outside)))
+
+
+def sample_map_model(mv, tau, eps, pilot: int, max_extra: int) -> np.ndarray:
+    """trhip_sample_map in numpy, operation by operation in Float32 (include/tracehip.h): mv (sb_h, sb_w, 2) -> counts (sb_h, sb_w) uint32."""
+    f = np.float32
+    mv = np.asarray(mv, dtype=f)
+    with np.errstate(all="ignore"):
+        a = np.abs(mv[..., 0]) + f(eps)
+        e = mv[..., 1] / (a * a)
+        e = np.where(np.abs(e) < f(np.inf), e, f(np.inf)).astype(f)
+        h, w = e.shape
+        pad = np.full((h + 2, w + 2), f(0.0), dtype=f)  # +0 loses every `e > E`, like a pixel outside the bounds
+        pad[1:-1, 1:-1] = e
+        E = np.zeros((h, w), dtype=f)
+        for dy in range(3):
+            for dx in range(3):
+                q = pad[dy:dy + h, dx:dx + w]
+                E = np.where(q > E, q, E)
+        x = (E / (f(tau) * f(tau))).astype(f)
+        below = x < f(int(pilot) + int(max_extra))
+        need = np.ceil(np.where(below, x, f(0.0))).astype(np.int64) - int(pilot)
+    return np.where(below, np.maximum(need, 0), int(max_extra)).astype(np.uint32)
+
+
+class AdaptivePathIntegrator:
+    """Adaptive sampling on the public calls (docs/design/24-adaptive.md): a pilot trhip_render_path_device frame at n0 = sampler.samples_per_pixel >= 2,
+    trhip_last_sample_stats_device and trhip_sample_map_device on its radiance records, then — when the map asks for any sample — a trhip_render_path_map_device frame at
+    sample_offset + n0, and trhip_film_sum of the two films.  Every pixel keeps its pilot samples.  ``counts`` (sb_h, sb_w; the extra samples), ``total`` and ``stats``
+    (the pilot's, and the map frame's or None) describe the last render."""
+
+    def __init__(self, camera: PerspectiveCamera, sampler: SeededSampler, max_depth: int, tau: Optional[float] = None, max_extra: Optional[int] = None, eps: Optional[float] = None):
+        if sampler.samples_per_pixel < 2:
+            raise TraceHipError("AdaptivePathIntegrator: the pilot frame needs at least 2 samples per pixel (a variance)")
+        self.camera, self.sampler, self.max_depth = camera, sampler, int(max_depth)
+        p = _ffi.SampleMapParams()
+        rc = _ffi.lib().trhip_sample_map_default_params(C.byref(p))
+        if rc:
+            raise TraceHipError(f"trhip_sample_map_default_params failed ({rc})")
+        p.pilot = sampler.samples_per_pixel
+        if tau is not None:
+            p.tau = tau
+        if max_extra is not None:
+            p.max_extra = int(max_extra)
+        if eps is not None:
+            p.eps = eps
+        self.params = p
+        self.counts: Optional[np.ndarray] = None
+        self.total = 0
+        self.mv: Optional[np.ndarray] = None
+        self.stats = (None, None)
+
+    def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
+        flat = scene.flatten(ctx)
+        ctx = flat.ctx
+        sn = self.camera.sensor()
+        film = self.camera.film
+        h, w = film.size
+        sbh, sbw, _, _ = sample_bounds_shape(film)
+        smp = self.sampler
+        n0 = smp.samples_per_pixel
+        L = _ffi.lib()
+        bufs = [_ffi.DeviceBuffer(h * w * 16), _ffi.DeviceBuffer(h * w * 16), _ffi.DeviceBuffer(sbh * sbw * 8), _ffi.DeviceBuffer(sbh * sbw * 4), _ffi.DeviceBuffer(8)]
+        d_pilot, d_extra, d_mv, d_counts, d_total = (C.c_void_p(b.ptr) for b in bufs)
+        try:
+            st0, st1 = _ffi.Stats(), None
+            ctx.check(L.trhip_render_path_device(ctx._h, flat._h, C.byref(sn), n0, self.max_depth, smp.seed, smp.sample_offset, d_pilot, C.byref(st0)))
+            ctx.check(L.trhip_last_sample_stats_device(ctx._h, d_mv))
+            ctx.check(L.trhip_sample_map_device(ctx._h, d_mv, sbw, sbh, C.byref(self.params), d_counts, d_total))
+            self.mv = bufs[2].to_host(np.float32, (sbh, sbw, 2))
+            self.counts = bufs[3].to_host(np.uint32, (sbh, sbw))
+            self.total = int(bufs[4].to_host(np.uint64, (1,))[0])
+            if self.total:
+                st1 = _ffi.Stats()
+                ctx.check(L.trhip_render_path_map_device(ctx._h, flat._h, C.byref(sn), d_counts, self.params.max_extra, self.max_depth, smp.seed, smp.sample_offset + n0, d_extra,
+                                                         C.byref(st1)))
+                ctx.check(L.trhip_film_sum_device(ctx._h, d_pilot, d_extra, w, h, d_pilot))
+            self.stats = (st0, st1)
+            out = bufs[0].to_host(np.float32, (h, w, 4))
+        finally:
+            for b in bufs:
+                b.free()
+        film.set_xyzw(out)
+        return out
+
+    def tau_for_budget(self, mv, target_total: int, iterations: int = 60):
+        """The tau whose map (sample_map_model: the kernel's arithmetic on the host, with this integrator's eps, pilot count and max_extra) totals closest to
+        ``target_total`` extra samples: a bisection on log tau, for equal-ray comparisons.  Returns (tau, total); the total falls as tau grows and moves in steps, so
+        it need not hit the target."""
+        eps, pilot, max_extra = self.params.eps, self.params.pilot, self.params.max_extra
+        total = lambda t: int(sample_map_model(mv, t, eps, pilot, max_extra).sum(dtype=np.uint64))
+        lo, hi = np.float32(1e-6), np.float32(1e6)  # total(lo) >= target >= total(hi) wherever the target can be met
+        best = min(((abs(total(t) - target_total), float(t)) for t in (lo, hi)))
+        for _ in range(iterations):
+            mid = np.float32(math.sqrt(float(lo) * float(hi)))
+            if mid == lo or mid == hi:
+                break
+            n = total(mid)
+            best = min(best, (abs(n - target_total), float(mid)))
+            if n > target_total:
+                lo = mid
+            else:
+                hi = mid
+        return np.float32(best[1]), total(np.float32(best[1]))
+
 
 # ---- first-hit feature buffers (include/tracehip.h, trhip_render_aov) -----------------------------------------------------------------
 def base_colour(material) -> np.ndarray:

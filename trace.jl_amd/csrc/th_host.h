@@ -4,7 +4,7 @@
 // tu_lbvh.hip (BVH build on the device), tu_trace.hip / tu_trace3.hip / tu_trace3c.hip / tu_trace7.hip / tu_trace8.hip (traversal launches and entry points),
 // tu_path.hip (PathIntegrator frames, film, and the out-of-line part of the frame scaffold below: the stats functions), tu_aov.hip (first-hit feature buffers),
 // tu_ao.hip (ambient occlusion; the two share their camera-ray front half, th_camera.h), tu_denoise.hip (the à-trous filters), tu_temporal.hip (temporal reprojection), tu_upscale.hip, tu_display.hip (the 8-bit display pass), tu_temporal_upsample.hip — these five, the
-// image-space passes, share their host side through th_image_pass.h —, tu_whitted.hip, tu_sppm.hip.
+// image-space passes, share their host side through th_image_pass.h —, tu_adaptive.hip (the job list of a map frame, the sample statistics and the sample map; th_adaptive.h), tu_whitted.hip, tu_sppm.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -152,6 +152,10 @@ struct trhip_ctx {
                        // trhip_temporal_upsample's likewise (th_temporal_upsample.h; 64 B per low pixel, 161 per full-size pixel); trhip_temporal_upsample_motion's: the same and
                        // the id plane, the body matrices and the body table (177 B per full-size pixel, 48 per body, 4 per primitive)
     DevBuf dp_work, dp_in;  // trhip_display: the 1 KiB metering histogram and a 16-byte state slot (th_display.h); the host entry point's copy of the film and its bytes (20 B per pixel)
+    // adaptive sampling (th_adaptive.h): the last map frame's counts (kept for trhip_last_sample_radiance), their exclusive sum, the job list, hipcub's workspace, the
+    // word k_map_reduce / k_sample_map sum into; the host entry points' copies of (m, v) and of the counts they return
+    DevBuf map_counts, map_offsets, map_jobs, map_tmp, map_word, map_mv, map_out;
+    uint32_t last_L_kind = 0;  // whose records Lbuf holds: 1 a one-band path frame or trhip_film_accumulate's records (trhip_last_sample_stats reads them), 2 a map frame (exported through map_counts), 0 anything else
     DevBuf cb_rc;      // one word: a host callback's return code, max-reduced over the ranks of a job (tu_sppm.hip)
     DevBuf ov8[2], fb_list[2], fb_counts[2];  // k_trace8: global stack levels, fallback lists + their counters / work cursors ([closest | any])
     Comm comm;  // multi-GPU job this context belongs to (trhip_comm_init); n_ranks == 1 without one
@@ -520,6 +524,9 @@ void launch_film(trhip_ctx* ctx, hipStream_t st, const DeviceSensor& ds, const D
 void stats_add_counters(trhip_stats& s, const Counters& h);  // += the ray, node-visit and primitive-test totals, the fallback totals and the fallback reasons (count_sub)
 void stats_fill_times(trhip_ctx* ctx, const trhip_scene* sc, Timer& tm, const FrameEvents& ev, trhip_stats& s);  // ms_total, Timer classes 0-4, the fallback share, traversal_info
 void stats_accumulate(trhip_stats& sum, const trhip_stats& band);  // a banded frame: += every additive field; max_depth_reached, traversal, node_bytes as the last band has them
+// tu_adaptive.hip: a map frame's job list from ctx->map_counts (npix counts, already on the device).  sum_on_device: Σ counts and "some count lies above max_spp" come from
+// the device (8 bytes read back) into *total and *above; otherwise the caller has both.  Nothing is built when *above or *total == 0.
+int map_job_list(trhip_ctx* ctx, uint32_t npix, uint32_t max_spp, bool sum_on_device, uint64_t* total, bool* above);
 // tu_whitted.hip
 int render_whitted_impl(trhip_ctx* ctx, const trhip_scene* scene, const DeviceSensor& ds, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
                         void* d_film, trhip_stats* stats);

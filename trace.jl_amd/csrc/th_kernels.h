@@ -175,6 +175,16 @@ TH_D uint32_t film_chunk_pos(uint32_t p) {  // p = pix & 63
 TH_D size_t film_index(uint32_t layout, uint32_t npix, uint32_t spp, uint32_t s, uint32_t pix) {
     return layout ? ((size_t)(pix >> 6) * spp + s) * 64u + film_chunk_pos(pix & 63u) : (size_t)s * npix + pix;
 }
+// What a film gather's sample loop runs to: one spp for the whole frame (uint32_t), or — a map frame, trhip_render_path_map — a count per sample pixel over records that
+// are laid out at max_spp.  The gathers take either as their `SPP` argument.
+struct MapSpp {
+    const uint32_t* counts;
+    uint32_t max_spp;
+};
+TH_D uint32_t spp_of_frame(uint32_t spp) { return spp; }
+TH_D uint32_t spp_of_frame(const MapSpp& m) { return m.max_spp; }
+TH_D uint32_t spp_of_pixel(uint32_t spp, uint32_t) { return spp; }
+TH_D uint32_t spp_of_pixel(const MapSpp& m, uint32_t pix) { return m.counts[pix]; }
 constexpr uint32_t kFilmPackSide = 0x80000000u;
 constexpr uint32_t kFilmPackOverflow = 0xffffffffu;
 constexpr uint32_t kFilmPackException = 0xffffffffu;  // what film_pack_desc returns for a descriptor that does not fit
@@ -239,11 +249,19 @@ TH_D void generate_ray(const DeviceSensor& se, f2 film, f2 lens, float time_u, f
 // Lf (optional, the path integrator's whole-frame launches): the sample's radiance record is initialised HERE, in the film pass's pixel-group-major layout
 // (film_index layout 1) with the packed splat descriptor in its .w lane, and the path carries that record's index as its slot — the frame then needs neither the
 // memset of L nor the pack / re-lay pass over it before the gather (2.9 ms of a 256-spp frame and a second copy of L)
-template <int TH_ONE_COPY = 0> __global__ __launch_bounds__(kBlock) void k_raygen(const DeviceSensor* __restrict__ sep, uint32_t slot0, uint32_t n, uint64_t seed, uint32_t sample_offset,
+// SLOT0 = MapJobs (a map frame, trhip_render_path_map): entry i of the launch is job job0 + i of a job list whose words are the drawn samples' dense sample-major slots
+// s * npix + pix (th_adaptive.h, k_map_expand), instead of slot slot0 + i itself; everything after that line is the same
+struct MapJobs {
+    const uint32_t* jobs;
+    uint32_t job0;
+};
+TH_D uint32_t raygen_slot(uint32_t slot0, uint32_t i) { return slot0 + i; }
+TH_D uint32_t raygen_slot(const MapJobs& m, uint32_t i) { return m.jobs[m.job0 + i]; }
+template <int TH_ONE_COPY = 0, class SLOT0 = uint32_t> __global__ __launch_bounds__(kBlock) void k_raygen(const DeviceSensor* __restrict__ sep, SLOT0 slot0, uint32_t n, uint64_t seed, uint32_t sample_offset,
                                                    PathQueue q, uint32_t cap, Counters* ctr, float4* __restrict__ Lf = nullptr, uint32_t spp_frame = 0, FilmSideTable side = FilmSideTable{nullptr, nullptr, 0}) {
     const DeviceSensor& se = *sep;
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-        uint32_t slot = slot0 + i;
+        uint32_t slot = raygen_slot(slot0, i);
         const SlotInfo si = slot_info(se, slot);
         const uint64_t key = ts_stream_key(seed, si.px, si.py, sample_offset + si.sample);
         if (Lf) {
@@ -887,10 +905,12 @@ TH_D void film_tile_bounds(const DeviceSensor& se, int ty, int tx, float rx, flo
 // (reach of the block: (BX + 2r + 2) x (BY + 2r + 2) sample pixels), and the filter index is computed once per row / column.
 // Per film pixel nothing changes: tiles in k order, sample pixels in Bounds2 order, samples in order, one csum per tile; a
 // tile or sample outside a pixel's own reach fails the same bounds tests as in k_film_gather and contributes nothing.
-template <int BX, int BY>
+// SPP = MapSpp (a map frame): the records are laid out at max_spp and sample pixel pix offers its first counts[pix] samples only; the other records are never read.
+template <int BX, int BY, class SPP = uint32_t>
 __global__ __launch_bounds__(kBlock) void k_film_gather_block(const DeviceSensor* __restrict__ sep, const float* __restrict__ table, const float4* __restrict__ L,
-                                                              const float2* __restrict__ pfilm, uint32_t spp, uint32_t layout, float4* __restrict__ out) {
+                                                              const float2* __restrict__ pfilm, SPP spp_arg, uint32_t layout, float4* __restrict__ out) {
     const DeviceSensor& se = *sep;
+    const uint32_t spp_frame = spp_of_frame(spp_arg);
     // the 16 x 16 filter table in LDS: a lookup in global memory queues behind the sample loads in flight (vector loads return in
     // order), so every weight waited for the whole next batch
     __shared__ float s_table[256];
@@ -949,6 +969,7 @@ __global__ __launch_bounds__(kBlock) void k_film_gather_block(const DeviceSensor
                     for (int sy = y0; sy <= y1; ++sy)
                         for (int sx = x0; sx <= x1; ++sx) {
                             const uint32_t pix = (uint32_t)(sy - se.band_y0) * (uint32_t)se.sb_w + (uint32_t)(sx - se.sb_min[0]);
+                            const uint32_t spp = spp_of_pixel(spp_arg, pix);  // samples this sample pixel offers
                             // kFilmUnroll samples per trip: their p_film and L loads are issued together (the gather is a chain of
                             // dependent trips otherwise), then they are splatted one after the other, in sample order
                             auto splat = [&](float2 pf, float4 l4) {
@@ -993,14 +1014,14 @@ __global__ __launch_bounds__(kBlock) void k_film_gather_block(const DeviceSensor
                                 float4 lv[kFilmUnroll];
 #pragma unroll
                                 for (uint32_t u = 0; u < kFilmUnroll; ++u) {
-                                    const size_t at = film_index(layout, npix, spp, s + u, pix);
+                                    const size_t at = film_index(layout, npix, spp_frame, s + u, pix);
                                     pfv[u] = pfilm[at];
                                     lv[u] = L[at];
                                 }
 #pragma unroll
                                 for (uint32_t u = 0; u < kFilmUnroll; ++u) splat(pfv[u], lv[u]);
                             }
-                            for (; s < spp; ++s) splat(pfilm[film_index(layout, npix, spp, s, pix)], L[film_index(layout, npix, spp, s, pix)]);
+                            for (; s < spp; ++s) splat(pfilm[film_index(layout, npix, spp_frame, s, pix)], L[film_index(layout, npix, spp_frame, s, pix)]);
                         }
                     for (int j = 0; j < BY; ++j)
                         for (int i = 0; i < BX; ++i)
@@ -1013,6 +1034,17 @@ __global__ __launch_bounds__(kBlock) void k_film_gather_block(const DeviceSensor
         for (int j = 0; j < BY; ++j)
             for (int i = 0; i < BX; ++i)
                 if (fx0 + i < se.film_w && fy0 + j < se.film_h) out[(size_t)(fy0 + j) * (size_t)se.film_w + (size_t)(fx0 + i)] = make_float4(xyz[j][i].x, xyz[j][i].y, xyz[j][i].z, wsum[j][i]);
+    }
+}
+// camera_sample.film of the drawn samples of a map frame alone: job i's word is its sample-major slot, which is also where the block gather looks (layout 0)
+template <int TH_ONE_COPY = 0> __global__ __launch_bounds__(kBlock) void k_film_positions_map(const DeviceSensor* __restrict__ sep, const uint32_t* __restrict__ jobs, uint64_t n, uint64_t seed,
+                                                               uint32_t sample_offset, float2* __restrict__ pfilm) {
+    const DeviceSensor& se = *sep;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        const uint32_t slot = jobs[i];
+        const SlotInfo si = slot_info(se, slot);
+        const uint64_t key = ts_stream_key(seed, si.px, si.py, sample_offset + si.sample);
+        pfilm[slot] = make_float2((float)si.px + ts_uniform(key, TS_DIM_FILM_X), (float)si.py + ts_uniform(key, TS_DIM_FILM_Y));
     }
 }
 
@@ -1215,10 +1247,12 @@ template <int TH_ONE_COPY = 0> __global__ __launch_bounds__(kBlock) void k_film_
 #ifndef TH_FILM_PACKED_PIPELINE
 #define TH_FILM_PACKED_PIPELINE 1
 #endif
-template <int BX, int BY>
-__global__ __launch_bounds__(kBlock) void k_film_gather_packed(const DeviceSensor* __restrict__ sep, const float* __restrict__ table, const float4* __restrict__ L, uint32_t spp, uint64_t seed,
+// SPP = MapSpp (a map frame): as in k_film_gather_block — max_spp lays the records out, counts[pix] bounds the sample loop.
+template <int BX, int BY, class SPP = uint32_t>
+__global__ __launch_bounds__(kBlock) void k_film_gather_packed(const DeviceSensor* __restrict__ sep, const float* __restrict__ table, const float4* __restrict__ L, SPP spp_arg, uint64_t seed,
                                                                uint32_t sample_offset, uint32_t layout, const uint4* __restrict__ side, float4* __restrict__ out, uint32_t xcd_bands) {
     const DeviceSensor& se = *sep;
+    const uint32_t spp_frame = spp_of_frame(spp_arg);
     __shared__ float s_table[256];
     for (uint32_t t = threadIdx.x; t < 256u; t += kBlock) s_table[t] = table[t];
     __syncthreads();
@@ -1296,6 +1330,7 @@ __global__ __launch_bounds__(kBlock) void k_film_gather_packed(const DeviceSenso
                     for (int sy = y0; sy <= y1; ++sy)
                         for (int sx = x0; sx <= x1; ++sx) {
                             const uint32_t pix = (uint32_t)(sy - se.band_y0) * (uint32_t)se.sb_w + (uint32_t)(sx - se.sb_min[0]);
+                            const uint32_t spp = spp_of_pixel(spp_arg, pix);  // samples this sample pixel offers
                             // offsets of the block's pixels from the sample pixel: the descriptor's range is relative to it
                             int rxi[BX], ryi[BY];
                             for (int i = 0; i < BX; ++i) rxi[i] = Xi[i] - sx;
@@ -1357,7 +1392,7 @@ __global__ __launch_bounds__(kBlock) void k_film_gather_packed(const DeviceSenso
                                     }
                             };
                             constexpr uint32_t kU = TH_FILM_PACKED_UNROLL;
-                            const float4* sp = L + film_index(layout, npix, spp, 0u, pix);  // sample 0 of this sample pixel; the next sample is `sstride` records on
+                            const float4* sp = L + film_index(layout, npix, spp_frame, 0u, pix);  // sample 0 of this sample pixel; the next sample is `sstride` records on
                             uint32_t s = 0;
 #if TH_FILM_PACKED_PIPELINE
                             // two batches of kU records in flight: the next batch's loads are issued before the current one is consumed (the frame has 2 waves per SIMD

@@ -48,6 +48,7 @@ int render_ao_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor*
     float* tmax = (float*)ctx->ao_tmax.p;
     float4* L = (float4*)ctx->Lbuf.p;
     ctx->last_L_count = 0;  // (until this frame's radiance is complete)
+    ctx->last_L_kind = 0;
 
     Timer tm(ctx, ctx->timing && stats);
     FrameEvents ev;

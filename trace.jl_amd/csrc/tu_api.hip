@@ -56,6 +56,7 @@ void trhip_shutdown(trhip_ctx* ctx) {
     release(ctx->dp_work);
     release(ctx->dp_in);
     release(ctx->cb_rc);
+    for (DevBuf* b : {&ctx->map_counts, &ctx->map_offsets, &ctx->map_jobs, &ctx->map_tmp, &ctx->map_word, &ctx->map_mv, &ctx->map_out}) release(*b);
     for (auto& pp : ctx->pipes) {
         for (auto& a : pp.q)
             for (auto& b : a) release(b);

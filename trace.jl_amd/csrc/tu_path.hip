@@ -1,6 +1,7 @@
 // tu_path.hip — PathIntegrator frames (classic per-depth wavefront, streaming wavefront, bands), the film pass, and the kernel-level entry
 // points that use the shading / film kernels.
 #include "th_host.h"
+#include "th_adaptive.h"
 
 // Film / sample-grid geometry derived from the sensor (film.jl:68-73, integrators/sampler.jl:13-20)
 void derive_sensor(const trhip_sensor* sn, DeviceSensor& d) {
@@ -149,6 +150,33 @@ void launch_film(trhip_ctx* ctx, hipStream_t st, const DeviceSensor& ds, const D
         else
             hipLaunchKernelGGL(k_film_gather, dim3(grid_for(ctx, npx, 8)), dim3(kBlock), 0, st, dsp, (const float*)ctx->table.p, L, (const float2*)ctx->pfilm.p, spp, layout, d_film);
     }
+}
+
+// ---- map frames (trhip_render_path_map): a per-pixel sample count instead of one spp ----
+// The records keep the dense max_spp layouts; the frame's camera samples are the job list (th_adaptive.h, k_map_expand) and the gather stops at counts[pix].
+struct MapFrame {
+    const uint32_t* counts;  // device: one per sample pixel
+    const uint32_t* jobs;    // device: `total` dense sample-major slots
+    uint64_t total;          // Σ counts
+};
+// Map frames take one film pass per case, whatever the film options say: a filter radius in (0, 1] goes through the fused pixel-group-major records with packed
+// descriptors and the 2 x 4 gather, anything wider through sample-major records, film positions and the 1 x 4 block gather.
+static bool map_uses_packed(const DeviceSensor& ds, uint32_t max_spp) {
+    const uint64_t npix = (uint64_t)ds.sb_w * ds.band_rows;
+    return std::fmax(ds.filter_radius[0], ds.filter_radius[1]) <= 1.0f && ds.filter_radius[0] > 0.0f && ds.filter_radius[1] > 0.0f && ((npix + 63u) / 64u) * 64u * max_spp < (1ull << 32);
+}
+static void launch_film_map(trhip_ctx* ctx, hipStream_t st, const DeviceSensor& ds, const DeviceSensor* dsp, const float4* L, const MapFrame& map, uint32_t max_spp, uint64_t seed,
+                            uint32_t sample_offset, float4* d_film, bool packed) {
+    const float* tb = (const float*)ctx->table.p;
+    if (packed) {  // k_raygen (its MapJobs form) wrote the drawn samples' records re-laid and with their descriptors
+        const uint64_t threads = (uint64_t)((ds.film_w + 1) / 2) * (uint64_t)((ds.film_h + 3) / 4);
+        hipLaunchKernelGGL((k_film_gather_packed<2, 4, MapSpp>), dim3(grid_for(ctx, threads, 8)), dim3(kBlock), 0, st, dsp, tb, L, MapSpp{map.counts, max_spp}, seed, sample_offset, 1u,
+                           (const uint4*)ctx->film_side.p + 1, d_film, 0u);
+        return;
+    }
+    hipLaunchKernelGGL(k_film_positions_map, dim3(grid_for(ctx, map.total, 8)), dim3(kBlock), 0, st, dsp, map.jobs, map.total, seed, sample_offset, (float2*)ctx->pfilm.p);
+    const uint64_t blocks = (uint64_t)ds.film_w * (uint64_t)((ds.film_h + 3) / 4);
+    hipLaunchKernelGGL((k_film_gather_block<1, 4, MapSpp>), dim3(grid_for(ctx, blocks, 8)), dim3(kBlock), 0, st, dsp, tb, L, (const float2*)ctx->pfilm.p, MapSpp{map.counts, max_spp}, 0u, d_film);
 }
 
 // ---- the frame scaffold's out-of-line part (th_host.h) ----
@@ -371,6 +399,9 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
     HIP_TRY(ctx, hipStreamSynchronize(st));
     ctx->last_L_count = total_slots;
     ctx->last_L_layout = 0;
+    ctx->last_L_npix = (uint32_t)npix;
+    ctx->last_L_spp = spp;
+    ctx->last_L_kind = 1;
     if (int rc = copy_back(ctx, out, out_is_device, d_film, film_bytes)) return rc;
     uint32_t left[8];
     HIP_TRY(ctx, hipMemcpy(left, lc, sizeof left, hipMemcpyDeviceToHost));
@@ -391,7 +422,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
 // One band of a frame (band == nullptr: the whole frame, the normal case).  A band is a range of whole tile rows; its DeviceSensor carries
 // the range and whether the film gather starts from zero or adds onto the bands before (th_scene.h).
 int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, int integrator, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out,
-                     bool out_is_device, trhip_stats* stats, const DeviceSensor* band) {
+                     bool out_is_device, trhip_stats* stats, const DeviceSensor* band, const MapFrame* map = nullptr) {
     HostClock hclk;
     if (!ctx || !scene || !sensor || !out) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
     if (!scene->committed) return fail(ctx, TRHIP_ERR_INVALID, "scene not committed");
@@ -430,14 +461,24 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         if (int rc = render_whitted_impl(ctx, scene, ds, sensor, spp, max_depth, seed, sample_offset, df, stats)) return rc;
         ctx->last_L_count = total_slots;
         ctx->last_L_layout = 0;
+        ctx->last_L_kind = 0;
         return copy_back(ctx, out, out_is_device, df, fb);
     }
-    if (!band && (ctx->streaming == 1 || (ctx->streaming < 0 && total_slots <= 96ull * scene->g->prims.size())) && ctx->traversal >= 2 && scene->wide_ok && scene->wide.root_cnt == 0 && scene->wide.root_ref != kRefNone && ctx->batch_paths == 0 && ctx->pipelines <= 1) {
+    if (!band && !map && (ctx->streaming == 1 || (ctx->streaming < 0 && total_slots <= 96ull * scene->g->prims.size())) && ctx->traversal >= 2 && scene->wide_ok && scene->wide.root_cnt == 0 && scene->wide.root_ref != kRefNone && ctx->batch_paths == 0 && ctx->pipelines <= 1) {
         bool declined = false;
         const int rc = render_stream_impl(ctx, scene, sensor, ds, spp, max_depth, seed, sample_offset, out, out_is_device, stats, &declined);
         if (!declined) return rc;
     }
-    // wavefront batch = whole sample passes; per path in flight: 2 x 3 queue float4 + 3 shadow float4 + 1 hit float4 = 160 B
+    // A map frame (`spp` is its max_spp) has no bands: its records, dense at max_spp, and the film pass's per-sample buffer must fit beside the queues.
+    const bool map_packed = map && map_uses_packed(ds, spp);
+    if (map) {
+        bool fits = false;
+        double free_gb = 0.0;
+        const double need = (double)total_slots * (map_packed ? 17.0 : 25.0) + (double)npix * 8.0 + (double)map->total * 4.0;
+        if (int rc = fits_in_hbm(ctx, 2.0 * need, ctx->Lbuf.bytes + ctx->pfilm.bytes + held_in_pipes(ctx), &fits, &free_gb)) return rc;  // half of what is free, as render_impl plans its bands
+        if (!fits) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "the per-sample buffers of a map frame (%.2f GB at max_spp %u) do not fit in half of free HBM (%.2f GB): there are no bands here", need * 1e-9, spp, free_gb);
+    }
+    // wavefront batch = whole sample passes (a map frame: ranges of its job list); per path in flight: 2 x 3 queue float4 + 3 shadow float4 + 1 hit float4 = 160 B
     uint64_t batch_paths = ctx->batch_paths;
     if (batch_paths == 0) {
         size_t free_b = 0, total_b = 0;
@@ -450,12 +491,17 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     spp_batch = std::min<uint64_t>(spp_batch, spp);
     // Several batches run concurrently (one per pipeline): the memory budget is shared and the frame is cut into at
     // least `pipelines` batches when it has that many sample passes.
-    const int want_pipes = std::max(1, std::min(ctx->pipelines, kMaxPipes));
+    const int want_pipes = map ? 1 : std::max(1, std::min(ctx->pipelines, kMaxPipes));  // (a map frame ignores "pipelines")
     spp_batch = std::max<uint64_t>(1, std::min<uint64_t>(spp_batch / want_pipes, (spp + want_pipes - 1) / want_pipes));
     while (npix * spp_batch >= (1ull << 31)) spp_batch = (spp_batch + 1) / 2;  // queue indices are 32-bit
-    const uint64_t n_batches_total = (spp + spp_batch - 1) / spp_batch;
+    const uint64_t total_jobs = map ? map->total : total_slots;  // the frame's camera samples: entries of the job list, or every slot
+    uint64_t P = npix * spp_batch;
+    if (map) {  // whole waves of jobs per batch; only the frame's last wave is partial
+        P = std::min<uint64_t>(std::max<uint64_t>(64, batch_paths / 64 * 64), (total_jobs + 63) / 64 * 64);
+        while (P >= (1ull << 31)) P = (P / 2 + 63) / 64 * 64;
+    }
+    const uint64_t n_batches_total = (total_jobs + P - 1) / P;
     const int NP = (int)std::min<uint64_t>(want_pipes, n_batches_total);
-    const uint64_t P = npix * spp_batch;
     const uint32_t cap = (uint32_t)queue_cap(P);
     const uint64_t Pphys = (uint64_t)cap * kSeg;
     if (int rc = upload(ctx, ctx->sensor, &ds, sizeof ds)) return rc;
@@ -492,11 +538,16 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
             if (int rc = ensure(ctx, pp.overflow[k], slab_bytes)) return rc;
     }
     // the radiance records: sample-major, or — when k_raygen can initialise them for the film pass (film_fused) — pixel-group-major, padded to whole groups of 64 pixels
-    const bool fused = film_fused(ctx, ds, spp);
+    const bool fused = map ? map_packed : film_fused(ctx, ds, spp);
     const uint64_t l_slots = fused ? ((npix + 63u) / 64u) * 64u * (uint64_t)spp : total_slots;
     if (int rc = ensure(ctx, ctx->poison, l_slots)) return rc;
     if (int rc = ensure(ctx, ctx->Lbuf, l_slots * sizeof(float4))) return rc;
-    if (int rc = ensure_film_samples(ctx, ds, total_slots)) return rc;
+    if (map) {
+        if (!map_packed)
+            if (int rc = ensure(ctx, ctx->pfilm, total_slots * sizeof(float2))) return rc;
+    } else if (int rc = ensure_film_samples(ctx, ds, total_slots)) {
+        return rc;
+    }
     const size_t film_bytes = (size_t)ds.film_w * ds.film_h * sizeof(float4);
     void* d_film;
     if (int rc = stage_output(ctx, out, out_is_device, film_bytes, &d_film)) return rc;
@@ -527,10 +578,10 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipes[pi].st, ev_start.e, 0));
         HIP_TRY(ctx, hipMemsetAsync(ctx->pipes[pi].counters.p, 0, sizeof(Counters), ctx->pipes[pi].st));
     }
-    for (uint64_t s0 = 0; s0 < spp; s0 += spp_batch) {
+    for (uint64_t j0 = 0; j0 < total_jobs; j0 += P) {  // (whole sample passes: j0 = s0 * npix)
         Pipe& pp = ctx->pipes[n_batches % NP];
         n_batches++;
-        const uint64_t nb = std::min<uint64_t>(spp_batch, spp - s0) * npix;
+        const uint64_t nb = std::min<uint64_t>(P, total_jobs - j0);
         // Within a batch, shadow rays of depth d (any-hit + accumulate) and closest-hit rays of depth d+1 are independent: two streams.
         hipStream_t ps = pp.st, ps2 = ctx->overlap ? pp.st2 : pp.st;
         Counters* ctr = (Counters*)pp.counters.p;
@@ -547,7 +598,10 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         float4* hits = (float4*)pp.hits.p;
         HIP_TRY(ctx, hipMemsetAsync(ctr, 0, offsetof(Counters, closest_total), ps));  // queue sizes + work cursors of this batch
         tm.begin(0, ps);
-        hipLaunchKernelGGL(k_raygen, dim3(grid_for(ctx, nb, 8)), dim3(kBlock), 0, ps, dsp, (uint32_t)(s0 * npix), (uint32_t)nb, seed, sample_offset, pq[0], cap, ctr, fused ? L : nullptr, spp, fside);
+        if (map)
+            hipLaunchKernelGGL((k_raygen<0, MapJobs>), dim3(grid_for(ctx, nb, 8)), dim3(kBlock), 0, ps, dsp, MapJobs{map->jobs, (uint32_t)j0}, (uint32_t)nb, seed, sample_offset, pq[0], cap, ctr, fused ? L : nullptr, spp, fside);
+        else
+            hipLaunchKernelGGL(k_raygen, dim3(grid_for(ctx, nb, 8)), dim3(kBlock), 0, ps, dsp, (uint32_t)j0, (uint32_t)nb, seed, sample_offset, pq[0], cap, ctr, fused ? L : nullptr, spp, fside);
         tm.end(0, ps);
         int cur = 0;
         for (int depth = 1; depth <= max_depth; ++depth) {
@@ -591,11 +645,15 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     }
     tm.begin(4, st);
     if (ctx->overlap) hipLaunchKernelGGL(k_apply_poison, dim3(grid_for(ctx, l_slots, 8)), dim3(kBlock), 0, st, L, (const uint8_t*)ctx->poison.p, l_slots);
-    launch_film(ctx, st, ds, dsp, L, total_slots, spp, seed, sample_offset, (float4*)d_film, fused);
+    if (map)
+        launch_film_map(ctx, st, ds, dsp, L, *map, spp, seed, sample_offset, (float4*)d_film, map_packed);
+    else
+        launch_film(ctx, st, ds, dsp, L, total_slots, spp, seed, sample_offset, (float4*)d_film, fused);
     tm.end(4, st);
     ctx->last_L_layout = fused ? 1u : 0u;
     ctx->last_L_npix = (uint32_t)npix;
     ctx->last_L_spp = spp;
+    ctx->last_L_kind = map ? 2u : band ? 0u : 1u;
     HIP_TRY(ctx, ev.end(st));
     HIP_TRY(ctx, hipGetLastError());
     hclk.tick("enqueue");
@@ -605,7 +663,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     if (int rc = copy_back(ctx, out, out_is_device, d_film, film_bytes)) return rc;
     if (stats) {
         std::memset(stats, 0, sizeof *stats);
-        stats->camera_samples = total_slots;
+        stats->camera_samples = total_jobs;
         for (int pi = 0; pi < NP; ++pi) {
             Counters h;
             HIP_TRY(ctx, hipMemcpy(&h, ctx->pipes[pi].counters.p, sizeof h, hipMemcpyDeviceToHost));
@@ -682,9 +740,45 @@ int render_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* se
     }
     ctx->last_L_count = 0;  // trhip_last_sample_radiance describes whole frames only
     ctx->last_L_layout = 0;
+    ctx->last_L_kind = 0;
     if (int rc = copy_back(ctx, out, out_is_device, d_film, film_bytes)) return rc;
     if (stats) *stats = sum;
     return 0;
+}
+// trhip_render_path_map[_device]: the refusals that belong to the map, in the header's order, then the job list, then the frame.
+int render_map_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, const void* counts, bool on_device, uint32_t max_spp, int max_depth, uint64_t seed, uint32_t sample_offset,
+                    void* out, trhip_stats* stats) {
+    if (!ctx || !scene || !sensor || !counts || !out) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
+    if (max_spp == 0) return fail(ctx, TRHIP_ERR_INVALID, "max_spp must be >= 1");
+    DeviceSensor ds;
+    derive_sensor(sensor, ds);
+    if (ds.film_w <= 0 || ds.film_h <= 0 || ds.sb_w <= 0 || ds.sb_h <= 0) return fail(ctx, TRHIP_ERR_INVALID, "empty film");
+    const uint64_t npix = (uint64_t)ds.sb_w * ds.sb_h;
+    if (npix >= (1ull << 31) || npix * max_spp >= (1ull << 32)) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "more than 2^32 camera samples at max_spp in a map frame");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint64_t total = 0;
+    bool above = false;
+    if (on_device) {
+        if (ctx->last_L_kind == 2) ctx->last_L_count = 0;  // the counts of the map frame before go with this copy
+        if (int rc = ensure(ctx, ctx->map_counts, npix * sizeof(uint32_t))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->map_counts.p, counts, npix * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        const uint32_t* c = (const uint32_t*)counts;
+        for (uint64_t p = 0; p < npix; ++p) {
+            total += c[p];
+            above = above || c[p] > max_spp;
+        }
+        if (!above && total)
+            if (int rc = upload(ctx, ctx->map_counts, counts, npix * sizeof(uint32_t))) return rc;
+    }
+    if (!above && (on_device || total))
+        if (int rc = map_job_list(ctx, (uint32_t)npix, max_spp, on_device, &total, &above)) return rc;
+    if (above) return fail(ctx, TRHIP_ERR_INVALID, "a count of the sample map lies above max_spp = %u", max_spp);
+    if (total == 0) return fail(ctx, TRHIP_ERR_INVALID, "the sample map draws no sample");
+    const MapFrame map{(const uint32_t*)ctx->map_counts.p, (const uint32_t*)ctx->map_jobs.p, total};
+    ctx->last_L_count = 0;  // (until this frame's radiance is complete: map_counts already belongs to it)
+    ctx->last_L_kind = 0;
+    return render_impl_band(ctx, scene, sensor, 1, max_spp, max_depth, seed, sample_offset, out, on_device, stats, nullptr, &map);
 }
 }  // namespace
 
@@ -721,13 +815,25 @@ int trhip_render_whitted(trhip_ctx* ctx, const trhip_scene* sc, const trhip_sens
 int trhip_render_whitted_device(trhip_ctx* ctx, const trhip_scene* sc, const trhip_sensor* sn, uint32_t spp, int max_depth, uint64_t seed, uint32_t off, void* d_out, trhip_stats* st) {
     return render_impl(ctx, sc, sn, 0, spp, max_depth, seed, off, d_out, true, st);
 }
+int trhip_render_path_map(trhip_ctx* ctx, const trhip_scene* sc, const trhip_sensor* sn, const uint32_t* counts, uint32_t max_spp, int max_depth, uint64_t seed, uint32_t off, float* out,
+                          trhip_stats* st) {
+    return render_map_impl(ctx, sc, sn, counts, false, max_spp, max_depth, seed, off, out, st);
+}
+int trhip_render_path_map_device(trhip_ctx* ctx, const trhip_scene* sc, const trhip_sensor* sn, const void* d_counts, uint32_t max_spp, int max_depth, uint64_t seed, uint32_t off, void* d_out,
+                                 trhip_stats* st) {
+    return render_map_impl(ctx, sc, sn, d_counts, true, max_spp, max_depth, seed, off, d_out, st);
+}
 int trhip_last_sample_radiance(trhip_ctx* ctx, float* out, uint64_t n_floats) {
     if (!ctx || !out) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
     if (n_floats != ctx->last_L_count * 3) return fail(ctx, TRHIP_ERR_INVALID, "expected %llu floats", (unsigned long long)(ctx->last_L_count * 3));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int rc = ensure(ctx, ctx->scratch[0], n_floats * sizeof(float))) return rc;
     const uint64_t n = ctx->last_L_count;
-    if (n) hipLaunchKernelGGL(k_export_L, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)ctx->Lbuf.p, n, (float*)ctx->scratch[0].p, ctx->last_L_layout, ctx->last_L_npix, ctx->last_L_spp);
+    if (n && ctx->last_L_kind == 2)  // a map frame: the records that were drawn, +0 elsewhere
+        hipLaunchKernelGGL(k_export_L_map, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)ctx->Lbuf.p, n, (float*)ctx->scratch[0].p, ctx->last_L_layout, ctx->last_L_npix,
+                           ctx->last_L_spp, (const uint32_t*)ctx->map_counts.p);
+    else if (n)
+        hipLaunchKernelGGL(k_export_L, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)ctx->Lbuf.p, n, (float*)ctx->scratch[0].p, ctx->last_L_layout, ctx->last_L_npix, ctx->last_L_spp);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(out, ctx->scratch[0].p, n_floats * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
@@ -792,6 +898,9 @@ int trhip_film_accumulate(trhip_ctx* ctx, const trhip_sensor* sn, uint32_t spp, 
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->last_L_count = n;
     ctx->last_L_layout = 0;
+    ctx->last_L_npix = (uint32_t)((uint64_t)ds.sb_w * ds.sb_h);
+    ctx->last_L_spp = spp;
+    ctx->last_L_kind = 1;  // (trhip_last_sample_stats reads a caller's records too)
     HIP_TRY(ctx, hipMemcpy(out_xyzw, ctx->film.p, film_bytes, hipMemcpyDeviceToHost));
     return 0;
 }

@@ -415,6 +415,8 @@ include("TraceHIPClipMotion.jl")
 include("TraceHIPUpsampleMotion.jl")
 # accumulate_split (trhip_temporal_split) and film_add (trhip_film_add), likewise (tests/golden/julia_shim_direct_split_calls.json)
 include("TraceHIPDirectSplit.jl")
+# render_path_map (trhip_render_path_map), sample_map and AdaptivePathIntegrator, likewise (tests/golden/julia_shim_adaptive_calls.json)
+include("TraceHIPAdaptive.jl")
 
 # SPPMIntegrator (integrators/sppm.jl:132-173) on the device: trhip_render_sppm returns the film after set_image!
 # (film.jl:195-202).  `seed` selects the seeded stream of the camera pass (the reference draws from the global RNG there).
