@@ -403,6 +403,61 @@ int trhip_render_ao(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor
 int trhip_render_ao_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset,
                            const trhip_ao_params* params, void* d_out_xyzw, trhip_stats* stats);
 
+/* ---- environment map and sky-lit frames (since ABI 3001, added without a version change: nothing existing moved) ---------------
+ * An environment E(w): the radiance that arrives from direction w.  It is an OCTAHEDRAL map of n x n RGB texels, chosen because its
+ * lookup is plain arithmetic (no atan2, no acos) and therefore reproducible bit for bit; docs/design/25-sky.md holds the
+ * specification.  The reference has no environment light (lights/light.jl:41 returns 0 for an escaping ray): this is the library's own.
+ *   rgb            n * n * 3 floats, row j, column i: texel (i, j) at rgb[3 * (j * n + i)].  Texel centre (i, j) lies at the point
+ *                  (px, py) = ((i + 0.5) / n * 2 - 1, (j + 0.5) / n * 2 - 1) of the octahedral square.
+ *   world_to_env   9 floats, row-major R[3 * r + c]: the lookup multiplies every direction by it, the identity included.
+ * The handle keeps (n + 2)^2 float4 texels in HBM: the map and a one-texel gutter filled at creation.  The gutter texel (i, j) with i outside
+ * [0, n) is the interior texel (clamp(i), n - 1 - j); with j outside, (n - 1 - i, clamp(j)); a corner applies one rule after the other (the
+ * octahedral edge wrap), so the lookup needs no clamp and no branch at the border.
+ * The lookup, one Float32 operation per line, in this order, no contraction, `/` correctly rounded:
+ *   e_r = (R[r][0] * w.x + R[r][1] * w.y) + R[r][2] * w.z                      r = 0, 1, 2
+ *   s = (|e.x| + |e.y|) + |e.z|;   !(s > 0) or s not finite: E = (+0, +0, +0)   (zero, NaN and Inf directions)
+ *   px = e.x / s,  py = e.y / s
+ *   e.z < 0:  qx = (1 - |py|) * sgn(px),  qy = (1 - |px|) * sgn(py),  (px, py) = (qx, qy)       sgn(v) = v < 0 ? -1 : 1
+ *   fx = (px * 0.5 + 0.5) * n - 0.5,  fy likewise                              (three operations each)
+ *   x0 = floor(fx),  tx = fx - x0,  y0 = floor(fy),  ty = fy - y0;  x0, y0 lie in [-1, n - 1] and are clamped there as integers
+ *   per channel: lerp(lerp(T[x0, y0], T[x0 + 1, y0], tx), lerp(T[x0, y0 + 1], T[x0 + 1, y0 + 1], tx), ty),  lerp(a, b, t) = a + t * (b - a)
+ * (a == b returns a exactly: a constant map evaluates to its constant in every bit).
+ * TRHIP_ERR_INVALID: a null pointer; n == 0 or n > 4096; a texel that is not finite or is negative (the contributions of a sky frame's
+ * any-hit queue carry no poison bits and must be finite); a matrix entry that is not finite — all checked before the context is looked at.
+ * trhip_env_eval evaluates `count` directions (count * 3 floats) on the device into count * 3 floats: the lookup on its own, for tests
+ * and tools.  An environment belongs to the context it was created with; free it before that context is shut down. */
+typedef struct trhip_env trhip_env;
+int trhip_env_create(trhip_ctx* ctx, const float* rgb, uint32_t n, const float world_to_env[9], trhip_env** out);
+void trhip_env_free(trhip_env* env);
+int trhip_env_size(const trhip_env* env, uint32_t* n);
+int trhip_env_eval(trhip_ctx* ctx, const trhip_env* env, const float* dirs3, uint64_t count, float* out_rgb3);
+
+/* A sky-lit frame: trhip_render_ao (above) with two substitutions.  The camera samples, the closest-hit walk, the occlusion ray (o, d,
+ * t_max, the 1e-6f offset, check_direction) and the any-hit walk are that frame's, step for step; then
+ *   the contribution of an unoccluded occlusion ray is c = E(wi) * scale per channel — times the base colour, per channel, under
+ *     TRHIP_SKY_ALBEDO (zero for a primitive without a material) — where trhip_render_ao has 1 or the base colour;
+ *   a camera ray that misses returns L = E(d) * scale for its direction d, or 0 under TRHIP_SKY_HIDE_BACKGROUND, where trhip_render_ao
+ *     has its background.
+ * With cosine-distributed wi the pdf cancels cos / pi, so c is the unbiased one-sample estimate of direct diffuse lighting under the
+ * environment.  The per-sample L goes through the path renderer's film pass; trhip_last_sample_radiance returns it.  Statistics are
+ * trhip_render_ao's; there are no bands (TRHIP_ERR_UNSUPPORTED when the per-sample buffers do not fit in free HBM).
+ * TRHIP_ERR_INVALID: trhip_render_ao's refusals in its order (the parameter block first, before any handle), with `scale` not finite or
+ * negative in the place of its background; then a null env, an env of another context, and a scale that takes the map's largest texel
+ * to +Inf.  trhip_sky_default_params needs no context and no GPU. */
+#define TRHIP_SKY_ALBEDO 1u          /* c = E(wi) * scale * base colour */
+#define TRHIP_SKY_HIDE_BACKGROUND 2u /* a camera ray that misses returns 0 */
+typedef struct {
+    float max_distance;       /* reach of the occlusion rays: > 0 or +Inf */
+    float scale;              /* multiplies every lookup: finite, >= 0 */
+    uint32_t flags;           /* TRHIP_SKY_ALBEDO | TRHIP_SKY_HIDE_BACKGROUND */
+    uint32_t reserved;        /* 0 */
+} trhip_sky_params;           /* 16 bytes */
+int trhip_sky_default_params(trhip_sky_params* out); /* {+Inf, 1, 0, 0} */
+int trhip_render_sky(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset,
+                     const trhip_env* env, const trhip_sky_params* params, float* out_xyzw, trhip_stats* stats);
+int trhip_render_sky_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset,
+                            const trhip_env* env, const trhip_sky_params* params, void* d_out_xyzw, trhip_stats* stats);
+
 /* ---- edge-avoiding denoiser for path / Whitted films (since ABI 3001, added without a version change: nothing existing moved) ----
  * An à-trous wavelet filter after Dammertz et al. 2010 ("Edge-Avoiding À-Trous Wavelet Transform for fast Global Illumination
  * Filtering") on the film state of a path or Whitted render, guided by the three planes of trhip_render_aov for the same sensor,
@@ -415,7 +470,7 @@ int trhip_render_ao_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip
  *   out_xyzw  the layout of xyzw; may be xyzw itself
  * A pixel is a SURFACE pixel when its filter weight, its total plane weight and its hit weight are positive, the hit weight is at
  * least min_coverage times the total weight, and its normal, position and colour are finite.  Only surface pixels are filtered and
- * only surface pixels are read as neighbours; every other pixel (a miss — the library has no environment light —, a silhouette
+ * only surface pixels are read as neighbours; every other pixel (a miss — path and Whitted frames have no environment term —, a silhouette
  * pixel under min_coverage, a NaN) is returned with its input bits.  The .w lane (the filter weight sum) is always returned as given.
  * iterations = 0 copies.  The step of iteration i is 2^i pixels and its colour sigma is sigma_colour * 2^-i.
  * TRHIP_ERR_INVALID: a null pointer, a zero dimension, iterations > 6, a sigma or albedo_floor that is not finite and > 0,
@@ -587,7 +642,7 @@ int trhip_denoise_var_device(trhip_ctx* ctx, const void* d_xyzw, const void* d_p
  * Joint bilateral upsampling (Kopf et al. 2007): the path frame is rendered through a sensor of lower resolution, the feature planes through
  * both sensors, and the full-size film is reconstructed from the low one with the normal and plane-distance edge tests of trhip_denoise
  * between a full-size pixel and its low-resolution neighbours.  Base-colour demodulation puts material edges back at full resolution; a miss
- * carries exactly zero radiance (the library has no environment light), so silhouettes are put back by coverage.  Specified operation by
+ * carries exactly zero radiance (path and Whitted frames have no environment term), so silhouettes are put back by coverage.  Specified operation by
  * operation in docs/design/17-upscale.md; bit-reproducible.
  *   lo_xyzw, lo_planes   lo_height * lo_width float4 and * 3 float4: what trhip_render_path (or trhip_denoise, trhip_temporal*) and
  *                        trhip_render_aov wrote for the low-resolution sensor

@@ -156,6 +156,21 @@ class AoParams(C.Structure):
 AO_ALBEDO = 1  # TRHIP_AO_ALBEDO
 
 
+class SkyParams(C.Structure):
+    """trhip_sky_params (16 bytes)"""
+    _fields_ = [
+        ("max_distance", C.c_float),
+        ("scale", C.c_float),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+SKY_ALBEDO = 1  # TRHIP_SKY_ALBEDO
+SKY_HIDE_BACKGROUND = 2  # TRHIP_SKY_HIDE_BACKGROUND
+ENV_MAX_N = 4096  # the largest map trhip_env_create takes
+
+
 class TemporalParams(C.Structure):
     """trhip_temporal_params (72 bytes)"""
     _fields_ = [
@@ -387,6 +402,13 @@ SIGNATURES = {
                                           C.POINTER(Stats)]),
     "trhip_temporal_upsample_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP, C.c_uint32, C.c_uint32, C.POINTER(TemporalUpsampleParams), _VP, _VP, _VP,
                                                  C.POINTER(Stats)]),
+    "trhip_env_create": (C.c_int, [_VP, _F, C.c_uint32, _F, C.POINTER(_VP)]),
+    "trhip_env_free": (None, [_VP]),
+    "trhip_env_size": (C.c_int, [_VP, _U32]),
+    "trhip_env_eval": (C.c_int, [_VP, _VP, _F, C.c_uint64, _F]),
+    "trhip_sky_default_params": (C.c_int, [C.POINTER(SkyParams)]),
+    "trhip_render_sky": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, C.POINTER(SkyParams), _F, C.POINTER(Stats)]),
+    "trhip_render_sky_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, C.POINTER(SkyParams), _VP, C.POINTER(Stats)]),
     "trhip_render_aov_ids": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _F, _VP, _VP, C.POINTER(Stats)]),
     "trhip_render_aov_ids_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, _VP, _VP, C.POINTER(Stats)]),
     "trhip_temporal_motion_default_params": (C.c_int, [C.POINTER(TemporalMotionParams)]),

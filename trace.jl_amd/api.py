@@ -1390,6 +1390,157 @@ class AmbientOcclusionIntegrator(_SamplerIntegrator):
         return out
 
 
+# ---- environment map and sky-lit frames (include/tracehip.h, trhip_env, trhip_render_sky) ----------------------------------------------------
+def octahedral_directions(n: int) -> np.ndarray:
+    """The unit direction (environment space) through the centre of every texel of an n x n octahedral map, (n, n, 3) Float64 indexed [j, i]: the inverse of the map
+    the lookup applies (docs/design/25-sky.md).  Texel centre (i, j) is the point ((i + 0.5) / n * 2 - 1, (j + 0.5) / n * 2 - 1) of the square; outside the diamond
+    |px| + |py| <= 1 lies the lower hemisphere, folded over the diamond's edges."""
+    if not 1 <= n <= _ffi.ENV_MAX_N:
+        raise TraceHipError(f"an environment map has n in [1, {_ffi.ENV_MAX_N}], not {n}")
+    c = (np.arange(n, dtype=np.float64) + 0.5) / n * 2.0 - 1.0
+    px, py = np.meshgrid(c, c, indexing="xy")
+    z = 1.0 - np.abs(px) - np.abs(py)
+    sgn = lambda v: np.where(v < 0, -1.0, 1.0)
+    x = np.where(z < 0, (1.0 - np.abs(py)) * sgn(px), px)
+    y = np.where(z < 0, (1.0 - np.abs(px)) * sgn(py), py)
+    d = np.stack([x, y, z], axis=-1)
+    return d / np.linalg.norm(d, axis=-1, keepdims=True)
+
+
+class Environment:
+    """An environment E(w), the radiance arriving from direction w: an octahedral map of n x n RGB texels (trhip_env; docs/design/25-sky.md).  `texels` is (n, n, 3),
+    row j, column i, finite and >= 0, n in [1, 4096]; `world_to_env` a 3 x 3 matrix applied to every direction before the lookup (None: the identity).  The lookup
+    itself is specified bit for bit; the texels are data, however they were made.  A device copy is created per context on first use and freed with this object."""
+
+    def __init__(self, texels, world_to_env=None):
+        t = np.asarray(texels)
+        if t.ndim != 3 or t.shape[0] != t.shape[1] or t.shape[2] != 3:
+            raise TraceHipError(f"Environment: texels must be (n, n, 3), not {t.shape}")
+        if not 1 <= t.shape[0] <= _ffi.ENV_MAX_N:
+            raise TraceHipError(f"Environment: n must be in [1, {_ffi.ENV_MAX_N}], not {t.shape[0]}")
+        t = np.ascontiguousarray(t, dtype=np.float32)
+        if not np.isfinite(t).all() or (t < 0).any():
+            raise TraceHipError("Environment: every texel must be finite and >= 0")
+        r = np.eye(3, dtype=np.float32) if world_to_env is None else np.asarray(world_to_env)
+        if r.shape != (3, 3):
+            raise TraceHipError(f"Environment: world_to_env must be 3 x 3, not {r.shape}")
+        r = np.ascontiguousarray(r, dtype=np.float32)
+        if not np.isfinite(r).all():
+            raise TraceHipError("Environment: every entry of world_to_env must be finite")
+        self.texels, self.world_to_env = t, r
+        self._handles = {}  # id(context) -> (context, trhip_env*)
+
+    @property
+    def n(self) -> int:
+        return int(self.texels.shape[0])
+
+    @classmethod
+    def constant(cls, rgb) -> "Environment":
+        """The same radiance from every direction: one texel."""
+        return cls(np.asarray(rgb, dtype=np.float32).reshape(1, 1, 3))
+
+    @classmethod
+    def gradient(cls, zenith, horizon, ground, up=(0, 0, 1), n: int = 64) -> "Environment":
+        """A sky that runs linearly in cos(angle to `up`) from `horizon` to `zenith` above the horizon and from `horizon` to `ground` below it."""
+        u = np.asarray(up, dtype=np.float64)
+        if u.shape != (3,) or not np.isfinite(u).all() or not np.linalg.norm(u) > 0:
+            raise TraceHipError(f"Environment.gradient: up must be a non-zero vector of 3, not {up}")
+        zenith, horizon, ground = (np.asarray(c, dtype=np.float64).reshape(3) for c in (zenith, horizon, ground))
+        t = np.clip(octahedral_directions(int(n)) @ (u / np.linalg.norm(u)), -1.0, 1.0)[..., None]
+        return cls(np.where(t >= 0, horizon + t * (zenith - horizon), horizon - t * (ground - horizon)))
+
+    @classmethod
+    def from_latlong(cls, image, n: Optional[int] = None) -> "Environment":
+        """From a latitude-longitude image (H, W, 3), +z up: row 0 is the zenith, the last row the nadir, column 0 starts at azimuth 0 (the +x axis) and the azimuth
+        grows towards +y.  Every texel centre's direction is found through the inverse octahedral map and the image is looked up there, bilinearly between pixel
+        centres (wrapping in azimuth, clamped at the poles).  n defaults to the image's height, at most 4096."""
+        img = np.asarray(image, dtype=np.float64)
+        if img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+            raise TraceHipError(f"Environment.from_latlong: the image must be (H, W, 3), not {img.shape}")
+        h, w = img.shape[:2]
+        d = octahedral_directions(int(n) if n is not None else min(h, _ffi.ENV_MAX_N))
+        v = np.arccos(np.clip(d[..., 2], -1.0, 1.0)) / np.pi * h - 0.5
+        u = (np.arctan2(d[..., 1], d[..., 0]) / (2.0 * np.pi) % 1.0) * w - 0.5
+        u0, v0 = np.floor(u), np.floor(v)
+        tu, tv = (u - u0)[..., None], (v - v0)[..., None]
+        c0, c1 = u0.astype(np.int64) % w, (u0.astype(np.int64) + 1) % w
+        r0, r1 = np.clip(v0.astype(np.int64), 0, h - 1), np.clip(v0.astype(np.int64) + 1, 0, h - 1)
+        top = img[r0, c0] * (1.0 - tu) + img[r0, c1] * tu
+        bottom = img[r1, c0] * (1.0 - tu) + img[r1, c1] * tu
+        return cls(top * (1.0 - tv) + bottom * tv)
+
+    def _handle(self, ctx: _ffi.Context):
+        """This map's trhip_env on `ctx`, created on first use."""
+        if id(ctx) not in self._handles:
+            h = C.c_void_p()
+            ctx.check(_ffi.lib().trhip_env_create(ctx._h, _ffi.fptr(self.texels), self.n, _ffi.fptr(self.world_to_env), C.byref(h)))
+            self._handles[id(ctx)] = (ctx, h)
+        return self._handles[id(ctx)][1]
+
+    def eval(self, dirs, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
+        """E(w) for every direction of `dirs` (..., 3), evaluated on the device by the lookup the sky frame uses (trhip_env_eval)."""
+        d = _ffi.f32(dirs)
+        if d.ndim < 1 or d.shape[-1] != 3:
+            raise TraceHipError(f"Environment.eval: directions must be (..., 3), not {d.shape}")
+        ctx = ctx or _ffi.default_context()
+        out = np.empty_like(d)
+        ctx.check(_ffi.lib().trhip_env_eval(ctx._h, self._handle(ctx), _ffi.fptr(d), d.size // 3, _ffi.fptr(out)))
+        return out
+
+    def close(self):
+        for ctx, h in self._handles.values():
+            if ctx._h:  # (a context that was shut down took its device memory with it)
+                _ffi.lib().trhip_env_free(h)
+        self._handles = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SkyIntegrator(_SamplerIntegrator):
+    """A sky-lit clay or albedo render (trhip_render_sky; docs/design/25-sky.md): AmbientOcclusionIntegrator's frame in which the occlusion ray that escapes brings
+    back `environment`'s radiance from its direction, times `scale` (times the base colour with ``albedo``), and a camera ray that misses shows the environment (or 0
+    with ``hide_background``).  No lights, no BSDF; one ray per camera sample, quality comes from the sampler's samples_per_pixel.  The film has the path frame's
+    weights, so it goes through Denoiser.denoise with AOVIntegrator's planes, as an AO film does."""
+
+    def __init__(self, camera: PerspectiveCamera, sampler: SeededSampler, environment: Environment, max_distance: float = math.inf, albedo: bool = False, scale: float = 1.0,
+                 hide_background: bool = False):
+        super().__init__(camera, sampler, 1)
+        if not isinstance(environment, Environment):
+            raise TraceHipError(f"SkyIntegrator: environment must be an Environment, not {type(environment).__name__}")
+        max_distance, scale = float(max_distance), float(scale)
+        if not max_distance > 0.0:
+            raise TraceHipError(f"SkyIntegrator: max_distance must be > 0 or inf, not {max_distance}")
+        if not (scale >= 0.0 and math.isfinite(scale)):
+            raise TraceHipError(f"SkyIntegrator: scale must be finite and >= 0, not {scale}")
+        p = _ffi.SkyParams()
+        rc = _ffi.lib().trhip_sky_default_params(C.byref(p))
+        if rc:
+            raise TraceHipError(f"trhip_sky_default_params failed ({rc})")
+        p.max_distance, p.scale, p.flags = max_distance, scale, (_ffi.SKY_ALBEDO if albedo else 0) | (_ffi.SKY_HIDE_BACKGROUND if hide_background else 0)
+        self.environment, self.params = environment, p
+
+    def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None) -> np.ndarray:
+        """Render into camera.film (and return xyzw, H x W x 4).  With ``device_out`` (a device pointer to H * W * 4 floats) the film accumulators are written there
+        instead, nothing is copied to the host and None is returned."""
+        flat = scene.flatten(ctx)
+        ctx = flat.ctx
+        sn, st, smp, L, env = self.camera.sensor(), _ffi.Stats(), self.sampler, _ffi.lib(), self.environment._handle(flat.ctx)
+        if device_out is not None:
+            ctx.check(L.trhip_render_sky_device(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, env, C.byref(self.params), C.c_void_p(device_out), C.byref(st)))
+            self.stats = st
+            return None
+        h, w = self.camera.film.size
+        out = np.empty((h, w, 4), dtype=np.float32)
+        ctx.check(L.trhip_render_sky(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, env, C.byref(self.params), _ffi.fptr(out), C.byref(st)))
+        self.stats = st
+        self.camera.film.set_xyzw(out)
+        return out
+
+
 # ---- edge-avoiding denoiser (include/tracehip.h, trhip_denoise) ----------------------------------------------------------------------------
 class Denoiser:
     """Edge-avoiding à-trous filter (Dammertz et al. 2010, Tukey's biweight as the edge-stopping function) for the film of a PathIntegrator or WhittedIntegrator render,

@@ -1,4 +1,4 @@
-// th_camera.h — the camera-ray front half that tu_aov.hip and tu_ao.hip share: every camera ray of the frame in one queue (the path integrator's k_raygen), walked to its
+// th_camera.h — the camera-ray front half that tu_aov.hip and the occlusion frames (th_occlusion.h: tu_ao.hip, tu_sky.hip) share: every camera ray of the frame in one queue (the path integrator's k_raygen), walked to its
 // first hit.  camera_pass_size checks the scene, spp and the film and sizes the queue; the caller's fit check and its own buffers go between the two; camera_pass_trace uploads
 // the sensor, grows the buffers, begins the frame's events and runs k_raygen and the closest-hit walk (Timer classes 0 and 1).
 // A header of these two units, not a function of tu_path.hip or th_host.h: k_raygen is instantiated by the unit that launches it, so each unit's device code stays what it was.

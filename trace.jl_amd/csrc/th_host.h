@@ -3,7 +3,8 @@
 // and linked into the one shared object): tu_api.hip (context, options, communicator), tu_scene.hip (scene flattening, commit, upload),
 // tu_lbvh.hip (BVH build on the device), tu_trace.hip / tu_trace3.hip / tu_trace3c.hip / tu_trace7.hip / tu_trace8.hip (traversal launches and entry points),
 // tu_path.hip (PathIntegrator frames, film, and the out-of-line part of the frame scaffold below: the stats functions), tu_aov.hip (first-hit feature buffers),
-// tu_ao.hip (ambient occlusion; the two share their camera-ray front half, th_camera.h), tu_denoise.hip (the à-trous filters), tu_temporal.hip (temporal reprojection), tu_upscale.hip, tu_display.hip (the 8-bit display pass), tu_temporal_upsample.hip — these five, the
+// tu_ao.hip (ambient occlusion; the two share their camera-ray front half, th_camera.h), tu_env.hip (the environment map, th_env.h) and tu_sky.hip (the sky-lit frame; it and
+// tu_ao.hip share the whole frame around their spawn kernels, th_occlusion.h), tu_denoise.hip (the à-trous filters), tu_temporal.hip (temporal reprojection), tu_upscale.hip, tu_display.hip (the 8-bit display pass), tu_temporal_upsample.hip — these five, the
 // image-space passes, share their host side through th_image_pass.h —, tu_adaptive.hip (the job list of a map frame, the sample statistics and the sample map; th_adaptive.h), tu_whitted.hip, tu_sppm.hip.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -415,6 +415,8 @@ include("TraceHIPClipMotion.jl")
 include("TraceHIPUpsampleMotion.jl")
 # accumulate_split (trhip_temporal_split) and film_add (trhip_film_add), likewise (tests/golden/julia_shim_direct_split_calls.json)
 include("TraceHIPDirectSplit.jl")
+# Environment (trhip_env) and SkyIntegrator (trhip_render_sky), likewise (tests/golden/julia_shim_sky_calls.json)
+include("TraceHIPSky.jl")
 # render_path_map (trhip_render_path_map), sample_map and AdaptivePathIntegrator, likewise (tests/golden/julia_shim_adaptive_calls.json)
 include("TraceHIPAdaptive.jl")
 
