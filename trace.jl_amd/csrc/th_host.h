@@ -1,11 +1,8 @@
-// th_host.h — what the translation units of libtracehip.so share on the host side: the context and scene objects behind the opaque
-// handles of include/tracehip.h, error / buffer helpers, and the functions one unit calls in another.  Units (each compiled on its own
-// and linked into the one shared object): tu_api.hip (context, options, communicator), tu_scene.hip (scene flattening, commit, upload),
-// tu_lbvh.hip (BVH build on the device), tu_trace.hip / tu_trace3.hip / tu_trace3c.hip / tu_trace7.hip / tu_trace8.hip (traversal launches and entry points),
-// tu_path.hip (PathIntegrator frames, film, and the out-of-line part of the frame scaffold below: the stats functions), tu_aov.hip (first-hit feature buffers),
-// tu_ao.hip (ambient occlusion; the two share their camera-ray front half, th_camera.h), tu_env.hip (the environment map, th_env.h) and tu_sky.hip (the sky-lit frame; it and
-// tu_ao.hip share the whole frame around their spawn kernels, th_occlusion.h), tu_denoise.hip (the à-trous filters), tu_temporal.hip (temporal reprojection), tu_upscale.hip, tu_display.hip (the 8-bit display pass), tu_temporal_upsample.hip — these five, the
-// image-space passes, share their host side through th_image_pass.h —, tu_adaptive.hip (the job list of a map frame, the sample statistics and the sample map; th_adaptive.h), tu_whitted.hip, tu_sppm.hip.
+// th_host.h — what the translation units of libtracehip.so (csrc/tu_*.hip, each compiled on its own and linked into the one shared object) share on the host side: the
+// context and scene objects behind the opaque handles of include/tracehip.h, error / buffer helpers, the frame scaffold, and the functions one unit calls in another.
+// Three pieces carry the host's bookkeeping.  th_owned.h: DevBuf, OwnedEvent, OwnedStream and Pipe free what they hold and cannot be copied — ownership is decided THERE, by
+// which object a member is declared in: trhip_ctx, trhip_scene, SceneGeometry and trhip_env are torn down by `delete`, a function's temporaries by its end, and nothing here
+// keeps a list of buffers.  th_options.h: the options, one table row each, behind ctx->opt.  LastRecords below: what Lbuf holds after the last frame, written as a whole.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,11 +15,11 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
-#pragma GCC visibility push(default)
-#include "../../include/tracehip.h"
-#pragma GCC visibility pop
+#include "th_options.h"  // (and include/tracehip.h)
+#include "th_owned.h"
 #include "th_bvh.h"
 #include "th_kernels.h"
 #include "th_trace2.h"
@@ -39,100 +36,39 @@ using namespace th;
 // ---- context ------------------------------------------------------------------------------------------------------------------
 extern thread_local std::string g_init_error;  // tu_api.hip: the message of a failed trhip_init
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
-constexpr int kMaxPipes = 8;
-// One wavefront pipeline: its own queues, counters and stream pair.  Several batches of one frame run concurrently on
-// different pipelines so that the long single-ray tail of one batch's traversal launch overlaps the bulk of another's.
-struct Pipe {
-    hipStream_t st = nullptr, st2 = nullptr;
-    hipEvent_t ev_shade = nullptr, ev_any = nullptr, ev_any2 = nullptr, ev_done = nullptr;
-    DevBuf q[2][3], sq[3], sq2[3], hits, counters, overflow[2];  // sq / sq2: the shadow queues of odd / even depths (any(d) may still run while shade(d+1) fills the other)
+// What Lbuf holds after the last frame (trhip_last_sample_radiance, trhip_last_sample_stats).  A function that writes Lbuf sets `ctx->last = LastRecords{}` ("no records")
+// after its refusals and before it first grows Lbuf, and assigns the whole struct once its stream has been synchronised: a frame that fails in between leaves no records.
+struct LastRecords {
+    uint64_t count = 0;  // float4 entries valid in Lbuf
+    uint32_t layout = 0, npix = 1, spp = 1;  // how they are laid out (th_kernels.h, film_index)
+    uint32_t kind = 0;  // whose they are: 1 a one-band path frame or trhip_film_accumulate's records (trhip_last_sample_stats reads them), 2 a map frame (exported through map_counts), 0 anything else
 };
 
 struct Timer;
+// Members are destroyed last to first: the workspace, then the pipes, then the two streams (trhip_shutdown, tu_api.hip).
 struct trhip_ctx {
     int device = 0;
     Timer* active_timer = nullptr;  // the Timer of the render call in progress (hybrid launches mark the hand-over between their two walks in it)
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;  // shadow rays of depth d overlap with the closest-hit rays of depth d+1
+    OwnedStream stream;
+    OwnedStream stream2;  // shadow rays of depth d overlap with the closest-hit rays of depth d+1
     std::string err;
     int num_cu = 256;
-    // options
-    bool count_visits = false;
-    bool timing = true;
-    uint64_t batch_paths = 0;  // 0 = as many whole sample passes as fit in free HBM (fewer launches, fewer traversal tails)
-    int pipelines = 1;    // concurrent wavefront batches (each on its own stream pair); measured: no gain, every batch pays every tail
-    Pipe pipes[kMaxPipes];
-    uint32_t debug_trace_budget = 0;  // DIAGNOSTIC: k_trace2 abandons rays after this many node fetches (results wrong; measures bulk vs tail)
+    Options opt;  // trhip_set_option (th_options.h)
+    LastRecords last;
     double bvh_device_ms = 0.0;  // device time of the last bvh_builder 3 build
-    int bvh_builder = -1;  // BVHAccel construction: 0 = binned SAH on the host (th_bvh.h), 1 = linear BVH on the device (th_lbvh.h), 3 = the host builder's
-                           // binned SAH on the device (th_sahb.h: the same tree), 2 = the reference's own construction node for node (th_bvh_ref.h:
-                           // the tree Trace.jl builds, hence its tie-breaks), -1 = automatic: builder 3 from 64 Ki primitives on, builder 0 below and
-                           // for the scenes builder 3 hands back.  Measured (r3): building the tree 18 ms (1 M triangles) / 53 ms (10 M) on the device
-                           // against ~0.17 s / ~1.5 s on the host, commit 0.39 -> 0.26 s and 3.67 -> 2.37 s; the LBVH builds a 25-35 % costlier tree
-    bool film_transpose = false;     // film pass on pixel-group-major copies of p_film / L (option "film_transpose"; launch_film)
-    bool occluder_pretest = true;    // any-hit rays test the scene's largest triangles before the walk (option "occluder_pretest")
-    int stream2_priority = -1;       // shadow-ray stream: 1 highest priority, -1 lowest, 0 the default level (option "stream2_priority", read when the streams are created)
-    bool leaf_kernel = true;         // one-leaf scenes run k_trace_leaf instead of k_trace2 (option "leaf_kernel", for A/B)
-    int slab_margin_log2 = 14;       // k_trace2 / k_trace3 add the slab clauses the reference's box test lost, on boxes grown by 2^-this x the ray's reach
-                                     // (th_trace2.h, slab_test2); 0 = the reference's loose test alone (its exact visit set)
-    int band_tile_rows = 0;          // DIAGNOSTIC / tests: render frames in bands of this many tile rows (0 = one band unless the samples do not fit in HBM)
-    uint32_t tiny_scene_prims = 16;  // scenes of at most this many primitives get a single-leaf BVH (th_bvh.h); 0 = always build the hierarchy
-    int film_block = 5;  // film gather: >= 4 (filter radius <= 1; wider filters run 2): from a 32-bit splat descriptor in the radiance record's .w lane, a thread owning
-                         // 4: 1 x 4, 5 (default): 2 x 4, 6: 4 x 4, 7: 2 x 2, 8: 4 x 2, 9: 8 x 4, 10: 1 x 8, 11: 1 x 16, 12: 1 x 2, 13: 1 x 1 film pixels (th_kernels.h,
-                         // k_film_gather_packed; measured at 1024^2 x 256 spp: 19.0 / 17.1 / 24.2 / 25.9 / 30.8 / 40.4 / 17.1 / - / 22.5 / 33.7 ms against 25.0 for 2);
-                         // 0 = one film pixel per thread, 1 = 2 x 2 pixels per thread, 2 = TH_FILM_BX x TH_FILM_BY = 1 x 4, all three recomputing a
-                         // sample's pixel range and table indices per thread; 3 = 1 x 4 from per-sample splat descriptors (k_film_descriptors): measured SLOWER
-                         // (1024^2, 256 spp: 29.0 ms against 24.3 ms: the 16-byte descriptor doubles the gather's loads and the arithmetic it saves was hidden)
-    bool film_relayout = true;  // packed film pass: gather from a pixel-group-major copy of the radiance records (k_film_pack_transpose) instead of the integrators' sample-major order
     bool warned_idle_accelerator = false;  // (tu_path.hip: the one-time stderr note)
     bool warned_fallback_cliff = false;    // … and the one about a frame whose certified walk handed back more than a fifth of its rays
     double last_fallback_share = 0.0;      // fallback rays / closest-hit rays of the last frame that reported statistics (trhip_accelerator_note)
-    int any_on_accelerator = -1;  // hybrid mode: any-hit rays without a zero direction component walk the library's tree (TraceOut::zero_mode): 1 always, 0 never, -1 where the
-                                  // integrator asks for it (TraceOut::any_acc_hint: SPPM).  Option "any_on_accelerator"
-    bool wide4 = true;  // hybrid mode: the accelerator is also laid out four children wide and the certified walk runs on that (th_trace3c4.h); option "wide4", read at commit and at launch
-    bool leaf_queue = false;  // hybrid mode: the certified walk queues the leaves it reaches and tests them 64 at a time with whichever lanes (th_trace3d.h, option "leaf_queue")
-    int node_layout = 0;  // children-in-parent nodes: 0 depth-first, 1 the two interior children of a node in one aligned 128-byte line (option "node_layout", read at commit; tu_scene.hip)
-    bool film_swizzle = false;  // packed film gather: XCD x owns the x-th contiguous eighth of the workgroups (option "film_swizzle"; measured: no effect, th_kernels.h)
-    bool film_tiled = false;  // LDS-staged film gather (k_film_gather_tiled): bit-identical, measured 2.7x SLOWER than k_film_gather (11 % lane use), kept as an option
-    bool overlap = true;   // shadow rays of depth d on a second stream beside the closest-hit rays of depth d+1 (option "overlap").  On again since round 5: with the four-wide
-                           // certified walk no longer saturating VALU issue the shadow kernels fill its gaps and tails — 256 spp, off / on: S-mesh 325.5 / 314.5 ms, S-blob 234.8 / 222.3,
-                           // S-cornell 160.4 / 157.1, 10.5 M triangles 376.4 / 367.7.  (Rounds 2-4 measured it neutral — S-cornell 158.2 / 157.9, S-mesh 399 / 393 — and kept it off.)
-    int compose_spheres = -1;  // commit: spheres as a chain of leaves above the triangles' subtree, what k_trace8 needs of a scene with spheres
-                               // (option "compose_spheres": 1 / 0 = one SAH tree over everything / -1 = when "traversal" is 4 at commit time)
-    int traversal = 3;  // 1 = literal accel/bvh.jl loop, 2 = children-in-parent nodes + per-lane ray replacement, 3 = 2 with leaves postponed (while-while),
-                        // 4 = 8-wide quantised nodes in the binary walk's order (th_trace8.h; scenes / rays it cannot take run 3), 6 = 3 with two rays per lane (th_trace4.h),
-                        // 7 = closest-hit rays front to back with tie detection, flagged rays re-traced by 3 (th_trace7.h); any-hit rays as 3
-    bool leaf_sorted = false;  // one-leaf scenes: rays grouped by the primitives they can hit before the leaf is walked (th_leaf2.h, option "leaf_sorted"); exact, measured SLOWER
-                               // (S-cornell closest-hit 49.2 -> 60.2 ms, any-hit 15.9 -> 30.8: twelve candidate tests cost as much as the exact tests they save), off
-    bool film_fused = true;    // the path integrator's k_raygen writes the radiance records in the film pass's layout with their splat descriptors (no memset, no pack pass; option "film_fused")
-    uint32_t last_L_layout = 0, last_L_npix = 1, last_L_spp = 1;  // how Lbuf is laid out after the last render (trhip_last_sample_radiance)
-    bool trace3_spec = true;   // k_trace3 (closest-hit): lanes park the leaf they reach and go on descending (th_trace2.h, TH_TRACE3_SPEC); 0 = wait for the leaf phase
-    bool hybrid = true;        // scenes committed with both trees (bvh_builder 4 / -1): closest-hit rays walk the ACCELERATOR with the order-independence certificate of
-                               // th_trace3c.h and only the flagged ones the canonical tree (option "hybrid"; 0 = every ray walks the canonical tree: same answers, slower)
-    bool trace7_cheap = true;  // k_trace7: conservative fma slab test on interior boxes, the reference's exact test once per leaf (th_trace7.h); 0 = exact test on every box
+    Pipe pipes[kMaxPipes];
     // workspace (grown on demand, reused across calls)
     DevBuf q[2][3], sq[3], hits, Lbuf, pfilm, counters, sensor, table, film, scratch[4], overflow, wh_L, wh_parent, wh_coef, wh_pdf, wh_flags, occl, film_Lt, surv_list, surv_counts;
-    uint64_t last_L_count = 0;  // float4 entries valid in Lbuf
     // SPPM state (th_sppm.h): per film pixel, kept after trhip_render_sppm for trhip_sppm_state
     DevBuf sp_vp[7], sp_Ld, sp_tau, sp_radius, sp_N, sp_phi, sp_M, sp_counts, sp_starts, sp_entries, sp_grid, sp_ldist, sp_snap_M, sp_snap_phi, sp_snap_p, sp_snap_beta;
     DevBuf sp_terms, sp_rec[3], sp_rec_valid, sp_raysnap;  // sp_raysnap: {closest_total, shadow_total} after every batch's camera pass and photon pass
-    // streaming wavefront (render_stream_impl)
-    DevBuf st_terms, st_tags[2], st_frozen, st_counts, st_list[2][2][7];  // [closest|any][ping-pong][o, d, b, trav, st, depth, stack]
-    int streaming = 0;             // PathIntegrator on scenes with a real hierarchy: suspend / resume stragglers.  1 = always, 0 = never (classic
-                                   // per-depth launches), -1 = automatic: when the frame has at most 96 camera samples per primitive, which is where the
-                                   // traversal tails dominate (measured, 1 M triangles: 16 spp 1170 -> 716 ms, 64 spp 1700 -> 1443, 128 spp 2288 vs
-                                   // 2412, 256 spp 3742 vs 3823; 10 M triangles, depth 16: 32 spp 6075 -> 2465 ms, 128 spp 8364 -> 4913)
-    uint32_t stream_budget_shift = 12;  // budget = max(stream_budget_min, fresh rays of the round >> shift)
-    uint32_t stream_list_cap = 0;       // suspended-ray list capacity (0 = max(65536, paths / 128)); tests shrink it
-    uint32_t stream_budget_min = 2048;  // interior fetches before a ray may be suspended (tests lower it to force suspensions)
-    uint64_t sppm_batch = 0;  // SPPM iterations per wavefront batch (0 = from free HBM, at most 128)
     uint32_t sp_pixels = 0;
     int64_t sp_photons = 0;
+    // streaming wavefront (render_stream_impl)
+    DevBuf st_terms, st_tags[2], st_frozen, st_counts, st_list[2][2][7];  // [closest|any][ping-pong][o, d, b, trav, st, depth, stack]
     DevBuf film_side;  // packed film pass: counter + the full descriptors of the samples whose range does not fit 30 bits (th_kernels.h, FilmSideTable)
     DevBuf fdesc;   // film_block 3: one SplatDesc (16 B) per camera sample of the band (th_kernels.h, k_film_descriptors)
     DevBuf poison;  // one byte per camera sample of the band: ShadeStream::poison
@@ -141,14 +77,11 @@ struct trhip_ctx {
     DevBuf ao_tmax;    // trhip_render_ao: the reach of every occlusion ray, beside the any-hit queue sq (th_ao.h, 4 B per queue entry)
     // dn_in, tp_in, up_in, dp_in: where the host entry points of the image-space passes stage their images, laid out by ImageStaging (th_image_pass.h) in the order a pass declares them
     DevBuf dn_work, dn_in;  // trhip_denoise: guides, two colour buffers and the base colour (th_denoise.h, 80 B per pixel); the host entry point's copy of film and planes
-    int denoise_lds = 3;    // bit i: iteration i (step 2^i, i < 2) of trhip_denoise runs the LDS-staged kernel (option "denoise_lds")
     DevBuf tp_in;           // trhip_temporal's host entry point: its copy of film, planes, history and the new history (th_temporal.h, 160 B per pixel); trhip_temporal_clip's: the same and
                             // the result's film (176 B); trhip_temporal_clip_device's film for a result that aliases its input (16 B); trhip_temporal_moments likewise (196 B; 16 B);
                             // trhip_temporal_motion's: trhip_temporal's and the id plane, the body matrices and the body table (176 B per pixel, 48 per body, 4 per primitive);
                             // trhip_temporal_clip_motion's: the same and the result's film (192 B per pixel); its _device variant's film for a result that aliases its input (16 B);
                             // trhip_temporal_split's: trhip_temporal_motion's and the direct film (192 B per pixel); trhip_film_add's two films (32 B per pixel)
-    int temporal_patch = 1; // trhip_temporal's lane-to-pixel mapping: 0 film order, 1 patches of 16 x 4 per wave, measured 11 % faster (option "temporal_patch", profiles/r11/temporal.txt)
-    int denoise_var_lds = 3;  // bit i: iteration i (step 2^i, i < 2) of trhip_denoise_var runs the LDS-staged kernel (option "denoise_var_lds", profiles/r13/variance.txt)
     DevBuf up_in;      // trhip_upscale's host entry point: its copies of the five images (th_upscale.h; 64 B per low pixel, 65 per full-size pixel);
                        // trhip_temporal_upsample's likewise (th_temporal_upsample.h; 64 B per low pixel, 161 per full-size pixel); trhip_temporal_upsample_motion's: the same and
                        // the id plane, the body matrices and the body table (177 B per full-size pixel, 48 per body, 4 per primitive)
@@ -156,11 +89,11 @@ struct trhip_ctx {
     // adaptive sampling (th_adaptive.h): the last map frame's counts (kept for trhip_last_sample_radiance), their exclusive sum, the job list, hipcub's workspace, the
     // word k_map_reduce / k_sample_map sum into; the host entry points' copies of (m, v) and of the counts they return
     DevBuf map_counts, map_offsets, map_jobs, map_tmp, map_word, map_mv, map_out;
-    uint32_t last_L_kind = 0;  // whose records Lbuf holds: 1 a one-band path frame or trhip_film_accumulate's records (trhip_last_sample_stats reads them), 2 a map frame (exported through map_counts), 0 anything else
     DevBuf cb_rc;      // one word: a host callback's return code, max-reduced over the ranks of a job (tu_sppm.hip)
     DevBuf ov8[2], fb_list[2], fb_counts[2];  // k_trace8: global stack levels, fallback lists + their counters / work cursors ([closest | any])
-    Comm comm;  // multi-GPU job this context belongs to (trhip_comm_init); n_ranks == 1 without one
+    Comm comm;  // multi-GPU job this context belongs to (trhip_comm_init); n_ranks == 1 without one; trhip_shutdown destroys its communicator before the context goes
 };
+static_assert(!std::is_copy_constructible_v<trhip_ctx>, "trhip_ctx owns its streams, pipes and workspace");
 
 struct HostPrim {
     uint32_t kind;       // 0 triangle, 1 sphere
@@ -170,10 +103,8 @@ struct HostPrim {
     uint32_t sphere_id;  // for spheres
 };
 
-inline void release(DevBuf& b);
-
 // What a commit derives from the primitives alone: the host records, both trees and every device buffer made from them.  A scene holds it through a shared_ptr: its relit
-// views (trhip_scene_relight) share it, each with its own lights.  The device buffers are released with the last handle that holds them.
+// views (trhip_scene_relight) share it, each with its own lights.  The device buffers go with the last handle that holds them.
 struct SceneGeometry {
     uint64_t id = 0;  // trhip_scene_geometry_id: a new value for every tree this geometry is committed with (0 = never committed)
     int max_node_primitives = -1;  // what the last trhip_scene_commit built the trees with (-1: a caller's tree alone, trhip_scene_set_bvh)
@@ -196,27 +127,13 @@ struct SceneGeometry {
     DevBuf d_nodes, d_prims, d_nrm, d_tan, d_shade, d_spheres, d_materials, d_base_colour, d_wnodes, d_w8nodes, d_w8tris;
     DevBuf d_acc_w4nodes;  // the accelerator four children wide (th_trace3c4.h)
     DevBuf d_acc_wnodes, d_acc_prims, d_slot_boxes, d_sphere_boxes, d_sphere_slots, d_sphere_cert;
-    SceneGeometry() = default;
-    SceneGeometry(const SceneGeometry&) = delete;
-    SceneGeometry& operator=(const SceneGeometry&) = delete;
-    ~SceneGeometry() {
-        for (DevBuf* b : {&d_leaf_boxes, &d_nodes, &d_prims, &d_nrm, &d_tan, &d_shade, &d_spheres, &d_materials, &d_base_colour, &d_wnodes, &d_w8nodes, &d_w8tris, &d_acc_w4nodes, &d_acc_wnodes,
-                          &d_acc_prims, &d_slot_boxes, &d_sphere_boxes, &d_sphere_slots, &d_sphere_cert})
-            release(*b);
-    }
 };
+static_assert(!std::is_copy_constructible_v<SceneGeometry>, "SceneGeometry owns its device buffers");
 
-struct trhip_scene {
-    trhip_ctx* ctx = nullptr;
-    std::shared_ptr<SceneGeometry> g = std::make_shared<SceneGeometry>();
-    bool relit = false;  // a relit view (trhip_scene_relight): its geometry is fixed, a commit runs the light stage alone
+// The views of a committed geometry: pointers into its buffers (the light pointers and orders patched in by the light stage) and what the commit found out about it.  Plain
+// values that own nothing: a relit view copies its base's (tu_scene.hip, trhip_scene_relight).
+struct SceneViews {
     bool has_materialless_prim = false;  // set at commit: some GeometricPrimitive has no material (path and Whitted refuse such a scene; SPPM crosses it, th_sppm.h XING; the trace entry points accept it)
-    std::vector<LightRec> lights;
-    bool committed = false;
-    // ---- what the light stage (tu_scene.hip, commit_lights) owns: the light records and the any-hit test orders computed from them
-    DevBuf d_lights, d_leaf_order, d_acc_leaf_order, d_occ_slots, d_occ_boxes;
-    uint32_t n_occluders = 0;     // the scene's largest triangles, tested first by any-hit rays (th_trace2.h, k_any_occluders)
-    // ---- views of the geometry (pointers into g's buffers; the light pointers and orders patched in by the light stage)
     DeviceScene dev{};
     WideScene wide{};
     Wide8Scene w8{};              // the 8-wide view of the triangles' subtree (th_wide8.h / th_trace8.h)
@@ -232,6 +149,18 @@ struct trhip_scene {
     DeviceScene dev_acc{};         // dev with the accelerator's primitive records
     CertScene cert{};
 };
+// A scene handle: the geometry it shares, the views above, and what the light stage (tu_scene.hip, commit_lights) owns — the lights, the light records and the any-hit test
+// orders computed from them.  It cannot be copied, so a relit view starts with the light stage's members default-constructed whatever is added to them.
+struct trhip_scene : SceneViews {
+    trhip_ctx* ctx = nullptr;
+    std::shared_ptr<SceneGeometry> g = std::make_shared<SceneGeometry>();
+    bool relit = false;  // a relit view (trhip_scene_relight): its geometry is fixed, a commit runs the light stage alone
+    std::vector<LightRec> lights;
+    bool committed = false;
+    DevBuf d_lights, d_leaf_order, d_acc_leaf_order, d_occ_slots, d_occ_boxes;
+    uint32_t n_occluders = 0;     // the scene's largest triangles, tested first by any-hit rays (th_trace2.h, k_any_occluders)
+};
+static_assert(!std::is_copy_constructible_v<trhip_scene>, "trhip_scene owns the light stage's buffers");
 
 // some light is a DirectionalLight (kind 2): the shading kernels run their DIRL variants (th_device.h, sample_li)
 inline bool has_directional_light(const trhip_scene* s) {
@@ -266,19 +195,13 @@ inline int fail(trhip_ctx* ctx, int code, const char* fmt, ...) {
 
 inline int ensure(trhip_ctx* ctx, DevBuf& b, size_t bytes) {
     if (b.bytes >= bytes && b.p) return 0;
-    if (b.p) HIP_TRY(ctx, hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
+    HIP_TRY(ctx, b.reset());
     if (bytes == 0) bytes = 16;
     HIP_TRY(ctx, hipMalloc(&b.p, bytes));
     b.bytes = bytes;
     return 0;
 }
-inline void release(DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-}
+inline void release(DevBuf& b) { (void)b.reset(); }  // for the places that free early on purpose; everything else goes with its owner
 inline int upload(trhip_ctx* ctx, DevBuf& b, const void* src, size_t bytes) {
     if (int rc = ensure(ctx, b, bytes)) return rc;
     if (bytes) HIP_TRY(ctx, hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
@@ -400,17 +323,10 @@ struct Timer {
 };
 // The event pair around the device work of one call (trhip_stats.ms_total).  Owned: whichever way the function returns, the events go with it.
 struct FrameEvents {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    FrameEvents() = default;
-    FrameEvents(const FrameEvents&) = delete;
-    FrameEvents& operator=(const FrameEvents&) = delete;
-    ~FrameEvents() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
+    OwnedEvent e0, e1;
     hipError_t begin(hipStream_t st) {  // creates the pair and records its first event
-        if (hipError_t e = hipEventCreate(&e0)) return e;
-        if (hipError_t e = hipEventCreate(&e1)) return e;
+        if (hipError_t e = e0.create_timed()) return e;
+        if (hipError_t e = e1.create_timed()) return e;
         return hipEventRecord(e0, st);
     }
     hipError_t end(hipStream_t st) { return hipEventRecord(e1, st); }
@@ -420,18 +336,6 @@ struct FrameEvents {
         return t;
     }
 };
-// One owned event without timing: a point in one stream that other streams wait for.
-struct OwnedEvent {
-    hipEvent_t e = nullptr;
-    OwnedEvent() = default;
-    OwnedEvent(const OwnedEvent&) = delete;
-    OwnedEvent& operator=(const OwnedEvent&) = delete;
-    ~OwnedEvent() {
-        if (e) (void)hipEventDestroy(e);
-    }
-    hipError_t create() { return hipEventCreateWithFlags(&e, hipEventDisableTiming); }
-};
-
 // ---- the frame scaffold of the render entry points ----------------------------------------------------------------------------------
 // Physical queue layout: kSeg segments of this many entries (th_kernels.h "SegQueue").  A segment receives at most P / kSeg + O(kSegGran) entries per bounce by
 // construction; `extra_segment_entries` is what an integrator appends to a segment on top of that (the streaming frame's resumed rays).
@@ -448,6 +352,19 @@ inline size_t held_in_pipes(const trhip_ctx* ctx) {
         for (auto& b : pp.sq) held += b.bytes;
     }
     return held;
+}
+// The streams and events of pipe `index` (th_owned.h): made on first use, and completed when an earlier call got only part of the way, so a frame never runs on a half-made
+// pipe.  honour_priority: the second stream is made at the level option "stream2_priority" asks for — the classic path frame passes true, the streaming frame and SPPM
+// false.  KNOWN, kept as it was: whichever of them runs first on a context makes the stream, so the first caller decides the shadow stream's priority for the context's life.
+inline int ensure_pipe(trhip_ctx* ctx, int index, bool honour_priority) {
+    Pipe& pp = ctx->pipes[index];
+    // the shadow-ray stream gets its own priority level: streams of one level can share a hardware queue (then any(d) and
+    // closest(d+1) run one after the other: measured in the first context of a process), streams of different levels cannot
+    int prio_lo = 0, prio_hi = 0;
+    if (honour_priority && !pp.st2 && ctx->opt.stream2_priority) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    const int prio = ctx->opt.stream2_priority > 0 ? prio_hi : prio_lo;
+    HIP_TRY(ctx, pp.complete(prio_hi != prio_lo ? &prio : nullptr));
+    return 0;
 }
 // The one-batch entry points (aov, ao, and the image-space passes: denoise, denoise_var, temporal and temporal_clip, temporal_moments, upscale, display, temporal_upsample) refuse a frame that needs more than 0.9 of what is free plus what the context already holds for it (`held`, reused).
 // *free_gb is that sum, for the caller's sentence.

@@ -169,7 +169,7 @@ struct PassWindow {
     Timer tm;
     FrameEvents ev;
     hipStream_t st;
-    PassWindow(trhip_ctx* ctx, const trhip_stats* stats) : tm(ctx, ctx->timing && stats), st(ctx->stream) {}
+    PassWindow(trhip_ctx* ctx, const trhip_stats* stats) : tm(ctx, ctx->opt.timing && stats), st(ctx->stream) {}
     hipError_t open() { return ev.begin(st); }
     void begin(int cls) { tm.begin(cls, st); }
     void end(int cls) { tm.end(cls, st); }

@@ -44,6 +44,7 @@ inline int occlusion_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip
     for (int j = 0; j < 3; ++j)
         if (int rc = ensure(ctx, ctx->sq[j], Pphys * sizeof(float4))) return rc;
     if (int rc = ensure(ctx, ctx->ao_tmax, Pphys * sizeof(float))) return rc;
+    ctx->last = LastRecords{};  // (until this frame's radiance is complete)
     if (int rc = ensure(ctx, ctx->Lbuf, total_slots * sizeof(float4))) return rc;
     if (int rc = ensure_film_samples(ctx, ds, total_slots)) return rc;
     void* d_film;
@@ -52,10 +53,8 @@ inline int occlusion_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip
     const ShadowQueue sq{(float4*)ctx->sq[0].p, (float4*)ctx->sq[1].p, (float4*)ctx->sq[2].p};
     float* tmax = (float*)ctx->ao_tmax.p;
     float4* L = (float4*)ctx->Lbuf.p;
-    ctx->last_L_count = 0;  // (until this frame's radiance is complete)
-    ctx->last_L_kind = 0;
 
-    Timer tm(ctx, ctx->timing && stats);
+    Timer tm(ctx, ctx->opt.timing && stats);
     FrameEvents ev;
     if (int rc = camera_pass_trace(ctx, scene, sensor, seed, sample_offset, tm, ev, cp)) return rc;
     Counters* ctr = cp.ctr;
@@ -72,8 +71,7 @@ inline int occlusion_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip
     HIP_TRY(ctx, ev.end(st));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    ctx->last_L_count = total_slots;
-    ctx->last_L_layout = 0;
+    ctx->last = LastRecords{total_slots, 0u, (uint32_t)((uint64_t)ds.sb_w * ds.sb_h), spp, 0u};
     if (int rc = copy_back(ctx, out, out_is_device, d_film, film_bytes)) return rc;
     if (stats) {
         std::memset(stats, 0, sizeof *stats);

@@ -36,17 +36,17 @@ namespace {
 
 int stats_impl(trhip_ctx* ctx, void* out_mv, bool is_device) {
     if (!ctx || !out_mv) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
-    if (ctx->last_L_kind != 1 || ctx->last_L_count == 0)
+    if (ctx->last.kind != 1 || ctx->last.count == 0)
         return fail(ctx, TRHIP_ERR_INVALID, "trhip_last_sample_stats: the context's last radiance records are not a one-band trhip_render_path frame's or trhip_film_accumulate's");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint32_t npix = ctx->last_L_npix, spp = ctx->last_L_spp;
+    const uint32_t npix = ctx->last.npix, spp = ctx->last.spp;
     const size_t bytes = (size_t)npix * sizeof(float2);
     void* d = out_mv;
     if (!is_device) {
         if (int rc = ensure(ctx, ctx->map_mv, bytes)) return rc;
         d = ctx->map_mv.p;
     }
-    hipLaunchKernelGGL(k_sample_stats, dim3(grid_for(ctx, npix, 8)), dim3(kBlock), 0, ctx->stream, (const float4*)ctx->Lbuf.p, ctx->last_L_layout, npix, spp, (float2*)d);
+    hipLaunchKernelGGL(k_sample_stats, dim3(grid_for(ctx, npix, 8)), dim3(kBlock), 0, ctx->stream, (const float4*)ctx->Lbuf.p, ctx->last.layout, npix, spp, (float2*)d);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (!is_device) HIP_TRY(ctx, hipMemcpy(out_mv, d, bytes, hipMemcpyDeviceToHost));

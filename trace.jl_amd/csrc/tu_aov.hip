@@ -57,7 +57,7 @@ int render_aov_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor
     }
     hipStream_t st = ctx->stream;
 
-    Timer tm(ctx, ctx->timing && stats);
+    Timer tm(ctx, ctx->opt.timing && stats);
     FrameEvents ev;
     if (int rc = camera_pass_trace(ctx, scene, sensor, seed, sample_offset, tm, ev, cp)) return rc;
     tm.begin(2, st);

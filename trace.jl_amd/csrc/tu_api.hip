@@ -21,7 +21,7 @@ int trhip_init(trhip_ctx** out, int device_id) {
     auto ctx = new trhip_ctx();
     ctx->device = device_id;
     ctx->num_cu = prop.multiProcessorCount;
-    if ((e = hipSetDevice(device_id)) != hipSuccess || (e = hipStreamCreate(&ctx->stream)) != hipSuccess || (e = hipStreamCreate(&ctx->stream2)) != hipSuccess) {
+    if ((e = hipSetDevice(device_id)) != hipSuccess || (e = ctx->stream.create()) != hipSuccess || (e = ctx->stream2.create()) != hipSuccess) {
         delete ctx;
         return fail(nullptr, TRHIP_ERR_HIP, "stream creation failed: %s", hipGetErrorString(e));
     }
@@ -32,78 +32,7 @@ void trhip_shutdown(trhip_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->comm.comm) (void)rccl_api()->CommDestroy(ctx->comm.comm);
-    for (auto& a : ctx->q)
-        for (auto& b : a) release(b);
-    for (auto& b : ctx->sq) release(b);
-    for (auto& b : ctx->scratch) release(b);
-    release(ctx->hits);
-    release(ctx->Lbuf);
-    release(ctx->counters);
-    release(ctx->sensor);
-    release(ctx->table);
-    release(ctx->film);
-    release(ctx->overflow);
-    release(ctx->pfilm);
-    release(ctx->fdesc);
-    release(ctx->film_side);
-    release(ctx->cert_cold);
-    release(ctx->aov_rec);
-    release(ctx->ao_tmax);
-    release(ctx->dn_work);
-    release(ctx->dn_in);
-    release(ctx->tp_in);
-    release(ctx->up_in);
-    release(ctx->dp_work);
-    release(ctx->dp_in);
-    release(ctx->cb_rc);
-    for (DevBuf* b : {&ctx->map_counts, &ctx->map_offsets, &ctx->map_jobs, &ctx->map_tmp, &ctx->map_word, &ctx->map_mv, &ctx->map_out}) release(*b);
-    for (auto& pp : ctx->pipes) {
-        for (auto& a : pp.q)
-            for (auto& b : a) release(b);
-        for (auto& b : pp.sq) release(b);
-        for (auto& b : pp.sq2) release(b);
-        if (pp.ev_any2) (void)hipEventDestroy(pp.ev_any2);
-        release(pp.hits);
-        release(pp.counters);
-        release(pp.overflow[0]);
-        release(pp.overflow[1]);
-        if (pp.ev_shade) (void)hipEventDestroy(pp.ev_shade);
-        if (pp.ev_any) (void)hipEventDestroy(pp.ev_any);
-        if (pp.ev_done) (void)hipEventDestroy(pp.ev_done);
-        if (pp.st) (void)hipStreamDestroy(pp.st);
-        if (pp.st2) (void)hipStreamDestroy(pp.st2);
-    }
-    release(ctx->wh_L);
-    release(ctx->wh_parent);
-    release(ctx->wh_coef);
-    release(ctx->wh_pdf);
-    release(ctx->wh_flags);
-    release(ctx->occl);
-    release(ctx->film_Lt);
-    release(ctx->surv_list);
-    release(ctx->surv_counts);
-    release(ctx->poison);
-    for (int k = 0; k < 2; ++k) {
-        release(ctx->ov8[k]);
-        release(ctx->fb_list[k]);
-        release(ctx->fb_counts[k]);
-    }
-    for (auto& b : ctx->sp_vp) release(b);
-    release(ctx->st_terms);
-    release(ctx->st_tags[0]);
-    release(ctx->st_tags[1]);
-    release(ctx->st_frozen);
-    release(ctx->st_counts);
-    for (auto& a : ctx->st_list)
-        for (auto& b : a)
-            for (auto& c : b) release(c);
-    for (DevBuf* b : {&ctx->sp_Ld, &ctx->sp_tau, &ctx->sp_radius, &ctx->sp_N, &ctx->sp_phi, &ctx->sp_M, &ctx->sp_counts, &ctx->sp_starts, &ctx->sp_entries, &ctx->sp_grid, &ctx->sp_ldist,
-                      &ctx->sp_snap_M, &ctx->sp_snap_phi, &ctx->sp_snap_p, &ctx->sp_snap_beta, &ctx->sp_terms, &ctx->sp_rec[0], &ctx->sp_rec[1], &ctx->sp_rec[2],
-                      &ctx->sp_rec_valid, &ctx->sp_raysnap})
-        release(*b);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
-    delete ctx;
+    delete ctx;  // every member frees what it owns (th_owned.h): the workspace, the pipes, then the two streams
 }
 const char* trhip_last_error(const trhip_ctx* ctx) { return ctx ? ctx->err.c_str() : g_init_error.c_str(); }
 
@@ -169,110 +98,17 @@ static int film_collective(trhip_ctx* ctx, void* d_xyzw, uint64_t n_pixels, int 
 int trhip_film_reduce(trhip_ctx* ctx, void* d_xyzw, uint64_t n_pixels, int root) { return film_collective(ctx, d_xyzw, n_pixels, root, false); }
 int trhip_film_allreduce(trhip_ctx* ctx, void* d_xyzw, uint64_t n_pixels) { return film_collective(ctx, d_xyzw, n_pixels, 0, true); }
 
-// Kernel families that lost their measurements (traversals 4 / 6 / 7, the leaf queue, the sorted one-leaf walk, the linear BVH builder) are compiled only with
-// -DTRHIP_EXPERIMENTS (__graft_entry__.build_library(extra_flags=["-DTRHIP_EXPERIMENTS"], out_name="libtracehip_experiments.so")); the default library refuses their options.
+// The options: th_options.h holds the fields, the table and its interpreter; this unit only knows which build it is.
 #ifdef TRHIP_EXPERIMENTS
 static constexpr bool kExperiments = true;
 #else
 static constexpr bool kExperiments = false;
 #endif
-static const char* const kNeedsExperiments = "needs the EXPERIMENTS build of the library (-DTRHIP_EXPERIMENTS): not in the default binary";
-static bool experiments_only(const char* name, int64_t value) {
-    if (!std::strcmp(name, "traversal")) return value == 4 || value == 6 || value == 7;
-    if (!std::strcmp(name, "bvh_builder")) return value == 1;
-    if (!std::strcmp(name, "leaf_sorted") || !std::strcmp(name, "leaf_queue")) return value != 0;
-    return false;
-}
-int trhip_option_in_build(const char* name, int64_t value) { return (name && (kExperiments || !experiments_only(name, value))) ? 1 : 0; }
+int trhip_option_in_build(const char* name, int64_t value) { return (name && option_in_build(kExperiments, name, value)) ? 1 : 0; }
 int trhip_set_option(trhip_ctx* ctx, const char* name, int64_t value) {
     if (!ctx || !name) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
-    if (!std::strcmp(name, "count_visits"))
-        ctx->count_visits = value != 0;
-    else if (!std::strcmp(name, "timing"))
-        ctx->timing = value != 0;
-    else if (!std::strcmp(name, "debug_trace_budget"))
-        ctx->debug_trace_budget = (uint32_t)value;
-    else if (!std::strcmp(name, "streaming"))
-        ctx->streaming = value < 0 ? -1 : (value != 0 ? 1 : 0);
-    else if (!std::strcmp(name, "stream_budget_shift"))
-        ctx->stream_budget_shift = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(31, value));
-    else if (!std::strcmp(name, "stream_list_cap"))
-        ctx->stream_list_cap = (uint32_t)std::max<int64_t>(0, value);
-    else if (!std::strcmp(name, "stream_budget_min"))
-        ctx->stream_budget_min = (uint32_t)std::max<int64_t>(1, value);
-    else if (!std::strcmp(name, "sppm_batch"))
-        ctx->sppm_batch = (uint64_t)std::max<int64_t>(0, value);
-    else if (!std::strcmp(name, "bvh_builder")) {
-        if (value == 1 && !kExperiments) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "bvh_builder = 1 (the linear BVH) %s", kNeedsExperiments);
-        ctx->bvh_builder = value < 0 ? -1 : (value > 4 ? 4 : (int)value);
-    }
-    else if (!std::strcmp(name, "hybrid"))
-        ctx->hybrid = value != 0;
-    else if (!std::strcmp(name, "film_transpose"))
-        ctx->film_transpose = value != 0;
-    else if (!std::strcmp(name, "band_tile_rows"))
-        ctx->band_tile_rows = (int)std::max<int64_t>(0, value);
-    else if (!std::strcmp(name, "compose_spheres"))
-        ctx->compose_spheres = value < 0 ? -1 : (value != 0 ? 1 : 0);
-    else if (!std::strcmp(name, "occluder_pretest"))
-        ctx->occluder_pretest = value != 0;
-    else if (!std::strcmp(name, "stream2_priority"))
-        ctx->stream2_priority = (int)value;
-    else if (!std::strcmp(name, "leaf_sorted")) {
-        if (value != 0 && !kExperiments) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "leaf_sorted %s", kNeedsExperiments);
-        ctx->leaf_sorted = value != 0;
-    }
-    else if (!std::strcmp(name, "film_fused"))
-        ctx->film_fused = value != 0;
-    else if (!std::strcmp(name, "trace3_spec"))
-        ctx->trace3_spec = value != 0;
-    else if (!std::strcmp(name, "trace7_cheap"))
-        ctx->trace7_cheap = value != 0;
-    else if (!std::strcmp(name, "leaf_kernel"))
-        ctx->leaf_kernel = value != 0;
-    else if (!std::strcmp(name, "slab_margin_log2"))
-        ctx->slab_margin_log2 = (int)std::max<int64_t>(0, std::min<int64_t>(20, value));
-    else if (!std::strcmp(name, "tiny_scene_prims"))
-        ctx->tiny_scene_prims = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(255, value));
-    else if (!std::strcmp(name, "film_block"))
-        ctx->film_block = (int)std::max<int64_t>(0, std::min<int64_t>(13, value));
-    else if (!std::strcmp(name, "film_relayout"))
-        ctx->film_relayout = value != 0;
-    else if (!std::strcmp(name, "any_on_accelerator"))
-        ctx->any_on_accelerator = value < 0 ? -1 : (value != 0 ? 1 : 0);
-    else if (!std::strcmp(name, "leaf_queue")) {
-        if (value != 0 && !kExperiments) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "leaf_queue %s", kNeedsExperiments);
-        ctx->leaf_queue = value != 0;
-    }
-    else if (!std::strcmp(name, "wide4"))
-        ctx->wide4 = value != 0;
-    else if (!std::strcmp(name, "node_layout")) {
-        if (value < 0 || value > 1) return fail(ctx, TRHIP_ERR_INVALID, "node_layout: 0 (depth-first) or 1 (sibling pairs per 128-byte line)");
-        ctx->node_layout = (int)value;
-    } else if (!std::strcmp(name, "film_swizzle"))
-        ctx->film_swizzle = value != 0;
-    else if (!std::strcmp(name, "film_tiled"))
-        ctx->film_tiled = value != 0;
-    else if (!std::strcmp(name, "denoise_lds"))
-        ctx->denoise_lds = (int)(value & 3);
-    else if (!std::strcmp(name, "temporal_patch"))
-        ctx->temporal_patch = value != 0;
-    else if (!std::strcmp(name, "denoise_var_lds"))
-        ctx->denoise_var_lds = (int)(value & 3);
-    else if (!std::strcmp(name, "pipelines")) {
-        if (value < 1 || value > kMaxPipes) return fail(ctx, TRHIP_ERR_INVALID, "pipelines must be in 1..%d", kMaxPipes);
-        ctx->pipelines = (int)value;
-    } else if (!std::strcmp(name, "overlap"))
-        ctx->overlap = value != 0;
-    else if (!std::strcmp(name, "traversal")) {
-        if (value < 1 || value > 7 || value == 5) return fail(ctx, TRHIP_ERR_INVALID, "traversal must be 1, 2, 3, 4, 6 or 7");
-        if ((value == 4 || value == 6 || value == 7) && !kExperiments) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "traversal %d %s", (int)value, kNeedsExperiments);
-        ctx->traversal = (int)value;
-    } else if (!std::strcmp(name, "batch_paths")) {
-        if (value < 0) return fail(ctx, TRHIP_ERR_INVALID, "batch_paths must be >= 0 (0 = auto)");
-        ctx->batch_paths = (uint64_t)value;
-    } else
-        return fail(ctx, TRHIP_ERR_INVALID, "unknown option %s", name);
+    char msg[512];
+    if (int rc = apply_option(ctx->opt, kExperiments, name, value, msg, sizeof msg)) return fail(ctx, rc, "%s", msg);
     return 0;
 }
 

@@ -71,7 +71,7 @@ int denoise_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, uint32_t 
             const float4* cin = col[i & 1];
             float4* cout = col[(i & 1) ^ 1];
             const dim3 grid(bx, by), block(kDnTile * kDnTile);
-            const bool lds = i < 2 && ((ctx->denoise_lds >> i) & 1);  // steps 1 and 2: measured faster staged, step 4 slower (profiles/r9/denoise.txt)
+            const bool lds = i < 2 && ((ctx->opt.denoise_lds >> i) & 1);  // steps 1 and 2: measured faster staged, step 4 slower (profiles/r9/denoise.txt)
             w.begin(6);
             if (lds && i == 0)
                 hipLaunchKernelGGL((k_denoise_atrous_lds<1>), grid, block, 0, st, gn, gp, cin, cout, (int)width, (int)height, sg);
@@ -145,7 +145,7 @@ int denoise_var_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const
         const float* vin = var[i & 1];
         float* vout = var[(i & 1) ^ 1];
         const dim3 grid(bx, by), block(kDnTile * kDnTile);
-        const bool lds = i < 2 && ((ctx->denoise_var_lds >> i) & 1);
+        const bool lds = i < 2 && ((ctx->opt.denoise_var_lds >> i) & 1);
         w.begin(6);
         if (lds && i == 0)
             hipLaunchKernelGGL((k_denoise_var_atrous_lds<1>), grid, block, 0, st, gn, gp, cin, vin, cout, vout, (int)width, (int)height, sg, vp->var_eps);

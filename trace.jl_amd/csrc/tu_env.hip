@@ -3,6 +3,8 @@
 
 #include <cmath>
 
+static_assert(!std::is_copy_constructible_v<trhip_env>, "trhip_env (th_env.h) owns its texels: trhip_env_free is `delete`");
+
 namespace {
 
 constexpr uint32_t kEnvMaxN = 4096;
@@ -58,10 +60,7 @@ int trhip_env_create(trhip_ctx* ctx, const float* rgb, uint32_t n, const float w
     e->n = n;
     e->max_texel = max_texel;
     std::memcpy(e->R, world_to_env, sizeof e->R);
-    if (int rc = upload(ctx, e->tex, st.data(), st.size() * sizeof(float))) {
-        release(e->tex);
-        return rc;
-    }
+    if (int rc = upload(ctx, e->tex, st.data(), st.size() * sizeof(float))) return rc;
     *out = e.release();
     return 0;
 }
@@ -69,7 +68,6 @@ int trhip_env_create(trhip_ctx* ctx, const float* rgb, uint32_t n, const float w
 void trhip_env_free(trhip_env* env) {
     if (!env) return;
     (void)hipSetDevice(env->ctx->device);
-    release(env->tex);
     delete env;
 }
 

@@ -14,26 +14,20 @@ int build_bvh_device(trhip_ctx* ctx, const std::vector<HostAABB>& pb, FlatBVH& o
     if (n < 2 || n >= (1u << 30)) return TRHIP_ERR_UNSUPPORTED;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     static_assert(sizeof(HostAABB) == 6 * sizeof(float), "HostAABB layout");
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() {
-            if (p) (void)hipFree(p);
-        }
-    };
-    Buf d_pb, d_keys, d_keys2, d_sorted, d_sorted2, d_tmp, d_u32, d_ib, d_misc, d_fb, d_fa, d_ff, d_fo;
+    DevBuf d_pb, d_keys, d_keys2, d_sorted, d_sorted2, d_tmp, d_u32, d_ib, d_misc, d_fb, d_fa, d_ff, d_fo;
     const size_t n_int = n - 1, total = 2 * (size_t)n - 1;
-    HIP_TRY(ctx, hipMalloc(&d_pb.p, (size_t)n * 6 * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc(&d_keys.p, (size_t)n * 8));
-    HIP_TRY(ctx, hipMalloc(&d_keys2.p, (size_t)n * 8));
-    HIP_TRY(ctx, hipMalloc(&d_sorted.p, (size_t)n * 4));
-    HIP_TRY(ctx, hipMalloc(&d_sorted2.p, (size_t)n * 4));
-    HIP_TRY(ctx, hipMalloc(&d_u32.p, (6 * n_int + n) * sizeof(uint32_t)));  // left, right, lo, split, parent_int, visits | parent_leaf
-    HIP_TRY(ctx, hipMalloc(&d_ib.p, n_int * 6 * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc(&d_misc.p, 8 * sizeof(uint32_t)));
-    HIP_TRY(ctx, hipMalloc(&d_fb.p, total * 6 * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc(&d_fa.p, total * sizeof(uint32_t)));
-    HIP_TRY(ctx, hipMalloc(&d_ff.p, total * sizeof(uint32_t)));
-    HIP_TRY(ctx, hipMalloc(&d_fo.p, (size_t)n * sizeof(uint32_t)));
+    if (int rc = ensure(ctx, d_pb, (size_t)n * 6 * sizeof(float))) return rc;
+    if (int rc = ensure(ctx, d_keys, (size_t)n * 8)) return rc;
+    if (int rc = ensure(ctx, d_keys2, (size_t)n * 8)) return rc;
+    if (int rc = ensure(ctx, d_sorted, (size_t)n * 4)) return rc;
+    if (int rc = ensure(ctx, d_sorted2, (size_t)n * 4)) return rc;
+    if (int rc = ensure(ctx, d_u32, (6 * n_int + n) * sizeof(uint32_t))) return rc;  // left, right, lo, split, parent_int, visits | parent_leaf
+    if (int rc = ensure(ctx, d_ib, n_int * 6 * sizeof(float))) return rc;
+    if (int rc = ensure(ctx, d_misc, 8 * sizeof(uint32_t))) return rc;
+    if (int rc = ensure(ctx, d_fb, total * 6 * sizeof(float))) return rc;
+    if (int rc = ensure(ctx, d_fa, total * sizeof(uint32_t))) return rc;
+    if (int rc = ensure(ctx, d_ff, total * sizeof(uint32_t))) return rc;
+    if (int rc = ensure(ctx, d_fo, (size_t)n * sizeof(uint32_t))) return rc;
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(d_pb.p, pb.data(), (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, st));
     uint32_t* u = (uint32_t*)d_u32.p;
@@ -47,7 +41,7 @@ int build_bvh_device(trhip_ctx* ctx, const std::vector<HostAABB>& pb, FlatBVH& o
     hipLaunchKernelGGL(k_lbvh_keys, grid, blk, 0, st, b);
     size_t tmp_bytes = 0;
     HIP_TRY(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const uint64_t*)d_keys.p, (uint64_t*)d_keys2.p, (const uint32_t*)d_sorted.p, (uint32_t*)d_sorted2.p, (int)n, 0, 63, st));
-    HIP_TRY(ctx, hipMalloc(&d_tmp.p, tmp_bytes));
+    if (int rc = ensure(ctx, d_tmp, tmp_bytes)) return rc;
     HIP_TRY(ctx, hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, (const uint64_t*)d_keys.p, (uint64_t*)d_keys2.p, (const uint32_t*)d_sorted.p, (uint32_t*)d_sorted2.p, (int)n, 0, 63, st));
     b.keys = (uint64_t*)d_keys2.p;
     b.sorted = (uint32_t*)d_sorted2.p;
@@ -84,31 +78,25 @@ int build_bvh_device_sah(trhip_ctx* ctx, const std::vector<HostAABB>& pb, int ma
     // than kSahSmall primitives without asking.  With a leaf hint of 65 .. 255 the two would differ: such scenes go to the host builder, whose tree this one promises.
     if (std::min(255, max_node_prims) > (int)kSahSmall) return TRHIP_ERR_UNSUPPORTED;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    struct Buf {
-        void* p = nullptr;
-        ~Buf() {
-            if (p) (void)hipFree(p);
-        }
-    };
     const uint32_t pool = 2 * n, cap_active = n / kSahSmall + 2;
-    Buf d_pb, d_cen, d_idx[2], d_pos[2], d_nb, d_nu, d_cnt, d_act, d_lvl, d_bins, d_flag, d_scan, d_tmp, d_fb, d_fa, d_ff;
-    HIP_TRY(ctx, hipMalloc(&d_pb.p, (size_t)n * 6 * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc(&d_cen.p, (size_t)n * 3 * sizeof(float)));
+    DevBuf d_pb, d_cen, d_idx[2], d_pos[2], d_nb, d_nu, d_cnt, d_act, d_lvl, d_bins, d_flag, d_scan, d_tmp, d_fb, d_fa, d_ff;
+    if (int rc = ensure(ctx, d_pb, (size_t)n * 6 * sizeof(float))) return rc;
+    if (int rc = ensure(ctx, d_cen, (size_t)n * 3 * sizeof(float))) return rc;
     for (int k = 0; k < 2; ++k) {
-        HIP_TRY(ctx, hipMalloc(&d_idx[k].p, (size_t)n * 4));
-        HIP_TRY(ctx, hipMalloc(&d_pos[k].p, (size_t)n * 4));
+        if (int rc = ensure(ctx, d_idx[k], (size_t)n * 4)) return rc;
+        if (int rc = ensure(ctx, d_pos[k], (size_t)n * 4)) return rc;
     }
-    HIP_TRY(ctx, hipMalloc(&d_nb.p, (size_t)pool * 6 * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc(&d_nu.p, (size_t)pool * 7 * sizeof(uint32_t)));                     // lo, hi, left, right, axis, depth, lefts
-    HIP_TRY(ctx, hipMalloc(&d_cnt.p, 8 * sizeof(uint32_t)));
-    HIP_TRY(ctx, hipMalloc(&d_act.p, ((size_t)cap_active * 5 + n) * sizeof(uint32_t)));         // act, act_next, split, cslot x 2 | small
-    HIP_TRY(ctx, hipMalloc(&d_lvl.p, (size_t)cap_active * 12 * sizeof(uint32_t)));
-    HIP_TRY(ctx, hipMalloc(&d_bins.p, (size_t)cap_active * kSahBinWords * sizeof(uint32_t)));
-    HIP_TRY(ctx, hipMalloc(&d_flag.p, ((size_t)n + 1) * 4));
-    HIP_TRY(ctx, hipMalloc(&d_scan.p, ((size_t)n + 1) * 4));
+    if (int rc = ensure(ctx, d_nb, (size_t)pool * 6 * sizeof(float))) return rc;
+    if (int rc = ensure(ctx, d_nu, (size_t)pool * 7 * sizeof(uint32_t))) return rc;                     // lo, hi, left, right, axis, depth, lefts
+    if (int rc = ensure(ctx, d_cnt, 8 * sizeof(uint32_t))) return rc;
+    if (int rc = ensure(ctx, d_act, ((size_t)cap_active * 5 + n) * sizeof(uint32_t))) return rc;         // act, act_next, split, cslot x 2 | small
+    if (int rc = ensure(ctx, d_lvl, (size_t)cap_active * 12 * sizeof(uint32_t))) return rc;
+    if (int rc = ensure(ctx, d_bins, (size_t)cap_active * kSahBinWords * sizeof(uint32_t))) return rc;
+    if (int rc = ensure(ctx, d_flag, ((size_t)n + 1) * 4)) return rc;
+    if (int rc = ensure(ctx, d_scan, ((size_t)n + 1) * 4)) return rc;
     size_t tmp_bytes = 0;
     HIP_TRY(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const uint32_t*)d_flag.p, (uint32_t*)d_scan.p, (int)(n + 1), ctx->stream));
-    HIP_TRY(ctx, hipMalloc(&d_tmp.p, tmp_bytes));
+    if (int rc = ensure(ctx, d_tmp, tmp_bytes)) return rc;
     hipStream_t st = ctx->stream;
     FrameEvents ev;
     static_assert(sizeof(HostAABB) == 6 * sizeof(float), "HostAABB layout");
@@ -180,9 +168,9 @@ int build_bvh_device_sah(trhip_ctx* ctx, const std::vector<HostAABB>& pb, int ma
     const uint32_t total = cnt[0];
     if (total > pool || (total & 1u) == 0u) return fail(ctx, TRHIP_ERR_HIP, "device SAH build: %u nodes", total);
     if (cnt[4] > (uint32_t)kStack2Total) return TRHIP_ERR_UNSUPPORTED;
-    HIP_TRY(ctx, hipMalloc(&d_fb.p, (size_t)total * 6 * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc(&d_fa.p, (size_t)total * sizeof(uint32_t)));
-    HIP_TRY(ctx, hipMalloc(&d_ff.p, (size_t)total * sizeof(uint32_t)));
+    if (int rc = ensure(ctx, d_fb, (size_t)total * 6 * sizeof(float))) return rc;
+    if (int rc = ensure(ctx, d_fa, (size_t)total * sizeof(uint32_t))) return rc;
+    if (int rc = ensure(ctx, d_ff, (size_t)total * sizeof(uint32_t))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(b.flag, 0, ((size_t)n + 1) * 4, st));
     const dim3 gridt(grid_for(ctx, total, 8));
     hipLaunchKernelGGL(k_sah_mark_leaves, gridt, blk, 0, st, b, total);

@@ -41,12 +41,12 @@ void derive_sensor(const trhip_sensor* sn, DeviceSensor& d) {
 // film_block = 3: the gather reads one 16-byte splat descriptor per sample (k_film_descriptors) instead of recomputing the sample's pixel range
 // and table indices in every thread it reaches; needs a filter radius <= 3 (<= 8 columns / rows per sample)
 bool film_uses_desc(const trhip_ctx* ctx, const DeviceSensor& ds) {
-    return ctx->film_block == 3 && !ctx->film_tiled && !ctx->film_transpose && std::fmax(ds.filter_radius[0], ds.filter_radius[1]) <= 3.0f && ds.film_w < 32000 && ds.film_h < 32000;
+    return ctx->opt.film_block == 3 && !ctx->opt.film_tiled && !ctx->opt.film_transpose && std::fmax(ds.filter_radius[0], ds.filter_radius[1]) <= 3.0f && ds.film_w < 32000 && ds.film_h < 32000;
 }
 // film_block >= 4: the gather reads a 32-bit descriptor from the .w lane of the radiance records (k_film_pack_w / k_film_gather_packed); needs a filter radius <= 1
 // (<= 4 columns / rows per sample) — every scene of the reference uses LanczosSincFilter(Point2f(1f0), 3f0)
 bool film_uses_packed(const trhip_ctx* ctx, const DeviceSensor& ds) {
-    return ctx->film_block >= 4 && !ctx->film_tiled && !ctx->film_transpose && std::fmax(ds.filter_radius[0], ds.filter_radius[1]) <= 1.0f && ds.filter_radius[0] > 0.0f && ds.filter_radius[1] > 0.0f;
+    return ctx->opt.film_block >= 4 && !ctx->opt.film_tiled && !ctx->opt.film_transpose && std::fmax(ds.filter_radius[0], ds.filter_radius[1]) <= 1.0f && ds.filter_radius[0] > 0.0f && ds.filter_radius[1] > 0.0f;
 }
 // the per-sample buffer the film pass needs next to the radiance: nothing (packed), descriptors (16 B) or film positions (8 B)
 int ensure_film_samples(trhip_ctx* ctx, const DeviceSensor& ds, uint64_t total_slots) {
@@ -57,7 +57,7 @@ int ensure_film_samples(trhip_ctx* ctx, const DeviceSensor& ds, uint64_t total_s
 // can k_raygen write the radiance records in the film pass's layout, descriptors included (th_kernels.h, k_raygen's Lf)?  Whole sample passes of one band, 32-bit indices.
 bool film_fused(const trhip_ctx* ctx, const DeviceSensor& ds, uint32_t spp) {
     const uint64_t npix_b = (uint64_t)ds.sb_w * ds.band_rows;
-    return ctx->film_fused && ctx->film_relayout && film_uses_packed(ctx, ds) && ((npix_b + 63u) / 64u) * 64u * spp < (1ull << 32);
+    return ctx->opt.film_fused && ctx->opt.film_relayout && film_uses_packed(ctx, ds) && ((npix_b + 63u) / 64u) * 64u * spp < (1ull << 32);
 }
 FilmSideTable film_side_table(trhip_ctx* ctx, hipStream_t st, uint64_t total_slots, bool* ok) {
     // side table for the descriptors that do not fit 30 bits (one sample in ~4000 at 1024^2): entry 0 of film_side is the counter, the descriptors follow
@@ -83,7 +83,7 @@ void launch_film(trhip_ctx* ctx, hipStream_t st, const DeviceSensor& ds, const D
             if (!ok) return;
         }
         if (fused) {
-        } else if (ctx->film_relayout && total_slots == (uint64_t)npix_b * spp && ensure(ctx, ctx->film_Lt, padded * sizeof(float4)) == 0) {
+        } else if (ctx->opt.film_relayout && total_slots == (uint64_t)npix_b * spp && ensure(ctx, ctx->film_Lt, padded * sizeof(float4)) == 0) {
             layout = 1;
             hipLaunchKernelGGL(k_film_pack_transpose, dim3(grid_for(ctx, padded, 8)), dim3(kBlock), 0, st, dsp, npix_b, spp, seed, sample_offset, L, (float4*)ctx->film_Lt.p, side);
             L = (const float4*)ctx->film_Lt.p;
@@ -92,8 +92,8 @@ void launch_film(trhip_ctx* ctx, hipStream_t st, const DeviceSensor& ds, const D
         }
         const float* tb = (const float*)ctx->table.p;
         auto threads = [&](int bx, int by) { return (uint64_t)((ds.film_w + bx - 1) / bx) * (uint64_t)((ds.film_h + by - 1) / by); };
-#define TH_FILM_PACKED(BXV, BYV) hipLaunchKernelGGL((k_film_gather_packed<BXV, BYV>), dim3(grid_for(ctx, threads(BXV, BYV), 8)), dim3(kBlock), 0, st, dsp, tb, L, spp, seed, sample_offset, layout, (const uint4*)side.desc, d_film, ctx->film_swizzle ? 1u : 0u)
-        switch (ctx->film_block) {
+#define TH_FILM_PACKED(BXV, BYV) hipLaunchKernelGGL((k_film_gather_packed<BXV, BYV>), dim3(grid_for(ctx, threads(BXV, BYV), 8)), dim3(kBlock), 0, st, dsp, tb, L, spp, seed, sample_offset, layout, (const uint4*)side.desc, d_film, ctx->opt.film_swizzle ? 1u : 0u)
+        switch (ctx->opt.film_block) {
         case 4: TH_FILM_PACKED(1, 4); break;
         case 7: TH_FILM_PACKED(2, 2); break;
         case 8: TH_FILM_PACKED(4, 2); break;
@@ -120,14 +120,14 @@ void launch_film(trhip_ctx* ctx, hipStream_t st, const DeviceSensor& ds, const D
     const uint64_t padded = (uint64_t)((npix + 63u) / 64u) * 64u * spp;
     uint32_t layout = 0;
     const bool whole = ds.band_rows == ds.sb_h;
-    if (whole && ctx->film_transpose && spp > 1 && total_slots == (uint64_t)npix * spp && ensure(ctx, ctx->pfilm, padded * sizeof(float2)) == 0 && ensure(ctx, ctx->film_Lt, padded * sizeof(float4)) == 0) {
+    if (whole && ctx->opt.film_transpose && spp > 1 && total_slots == (uint64_t)npix * spp && ensure(ctx, ctx->pfilm, padded * sizeof(float2)) == 0 && ensure(ctx, ctx->film_Lt, padded * sizeof(float4)) == 0) {
         layout = 1;
         hipLaunchKernelGGL(k_film_transpose, dim3(grid_for(ctx, padded, 8)), dim3(kBlock), 0, st, L, npix, spp, (float4*)ctx->film_Lt.p);
         L = (const float4*)ctx->film_Lt.p;
     }
     hipLaunchKernelGGL(k_film_positions, dim3(grid_for(ctx, total_slots, 8)), dim3(kBlock), 0, st, dsp, total_slots, seed, sample_offset, (float2*)ctx->pfilm.p, layout, spp);
     const float rmax = std::fmax(ds.filter_radius[0], ds.filter_radius[1]);
-    if (whole && ctx->film_tiled && rmax <= 6.0f) {  // reach of a pixel = 2r + 3 sample pixels <= 16: at most 2 x 2 sample tiles
+    if (whole && ctx->opt.film_tiled && rmax <= 6.0f) {  // reach of a pixel = 2r + 3 sample pixels <= 16: at most 2 x 2 sample tiles
         const uint32_t budget = 24 * 1024 / 20;  // staged {p_film, L} elements in 24 KiB of LDS: ~6 blocks per CU
         const uint32_t nc_max = 16 + 2 * (uint32_t)std::ceil(rmax) + 4;
         uint32_t cols, ns;
@@ -142,7 +142,7 @@ void launch_film(trhip_ctx* ctx, hipStream_t st, const DeviceSensor& ds, const D
         hipLaunchKernelGGL(k_film_gather_tiled, grid, dim3(kBlock), (size_t)cols * ns * 20 + 16, st, dsp, (const float*)ctx->table.p, L, (const float2*)ctx->pfilm.p, spp, layout, cols, ns, d_film);
     } else {
         const uint64_t npx = (uint64_t)ds.film_w * ds.film_h;
-        const int fblock = ctx->film_block >= 4 ? 2 : ctx->film_block;  // a filter too wide for the packed descriptor: the 1 x 4 block gather
+        const int fblock = ctx->opt.film_block >= 4 ? 2 : ctx->opt.film_block;  // a filter too wide for the packed descriptor: the 1 x 4 block gather
         if (fblock == 1)
             hipLaunchKernelGGL((k_film_gather_block<2, 2>), dim3(grid_for(ctx, (npx + 3) / 4, 8)), dim3(kBlock), 0, st, dsp, (const float*)ctx->table.p, L, (const float2*)ctx->pfilm.p, spp, layout, d_film);
         else if (fblock == 2)
@@ -249,7 +249,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
     if ((uint64_t)max_depth * total_slots >= (1ull << 32)) return 0;
     if (total_slots >= (1ull << 31)) return 0;  // one batch: queue indices are 32-bit
     const uint64_t P = total_slots;
-    const uint32_t list_cap = ctx->stream_list_cap ? ctx->stream_list_cap : (uint32_t)std::max<uint64_t>(65536, P / 128);
+    const uint32_t list_cap = ctx->opt.stream_list_cap ? ctx->opt.stream_list_cap : (uint32_t)std::max<uint64_t>(65536, P / 128);
     const uint32_t cap = (uint32_t)queue_cap(P, list_cap / kSeg + 64);  // every segment keeps room for the resumed rays appended to it
     const uint64_t Pphys = (uint64_t)cap * kSeg;
     const size_t list_bytes = (size_t)list_cap * (4 * 16 + 16 + 4 + (size_t)kStack2Total * 8);
@@ -271,13 +271,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
     }
     *declined = false;
     Pipe& pp = ctx->pipes[0];
-    if (!pp.st) {
-        HIP_TRY(ctx, hipStreamCreate(&pp.st));
-        HIP_TRY(ctx, hipStreamCreate(&pp.st2));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&pp.ev_shade, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&pp.ev_any, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&pp.ev_done, hipEventDisableTiming));
-    }
+    if (int rc = ensure_pipe(ctx, 0, false)) return rc;
     if (int rc = upload(ctx, ctx->sensor, &ds, sizeof ds)) return rc;
     if (int rc = upload(ctx, ctx->table, sensor->filter_table, 256 * sizeof(float))) return rc;
     for (int k = 0; k < 2; ++k)
@@ -290,6 +284,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
     const size_t slab_bytes = (size_t)trace_grid(ctx) * kBlock * (size_t)kStackSlabLevels * sizeof(uint2);
     for (int k = 0; k < 2; ++k)
         if (int rc = ensure(ctx, pp.overflow[k], slab_bytes)) return rc;
+    ctx->last = LastRecords{};
     if (int rc = ensure(ctx, ctx->Lbuf, total_slots * sizeof(float4))) return rc;
     if (int rc = ensure_film_samples(ctx, ds, total_slots)) return rc;
     if (int rc = ensure(ctx, ctx->st_terms, terms_bytes)) return rc;
@@ -311,7 +306,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
         return SuspendList{(float4*)b[0].p, (float4*)b[1].p, (float4*)b[2].p, (float4*)b[3].p, (uint4*)b[4].p, (uint32_t*)b[5].p, (uint2*)b[6].p, list_cap};
     };
     uint32_t* lc = (uint32_t*)ctx->st_counts.p;  // [0..1] closest list counts (ping-pong), [2] closest cursor, [4..5] any counts, [6] any cursor
-    hipStream_t st = ctx->stream, ps = pp.st, ps2 = ctx->overlap ? pp.st2 : pp.st;
+    hipStream_t st = ctx->stream, ps = pp.st, ps2 = ctx->opt.overlap ? pp.st2 : pp.st;
     const DeviceSensor* dsp = (const DeviceSensor*)ctx->sensor.p;
     float4* L = (float4*)ctx->Lbuf.p;
     float4* terms = (float4*)ctx->st_terms.p;
@@ -323,7 +318,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
     float4* hits = (float4*)pp.hits.p;
     uint32_t* frozen = (uint32_t*)ctx->st_frozen.p;
 
-    Timer tm(ctx, ctx->timing && stats);
+    Timer tm(ctx, ctx->opt.timing && stats);
     FrameEvents ev;
     OwnedEvent ev_start;
     HIP_TRY(ctx, ev_start.create());
@@ -340,13 +335,13 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
     const int g_shade = ctx->num_cu * 8;
     int cur = 0;
     for (int r = 0; r < R; ++r) {
-        const uint32_t budget_min = r < R_b ? ctx->stream_budget_min : 0u;  // the last max_depth rounds run every ray to its end
+        const uint32_t budget_min = r < R_b ? ctx->opt.stream_budget_min : 0u;  // the last max_depth rounds run every ray to its end
         const int in_pg = r & 1, out_pg = (r + 1) & 1;
         // ---- closest hits: fresh rays through frozen counts (finished resumed rays are appended to the live queue) ----
         HIP_TRY(ctx, hipMemcpyAsync(frozen, ctr->n_queue[r], row_bytes, hipMemcpyDeviceToDevice, ps));
         HIP_TRY(ctx, hipMemsetAsync(&lc[out_pg], 0, sizeof(uint32_t), ps));
         HIP_TRY(ctx, hipMemsetAsync(&lc[2], 0, sizeof(uint32_t), ps));
-        StreamCtl sc_c{list_of(0, in_pg), list_of(0, out_pg), &lc[in_pg], &lc[2], &lc[out_pg], budget_min, ctx->stream_budget_shift, pq[cur].beta, tags[cur], pq[cur].o, pq[cur].d, pq[cur].beta, hits, tags[cur],
+        StreamCtl sc_c{list_of(0, in_pg), list_of(0, out_pg), &lc[in_pg], &lc[2], &lc[out_pg], budget_min, ctx->opt.stream_budget_shift, pq[cur].beta, tags[cur], pq[cur].o, pq[cur].d, pq[cur].beta, hits, tags[cur],
                        ctr->n_queue[r], cap};
         const SegQueue qc{frozen, cap, 0u};
         const TraceOut oc{hits, nullptr, nullptr, nullptr, 1u};
@@ -374,7 +369,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
         // ---- shadow rays: unoccluded ones add their contribution to the term slot ----
         HIP_TRY(ctx, hipMemsetAsync(&lc[4 + out_pg], 0, sizeof(uint32_t), ps2));
         HIP_TRY(ctx, hipMemsetAsync(&lc[6], 0, sizeof(uint32_t), ps2));
-        StreamCtl sc_a{list_of(1, in_pg), list_of(1, out_pg), &lc[4 + in_pg], &lc[6], &lc[4 + out_pg], budget_min, ctx->stream_budget_shift, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u};
+        StreamCtl sc_a{list_of(1, in_pg), list_of(1, out_pg), &lc[4 + in_pg], &lc[6], &lc[4 + out_pg], budget_min, ctx->opt.stream_budget_shift, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u};
         const SegQueue qa{ctr->n_shadow[r], cap, 0u};
         const TraceOut oa{nullptr, terms, sq.c, nullptr, 0u};
         tm.begin(3, ps2);
@@ -397,11 +392,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
     HIP_TRY(ctx, ev.end(st));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    ctx->last_L_count = total_slots;
-    ctx->last_L_layout = 0;
-    ctx->last_L_npix = (uint32_t)npix;
-    ctx->last_L_spp = spp;
-    ctx->last_L_kind = 1;
+    ctx->last = LastRecords{total_slots, 0u, (uint32_t)npix, spp, 1u};
     if (int rc = copy_back(ctx, out, out_is_device, d_film, film_bytes)) return rc;
     uint32_t left[8];
     HIP_TRY(ctx, hipMemcpy(left, lc, sizeof left, hipMemcpyDeviceToHost));
@@ -432,7 +423,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     if (scene->has_materialless_prim)  // found once, at commit: walking a million host records here cost 2.8 ms of every frame
             return fail(ctx, TRHIP_ERR_UNSUPPORTED, "rendering a scene with a material-less primitive is not supported (the trace entry points accept it)");
     if (spp == 0 || max_depth < 1 || max_depth > kMaxDepth) return fail(ctx, TRHIP_ERR_INVALID, "spp must be >= 1 and max_depth in 1..%d", kMaxDepth);
-    if (!ctx->warned_idle_accelerator && ctx->hybrid) {  // a two-tree scene rendered with options that leave its accelerator idle: said once per context (trhip_accelerator_note has it too)
+    if (!ctx->warned_idle_accelerator && ctx->opt.hybrid) {  // a two-tree scene rendered with options that leave its accelerator idle: said once per context (trhip_accelerator_note has it too)
         const char* why = hybrid_idle_reason(ctx, scene);
         if (why[0]) {
             ctx->warned_idle_accelerator = true;
@@ -452,6 +443,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     if (integrator == 0) {
         if (int rc = upload(ctx, ctx->sensor, &ds, sizeof ds)) return rc;
         if (int rc = upload(ctx, ctx->table, sensor->filter_table, 256 * sizeof(float))) return rc;
+        ctx->last = LastRecords{};
         if (int rc = ensure(ctx, ctx->Lbuf, total_slots * sizeof(float4))) return rc;
         if (int rc = ensure_film_samples(ctx, ds, total_slots)) return rc;
         if (int rc = ensure(ctx, ctx->counters, sizeof(Counters))) return rc;
@@ -459,12 +451,10 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         void* df;
         if (int rc = stage_output(ctx, out, out_is_device, fb, &df)) return rc;
         if (int rc = render_whitted_impl(ctx, scene, ds, sensor, spp, max_depth, seed, sample_offset, df, stats)) return rc;
-        ctx->last_L_count = total_slots;
-        ctx->last_L_layout = 0;
-        ctx->last_L_kind = 0;
+        ctx->last = LastRecords{total_slots, 0u, (uint32_t)npix, spp, 0u};  // (render_whitted_impl has synchronised its stream)
         return copy_back(ctx, out, out_is_device, df, fb);
     }
-    if (!band && !map && (ctx->streaming == 1 || (ctx->streaming < 0 && total_slots <= 96ull * scene->g->prims.size())) && ctx->traversal >= 2 && scene->wide_ok && scene->wide.root_cnt == 0 && scene->wide.root_ref != kRefNone && ctx->batch_paths == 0 && ctx->pipelines <= 1) {
+    if (!band && !map && (ctx->opt.streaming == 1 || (ctx->opt.streaming < 0 && total_slots <= 96ull * scene->g->prims.size())) && ctx->opt.traversal >= 2 && scene->wide_ok && scene->wide.root_cnt == 0 && scene->wide.root_ref != kRefNone && ctx->opt.batch_paths == 0 && ctx->opt.pipelines <= 1) {
         bool declined = false;
         const int rc = render_stream_impl(ctx, scene, sensor, ds, spp, max_depth, seed, sample_offset, out, out_is_device, stats, &declined);
         if (!declined) return rc;
@@ -479,7 +469,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         if (!fits) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "the per-sample buffers of a map frame (%.2f GB at max_spp %u) do not fit in half of free HBM (%.2f GB): there are no bands here", need * 1e-9, spp, free_gb);
     }
     // wavefront batch = whole sample passes (a map frame: ranges of its job list); per path in flight: 2 x 3 queue float4 + 3 shadow float4 + 1 hit float4 = 160 B
-    uint64_t batch_paths = ctx->batch_paths;
+    uint64_t batch_paths = ctx->opt.batch_paths;
     if (batch_paths == 0) {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
@@ -491,7 +481,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     spp_batch = std::min<uint64_t>(spp_batch, spp);
     // Several batches run concurrently (one per pipeline): the memory budget is shared and the frame is cut into at
     // least `pipelines` batches when it has that many sample passes.
-    const int want_pipes = map ? 1 : std::max(1, std::min(ctx->pipelines, kMaxPipes));  // (a map frame ignores "pipelines")
+    const int want_pipes = map ? 1 : std::max(1, std::min(ctx->opt.pipelines, kMaxPipes));  // (a map frame ignores "pipelines")
     spp_batch = std::max<uint64_t>(1, std::min<uint64_t>(spp_batch / want_pipes, (spp + want_pipes - 1) / want_pipes));
     while (npix * spp_batch >= (1ull << 31)) spp_batch = (spp_batch + 1) / 2;  // queue indices are 32-bit
     const uint64_t total_jobs = map ? map->total : total_slots;  // the frame's camera samples: entries of the job list, or every slot
@@ -509,29 +499,15 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     const size_t slab_bytes = (size_t)trace_grid(ctx) * kBlock * (size_t)kStackSlabLevels * sizeof(uint2);
     for (int pi = 0; pi < NP; ++pi) {
         Pipe& pp = ctx->pipes[pi];
-        if (!pp.st) {
-            // the shadow-ray stream gets its own priority level: streams of one level can share a hardware queue (then any(d) and
-            // closest(d+1) run one after the other: measured in the first context of a process), streams of different levels cannot
-            int prio_lo = 0, prio_hi = 0;
-            (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-            HIP_TRY(ctx, hipStreamCreate(&pp.st));
-            if (ctx->stream2_priority && prio_hi != prio_lo)
-                HIP_TRY(ctx, hipStreamCreateWithPriority(&pp.st2, hipStreamDefault, ctx->stream2_priority > 0 ? prio_hi : prio_lo));
-            else
-                HIP_TRY(ctx, hipStreamCreate(&pp.st2));
-            HIP_TRY(ctx, hipEventCreateWithFlags(&pp.ev_shade, hipEventDisableTiming));
-            HIP_TRY(ctx, hipEventCreateWithFlags(&pp.ev_any, hipEventDisableTiming));
-            HIP_TRY(ctx, hipEventCreateWithFlags(&pp.ev_done, hipEventDisableTiming));
-        }
+        if (int rc = ensure_pipe(ctx, pi, true)) return rc;
         for (int k = 0; k < 2; ++k)
             for (int j = 0; j < 3; ++j)
                 if (int rc = ensure(ctx, pp.q[k][j], Pphys * sizeof(float4))) return rc;
         for (int j = 0; j < 3; ++j)
             if (int rc = ensure(ctx, pp.sq[j], Pphys * sizeof(float4))) return rc;
-        if (ctx->overlap)
+        if (ctx->opt.overlap)
             for (int j = 0; j < 3; ++j)
                 if (int rc = ensure(ctx, pp.sq2[j], Pphys * sizeof(float4))) return rc;
-        if (!pp.ev_any2) HIP_TRY(ctx, hipEventCreateWithFlags(&pp.ev_any2, hipEventDisableTiming));
         if (int rc = ensure(ctx, pp.hits, Pphys * sizeof(float4))) return rc;
         if (int rc = ensure(ctx, pp.counters, sizeof(Counters))) return rc;
         for (int k = 0; k < 2; ++k)
@@ -540,6 +516,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     // the radiance records: sample-major, or — when k_raygen can initialise them for the film pass (film_fused) — pixel-group-major, padded to whole groups of 64 pixels
     const bool fused = map ? map_packed : film_fused(ctx, ds, spp);
     const uint64_t l_slots = fused ? ((npix + 63u) / 64u) * 64u * (uint64_t)spp : total_slots;
+    ctx->last = LastRecords{};
     if (int rc = ensure(ctx, ctx->poison, l_slots)) return rc;
     if (int rc = ensure(ctx, ctx->Lbuf, l_slots * sizeof(float4))) return rc;
     if (map) {
@@ -556,7 +533,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     float4* L = (float4*)ctx->Lbuf.p;
 
     hclk.tick("setup (budget, buffers)");
-    Timer tm(ctx, ctx->timing && stats);
+    Timer tm(ctx, ctx->opt.timing && stats);
     FrameEvents ev;
     OwnedEvent ev_start;
     HIP_TRY(ctx, ev_start.create());
@@ -572,7 +549,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     HIP_TRY(ctx, hipMemsetAsync(ctx->poison.p, 0, l_slots, st));
     HIP_TRY(ctx, hipEventRecord(ev_start.e, st));
     const int g_shade = ctx->num_cu * 8;
-    const uint32_t bary_mode = (ctx->traversal >= 2 && scene->wide_ok) ? 1u : 0u;  // k_trace2 hands the barycentrics to the shading kernel
+    const uint32_t bary_mode = (ctx->opt.traversal >= 2 && scene->wide_ok) ? 1u : 0u;  // k_trace2 hands the barycentrics to the shading kernel
     uint32_t n_batches = 0;
     for (int pi = 0; pi < NP; ++pi) {
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipes[pi].st, ev_start.e, 0));
@@ -583,7 +560,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         n_batches++;
         const uint64_t nb = std::min<uint64_t>(P, total_jobs - j0);
         // Within a batch, shadow rays of depth d (any-hit + accumulate) and closest-hit rays of depth d+1 are independent: two streams.
-        hipStream_t ps = pp.st, ps2 = ctx->overlap ? pp.st2 : pp.st;
+        hipStream_t ps = pp.st, ps2 = ctx->opt.overlap ? pp.st2 : pp.st;
         Counters* ctr = (Counters*)pp.counters.p;
         PathQueue pq[2];
         for (int k = 0; k < 2; ++k) pq[k] = PathQueue{(float4*)pp.q[k][0].p, (float4*)pp.q[k][1].p, (float4*)pp.q[k][2].p};
@@ -644,22 +621,18 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->pipes[pi].ev_done, 0));
     }
     tm.begin(4, st);
-    if (ctx->overlap) hipLaunchKernelGGL(k_apply_poison, dim3(grid_for(ctx, l_slots, 8)), dim3(kBlock), 0, st, L, (const uint8_t*)ctx->poison.p, l_slots);
+    if (ctx->opt.overlap) hipLaunchKernelGGL(k_apply_poison, dim3(grid_for(ctx, l_slots, 8)), dim3(kBlock), 0, st, L, (const uint8_t*)ctx->poison.p, l_slots);
     if (map)
         launch_film_map(ctx, st, ds, dsp, L, *map, spp, seed, sample_offset, (float4*)d_film, map_packed);
     else
         launch_film(ctx, st, ds, dsp, L, total_slots, spp, seed, sample_offset, (float4*)d_film, fused);
     tm.end(4, st);
-    ctx->last_L_layout = fused ? 1u : 0u;
-    ctx->last_L_npix = (uint32_t)npix;
-    ctx->last_L_spp = spp;
-    ctx->last_L_kind = map ? 2u : band ? 0u : 1u;
     HIP_TRY(ctx, ev.end(st));
     HIP_TRY(ctx, hipGetLastError());
     hclk.tick("enqueue");
     HIP_TRY(ctx, hipStreamSynchronize(st));
     hclk.tick("stream sync");
-    ctx->last_L_count = total_slots;
+    ctx->last = LastRecords{total_slots, fused ? 1u : 0u, (uint32_t)npix, spp, map ? 2u : band ? 0u : 1u};
     if (int rc = copy_back(ctx, out, out_is_device, d_film, film_bytes)) return rc;
     if (stats) {
         std::memset(stats, 0, sizeof *stats);
@@ -714,8 +687,8 @@ int render_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* se
     int rows_per_band = ds.tiles_y;  // in tile rows
     if (integrator == 1 && ds.sb_w > 0 && ds.sb_h > 0 && spp > 0) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        if (ctx->band_tile_rows > 0) {
-            rows_per_band = std::min<int>(ds.tiles_y, ctx->band_tile_rows);
+        if (ctx->opt.band_tile_rows > 0) {
+            rows_per_band = std::min<int>(ds.tiles_y, ctx->opt.band_tile_rows);
         } else {
             size_t free_b = 0, total_b = 0;
             HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
@@ -738,9 +711,7 @@ int render_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* se
         if (int rc = render_impl_band(ctx, scene, sensor, integrator, spp, max_depth, seed, sample_offset, d_film, true, &st, &b)) return rc;
         stats_accumulate(sum, st);
     }
-    ctx->last_L_count = 0;  // trhip_last_sample_radiance describes whole frames only
-    ctx->last_L_layout = 0;
-    ctx->last_L_kind = 0;
+    ctx->last = LastRecords{};  // trhip_last_sample_radiance describes whole frames only
     if (int rc = copy_back(ctx, out, out_is_device, d_film, film_bytes)) return rc;
     if (stats) *stats = sum;
     return 0;
@@ -759,7 +730,7 @@ int render_map_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor
     uint64_t total = 0;
     bool above = false;
     if (on_device) {
-        if (ctx->last_L_kind == 2) ctx->last_L_count = 0;  // the counts of the map frame before go with this copy
+        if (ctx->last.kind == 2) ctx->last = LastRecords{};  // the counts of the map frame before go with this copy
         if (int rc = ensure(ctx, ctx->map_counts, npix * sizeof(uint32_t))) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->map_counts.p, counts, npix * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
     } else {
@@ -776,8 +747,7 @@ int render_map_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor
     if (above) return fail(ctx, TRHIP_ERR_INVALID, "a count of the sample map lies above max_spp = %u", max_spp);
     if (total == 0) return fail(ctx, TRHIP_ERR_INVALID, "the sample map draws no sample");
     const MapFrame map{(const uint32_t*)ctx->map_counts.p, (const uint32_t*)ctx->map_jobs.p, total};
-    ctx->last_L_count = 0;  // (until this frame's radiance is complete: map_counts already belongs to it)
-    ctx->last_L_kind = 0;
+    ctx->last = LastRecords{};  // (until this frame's radiance is complete: map_counts already belongs to it)
     return render_impl_band(ctx, scene, sensor, 1, max_spp, max_depth, seed, sample_offset, out, on_device, stats, nullptr, &map);
 }
 }  // namespace
@@ -825,15 +795,16 @@ int trhip_render_path_map_device(trhip_ctx* ctx, const trhip_scene* sc, const tr
 }
 int trhip_last_sample_radiance(trhip_ctx* ctx, float* out, uint64_t n_floats) {
     if (!ctx || !out) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
-    if (n_floats != ctx->last_L_count * 3) return fail(ctx, TRHIP_ERR_INVALID, "expected %llu floats", (unsigned long long)(ctx->last_L_count * 3));
+    const LastRecords& last = ctx->last;
+    if (n_floats != last.count * 3) return fail(ctx, TRHIP_ERR_INVALID, "expected %llu floats", (unsigned long long)(last.count * 3));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int rc = ensure(ctx, ctx->scratch[0], n_floats * sizeof(float))) return rc;
-    const uint64_t n = ctx->last_L_count;
-    if (n && ctx->last_L_kind == 2)  // a map frame: the records that were drawn, +0 elsewhere
-        hipLaunchKernelGGL(k_export_L_map, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)ctx->Lbuf.p, n, (float*)ctx->scratch[0].p, ctx->last_L_layout, ctx->last_L_npix,
-                           ctx->last_L_spp, (const uint32_t*)ctx->map_counts.p);
+    const uint64_t n = last.count;
+    if (n && last.kind == 2)  // a map frame: the records that were drawn, +0 elsewhere
+        hipLaunchKernelGGL(k_export_L_map, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)ctx->Lbuf.p, n, (float*)ctx->scratch[0].p, last.layout, last.npix,
+                           last.spp, (const uint32_t*)ctx->map_counts.p);
     else if (n)
-        hipLaunchKernelGGL(k_export_L, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)ctx->Lbuf.p, n, (float*)ctx->scratch[0].p, ctx->last_L_layout, ctx->last_L_npix, ctx->last_L_spp);
+        hipLaunchKernelGGL(k_export_L, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)ctx->Lbuf.p, n, (float*)ctx->scratch[0].p, last.layout, last.npix, last.spp);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(out, ctx->scratch[0].p, n_floats * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
@@ -888,6 +859,7 @@ int trhip_film_accumulate(trhip_ctx* ctx, const trhip_sensor* sn, uint32_t spp, 
     if (int rc = upload(ctx, ctx->sensor, &ds, sizeof ds)) return rc;
     if (int rc = upload(ctx, ctx->table, sn->filter_table, 256 * sizeof(float))) return rc;
     if (int rc = upload(ctx, ctx->scratch[0], sample_L, n * 3 * sizeof(float))) return rc;
+    ctx->last = LastRecords{};
     if (int rc = ensure(ctx, ctx->Lbuf, n * sizeof(float4))) return rc;
     const size_t film_bytes = (size_t)ds.film_w * ds.film_h * sizeof(float4);
     if (int rc = ensure(ctx, ctx->film, film_bytes)) return rc;
@@ -896,11 +868,7 @@ int trhip_film_accumulate(trhip_ctx* ctx, const trhip_sensor* sn, uint32_t spp, 
     launch_film(ctx, ctx->stream, ds, (const DeviceSensor*)ctx->sensor.p, (const float4*)ctx->Lbuf.p, n, spp, seed, sample_offset, (float4*)ctx->film.p, false);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->last_L_count = n;
-    ctx->last_L_layout = 0;
-    ctx->last_L_npix = (uint32_t)((uint64_t)ds.sb_w * ds.sb_h);
-    ctx->last_L_spp = spp;
-    ctx->last_L_kind = 1;  // (trhip_last_sample_stats reads a caller's records too)
+    ctx->last = LastRecords{n, 0u, (uint32_t)((uint64_t)ds.sb_w * ds.sb_h), spp, 1u};  // (trhip_last_sample_stats reads a caller's records too)
     HIP_TRY(ctx, hipMemcpy(out_xyzw, ctx->film.p, film_bytes, hipMemcpyDeviceToHost));
     return 0;
 }

@@ -297,7 +297,7 @@ int upload_scene(trhip_scene* s) {
     } else {
         release(s->g->d_tan);
     }
-    DevBuf d_uv;
+    DevBuf d_uv;  // (a temporary: freed when this function returns, whichever way)
     if (any_uv) {
         std::vector<float4> uvs((size_t)n_prims * 2, make_float4(0, 0, 0, 0));
         parallel_for(n_prims, [&](size_t k0, size_t k1) {
@@ -310,21 +310,13 @@ int upload_scene(trhip_scene* s) {
                 }
             }
         });
-        if (int rc = upload(ctx, d_uv, uvs.data(), uvs.size() * sizeof(float4))) {
-            release(d_uv);
-            return rc;
-        }
+        if (int rc = upload(ctx, d_uv, uvs.data(), uvs.size() * sizeof(float4))) return rc;
     }
     {  // the shading kernels' interleaved view (th_scene.h): one 128-byte line per slot, put together on the device from the two arrays just uploaded
-        if (int rc = ensure(ctx, s->g->d_shade, (size_t)n_prims * 8 * sizeof(float4))) {
-            release(d_uv);
-            return rc;
-        }
+        if (int rc = ensure(ctx, s->g->d_shade, (size_t)n_prims * 8 * sizeof(float4))) return rc;
         hipLaunchKernelGGL(k_shade_constants, dim3(std::max(1u, std::min((n_prims + kBlock - 1) / kBlock, 4096u))), dim3(kBlock), 0, ctx->stream, (float4*)s->g->d_shade.p, (const float4*)s->g->d_prims.p, (const float4*)s->g->d_nrm.p, (const float4*)d_uv.p, n_prims);
-        const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(ctx->stream);
-        release(d_uv);
-        HIP_TRY(ctx, e1);
-        HIP_TRY(ctx, e2);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     clk.tick("upload: shade records");
     if (int rc = upload(ctx, s->g->d_spheres, s->g->spheres.data(), s->g->spheres.size() * sizeof(SphereRec))) return rc;
@@ -349,10 +341,10 @@ int upload_scene(trhip_scene* s) {
     s->wide.root_ref = kRefNone;
     if (n_nodes > 0 && n_prims < (1u << 24) && !s->literal_only) {
         std::vector<uint32_t> widx;
-        const uint32_t n_int = wide_node_order(s->g->bvh, ctx->node_layout, widx);
+        const uint32_t n_int = wide_node_order(s->g->bvh, ctx->opt.node_layout, widx);
         bool ok = n_int < (1u << 24);
         RawArray<float4> wn((size_t)n_int * 4);  // every interior node writes its four records below (layout 1: the alignment gaps are zeroed first)
-        if (ctx->node_layout == 1 && ok) std::memset((void*)wn.data(), 0, (size_t)n_int * 4 * sizeof(float4));
+        if (ctx->opt.node_layout == 1 && ok) std::memset((void*)wn.data(), 0, (size_t)n_int * 4 * sizeof(float4));
         has_empty_leaf = false;
         // subtrees that hold a sphere keep the reference's loose slab test (th_trace2.h, slab_test2): the fp32 sphere quadratic
         // (sphere.jl:120-150) accepts rays that pass the sphere at a distance far beyond the tight test's margin
@@ -1027,7 +1019,7 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
     }
     // children-in-parent nodes (as upload_scene's, th_trace2.h)
     std::vector<uint32_t> widx;
-    const uint32_t n_int = wide_node_order(s->g->acc, ctx->node_layout, widx);
+    const uint32_t n_int = wide_node_order(s->g->acc, ctx->opt.node_layout, widx);
     if (n_int >= (1u << 24)) return 0;
     std::vector<uint8_t> has_sphere(n_anodes, 0);
     for (uint32_t i = n_anodes; i-- > 0;) {  // bottom-up (second children and first children both come later in the depth-first layout)
@@ -1040,7 +1032,7 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
         }
     }
     RawArray<float4> wn((size_t)n_int * 4);
-    if (ctx->node_layout == 1) std::memset((void*)wn.data(), 0, (size_t)n_int * 4 * sizeof(float4));
+    if (ctx->opt.node_layout == 1) std::memset((void*)wn.data(), 0, (size_t)n_int * 4 * sizeof(float4));
     parallel_for(n_anodes, [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; ++i) {
             if ((s->g->acc.flags[i] & 3u) == 3u) continue;
@@ -1078,7 +1070,7 @@ static int upload_accelerator_impl(trhip_scene* s, bool conformed) {
     //      the dependent node fetches per ray.
     s->wide_acc.w4nodes = nullptr;
     s->wide_acc.n_w4nodes = 0;
-    if (ctx->wide4) {
+    if (ctx->opt.wide4) {
         struct Frame { uint32_t node, out; };
         std::vector<float4> w4;
         w4.reserve((size_t)n_int / 2 * 8 + 64);
@@ -1208,13 +1200,7 @@ int trhip_scene_new(trhip_ctx* ctx, trhip_scene** out) {
 void trhip_scene_free(trhip_scene* s) {
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
-    release(s->d_lights);
-    release(s->d_leaf_order);
-    release(s->d_acc_leaf_order);
-    release(s->d_occ_slots);
-    release(s->d_occ_boxes);
-    s->g.reset();  // the geometry's buffers go with the last handle that holds them (~SceneGeometry)
-    delete s;
+    delete s;  // the light stage's buffers; the geometry's go with the last handle that holds them
 }
 int trhip_scene_add_material(trhip_scene* s, int kind, const float* params, int n_params, uint32_t* id_out) {
     if (!s || !params) return fail(s ? s->ctx : nullptr, TRHIP_ERR_INVALID, "null argument");
@@ -1412,7 +1398,7 @@ static void primitive_bounds(const trhip_scene* s, std::vector<HostAABB>& pb) {
 static int build_library_tree(trhip_ctx* ctx, const std::vector<HostAABB>& pb_build, int max_node_primitives, int mode, bool want_chain, FlatBVH& out) {
     bool built = false;
     ctx->bvh_device_ms = 0.0;
-    if ((mode == 3 || ((mode < 0 || mode == 4) && pb_build.size() >= (64u << 10))) && pb_build.size() > ctx->tiny_scene_prims) {
+    if ((mode == 3 || ((mode < 0 || mode == 4) && pb_build.size() >= (64u << 10))) && pb_build.size() > ctx->opt.tiny_scene_prims) {
         // the host builder's binned SAH, on the device (th_sahb.h); scenes it hands back (TRHIP_ERR_UNSUPPORTED) go to the host builder below
         FlatBVH dev;
         const int rc = build_bvh_device_sah(ctx, pb_build, max_node_primitives, want_chain, dev, &ctx->bvh_device_ms);
@@ -1423,7 +1409,7 @@ static int build_library_tree(trhip_ctx* ctx, const std::vector<HostAABB>& pb_bu
             return rc;
         }
     }
-    if (!built && mode == 1 && pb_build.size() > ctx->tiny_scene_prims) {
+    if (!built && mode == 1 && pb_build.size() > ctx->opt.tiny_scene_prims) {
         FlatBVH dev;
         const int rc = build_bvh_device(ctx, pb_build, dev);
         if (rc == 0) {
@@ -1434,7 +1420,7 @@ static int build_library_tree(trhip_ctx* ctx, const std::vector<HostAABB>& pb_bu
         }
     }
     if (!built) {
-        BVHBuilder builder(pb_build, max_node_primitives, ctx->tiny_scene_prims, want_chain);  // traversal 4 wants one primitive per leaf
+        BVHBuilder builder(pb_build, max_node_primitives, ctx->opt.tiny_scene_prims, want_chain);  // traversal 4 wants one primitive per leaf
         out = builder.build();
     }
     return 0;
@@ -1470,9 +1456,9 @@ static int commit_geometry(trhip_scene* s, int max_node_primitives) {
     // kernel then walks with conservative interior boxes (th_wide8.h).  The leaf-size hint is a hint (bvh.jl:159-165 decides by cost).
     std::vector<uint32_t> sph_ids, tri_ids;
     for (size_t i = 0; i < s->g->prims.size(); ++i) (s->g->prims[i].kind == 1 ? sph_ids : tri_ids).push_back((uint32_t)i);
-    const int mode = s->ctx->bvh_builder;
-    const bool want_chain = s->ctx->compose_spheres > 0 || (s->ctx->compose_spheres < 0 && s->ctx->traversal == 4);
-    const bool compose = mode != 2 && want_chain && !sph_ids.empty() && sph_ids.size() <= (size_t)kW8MaxSpheres && tri_ids.size() >= 2 && pb.size() > s->ctx->tiny_scene_prims;
+    const int mode = s->ctx->opt.bvh_builder;
+    const bool want_chain = s->ctx->opt.compose_spheres > 0 || (s->ctx->opt.compose_spheres < 0 && s->ctx->opt.traversal == 4);
+    const bool compose = mode != 2 && want_chain && !sph_ids.empty() && sph_ids.size() <= (size_t)kW8MaxSpheres && tri_ids.size() >= 2 && pb.size() > s->ctx->opt.tiny_scene_prims;
     // HYBRID (mode 4, and the default -1): the canonical tree is the reference's own construction — the answers are Trace.jl's, ray for ray — and the library's tree
     // rides along as the accelerator most rays walk instead (th_trace3c.h).  Not with the sphere chain (a layout only traversal 4 asks for).
     const bool want_hybrid = (mode == 4 || mode < 0) && !want_chain;
@@ -1589,7 +1575,7 @@ static int commit_geometry(trhip_scene* s, int max_node_primitives) {
     // A DEFAULT commit that ended with the library's tree as its one (canonical) tree — the reference's construction failed on the scene: 10 M triangles — still gets the
     // four-wide certified walk: the same tree rides along as its own accelerator (mode 3).  The answers are the canonical tree's own walk's, as always; explicit requests
     // (bvh_builder 0 / 3) keep the single tree.
-    if (mode < 0 && s->ctx->wide4 && !want_chain && !compose && s->wide_ok && s->wide.root_cnt == 0) {
+    if (mode < 0 && s->ctx->opt.wide4 && !want_chain && !compose && s->wide_ok && s->wide.root_cnt == 0) {
         s->g->acc = s->g->bvh;
         if (int rc = upload_accelerator(s)) return rc;
         if (s->hybrid_ok && s->wide_acc.w4nodes)
@@ -1613,17 +1599,12 @@ int trhip_scene_commit(trhip_scene* s, int max_node_primitives) {
 int trhip_scene_relight(const trhip_scene* base, trhip_scene** out) {
     if (!base || !out) return fail(base ? base->ctx : nullptr, TRHIP_ERR_INVALID, "null argument");
     if (!base->committed) return fail(base->ctx, TRHIP_ERR_INVALID, "trhip_scene_relight: the base scene is not committed (commit it, or commit the relit view it came from, first)");
-    auto v = new trhip_scene(*base);  // the geometry (shared) and its views; the light stage's buffers are the view's own, made at its commit
+    auto v = new trhip_scene();  // the light stage's members are the view's own, made at its commit
+    static_cast<SceneViews&>(*v) = *base;
+    v->ctx = base->ctx;
+    v->g = base->g;
     v->relit = true;
-    v->committed = false;
-    v->lights.clear();
-    v->d_lights = DevBuf{};
-    v->d_leaf_order = DevBuf{};
-    v->d_acc_leaf_order = DevBuf{};
-    v->d_occ_slots = DevBuf{};
-    v->d_occ_boxes = DevBuf{};
-    v->n_occluders = 0;
-    v->dev.lights = v->dev_acc.lights = nullptr;
+    v->dev.lights = v->dev_acc.lights = nullptr;  // (what the base's light stage patched into the views)
     v->dev.n_lights = v->dev_acc.n_lights = 0;
     v->wide.leaf_order = v->wide_acc.leaf_order = nullptr;
     *out = v;
@@ -1768,8 +1749,8 @@ int trhip_scene_set_bvh(trhip_scene* s, const float* bounds, const uint32_t* a, 
     if (int rc = upload_scene(s)) return rc;
     // The host's own tree is the canonical one (Trace.jl's BVHAccel through TraceHIP.jl): under the default / hybrid builder the library's tree over the same
     // primitives rides along as the accelerator (th_trace3c.h) — same answers, most rays on the cheaper tree.  Needs every primitive in the tree exactly once.
-    const int mode = s->ctx->bvh_builder;
-    const bool want_chain = s->ctx->compose_spheres > 0 || (s->ctx->compose_spheres < 0 && s->ctx->traversal == 4);
+    const int mode = s->ctx->opt.bvh_builder;
+    const bool want_chain = s->ctx->opt.compose_spheres > 0 || (s->ctx->opt.compose_spheres < 0 && s->ctx->opt.traversal == 4);
     if ((mode == 4 || mode < 0) && !want_chain && nested && n_prims == s->g->prims.size()) {
         std::vector<uint8_t> seen(n_prims, 0);
         bool perm = true;

@@ -84,7 +84,7 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     const int rec_depths = max_depth - 1 + (xing ? (int)kMaxCrossings : 0);
     const int ndep = std::max(1, rec_depths);
     const double per_iter = (double)n * (7 * 16.0 + max_depth * 16.0) + (double)P * ndep * 49.0 + (double)Qit * 10 * 16.0;
-    uint64_t B = ctx->sppm_batch;
+    uint64_t B = ctx->opt.sppm_batch;
     if (B == 0) {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
@@ -99,13 +99,7 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     const uint32_t cap = (uint32_t)queue_cap(Q);
     const uint64_t Pphys = (uint64_t)cap * kSeg;
     Pipe& pp = ctx->pipes[0];
-    if (!pp.st) {
-        HIP_TRY(ctx, hipStreamCreate(&pp.st));
-        HIP_TRY(ctx, hipStreamCreate(&pp.st2));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&pp.ev_shade, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&pp.ev_any, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&pp.ev_done, hipEventDisableTiming));
-    }
+    if (int rc = ensure_pipe(ctx, 0, false)) return rc;
     for (int k = 0; k < 2; ++k)
         for (int j = 0; j < 3; ++j)
             if (int rc = ensure(ctx, pp.q[k][j], Pphys * sizeof(float4))) return rc;
@@ -170,7 +164,7 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     if (int rc = ensure(ctx, ctx->scratch[2], (size_t)n * sizeof(uint32_t))) return rc;
     uint32_t* hot_list = (uint32_t*)ctx->scratch[2].p;
 
-    Timer tm(ctx, ctx->timing && stats);
+    Timer tm(ctx, ctx->opt.timing && stats);
     FrameEvents ev;
     HIP_TRY(ctx, ev.begin(st));
     // pixels = [SPPMPixel(radius = initial_search_radius) …] (:136-139)
@@ -314,8 +308,8 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
                                    (const uint32_t*)starts, entries, 1);
             tm.end(6, st);
             tm.begin(5, st);
-            hipLaunchKernelGGL(k_sppm_gather, g_pix, blk, 0, st, scene->dev, rec, vp, px, n, grid, (const uint32_t*)starts, (const float4*)entries, n, hot_list, it0 + j == n_iterations ? 1u : 0u, ctx->count_visits ? 1u : 0u);
-            hipLaunchKernelGGL(k_sppm_gather_hot, g_shade, blk, 0, st, scene->dev, rec, vp, px, grid, (const uint32_t*)starts, (const float4*)entries, n, (const uint32_t*)hot_list, ctx->count_visits ? 1u : 0u);
+            hipLaunchKernelGGL(k_sppm_gather, g_pix, blk, 0, st, scene->dev, rec, vp, px, n, grid, (const uint32_t*)starts, (const float4*)entries, n, hot_list, it0 + j == n_iterations ? 1u : 0u, ctx->opt.count_visits ? 1u : 0u);
+            hipLaunchKernelGGL(k_sppm_gather_hot, g_shade, blk, 0, st, scene->dev, rec, vp, px, grid, (const uint32_t*)starts, (const float4*)entries, n, (const uint32_t*)hot_list, ctx->opt.count_visits ? 1u : 0u);
             tm.end(5, st);
             if (ctx->comm.comm && ctx->comm.n_ranks > 1) {
                 // the one exchange of an iteration: every rank traced its slice of the photons, ϕ and M are the sums over all of
@@ -385,7 +379,7 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         stats->launches_shade = stats->launches_sub[0] + stats->launches_sub[1] + stats->launches_sub[2] + stats->launches_sub[3];
         stats->n_batches = n_batches;
         stats->max_depth_reached = (uint32_t)max_depth;
-        if (ctx->count_visits) {  // the gather's counts take the place of the fallback reasons
+        if (ctx->opt.count_visits) {  // the gather's counts take the place of the fallback reasons
             stats->count_sub[0] = gi.stat_candidates;
             stats->count_sub[1] = gi.stat_accepted;
             stats->count_sub[2] = gi.photon_hits;

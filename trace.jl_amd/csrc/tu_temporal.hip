@@ -99,7 +99,7 @@ int temporal_impl(trhip_ctx* ctx, const void* xyzw, const void* planes, const vo
             hipLaunchKernelGGL((k_temporal_clip<2>), grid, block, 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, gamma, d_out, d_out_history);
         else
             hipLaunchKernelGGL((k_temporal_clip<3>), grid, block, 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, gamma, d_out, d_out_history);
-    } else if (ctx->temporal_patch)  // measured 0.0347 ms against 0.0391 ms at 1024 x 1024 (profiles/r11/temporal.txt)
+    } else if (ctx->opt.temporal_patch)  // measured 0.0347 ms against 0.0391 ms at 1024 x 1024 (profiles/r11/temporal.txt)
         hipLaunchKernelGGL((k_temporal<true>), dim3(bx, by), dim3(kDnTile * kDnTile), 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, d_out, d_out_history);
     else
         hipLaunchKernelGGL((k_temporal<false>), dim3((uint32_t)lin_blocks), dim3(kDnTile * kDnTile), 0, st, d_beauty, d_planes, d_history, (int)width, (int)height, k, d_out, d_out_history);

@@ -19,11 +19,11 @@ int ensure_overflow(trhip_ctx* ctx) {
 // the scene's children-in-parent view with the context's slab margin (option "slab_margin_log2")
 WideScene wide_view(const trhip_ctx* ctx, const trhip_scene* sc) {
     WideScene w = sc->wide;
-    w.tight_scale = ctx->slab_margin_log2 > 0 ? std::ldexp(1.0f, -ctx->slab_margin_log2) : 0.0f;
+    w.tight_scale = ctx->opt.slab_margin_log2 > 0 ? std::ldexp(1.0f, -ctx->opt.slab_margin_log2) : 0.0f;
     // k_trace3's postponed leaves need a non-increasing t_max: the rays that can see it raised start inside (or on) a sphere (A.18) — inside its world bound
     // grown by a thousandth of its size
     w.spec_spheres = 0xffffffffu;
-    if (ctx->trace3_spec && sc->g->sphere_bounds.size() <= 8) {
+    if (ctx->opt.trace3_spec && sc->g->sphere_bounds.size() <= 8) {
         w.spec_spheres = (uint32_t)sc->g->sphere_bounds.size();
         for (size_t k = 0; k < sc->g->sphere_bounds.size(); ++k) {
             const HostAABB& b = sc->g->sphere_bounds[k];
@@ -40,9 +40,9 @@ WideScene wide_view(const trhip_ctx* ctx, const trhip_scene* sc) {
 // k_trace8 takes the launch (traversal 4) only with the tight slab clauses on and a single pipeline; otherwise k_trace3 walks the 32-byte boxes.
 #ifdef TRHIP_EXPERIMENTS
 static constexpr bool kExperimentsBuild = true;
-static bool uses_trace8(const trhip_ctx* ctx, const trhip_scene* sc) { return ctx->traversal == 4 && sc->w8_ok && ctx->slab_margin_log2 > 0 && ctx->pipelines <= 1; }
+static bool uses_trace8(const trhip_ctx* ctx, const trhip_scene* sc) { return ctx->opt.traversal == 4 && sc->w8_ok && ctx->opt.slab_margin_log2 > 0 && ctx->opt.pipelines <= 1; }
 // k_trace7 (traversal 7) takes the closest-hit launches of scenes with a hierarchy when the tight slab clauses are on (its margins derive from them)
-static bool uses_trace7(const trhip_ctx* ctx, const trhip_scene* sc) { return ctx->traversal == 7 && sc->wide_ok && sc->wide.root_cnt == 0 && ctx->slab_margin_log2 > 0 && ctx->pipelines <= 1; }
+static bool uses_trace7(const trhip_ctx* ctx, const trhip_scene* sc) { return ctx->opt.traversal == 7 && sc->wide_ok && sc->wide.root_cnt == 0 && ctx->opt.slab_margin_log2 > 0 && ctx->opt.pipelines <= 1; }
 #else  // traversals 4, 6, 7, leaf_sorted, leaf_queue: kernels of the EXPERIMENTS build (trhip_set_option refuses them here)
 static constexpr bool kExperimentsBuild = false;
 static bool uses_trace8(const trhip_ctx*, const trhip_scene*) { return false; }
@@ -54,11 +54,11 @@ static bool exceeds_llc(uint32_t n_wnodes, uint32_t n_prims) { return (size_t)n_
 
 // closest-hit rays on the canonical tree alone: scenes without an accelerator, options that leave it idle, indirect queues, and a hybrid launch whose lists could not be allocated
 static ClosestChoice canonical_kernel(const trhip_ctx* ctx, const trhip_scene* sc, bool cnt) {
-    if (!(ctx->traversal >= 2 && sc->wide_ok)) return {ClosestKernel::Literal, false};
+    if (!(ctx->opt.traversal >= 2 && sc->wide_ok)) return {ClosestKernel::Literal, false};
     if (sc->wide.root_cnt > 0)  // a single-leaf scene has nothing to postpone
-        return {ctx->leaf_kernel && ctx->debug_trace_budget == 0 ? ClosestKernel::Leaf : ClosestKernel::Trace2, false};
-    if (ctx->traversal == 2) return {ClosestKernel::Trace2, false};
-    if (ctx->traversal == 6 && kExperimentsBuild) return {ClosestKernel::Trace4, false};
+        return {ctx->opt.leaf_kernel && ctx->opt.debug_trace_budget == 0 ? ClosestKernel::Leaf : ClosestKernel::Trace2, false};
+    if (ctx->opt.traversal == 2) return {ClosestKernel::Trace2, false};
+    if (ctx->opt.traversal == 6 && kExperimentsBuild) return {ClosestKernel::Trace4, false};
     const bool big = !cnt && exceeds_llc(sc->wide.n_wnodes, sc->dev.n_prims);  // (k_trace7 and k_trace8 hand rays back to k_trace3: their BIG is its)
     return {uses_trace8(ctx, sc) ? ClosestKernel::Trace8 : (uses_trace7(ctx, sc) ? ClosestKernel::Trace7 : ClosestKernel::Trace3), big};
 }
@@ -68,8 +68,8 @@ ClosestChoice closest_kernel(const trhip_ctx* ctx, const trhip_scene* sc, bool c
     // the certified walk on the accelerator tree; the rays it flags go through k_trace3 on the canonical tree right after (th_trace3c.h)
     if (sc->wide_acc.root_cnt > 0) return {ClosestKernel::LeafC, false};
     const bool big = !cnt && exceeds_llc(sc->wide_acc.n_wnodes, sc->dev.n_prims);
-    if (kExperimentsBuild && ctx->leaf_queue && !big) return {ClosestKernel::Trace3d, false};  // option "leaf_queue": the same walk with queued leaves (th_trace3d.h)
-    return {ctx->wide4 && sc->wide_acc.w4nodes ? ClosestKernel::Trace3c4 : ClosestKernel::Trace3c, big};  // four children wide (th_trace3c4.h): one form for every launch
+    if (kExperimentsBuild && ctx->opt.leaf_queue && !big) return {ClosestKernel::Trace3d, false};  // option "leaf_queue": the same walk with queued leaves (th_trace3d.h)
+    return {ctx->opt.wide4 && sc->wide_acc.w4nodes ? ClosestKernel::Trace3c4 : ClosestKernel::Trace3c, big};  // four children wide (th_trace3c4.h): one form for every launch
 }
 
 // per kernel family: its name, the value of trhip_stats.traversal, and the bytes one unit of the visit counters stands for (ClosestKernel's order)
@@ -81,7 +81,7 @@ static const struct {
 
 // which kernel launch_trace picks for this scene under the context's current options, as trhip_stats reports it
 void traversal_info(const trhip_ctx* ctx, const trhip_scene* sc, uint32_t* trav, uint32_t* node_bytes) {
-    const auto& info = kClosestInfo[(int)closest_kernel(ctx, sc, ctx->count_visits, false).kernel];
+    const auto& info = kClosestInfo[(int)closest_kernel(ctx, sc, ctx->opt.count_visits, false).kernel];
     *trav = info.trav;
     *node_bytes = info.node_bytes;
 }
@@ -90,16 +90,16 @@ void traversal_info(const trhip_ctx* ctx, const trhip_scene* sc, uint32_t* trav,
 // the option string suggests).
 extern "C" __attribute__((visibility("default"))) int trhip_closest_kernel_name(const trhip_ctx* ctx, const trhip_scene* sc, char* buf, size_t n) {
     if (!ctx || !sc || !buf || !n) return TRHIP_ERR_INVALID;
-    std::snprintf(buf, n, "%s", kClosestInfo[(int)closest_kernel(ctx, sc, ctx->count_visits, false).kernel].name);
+    std::snprintf(buf, n, "%s", kClosestInfo[(int)closest_kernel(ctx, sc, ctx->opt.count_visits, false).kernel].name);
     return 0;
 }
 
 // One traversal launch over a queue (count in HBM at count_ptr, or n_max when count_ptr is null).
-// ctx->traversal == 1: the literal accel/bvh.jl loop (k_trace_closest / k_trace_any); 2: k_trace2 (same results).
+// ctx->opt.traversal == 1: the literal accel/bvh.jl loop (k_trace_closest / k_trace_any); 2: k_trace2 (same results).
 void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool any, SegQueue q, const float4* ro, const float4* rd, const float* tmax, TraceOut out, uint32_t* work_cursors,
                   Counters* ctr, void* overflow_slab) {
     const dim3 grid(trace_grid(ctx)), block(kBlock);
-    const bool cnt = ctx->count_visits;
+    const bool cnt = ctx->opt.count_visits;
     const bool full_only = !sc->partial_spheres;  // no clipped sphere in the scene: kernels without the Float64 atan2 path
     ClosestChoice pick = closest_kernel(ctx, sc, cnt, q.indirect != nullptr);  // (any-hit rays take the same family's any-hit kernel, where it has one)
     const bool certified = pick.kernel == ClosestKernel::LeafC || pick.kernel == ClosestKernel::Trace3c || pick.kernel == ClosestKernel::Trace3c4 || pick.kernel == ClosestKernel::Trace3d;
@@ -132,7 +132,7 @@ void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool an
     if (certified) pick = canonical_kernel(ctx, sc, cnt);  // any-hit rays of a hierarchy; a launch whose fallback lists could not be allocated
     if (pick.kernel == ClosestKernel::Trace3 || pick.kernel == ClosestKernel::Trace4 || pick.kernel == ClosestKernel::Trace7 || pick.kernel == ClosestKernel::Trace8) {
         uint2* ov = (uint2*)(overflow_slab ? overflow_slab : ctx->overflow.p);
-        if (any && sc->n_occluders && ctx->occluder_pretest && ctx->pipelines <= 1 && !q.indirect) {
+        if (any && sc->n_occluders && ctx->opt.occluder_pretest && ctx->opt.pipelines <= 1 && !q.indirect) {
             // the largest triangles first (k_any_occluders); what they do not stop goes through per-segment survivor lists
             // a survivor list takes the rays of every kSeg-th 64-ray chunk of the padded work space (k_any_occluders): at most (sum of the segment
             // counts + kSeg * (kSegGran - 1)) / kSeg + 64 <= the queue's per-segment capacity + 319 entries, whatever the caller's slack
@@ -163,7 +163,7 @@ void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool an
                 uint32_t* fcounts = (uint32_t*)ctx->fb_counts[w].p;
                 (void)hipMemsetAsync(fcounts, 0, ctr_words * sizeof(uint32_t), st);
                 Wide8Scene w8 = sc->w8;
-                w8.tight_scale = std::ldexp(1.0f, -ctx->slab_margin_log2);
+                w8.tight_scale = std::ldexp(1.0f, -ctx->opt.slab_margin_log2);
                 const FallbackList fb{(uint32_t*)ctx->fb_list[w].p, fcounts, fcap};
                 uint32_t* ov8 = (uint32_t*)ctx->ov8[w].p;
                 launch_trace8(ctx, st, sc, any, cnt, full_only, w8, q, ro, rd, tmax, out, work_cursors, ov8, ctr, fb);
@@ -192,7 +192,7 @@ void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool an
         }
 #endif
         const bool big = !any && pick.big;  // (k_trace3's BIG variant)
-        if (any && hybrid_active(ctx, sc) && (ctx->any_on_accelerator > 0 || (ctx->any_on_accelerator < 0 && out.any_acc_hint)) && sc->wide_acc.root_cnt == 0) {
+        if (any && hybrid_active(ctx, sc) && (ctx->opt.any_on_accelerator > 0 || (ctx->opt.any_on_accelerator < 0 && out.any_acc_hint)) && sc->wide_acc.root_cnt == 0) {
             // any-hit rays of a two-tree scene (TraceOut::zero_mode): the library's tree for every ray without a zero direction component, the canonical tree for the rest
             const size_t words = 16 + (size_t)kSeg * kCtrStride;  // the flag, then the second launch's work cursors
             if (ensure(ctx, ctx->fb_counts[1], words * sizeof(uint32_t)) == 0) {
@@ -216,7 +216,7 @@ void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool an
         if (pick.kernel == ClosestKernel::Leaf) {  // one-leaf scene: the dedicated kernel (th_trace2.h, k_trace_leaf)
             const dim3 lgrid(ctx->num_cu * 8);
 #ifdef TRHIP_EXPERIMENTS
-            if (ctx->leaf_sorted && sc->g->d_leaf_boxes.p && sc->wide.root_cnt <= 30 && ctx->slab_margin_log2 > 0) {  // rays grouped by what they can hit (th_leaf2.h)
+            if (ctx->opt.leaf_sorted && sc->g->d_leaf_boxes.p && sc->wide.root_cnt <= 30 && ctx->opt.slab_margin_log2 > 0) {  // rays grouped by what they can hit (th_leaf2.h)
                 const float* lb = (const float*)sc->g->d_leaf_boxes.p;
                 const WideScene wsv = wide_view(ctx, sc);
 #define TH_LEAF2(A, C, F) hipLaunchKernelGGL((k_leaf_sorted<A, C, F>), lgrid, block, 0, st, sc->dev, wsv, q, ro, rd, tmax, out, ctr, lb)
@@ -247,14 +247,14 @@ void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool an
         uint2* ov = (uint2*)(overflow_slab ? overflow_slab : ctx->overflow.p);
         if (any) {
             if (cnt)
-                hipLaunchKernelGGL((k_trace2<true, true>), grid, block, 0, st, sc->dev, wide_view(ctx, sc), q, ro, rd, tmax, out, work_cursors, ov, ctr, ctx->debug_trace_budget);
+                hipLaunchKernelGGL((k_trace2<true, true>), grid, block, 0, st, sc->dev, wide_view(ctx, sc), q, ro, rd, tmax, out, work_cursors, ov, ctr, ctx->opt.debug_trace_budget);
             else
-                hipLaunchKernelGGL((k_trace2<true, false>), grid, block, 0, st, sc->dev, wide_view(ctx, sc), q, ro, rd, tmax, out, work_cursors, ov, ctr, ctx->debug_trace_budget);
+                hipLaunchKernelGGL((k_trace2<true, false>), grid, block, 0, st, sc->dev, wide_view(ctx, sc), q, ro, rd, tmax, out, work_cursors, ov, ctr, ctx->opt.debug_trace_budget);
         } else {
             if (cnt)
-                hipLaunchKernelGGL((k_trace2<false, true>), grid, block, 0, st, sc->dev, wide_view(ctx, sc), q, ro, rd, tmax, out, work_cursors, ov, ctr, ctx->debug_trace_budget);
+                hipLaunchKernelGGL((k_trace2<false, true>), grid, block, 0, st, sc->dev, wide_view(ctx, sc), q, ro, rd, tmax, out, work_cursors, ov, ctr, ctx->opt.debug_trace_budget);
             else
-                hipLaunchKernelGGL((k_trace2<false, false>), grid, block, 0, st, sc->dev, wide_view(ctx, sc), q, ro, rd, tmax, out, work_cursors, ov, ctr, ctx->debug_trace_budget);
+                hipLaunchKernelGGL((k_trace2<false, false>), grid, block, 0, st, sc->dev, wide_view(ctx, sc), q, ro, rd, tmax, out, work_cursors, ov, ctr, ctx->opt.debug_trace_budget);
         }
         return;
     }
@@ -275,7 +275,7 @@ void launch_trace(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool an
 void launch_trace2_stream(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool any, SegQueue q, const float4* ro, const float4* rd, TraceOut out, uint32_t* work_cursors, void* overflow_slab,
                           Counters* ctr, const StreamCtl& sx) {
     const dim3 grid(trace_grid(ctx)), block(kBlock);
-    const bool cnt = ctx->count_visits;
+    const bool cnt = ctx->opt.count_visits;
     uint2* ov = (uint2*)overflow_slab;
     if (any) {
         if (cnt)

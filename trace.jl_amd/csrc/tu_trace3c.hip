@@ -10,18 +10,18 @@
 // Every ray of a scene committed with both trees walks the accelerator when: the option is on, the default traversal is selected (the others are the A/B kernels
 // and walk the canonical tree), the tight slab clauses are on (the certificate's margins derive from the same reach D), one pipeline, no diagnostic budget.
 bool hybrid_active(const trhip_ctx* ctx, const trhip_scene* sc) {
-    return sc->hybrid_ok && ctx->hybrid && ctx->traversal == 3 && ctx->slab_margin_log2 > 0 && ctx->pipelines <= 1 && ctx->debug_trace_budget == 0 && sc->wide_ok;
+    return sc->hybrid_ok && ctx->opt.hybrid && ctx->opt.traversal == 3 && ctx->opt.slab_margin_log2 > 0 && ctx->opt.pipelines <= 1 && ctx->opt.debug_trace_budget == 0 && sc->wide_ok;
 }
 
 // Why a scene that holds both trees is NOT walked through its accelerator under the context's current options ("" when it is, or when the scene holds one tree): those
 // launches walk the reference's tree alone — exact, at about twice the closest-hit time.  trhip_accelerator_note; a frame says it once on stderr (tu_path.hip).
 const char* hybrid_idle_reason(const trhip_ctx* ctx, const trhip_scene* sc) {
     if (!sc->hybrid_ok || !sc->wide_ok) return "";
-    if (!ctx->hybrid) return "option hybrid = 0: every ray walks the canonical tree";
-    if (ctx->traversal != 3) return "option traversal != 3: only the default traversal walks the accelerator, the A/B kernels walk the canonical tree (pair them with bvh_builder = 0 for the library's tree)";
-    if (ctx->slab_margin_log2 <= 0) return "option slab_margin_log2 = 0: the certificate's margins derive from the tight slab clauses";
-    if (ctx->pipelines > 1) return "option pipelines > 1: the certified walk runs with one pipeline";
-    if (ctx->debug_trace_budget != 0) return "option debug_trace_budget: diagnostic walks use the canonical tree";
+    if (!ctx->opt.hybrid) return "option hybrid = 0: every ray walks the canonical tree";
+    if (ctx->opt.traversal != 3) return "option traversal != 3: only the default traversal walks the accelerator, the A/B kernels walk the canonical tree (pair them with bvh_builder = 0 for the library's tree)";
+    if (ctx->opt.slab_margin_log2 <= 0) return "option slab_margin_log2 = 0: the certificate's margins derive from the tight slab clauses";
+    if (ctx->opt.pipelines > 1) return "option pipelines > 1: the certified walk runs with one pipeline";
+    if (ctx->opt.debug_trace_budget != 0) return "option debug_trace_budget: diagnostic walks use the canonical tree";
     return "";
 }
 extern "C" __attribute__((visibility("default"))) int trhip_accelerator_note(const trhip_ctx* ctx, const trhip_scene* sc, char* buf, size_t n) {
@@ -36,14 +36,14 @@ extern "C" __attribute__((visibility("default"))) int trhip_accelerator_note(con
 
 WideScene wide_view_acc(const trhip_ctx* ctx, const trhip_scene* sc) {
     WideScene w = sc->wide_acc;
-    w.tight_scale = std::ldexp(1.0f, -ctx->slab_margin_log2);
+    w.tight_scale = std::ldexp(1.0f, -ctx->opt.slab_margin_log2);
     w.spec_spheres = 0xffffffffu;
     return w;
 }
 
 static CertScene cert_view(const trhip_ctx* ctx, const trhip_scene* sc) {
     CertScene c = sc->cert;
-    c.inv_tight = std::ldexp(1.0f, ctx->slab_margin_log2);
+    c.inv_tight = std::ldexp(1.0f, ctx->opt.slab_margin_log2);
     return c;
 }
 

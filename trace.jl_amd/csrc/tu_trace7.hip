@@ -14,7 +14,7 @@ void launch_trace7(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool c
                    const TraceOut& out, uint32_t* work_cursors, uint2* ov, Counters* ctr, const FallbackList& fb) {
     const dim3 grid(trace_grid(ctx)), block(kBlock);
     // the cheap interior test needs leaf boxes that are exactly their triangles' (every tree built here; option "trace7_cheap" 0 keeps the reference's test on every box)
-    const bool cheap = ctx->trace7_cheap && sc->wide.leaf_tight != 0u;
+    const bool cheap = ctx->opt.trace7_cheap && sc->wide.leaf_tight != 0u;
     if (cnt) {
         if (full_only) TH_LAUNCH7(true, true, false); else TH_LAUNCH7(true, false, false);
     } else if (big) {

@@ -10,7 +10,7 @@ int render_whitted_impl(trhip_ctx* ctx, const trhip_scene* scene, const DeviceSe
     const uint32_t n_lights = std::max<uint32_t>(1u, scene->dev.n_lights);
     // bytes per camera ray of a batch: tree pool (growth factor 2 per level budgeted) + queues
     const double per_ray = 2.0 * (max_depth * 44.0 + 2 * 2 * 16.0 + 16.0 + n_lights * (48.0 + 1.0));
-    uint64_t batch = ctx->batch_paths;
+    uint64_t batch = ctx->opt.batch_paths;
     if (batch == 0) {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
@@ -53,7 +53,7 @@ int render_whitted_impl(trhip_ctx* ctx, const trhip_scene* scene, const DeviceSe
     void* saved_call_ctr = flags + 1;
     float4* L = (float4*)ctx->Lbuf.p;
     float4* hits = (float4*)ctx->hits.p;
-    Timer tm(ctx, ctx->timing && stats);
+    Timer tm(ctx, ctx->opt.timing && stats);
     FrameEvents ev;
     HIP_TRY(ctx, ev.begin(st));
     HIP_TRY(ctx, hipMemsetAsync(ctr, 0, sizeof(Counters), st));
