@@ -458,6 +458,46 @@ int trhip_render_sky(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
 int trhip_render_sky_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset,
                             const trhip_env* env, const trhip_sky_params* params, void* d_out_xyzw, trhip_stats* stats);
 
+/* ---- environment light in path frames (since ABI 3001, added without a version change: nothing existing moved) -----------------
+ * trhip_render_path with one change (docs/design/26-path-env.md): where the closest-hit walk finds nothing at depth d (1 <= d <=
+ * max_depth) the path records an ESCAPE — the depth d, its throughput beta at that moment and the ray's direction dir — and ends, as it
+ * ends in trhip_render_path.  The sample's radiance is
+ *   L' = L + beta * (E(dir) * scale)          c = E * scale, t = beta * c, L' = L + t per channel: one Float32 operation each, no contraction
+ * where L is exactly what trhip_render_path computes for that sample and E the lookup above; the escape is the last addend in depth order.
+ * Under TRHIP_PATH_ENV_HIDE_BACKGROUND a depth-1 escape adds nothing (its record is still written).  A path escapes at most once; a path
+ * that is absorbed, loses Russian roulette or is cut at max_depth has no escape (depth 0).  A non-finite beta gives what IEEE gives; the
+ * film pass and trhip_last_sample_radiance apply the NaN rule to L' as they apply it to L.  No importance sampling of the map: with BSDF
+ * sampling beta * E(dir) is an unbiased estimate, and for specular lobes the only one.
+ * The frame is the classic per-depth wavefront: options "streaming" and "band_tile_rows" are ignored, "pipelines", "overlap" and
+ * "batch_paths" hold.  There are no bands: TRHIP_ERR_UNSUPPORTED when the per-sample buffers (64 bytes per camera sample beside the film
+ * pass's own) do not fit in half of free HBM.  Statistics are trhip_render_path's.
+ * TRHIP_ERR_INVALID, in this order: the parameter block (NULL; scale not finite or negative; unknown flag bits; reserved), checked before
+ * any handle is looked at; trhip_render_path's refusals in its order; a null env; an env of another context; a scale that takes the
+ * map's largest texel to +Inf.  trhip_path_env_default_params needs no context and no GPU.
+ *
+ * trhip_last_escapes: after a path-env frame (TRHIP_ERR_INVALID after anything else), 8 floats per camera sample — beta.xyz, the escape
+ * depth as a number (0 = none), dir.xyz, 0 — indexed like trhip_last_sample_radiance; n_floats must be 8 times its sample count.
+ *
+ * trhip_path_env_relight: folds the frame's retained radiance and escape records with ANOTHER environment and / or other parameters, then
+ * runs the film pass exactly as the frame ran it: film and trhip_last_sample_radiance equal a fresh trhip_render_path_env with those
+ * arguments bit for bit, without a single ray.  Valid only while the context's last frame is a path-env frame: after any other render,
+ * film or image-pass call it returns TRHIP_ERR_INVALID.  Refusals otherwise as the frame's: parameter block, null arguments, no such
+ * frame, then the environment's three. */
+#define TRHIP_PATH_ENV_HIDE_BACKGROUND 1u /* a depth-1 escape (a camera ray that misses) adds nothing */
+typedef struct {
+    float scale;              /* multiplies every lookup: finite, >= 0 */
+    uint32_t flags;           /* TRHIP_PATH_ENV_HIDE_BACKGROUND */
+    uint32_t reserved[2];     /* 0 */
+} trhip_path_env_params;      /* 16 bytes */
+int trhip_path_env_default_params(trhip_path_env_params* out); /* {1, 0, {0, 0}} */
+int trhip_render_path_env(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
+                          const trhip_env* env, const trhip_path_env_params* params, float* out_xyzw, trhip_stats* stats);
+int trhip_render_path_env_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
+                                 const trhip_env* env, const trhip_path_env_params* params, void* d_out_xyzw, trhip_stats* stats);
+int trhip_last_escapes(trhip_ctx* ctx, float* out8, uint64_t n_floats);
+int trhip_path_env_relight(trhip_ctx* ctx, const trhip_env* env, const trhip_path_env_params* params, float* out_xyzw);
+int trhip_path_env_relight_device(trhip_ctx* ctx, const trhip_env* env, const trhip_path_env_params* params, void* d_out_xyzw);
+
 /* ---- edge-avoiding denoiser for path / Whitted films (since ABI 3001, added without a version change: nothing existing moved) ----
  * An à-trous wavelet filter after Dammertz et al. 2010 ("Edge-Avoiding À-Trous Wavelet Transform for fast Global Illumination
  * Filtering") on the film state of a path or Whitted render, guided by the three planes of trhip_render_aov for the same sensor,

@@ -171,6 +171,18 @@ SKY_HIDE_BACKGROUND = 2  # TRHIP_SKY_HIDE_BACKGROUND
 ENV_MAX_N = 4096  # the largest map trhip_env_create takes
 
 
+class PathEnvParams(C.Structure):
+    """trhip_path_env_params (16 bytes)"""
+    _fields_ = [
+        ("scale", C.c_float),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+PATH_ENV_HIDE_BACKGROUND = 1  # TRHIP_PATH_ENV_HIDE_BACKGROUND
+
+
 class TemporalParams(C.Structure):
     """trhip_temporal_params (72 bytes)"""
     _fields_ = [
@@ -409,6 +421,12 @@ SIGNATURES = {
     "trhip_sky_default_params": (C.c_int, [C.POINTER(SkyParams)]),
     "trhip_render_sky": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, C.POINTER(SkyParams), _F, C.POINTER(Stats)]),
     "trhip_render_sky_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, C.POINTER(SkyParams), _VP, C.POINTER(Stats)]),
+    "trhip_path_env_default_params": (C.c_int, [C.POINTER(PathEnvParams)]),
+    "trhip_render_path_env": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(PathEnvParams), _F, C.POINTER(Stats)]),
+    "trhip_render_path_env_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(PathEnvParams), _VP, C.POINTER(Stats)]),
+    "trhip_last_escapes": (C.c_int, [_VP, _F, C.c_uint64]),
+    "trhip_path_env_relight": (C.c_int, [_VP, _VP, C.POINTER(PathEnvParams), _F]),
+    "trhip_path_env_relight_device": (C.c_int, [_VP, _VP, C.POINTER(PathEnvParams), _VP]),
     "trhip_render_aov_ids": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _F, _VP, _VP, C.POINTER(Stats)]),
     "trhip_render_aov_ids_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, _VP, _VP, C.POINTER(Stats)]),
     "trhip_temporal_motion_default_params": (C.c_int, [C.POINTER(TemporalMotionParams)]),

@@ -1053,9 +1053,30 @@ class PathIntegrator(_SamplerIntegrator):
     _entry = "trhip_render_path"
     _entry_device = "trhip_render_path_device"
 
-    def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None, sample_map: Optional["SampleMap"] = None) -> np.ndarray:
+    def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None, sample_map: Optional["SampleMap"] = None,
+               environment: Optional["Environment"] = None, env_scale: float = 1.0, hide_background: bool = False) -> np.ndarray:
         """_SamplerIntegrator.render; with ``sample_map`` a map frame (trhip_render_path_map): sample pixel p draws ``sample_map.counts[p]`` samples from the sampler's
-        sample_offset on, and ``sampler.samples_per_pixel`` is not read."""
+        sample_offset on, and ``sampler.samples_per_pixel`` is not read.  With ``environment`` a path-env frame (trhip_render_path_env; docs/design/26-path-env.md): a path
+        that leaves the scene brings back beta * E(dir) * env_scale — not at depth 1 with ``hide_background`` — and escapes() / relight() work on the frame afterwards.
+        Without either it is trhip_render_path, the same call and the same bits."""
+        if environment is not None:
+            if sample_map is not None:
+                raise TraceHipError("PathIntegrator.render: sample_map and environment cannot be combined (map frames have no environment term)")
+            prm = path_env_params(environment, env_scale, hide_background, "PathIntegrator.render")
+            flat = scene.flatten(ctx)
+            ctx = flat.ctx
+            sn, st, smp, L, env = self.camera.sensor(), _ffi.Stats(), self.sampler, _ffi.lib(), environment._handle(flat.ctx)
+            if device_out is not None:
+                ctx.check(L.trhip_render_path_env_device(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, self.max_depth, smp.seed, smp.sample_offset, env, C.byref(prm),
+                                                         C.c_void_p(device_out), C.byref(st)))
+                self.stats = st
+                return None
+            h, w = self.camera.film.size
+            out = np.empty((h, w, 4), dtype=np.float32)
+            ctx.check(L.trhip_render_path_env(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, self.max_depth, smp.seed, smp.sample_offset, env, C.byref(prm), _ffi.fptr(out), C.byref(st)))
+            self.stats = st
+            self.camera.film.set_xyzw(out)
+            return out
         if sample_map is None:
             return super().render(scene, ctx, device_out)
         flat = scene.flatten(ctx)
@@ -1081,6 +1102,46 @@ class PathIntegrator(_SamplerIntegrator):
         self.stats = st
         film.set_xyzw(out)
         return out
+
+    def escapes(self, scene: Scene):
+        """(beta, depth, dir) of the last render(environment=...) on the scene's context (trhip_last_escapes): beta and dir (spp, sb_h, sb_w, 3), depth (spp, sb_h, sb_w)
+        int32 with 0 where the path did not escape; shaped like sample_radiance."""
+        flat = scene.flatten()
+        sbh, sbw, _, _ = sample_bounds_shape(self.camera.film)
+        rec = np.empty((self.sampler.samples_per_pixel, sbh, sbw, 8), dtype=np.float32)
+        flat.ctx.check(_ffi.lib().trhip_last_escapes(flat.ctx._h, _ffi.fptr(rec), rec.size))
+        return rec[..., 0:3].copy(), rec[..., 3].astype(np.int32), rec[..., 4:7].copy()
+
+    def relight(self, scene: Scene, environment: "Environment", env_scale: float = 1.0, hide_background: bool = False, device_out: Optional[int] = None) -> np.ndarray:
+        """The film of the last render(environment=...) under another environment and / or other parameters, without tracing a ray (trhip_path_env_relight): film and
+        sample_radiance equal a fresh render with these arguments bit for bit.  Valid only while that frame is the context's last; the counterpart of Scene.with_lights
+        for the environment."""
+        prm = path_env_params(environment, env_scale, hide_background, "PathIntegrator.relight")
+        flat = scene.flatten()
+        ctx, L = flat.ctx, _ffi.lib()
+        if device_out is not None:
+            ctx.check(L.trhip_path_env_relight_device(ctx._h, environment._handle(ctx), C.byref(prm), C.c_void_p(device_out)))
+            return None
+        h, w = self.camera.film.size
+        out = np.empty((h, w, 4), dtype=np.float32)
+        ctx.check(L.trhip_path_env_relight(ctx._h, environment._handle(ctx), C.byref(prm), _ffi.fptr(out)))
+        self.camera.film.set_xyzw(out)
+        return out
+
+
+def path_env_params(environment, env_scale, hide_background, who: str) -> "_ffi.PathEnvParams":
+    """trhip_path_env_params from the Python arguments, with the checks that need no library call answered here."""
+    if not isinstance(environment, Environment):
+        raise TraceHipError(f"{who}: environment must be an Environment, not {type(environment).__name__}")
+    scale = float(env_scale)
+    if not (scale >= 0.0 and math.isfinite(scale)):
+        raise TraceHipError(f"{who}: env_scale must be finite and >= 0, not {env_scale}")
+    p = _ffi.PathEnvParams()
+    rc = _ffi.lib().trhip_path_env_default_params(C.byref(p))
+    if rc:
+        raise TraceHipError(f"trhip_path_env_default_params failed ({rc})")
+    p.scale, p.flags = scale, _ffi.PATH_ENV_HIDE_BACKGROUND if hide_background else 0
+    return p
 
 
 # ---- adaptive sampling (include/tracehip.h, trhip_render_path_map; docs/design/24-adaptive.md) ---------------------------------------------

@@ -42,6 +42,15 @@ struct LastRecords {
     uint64_t count = 0;  // float4 entries valid in Lbuf
     uint32_t layout = 0, npix = 1, spp = 1;  // how they are laid out (th_kernels.h, film_index)
     uint32_t kind = 0;  // whose they are: 1 a one-band path frame or trhip_film_accumulate's records (trhip_last_sample_stats reads them), 2 a map frame (exported through map_counts), 0 anything else
+    uint32_t path_env = 0;  // 1: a path-env frame's (tu_path_env.hip): Lbuf holds the folded records, env_base and env_rec what they were folded from (ctx->env_keep says how)
+};
+// What trhip_path_env_relight needs of the path-env frame before it to run the film pass "exactly as the frame ran it" (valid while ctx->last.path_env).
+struct PathEnvKeep {
+    DeviceSensor ds{};
+    float filter_table[256] = {};
+    uint32_t spp = 0, sample_offset = 0;
+    uint64_t seed = 0, total_slots = 0, l_slots = 0;
+    bool fused = false;
 };
 
 struct Timer;
@@ -89,6 +98,8 @@ struct trhip_ctx {
     // adaptive sampling (th_adaptive.h): the last map frame's counts (kept for trhip_last_sample_radiance), their exclusive sum, the job list, hipcub's workspace, the
     // word k_map_reduce / k_sample_map sum into; the host entry points' copies of (m, v) and of the counts they return
     DevBuf map_counts, map_offsets, map_jobs, map_tmp, map_word, map_mv, map_out;
+    DevBuf env_base, env_rec;  // a path-env frame (th_path_env.h): the path's own radiance records (16 B per slot) and the escape records (32 B per slot); Lbuf holds their fold
+    PathEnvKeep env_keep;
     DevBuf cb_rc;      // one word: a host callback's return code, max-reduced over the ranks of a job (tu_sppm.hip)
     DevBuf ov8[2], fb_list[2], fb_counts[2];  // k_trace8: global stack levels, fallback lists + their counters / work cursors ([closest | any])
     Comm comm;  // multi-GPU job this context belongs to (trhip_comm_init); n_ranks == 1 without one; trhip_shutdown destroys its communicator before the context goes
@@ -445,6 +456,23 @@ void stats_accumulate(trhip_stats& sum, const trhip_stats& band);  // a banded f
 // tu_adaptive.hip: a map frame's job list from ctx->map_counts (npix counts, already on the device).  sum_on_device: Σ counts and "some count lies above max_spp" come from
 // the device (8 bytes read back) into *total and *above; otherwise the caller has both.  Nothing is built when *above or *total == 0.
 int map_job_list(trhip_ctx* ctx, uint32_t npix, uint32_t max_spp, bool sum_on_device, uint64_t* total, bool* above);
+// tu_path_env.hip: the two kernels of a path-env frame (th_path_env.h), launched from the classic wavefront's loop (tu_path.hip, render_impl_band), and the frame's entry points.
+// PathEnvFrame is what the loop is handed, the way it is handed a MapFrame: where the path's own records and the escape records go, and what they are folded with.
+struct trhip_env;
+struct PathEnvFrame {
+    const trhip_env* env;
+    float scale;
+    uint32_t flags;
+    float4* base;  // l_slots records: the shading kernels' and the shadow rays' target in Lbuf's place
+    float4* rec;   // 2 * l_slots: {beta.xyz, depth}, {dir.xyz, 0}
+};
+int path_env_check(trhip_ctx* ctx, const trhip_env* env, float scale);  // null, another context's, a scale that takes the largest texel to +Inf
+void launch_path_escape(trhip_ctx* ctx, hipStream_t st, const uint32_t* counts, uint32_t cap, const PathQueue& q, const float4* hits, int depth, float4* rec);
+void launch_escape_fold(trhip_ctx* ctx, hipStream_t st, const PathEnvFrame& f, uint64_t l_slots, float4* out);
+// tu_path.hip: trhip_render_path's frame — its refusals in its order, the classic wavefront without bands — with the environment frame
+int render_path_env_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out, bool out_is_device,
+                          trhip_stats* stats, const trhip_env* env, float scale, uint32_t flags);
+bool film_fused(const trhip_ctx* ctx, const DeviceSensor& ds, uint32_t spp);
 // tu_whitted.hip
 int render_whitted_impl(trhip_ctx* ctx, const trhip_scene* scene, const DeviceSensor& ds, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
                         void* d_film, trhip_stats* stats);

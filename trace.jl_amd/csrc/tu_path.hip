@@ -413,7 +413,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
 // One band of a frame (band == nullptr: the whole frame, the normal case).  A band is a range of whole tile rows; its DeviceSensor carries
 // the range and whether the film gather starts from zero or adds onto the bands before (th_scene.h).
 int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, int integrator, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out,
-                     bool out_is_device, trhip_stats* stats, const DeviceSensor* band, const MapFrame* map = nullptr) {
+                     bool out_is_device, trhip_stats* stats, const DeviceSensor* band, const MapFrame* map = nullptr, const PathEnvFrame* envf_in = nullptr) {
     HostClock hclk;
     if (!ctx || !scene || !sensor || !out) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
     if (!scene->committed) return fail(ctx, TRHIP_ERR_INVALID, "scene not committed");
@@ -440,6 +440,8 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     const uint64_t npix = (uint64_t)ds.sb_w * ds.band_rows;
     const uint64_t total_slots = npix * spp;
     if (total_slots >= (1ull << 32)) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "more than 2^32 camera samples in one band of a frame");
+    if (envf_in)  // a path-env frame: the environment's refusals come after the path frame's
+        if (int rc = path_env_check(ctx, envf_in->env, envf_in->scale)) return rc;
     if (integrator == 0) {
         if (int rc = upload(ctx, ctx->sensor, &ds, sizeof ds)) return rc;
         if (int rc = upload(ctx, ctx->table, sensor->filter_table, 256 * sizeof(float))) return rc;
@@ -454,7 +456,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         ctx->last = LastRecords{total_slots, 0u, (uint32_t)npix, spp, 0u};  // (render_whitted_impl has synchronised its stream)
         return copy_back(ctx, out, out_is_device, df, fb);
     }
-    if (!band && !map && (ctx->opt.streaming == 1 || (ctx->opt.streaming < 0 && total_slots <= 96ull * scene->g->prims.size())) && ctx->opt.traversal >= 2 && scene->wide_ok && scene->wide.root_cnt == 0 && scene->wide.root_ref != kRefNone && ctx->opt.batch_paths == 0 && ctx->opt.pipelines <= 1) {
+    if (!band && !map && !envf_in && (ctx->opt.streaming == 1 || (ctx->opt.streaming < 0 && total_slots <= 96ull * scene->g->prims.size())) && ctx->opt.traversal >= 2 && scene->wide_ok && scene->wide.root_cnt == 0 && scene->wide.root_ref != kRefNone && ctx->opt.batch_paths == 0 && ctx->opt.pipelines <= 1) {
         bool declined = false;
         const int rc = render_stream_impl(ctx, scene, sensor, ds, spp, max_depth, seed, sample_offset, out, out_is_device, stats, &declined);
         if (!declined) return rc;
@@ -468,13 +470,25 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         if (int rc = fits_in_hbm(ctx, 2.0 * need, ctx->Lbuf.bytes + ctx->pfilm.bytes + held_in_pipes(ctx), &fits, &free_gb)) return rc;  // half of what is free, as render_impl plans its bands
         if (!fits) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "the per-sample buffers of a map frame (%.2f GB at max_spp %u) do not fit in half of free HBM (%.2f GB): there are no bands here", need * 1e-9, spp, free_gb);
     }
+    // A path-env frame (docs/design/26-path-env.md) has no bands either: the path's records, their fold, the escape records (16 + 16 + 32 B per slot), the poison byte and
+    // what the film pass keeps per sample must fit the same way.
+    if (envf_in) {
+        bool fits = false;
+        double free_gb = 0.0;
+        const double film_own = film_uses_packed(ctx, ds) ? (film_fused(ctx, ds, spp) ? 0.0 : 16.0) : film_uses_desc(ctx, ds) ? 16.0 : 24.0;
+        const double need = (double)total_slots * (65.0 + film_own);
+        const size_t held = ctx->Lbuf.bytes + ctx->pfilm.bytes + ctx->env_base.bytes + ctx->env_rec.bytes + held_in_pipes(ctx);
+        if (int rc = fits_in_hbm(ctx, 2.0 * need, held, &fits, &free_gb)) return rc;
+        if (!fits) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "the per-sample buffers of a path-env frame (%.2f GB at %u spp) do not fit in half of free HBM (%.2f GB): there are no bands here", need * 1e-9, spp, free_gb);
+    }
     // wavefront batch = whole sample passes (a map frame: ranges of its job list); per path in flight: 2 x 3 queue float4 + 3 shadow float4 + 1 hit float4 = 160 B
     uint64_t batch_paths = ctx->opt.batch_paths;
     if (batch_paths == 0) {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
         const size_t held = ctx->Lbuf.bytes + ctx->pfilm.bytes + held_in_pipes(ctx);  // reused below, so it counts as available
-        const double avail = 0.85 * (double)(free_b + held) - (double)total_slots * (sizeof(float4) + sizeof(float2)) - 2.5e9;
+        const double avail = 0.85 * (double)(free_b + held) - (double)total_slots * (sizeof(float4) + sizeof(float2)) - 2.5e9 -
+                             (envf_in ? (double)total_slots * 3.0 * sizeof(float4) : 0.0);  // (a path-env frame: the base records and the escape records beside Lbuf)
         batch_paths = avail > 0 ? (uint64_t)(avail / 212.0) : npix;  // per path in flight: 2 x 3 queue float4 + 2 x 3 shadow float4 + 1 hit float4 + counters
     }
     uint64_t spp_batch = std::max<uint64_t>(1, batch_paths / npix);
@@ -519,6 +533,14 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     ctx->last = LastRecords{};
     if (int rc = ensure(ctx, ctx->poison, l_slots)) return rc;
     if (int rc = ensure(ctx, ctx->Lbuf, l_slots * sizeof(float4))) return rc;
+    PathEnvFrame envf{};
+    if (envf_in) {
+        if (int rc = ensure(ctx, ctx->env_base, l_slots * sizeof(float4))) return rc;
+        if (int rc = ensure(ctx, ctx->env_rec, l_slots * 2 * sizeof(float4))) return rc;
+        envf = *envf_in;
+        envf.base = (float4*)ctx->env_base.p;
+        envf.rec = (float4*)ctx->env_rec.p;
+    }
     if (map) {
         if (!map_packed)
             if (int rc = ensure(ctx, ctx->pfilm, total_slots * sizeof(float2))) return rc;
@@ -530,7 +552,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     if (int rc = stage_output(ctx, out, out_is_device, film_bytes, &d_film)) return rc;
     hipStream_t st = ctx->stream;
     const DeviceSensor* dsp = (const DeviceSensor*)ctx->sensor.p;
-    float4* L = (float4*)ctx->Lbuf.p;
+    float4* L = envf_in ? envf.base : (float4*)ctx->Lbuf.p;  // a path-env frame: the paths add into the base records, Lbuf receives their fold with the escapes
 
     hclk.tick("setup (budget, buffers)");
     Timer tm(ctx, ctx->opt.timing && stats);
@@ -547,6 +569,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         HIP_TRY(ctx, hipMemsetAsync(L, 0, total_slots * sizeof(float4), st));
     }
     HIP_TRY(ctx, hipMemsetAsync(ctx->poison.p, 0, l_slots, st));
+    if (envf_in) HIP_TRY(ctx, hipMemsetAsync(envf.rec, 0, l_slots * 2 * sizeof(float4), st));  // depth 0: no escape
     HIP_TRY(ctx, hipEventRecord(ev_start.e, st));
     const int g_shade = ctx->num_cu * 8;
     const uint32_t bary_mode = (ctx->opt.traversal >= 2 && scene->wide_ok) ? 1u : 0u;  // k_trace2 hands the barycentrics to the shading kernel
@@ -589,6 +612,8 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
             tm.end(1, ps);
             if (two && depth > 2) HIP_TRY(ctx, hipStreamWaitEvent(ps, ev_anys[depth & 1], 0));  // shade(d) refills the queue the shadow rays of depth d - 2 read
             tm.begin(2, ps);
+            // every ray of this depth has its final answer: the entries that missed leave their record (one writer per slot; never L, which the shadow rays of depth - 1 may still add to)
+            if (envf_in) launch_path_escape(ctx, ps, ctr->n_queue[depth - 1], cap, pq[cur], hits, depth, envf.rec);
             const ShadeStream sst{nullptr, nullptr, 0u, two ? (uint8_t*)ctx->poison.p : nullptr};
             if (has_directional_light(scene)) {
                 if (scene->dev.tri_tan)
@@ -622,6 +647,10 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     }
     tm.begin(4, st);
     if (ctx->opt.overlap) hipLaunchKernelGGL(k_apply_poison, dim3(grid_for(ctx, l_slots, 8)), dim3(kBlock), 0, st, L, (const uint8_t*)ctx->poison.p, l_slots);
+    if (envf_in) {  // out = base, + beta * (E(dir) * scale) where a record contributes; the film pass and trhip_last_sample_radiance read out
+        launch_escape_fold(ctx, st, envf, l_slots, (float4*)ctx->Lbuf.p);
+        L = (float4*)ctx->Lbuf.p;
+    }
     if (map)
         launch_film_map(ctx, st, ds, dsp, L, *map, spp, seed, sample_offset, (float4*)d_film, map_packed);
     else
@@ -632,7 +661,13 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     hclk.tick("enqueue");
     HIP_TRY(ctx, hipStreamSynchronize(st));
     hclk.tick("stream sync");
-    ctx->last = LastRecords{total_slots, fused ? 1u : 0u, (uint32_t)npix, spp, map ? 2u : band ? 0u : 1u};
+    ctx->last = LastRecords{total_slots, fused ? 1u : 0u, (uint32_t)npix, spp, map ? 2u : band ? 0u : 1u, envf_in ? 1u : 0u};
+    if (envf_in) {  // what trhip_path_env_relight repeats the film pass with
+        PathEnvKeep& k = ctx->env_keep;
+        k.ds = ds;
+        std::memcpy(k.filter_table, sensor->filter_table, sizeof k.filter_table);
+        k.spp = spp, k.sample_offset = sample_offset, k.seed = seed, k.total_slots = total_slots, k.l_slots = l_slots, k.fused = fused;
+    }
     if (int rc = copy_back(ctx, out, out_is_device, d_film, film_bytes)) return rc;
     if (stats) {
         std::memset(stats, 0, sizeof *stats);
@@ -751,6 +786,12 @@ int render_map_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor
     return render_impl_band(ctx, scene, sensor, 1, max_spp, max_depth, seed, sample_offset, out, on_device, stats, nullptr, &map);
 }
 }  // namespace
+
+int render_path_env_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out, bool out_is_device,
+                          trhip_stats* stats, const trhip_env* env, float scale, uint32_t flags) {
+    const PathEnvFrame f{env, scale, flags, nullptr, nullptr};
+    return render_impl_band(ctx, scene, sensor, 1, spp, max_depth, seed, sample_offset, out, out_is_device, stats, nullptr, nullptr, &f);
+}
 
 extern "C" {
 

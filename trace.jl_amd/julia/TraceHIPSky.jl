@@ -107,3 +107,6 @@ function (i::SkyIntegrator)(scene::Trace.Scene)
     write_film!(film, out, h, w)
     Trace.save(film)
 end
+
+# the environment term of path frames (trhip_render_path_env): PathEnvIntegrator, last_escapes, relight! (tests/golden/julia_shim_path_env_calls.json)
+include("TraceHIPPathEnv.jl")
