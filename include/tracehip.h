@@ -257,7 +257,7 @@ int trhip_last_sample_radiance(trhip_ctx* ctx, float* out_rgb, uint64_t n_floats
  * reads 8 bytes back after a reduction over the map on the device.
  * Film passes: a filter radius in (0, 1] on both axes takes the pixel-group-major records with packed splat descriptors and the 2 x 4 gather;
  * any other radius takes sample-major records, film positions for the drawn samples and the 1 x 4 block gather.  The options that select other
- * film passes ("film_block", "film_tiled", "film_transpose", "film_fused", "film_relayout", "film_swizzle"), "streaming" and "pipelines" are
+ * record paths into the film pass ("film_fused", "film_relayout"), "streaming" and "pipelines" are
  * IGNORED by map frames; "batch_paths" (rounded down to whole waves of 64) and "overlap" hold.
  * trhip_last_sample_radiance after a map frame: the dense max_spp * n_sample_pixels * 3 array, +0.0 in every entry with s >= counts[p].
  * TRHIP_ERR_INVALID, in this order: a null pointer (stats excepted); max_spp == 0; an empty film; a count above max_spp (looked for on the host
@@ -1115,6 +1115,9 @@ int trhip_film_allreduce(trhip_ctx* ctx, void* d_xyzw, uint64_t n_pixels);
  * "pipelines" (1..8): wavefront batches in flight at once (default 1).
  * "film_fused" (0/1, default 1): the path integrator's ray generation writes every sample's radiance record in the film pass's own layout, with its splat
  *     descriptor, so that a frame needs no memset of the records and no pack / re-lay pass before the gather (film.jl:134-164 replaced; same film bit for bit).
+ * "film_relayout" (0/1, default 1): records that were not written that way (film_fused 0, Whitted, trhip_film_accumulate, …) are copied into that layout on their
+ *     way to the gather, when there is room for the copy; 0 = their descriptors are written in place and the gather reads the sample-major records.  Same film
+ *     bit for bit.  Both options concern filter radii in (0, 1] alone: any other radius takes the one wide film pass (film positions, 1 x 4 blocks per thread).
  * "bvh_builder" (-1/0/1/2/3): how trhip_scene_commit builds the BVH: 0 = binned SAH on the host, 1 = linear BVH on the device
  *     (Morton keys, radix sort, Karras hierarchy; 25-35 % more node visits per ray), 3 = the host builder's binned SAH run on the
  *     device (the same tree, 18 ms per million primitives instead of ~170 ms; scenes it cannot take go to the host builder),
@@ -1135,17 +1138,12 @@ int trhip_film_allreduce(trhip_ctx* ctx, void* d_xyzw, uint64_t n_pixels);
  *     hierarchy only when none of them stops the ray; exact (th_trace2.h, k_any_occluders).
  * "sppm_batch": SPPM iterations whose camera / photon paths share the traversal launches (default 0 = as many as fit in
  *     free HBM, at most 128); the result does not depend on it.
- * "film_block" (0/1/2/3): film pixels per thread of the film gather: 1, 2 x 2, 1 x 4 (2, default), and (3) 1 x 4 reading one precomputed
- *     16-byte splat descriptor per sample (pixel range + filter-table indices, the same Float32 operations done once per sample instead of
- *     once per thread the sample reaches; filter radius <= 3, else 2; measured 20 % slower than 2); same film bit for bit.
- * "film_tiled" (0/1): LDS-staged film gather (default 0: measured slower).
  * "denoise_lds" (bit mask 0..3, default 3): bit i set = iteration i of trhip_denoise (i = 0, 1: steps 1, 2) stages its blocks' pixels and halo in LDS
  *     instead of gathering them from memory (measured 7 % and 3 % faster); same result bit for bit (th_denoise.h).
  * "temporal_patch" (0/1, default 1): which lane of trhip_temporal's kernel computes which pixel — 0 film order (a wave is 64 pixels of a row), 1 the à-trous
  *     kernel's patches of 16 x 4 pixels per wave (measured 11 % faster); same result bit for bit (th_temporal.h).  No effect on
  *     trhip_temporal_clip, whose kernel has the patch mapping only.
  * "denoise_var_lds" (bit mask 0..3, default 3): as "denoise_lds", for trhip_denoise_var's iterations (measured 17 % and 16 % faster staged; th_denoise_var.h).
- * "film_transpose" (0/1): film pass on pixel-group-major copies of the per-sample radiance / film positions (default 0: no gain).
  * "leaf_kernel" (0/1): one-leaf scenes (tiny_scene_prims) run the dedicated uniform-walk kernel instead of traversal 2 (default 1).
  * "band_tile_rows": PathIntegrator frames whose per-sample buffers (24 B per camera sample) do not fit in HBM are rendered in bands of
  *     whole 16-row tile rows into the same film — bit-identical to one band (tiles reach a film pixel in the reference's order either

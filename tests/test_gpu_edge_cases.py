@@ -42,26 +42,21 @@ def test_empty_scene(T, ctx):
 
 
 def test_cropped_film(T, ob, ctx):
-    """Film crop window (film.jl:41-44): sample bounds, tiles and the gather all start away from (1, 1)."""
-    flt = T.LanczosSincFilter([1.0, 1.0], 3.0)
-    film = T.Film([40, 30], T.Bounds2([0.3, 0.2], [0.8, 0.9]), flt, 1.0, 1.0, "")
+    """Film crop window (film.jl:41-44): sample bounds, tiles and the gather all start away from (1, 1) — in the packed film pass (radius 1) and in the
+    wide one (radius 2.5 x 1.5: film positions and the block gather)."""
     base = T.scenes.cornell_camera(40)
-    cam = T.PerspectiveCamera(base.camera_to_world, T.Bounds2([-1.0, -1.0], [1.0, 1.0]), 0.0, 1.0, 0.0, 1e6, 90.0, film)
     scene = T.scenes.cornell_scene()
     osc = ob.OracleScene.from_scene(scene, bvh=scene.flatten(ctx).bvh())
-    sn = ob.make_sensor(cam, crop=(0.3, 0.2, 0.8, 0.9))
-    ref, ref_L, _ = osc.render(cam, "path", 3, 4, seed=8, want_samples=True, sensor=sn)
-    integ = T.PathIntegrator(cam, T.SeededSampler(3, seed=8), 4)
-    got = integ.render(scene, ctx)
-    assert got.shape == ref.shape == (21, 20, 4)
-    assert_bits_equal(integ.sample_radiance(scene), ref_L, "per-sample radiance (cropped film)")
-    assert_bits_equal(got, ref, "cropped film")
-    for mode in (0, 1, 2, 3, 4, 9):  # 3 = splat descriptors; the default is 6 (4 x 4 pixels per thread from packed descriptors)
-        ctx.set_option("film_block", mode)
-        try:
-            assert_bits_equal(T.PathIntegrator(cam, T.SeededSampler(3, seed=8), 4).render(scene, ctx), ref, f"cropped film, film_block {mode}")
-        finally:
-            ctx.set_option("film_block", 5)
+    for radius in ([1.0, 1.0], [2.5, 1.5]):
+        film = T.Film([40, 30], T.Bounds2([0.3, 0.2], [0.8, 0.9]), T.LanczosSincFilter(radius, 3.0), 1.0, 1.0, "")
+        cam = T.PerspectiveCamera(base.camera_to_world, T.Bounds2([-1.0, -1.0], [1.0, 1.0]), 0.0, 1.0, 0.0, 1e6, 90.0, film)
+        sn = ob.make_sensor(cam, crop=(0.3, 0.2, 0.8, 0.9))
+        ref, ref_L, _ = osc.render(cam, "path", 3, 4, seed=8, want_samples=True, sensor=sn)
+        integ = T.PathIntegrator(cam, T.SeededSampler(3, seed=8), 4)
+        got = integ.render(scene, ctx)
+        assert got.shape == ref.shape == (21, 20, 4)
+        assert_bits_equal(integ.sample_radiance(scene), ref_L, f"per-sample radiance (cropped film, radius {radius})")
+        assert_bits_equal(got, ref, f"cropped film, radius {radius}")
 
 
 def GP_sphere(T, centre, material, radius=0.03):
@@ -134,7 +129,7 @@ def test_material_less_primitive_is_rejected_by_render_but_traced(T, ctx):
 def test_bench_size_properties(T, ctx):
     """At the size of the bench (1024 x 1024, S-cornell, depth 8; all 256 spp) the oracle is too
     slow to compare against; size-independent properties instead: the render is reproducible bit for bit, does not depend on
-    the traversal kernel, the film-gather variant or the batch size, and the two halves of the sample range add up to the whole."""
+    the traversal kernel or the batch size, and the two halves of the sample range add up to the whole."""
     scene, cam = T.scenes.cornell_scene(), T.scenes.cornell_camera(1024)
 
     def render(spp=256, offset=0, **opts):
@@ -143,16 +138,13 @@ def test_bench_size_properties(T, ctx):
         try:
             return T.PathIntegrator(cam, T.SeededSampler(spp, seed=0x5EED0001, sample_offset=offset), 8).render(scene, ctx).copy()
         finally:
-            for k, v in {"traversal": 3, "film_block": 5, "batch_paths": 0, "overlap": 1}.items():
+            for k, v in {"traversal": 3, "batch_paths": 0, "overlap": 1}.items():
                 ctx.set_option(k, v)
 
     a = render()
     assert np.isfinite(a).all() and a[..., 3].min() > 0
     assert_bits_equal(render(), a, "second run")
     assert_bits_equal(render(traversal=1), a, "literal traversal kernel")
-    assert_bits_equal(render(film_block=0), a, "one film pixel per thread")
-    assert_bits_equal(render(film_block=3), a, "film gather from splat descriptors")
-    assert_bits_equal(render(film_block=2), a, "1 x 4 blocks recomputing the ranges (round 2's default)")
     assert_bits_equal(render(batch_paths=16 * 1026 * 1026, overlap=0), a, "four batches, one stream")
     assert_bits_equal(render(traversal=3), a, "binary children-in-parent walk (k_trace_leaf here: one-leaf scene)")
     h0, h1 = render(128, 0), render(128, 128)
@@ -264,7 +256,7 @@ def test_nested_bvh_as_primitive(T, ob, ctx):
 def test_banded_frame_equals_whole_frame(T, ob, ctx, rows):
     """A frame whose per-sample buffers do not fit in HBM (4096^2 x 1024 spp: 412 GB) is rendered in bands of whole tile rows into one
     film (option band_tile_rows forces it here): every film pixel still receives its tiles in the reference's k order, so the film is
-    the one-band film — and the oracle's — bit for bit, with every film-gather variant.  The bands trace the frame's rays, each once: every
+    the one-band film — and the oracle's — bit for bit (the packed film pass here; the wide one in the test below).  The bands trace the frame's rays, each once: every
     additive counter of the banded frame's statistics equals the one-band frame's (the visit counts and the fallback reasons under
     "count_visits", zeros without it), and n_batches counts the bands.  prims_tested_shadow is not compared: the any-hit pre-pass counts a
     record once per WAVE (include/tracehip.h), and bands pack the same shadow rays into other waves (measured with one tile row per band:
@@ -275,18 +267,15 @@ def test_banded_frame_equals_whole_frame(T, ob, ctx, rows):
     osc = ob.OracleScene.from_scene(scene, bvh=scene.flatten(ctx).bvh())
     ref, _, st_ref = osc.render(cam, "path", 3, 5, seed=12, threads=ob.lib().orc_num_threads())
     assert_bits_equal(whole, ref, "one band vs oracle")
-    for film_block in (6, 2, 3, 0, 1, 5):
-        ctx.set_option("band_tile_rows", rows)
-        ctx.set_option("film_block", film_block)
-        try:
-            integ = T.PathIntegrator(cam, T.SeededSampler(3, seed=12), 5)
-            banded = integ.render(scene, ctx).copy()
-        finally:
-            ctx.set_option("band_tile_rows", 0)
-            ctx.set_option("film_block", 5)
-        assert_bits_equal(banded, whole, f"bands of {rows} tile rows, film_block {film_block}")
-        assert integ.stats.camera_samples == 102 * 102 * 3 and integ.stats.closest_rays == st_ref.closest_rays and integ.stats.launches_film == -(-7 // rows)
-        assert_counters_equal(integ.stats, whole_integ.stats, -(-7 // rows), f"bands of {rows} tile rows, film_block {film_block}")
+    ctx.set_option("band_tile_rows", rows)
+    try:
+        integ = T.PathIntegrator(cam, T.SeededSampler(3, seed=12), 5)
+        banded = integ.render(scene, ctx).copy()
+    finally:
+        ctx.set_option("band_tile_rows", 0)
+    assert_bits_equal(banded, whole, f"bands of {rows} tile rows")
+    assert integ.stats.camera_samples == 102 * 102 * 3 and integ.stats.closest_rays == st_ref.closest_rays and integ.stats.launches_film == -(-7 // rows)
+    assert_counters_equal(integ.stats, whole_integ.stats, -(-7 // rows), f"bands of {rows} tile rows")
     ctx.set_option("count_visits", 1)
     try:
         counted_whole = T.PathIntegrator(cam, T.SeededSampler(3, seed=12), 5)
@@ -303,6 +292,33 @@ def test_banded_frame_equals_whole_frame(T, ob, ctx, rows):
 
 ADDITIVE_COUNTERS = ("camera_samples", "closest_rays", "shadow_rays", "nodes_visited", "prims_tested", "nodes_visited_shadow", "fallback_rays", "nodes_visited_fallback",
                      "prims_tested_fallback")  # (not prims_tested_shadow: see test_banded_frame_equals_whole_frame)
+
+
+def test_banded_frame_equals_whole_frame_wide_filter(T, ob, ctx):
+    """The same through the wide film pass (a filter radius above 1: film positions and the 1 x 4 block gather, whose later bands add onto the film of the bands
+    before — DeviceSensor::accumulate): a 40 x 30 Cornell film, radius 2.5 x 1.5, one tile row per band, against the one-band frame and the oracle."""
+    base = T.scenes.cornell_camera(40)
+    film = T.Film([40, 30], T.Bounds2([0.0, 0.0], [1.0, 1.0]), T.LanczosSincFilter([2.5, 1.5], 3.0), 1.0, 1.0, "")
+    cam = T.PerspectiveCamera(base.camera_to_world, T.Bounds2([-1.0, -1.0], [1.0, 1.0]), 0.0, 1.0, 0.0, 1e6, 90.0, film)
+    scene = T.scenes.cornell_scene()
+    sb = film.get_sample_bounds()
+    sbw, sbh = int(sb.p_max[0] - sb.p_min[0]) + 1, int(sb.p_max[1] - sb.p_min[1]) + 1
+    n_bands = (sbh - 1 + 16) // 16  # tile rows of the sample bounds (integrators/sampler.jl:24-28)
+    assert n_bands >= 2
+    whole_integ = T.PathIntegrator(cam, T.SeededSampler(3, seed=12), 4)
+    whole = whole_integ.render(scene, ctx).copy()
+    osc = ob.OracleScene.from_scene(scene, bvh=scene.flatten(ctx).bvh())
+    ref, _, st_ref = osc.render(cam, "path", 3, 4, seed=12)
+    assert_bits_equal(whole, ref, "one band vs oracle (wide filter)")
+    ctx.set_option("band_tile_rows", 1)
+    try:
+        integ = T.PathIntegrator(cam, T.SeededSampler(3, seed=12), 4)
+        banded = integ.render(scene, ctx).copy()
+    finally:
+        ctx.set_option("band_tile_rows", 0)
+    assert_bits_equal(banded, whole, "one tile row per band (wide filter)")
+    assert integ.stats.camera_samples == sbw * sbh * 3 and integ.stats.closest_rays == st_ref.closest_rays and integ.stats.launches_film == n_bands
+    assert_counters_equal(integ.stats, whole_integ.stats, n_bands, "one tile row per band (wide filter)")
 
 
 def assert_counters_equal(banded, whole, n_bands, what):

@@ -10,9 +10,9 @@ NEEDS = "needs the EXPERIMENTS build of the library (-DTRHIP_EXPERIMENTS): not i
 
 # every option with the value a new context holds for it (csrc/th_options.h; INTEGRATION.md's tables for the ones listed there)
 DEFAULTS = {
-    "count_visits": 0, "timing": 1, "batch_paths": 0, "pipelines": 1, "debug_trace_budget": 0, "bvh_builder": -1, "film_transpose": 0, "occluder_pretest": 1,
-    "stream2_priority": -1, "leaf_kernel": 1, "slab_margin_log2": 14, "band_tile_rows": 0, "tiny_scene_prims": 16, "film_block": 5, "film_relayout": 1,
-    "any_on_accelerator": -1, "wide4": 1, "leaf_queue": 0, "node_layout": 0, "film_swizzle": 0, "film_tiled": 0, "overlap": 1, "compose_spheres": -1, "traversal": 3,
+    "count_visits": 0, "timing": 1, "batch_paths": 0, "pipelines": 1, "debug_trace_budget": 0, "bvh_builder": -1, "occluder_pretest": 1,
+    "stream2_priority": -1, "leaf_kernel": 1, "slab_margin_log2": 14, "band_tile_rows": 0, "tiny_scene_prims": 16, "film_relayout": 1,
+    "any_on_accelerator": -1, "wide4": 1, "leaf_queue": 0, "node_layout": 0, "overlap": 1, "compose_spheres": -1, "traversal": 3,
     "leaf_sorted": 0, "film_fused": 1, "trace3_spec": 1, "hybrid": 1, "trace7_cheap": 1, "streaming": 0, "stream_budget_shift": 12, "stream_list_cap": 0,
     "stream_budget_min": 2048, "sppm_batch": 0, "denoise_lds": 3, "temporal_patch": 1, "denoise_var_lds": 3,
 }

@@ -267,29 +267,16 @@ def test_film_accumulate_matches_oracle_tile_order(T, ob, ctx):
     sn = cam.sensor()
     out = np.empty_like(ref_xyzw)
     ctx.check(T.lib().trhip_film_accumulate(ctx._h, C.byref(sn), spp, 5, 0, T._ffi.fptr(ref_L), T._ffi.fptr(out)))
-    assert_bits_equal(out, ref_xyzw, "film accumulate (wide anisotropic filter)")
-    ctx.set_option("film_tiled", 1)  # the LDS-staged variant of the gather
-    try:
-        out2 = np.empty_like(ref_xyzw)
-        ctx.check(T.lib().trhip_film_accumulate(ctx._h, C.byref(sn), spp, 5, 0, T._ffi.fptr(ref_L), T._ffi.fptr(out2)))
-    finally:
-        ctx.set_option("film_tiled", 0)
-    assert_bits_equal(out2, ref_xyzw, "film accumulate, LDS-tiled gather")
-    for mode in (0, 1, 2, 3, 5):  # one film pixel per thread, 2 x 2 blocks, 1 x 4 blocks, 1 x 4 from splat descriptors (odd film sizes: 37 x 29); 5: this filter is too wide for
-        ctx.set_option("film_block", mode)  # the packed descriptor, the library must fall back to the 1 x 4 block gather
-        try:
-            out3 = np.empty_like(ref_xyzw)
-            ctx.check(T.lib().trhip_film_accumulate(ctx._h, C.byref(sn), spp, 5, 0, T._ffi.fptr(ref_L), T._ffi.fptr(out3)))
-        finally:
-            ctx.set_option("film_block", 5)
-        assert_bits_equal(out3, ref_xyzw, f"film accumulate, film_block={mode}")
+    assert_bits_equal(out, ref_xyzw, "film accumulate (wide anisotropic filter)")  # too wide for the packed descriptor: the 1 x 4 block gather, on an odd film size
 
 
 def test_film_gather_from_packed_descriptors(T, ob, ctx):
     """The default film pass for filter radii <= 1 (every scene of the reference): the sample's pixel range and filter-table indices ride as 30 bits in the
-    .w lane of its radiance record (k_film_pack_w) and a thread owns BX x BY film pixels (k_film_gather_packed).  Every block shape, odd film sizes, a crop
-    window, radii 1, 0.5 and anisotropic, NaN samples — against the oracle's add_sample! / merge_film_tile! loop and against the per-pixel gather."""
+    .w lane of its radiance record and a thread owns 2 x 4 film pixels (k_film_gather_packed).  Records re-laid pixel-group-major (k_film_pack_transpose) and
+    in place (k_film_pack_w, film_relayout 0), odd film sizes, a crop window, radii 1, 0.5 and anisotropic — against the oracle's add_sample! / merge_film_tile!
+    loop; NaN samples against the film the oracle's film-tile calls make of the records after the NaN rule (sample_map_model.film_model)."""
     import ctypes as C
+    import sample_map_model as sm
     scene = T.scenes.shadows_scene()
     osc = ob.OracleScene.from_scene(scene)
     for res, crop, radius, spp in (([37, 29], ([0.0, 0.0], [1.0, 1.0]), [1.0, 1.0], 3), ([64, 48], ([0.0, 0.0], [1.0, 1.0]), [1.0, 1.0], 5), ([53, 41], ([0.2, 0.1], [0.9, 0.8]), [1.0, 0.5], 2),
@@ -299,30 +286,23 @@ def test_film_gather_from_packed_descriptors(T, ob, ctx):
         cam = T.PerspectiveCamera(T.look_at([0, 15, 50], [0, 0, -2], [0, 1, 0]), T.Bounds2([-1.0, -1.0], [1.0, 1.0]), 0.0, 1.0, 0.0, 1e6, 90.0, film)
         ref_xyzw, ref_L, _ = osc.render(cam, "path", spp, 3, seed=5, want_samples=True)
         sn = cam.sensor()
-        outs = {}
-        for mode, relayout in [(m, 1) for m in (0, 4, 5, 6, 7, 8, 9, 10, 12, 13)] + [(5, 0), (4, 0)]:  # relayout 0: descriptors written in place, sample-major gather
-            ctx.set_option("film_block", mode)
-            ctx.set_option("film_relayout", relayout)
-            try:
-                out = np.empty_like(ref_xyzw)
-                ctx.check(T.lib().trhip_film_accumulate(ctx._h, C.byref(sn), spp, 5, 0, T._ffi.fptr(ref_L), T._ffi.fptr(out)))
-            finally:
-                ctx.set_option("film_block", 5)
-                ctx.set_option("film_relayout", 1)
-            assert_bits_equal(out, ref_xyzw, f"film {res}, radius {radius}, film_block={mode}, relayout={relayout}")
-        # NaN samples are zeroed (integrators/sampler.jl:46): every variant against the one-pixel-per-thread gather
+        # NaN samples are zeroed (integrators/sampler.jl:46): a record that holds a NaN counts as (0, 0, 0), its filter weight still counts
         bad_L = ref_L.copy()
         bad_L.reshape(-1, 3)[::97, 1] = np.nan
-        for mode in (0, 5, 4, 9):
-            ctx.set_option("film_block", mode)
+        ruled = bad_L.reshape(-1, 3).copy()
+        ruled[np.isnan(ruled).any(axis=1)] = 0.0
+        sbh, sbw, _, _ = sm.sample_shape(cam)
+        ref_nan = sm.film_model(ob, cam, ruled.reshape(spp, sbh, sbw, 3), np.full((sbh, sbw), spp), 5)
+        for relayout in (1, 0):  # 0: descriptors written in place, sample-major gather
+            ctx.set_option("film_relayout", relayout)
             try:
-                out = np.empty_like(ref_xyzw)
-                ctx.check(T.lib().trhip_film_accumulate(ctx._h, C.byref(sn), spp, 5, 0, T._ffi.fptr(bad_L), T._ffi.fptr(out)))
+                out, out_nan = np.empty_like(ref_xyzw), np.empty_like(ref_xyzw)
+                ctx.check(T.lib().trhip_film_accumulate(ctx._h, C.byref(sn), spp, 5, 0, T._ffi.fptr(ref_L), T._ffi.fptr(out)))
+                ctx.check(T.lib().trhip_film_accumulate(ctx._h, C.byref(sn), spp, 5, 0, T._ffi.fptr(bad_L), T._ffi.fptr(out_nan)))
             finally:
-                ctx.set_option("film_block", 5)
-            outs[mode] = out
-        for mode in (5, 4, 9):
-            assert_bits_equal(outs[mode], outs[0], f"NaN samples, film_block={mode}")
+                ctx.set_option("film_relayout", 1)
+            assert_bits_equal(out, ref_xyzw, f"film {res}, radius {radius}, relayout={relayout}")
+            assert_bits_equal(out_nan, ref_nan, f"NaN samples, film {res}, radius {radius}, relayout={relayout}")
 
 
 def test_film_to_rgb(T, ob, ctx, shadows):

@@ -81,13 +81,13 @@ def traversal(v, exp):
 
 # name -> (rule, a value the option takes that is not its default: what the field holds before the value under test is applied)
 RULES = {
-    **{n: (flag, p) for n, p in (("count_visits", 1), ("timing", 0), ("hybrid", 0), ("film_transpose", 1), ("occluder_pretest", 0), ("film_fused", 0), ("trace3_spec", 0),
-                                 ("trace7_cheap", 0), ("leaf_kernel", 0), ("film_relayout", 0), ("wide4", 0), ("film_swizzle", 1), ("film_tiled", 1), ("overlap", 0),
+    **{n: (flag, p) for n, p in (("count_visits", 1), ("timing", 0), ("hybrid", 0), ("occluder_pretest", 0), ("film_fused", 0), ("trace3_spec", 0),
+                                 ("trace7_cheap", 0), ("leaf_kernel", 0), ("film_relayout", 0), ("wide4", 0), ("overlap", 0),
                                  ("temporal_patch", 0))},
     "leaf_sorted": (experiments_flag("leaf_sorted"), 1),
     "leaf_queue": (experiments_flag("leaf_queue"), 1),
     "streaming": (tri, 1), "compose_spheres": (tri, 1), "any_on_accelerator": (tri, 1),
-    "stream_budget_shift": (clamp(0, 31, u32), 3), "slab_margin_log2": (clamp(0, 20, i32), 3), "tiny_scene_prims": (clamp(0, 255, u32), 3), "film_block": (clamp(0, 13, i32), 3),
+    "stream_budget_shift": (clamp(0, 31, u32), 3), "slab_margin_log2": (clamp(0, 20, i32), 3), "tiny_scene_prims": (clamp(0, 255, u32), 3),
     "bvh_builder": (bvh_builder, 2),
     "stream_list_cap": (clamp(0, NO_MAX, u32), 77), "sppm_batch": (clamp(0, NO_MAX, same), 77), "band_tile_rows": (clamp(0, NO_MAX, i32), 77),
     "stream_budget_min": (clamp(1, NO_MAX, u32), 77),
@@ -95,6 +95,8 @@ RULES = {
     "debug_trace_budget": (lambda v, exp: ok(u32(v)), 77), "stream2_priority": (lambda v, exp: ok(i32(v)), 77),
     "node_layout": (node_layout, 1), "pipelines": (pipelines, 2), "batch_paths": (batch_paths, 77), "traversal": (traversal, 2),
 }
+# names the table does not hold: one that never was an option, and the film-pass variants that lost their measurements and went with their kernels (docs/design/04-kernels.md)
+UNKNOWN = ("no_such_option", "film_block", "film_tiled", "film_transpose", "film_swizzle")
 
 
 @pytest.fixture(scope="module")
@@ -120,7 +122,7 @@ def test_rows_are_the_documented_options(program):
 @pytest.mark.parametrize("experiments", [False, True])
 def test_every_option_follows_its_rule(program, experiments):
     cases = [(name, prime, v) for name, (_, prime) in RULES.items() for v in VALUES]
-    cases += [("no_such_option", 0, v) for v in (0, 1)]
+    cases += [(name, 0, v) for name in UNKNOWN for v in (0, 1)]
     fed = "".join(f"{n} {p} {v}\n" for n, p, v in cases)
     done = subprocess.run([program, str(int(experiments))], input=fed, capture_output=True, text=True, timeout=60)
     assert done.returncode == 0, done.stdout[-2000:] + done.stderr
@@ -128,8 +130,8 @@ def test_every_option_follows_its_rule(program, experiments):
     assert len(lines) == len(cases)
     for (name, prime, v), line in zip(cases, lines):
         rc, before, after, msg = line.split("\t")
-        if name == "no_such_option":
-            assert (int(rc), before, after, msg) == (INVALID, "-", "-", "unknown option no_such_option")
+        if name in UNKNOWN:
+            assert (int(rc), before, after, msg) == (INVALID, "-", "-", f"unknown option {name}")
             continue
         want_rc, want, want_msg = RULES[name][0](v, experiments)
         assert int(before) == RULES[name][0](prime, True)[1], (name, prime)

@@ -79,7 +79,6 @@ struct trhip_ctx {
     // streaming wavefront (render_stream_impl)
     DevBuf st_terms, st_tags[2], st_frozen, st_counts, st_list[2][2][7];  // [closest|any][ping-pong][o, d, b, trav, st, depth, stack]
     DevBuf film_side;  // packed film pass: counter + the full descriptors of the samples whose range does not fit 30 bits (th_kernels.h, FilmSideTable)
-    DevBuf fdesc;   // film_block 3: one SplatDesc (16 B) per camera sample of the band (th_kernels.h, k_film_descriptors)
     DevBuf poison;  // one byte per camera sample of the band: ShadeStream::poison
     DevBuf cert_cold;  // k_trace3c's CertCold (th_trace3c.h)
     DevBuf aov_rec;    // trhip_render_aov: the frame's per-sample records (th_aov.h, 80 B per camera sample)
@@ -443,11 +442,19 @@ void launch_trace8(trhip_ctx* ctx, hipStream_t st, const trhip_scene* sc, bool a
                    const float* tmax, const TraceOut& out, uint32_t* work_cursors, uint32_t* ov8, Counters* ctr, const FallbackList& fb);
 // tu_path.hip
 void derive_sensor(const trhip_sensor* sn, DeviceSensor& d);
-bool film_uses_desc(const trhip_ctx* ctx, const DeviceSensor& ds);
-bool film_uses_packed(const trhip_ctx* ctx, const DeviceSensor& ds);
-int ensure_film_samples(trhip_ctx* ctx, const DeviceSensor& ds, uint64_t total_slots);
+// … the film pass: packed (both filter radii in (0, 1]) or wide.  A frame asks film_packed which pass it gets, gets the wide pass's film positions from
+// ensure_film_samples and hands its records to launch_film.
+// A map frame (trhip_render_path_map) has a per-pixel sample count instead of one spp: the records keep the dense max_spp layouts, the frame's camera samples are the job
+// list (th_adaptive.h, k_map_expand) and the gather stops at counts[pix].
+struct MapFrame {
+    const uint32_t* counts;  // device: one per sample pixel
+    const uint32_t* jobs;    // device: `total` dense sample-major slots
+    uint64_t total;          // Σ counts
+};
+bool film_packed(const DeviceSensor& ds);
+int ensure_film_samples(trhip_ctx* ctx, bool packed, uint64_t total_slots);
 void launch_film(trhip_ctx* ctx, hipStream_t st, const DeviceSensor& ds, const DeviceSensor* dsp, const float4* L, uint64_t total_slots, uint32_t spp, uint64_t seed, uint32_t sample_offset,
-                 float4* d_film, bool fused);
+                 float4* d_film, bool fused, const MapFrame* map = nullptr);
 // … the one place that turns device counters and event times into trhip_stats.  A frame's stats are: zeros, stats_add_counters for every Counters block it ran on,
 // stats_fill_times, and what only the caller knows (camera_samples, n_batches, max_depth_reached, an integrator's ms_sub / count_sub)
 void stats_add_counters(trhip_stats& s, const Counters& h);  // += the ray, node-visit and primitive-test totals, the fallback totals and the fallback reasons (count_sub)
@@ -472,7 +479,6 @@ void launch_escape_fold(trhip_ctx* ctx, hipStream_t st, const PathEnvFrame& f, u
 // tu_path.hip: trhip_render_path's frame — its refusals in its order, the classic wavefront without bands — with the environment frame
 int render_path_env_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out, bool out_is_device,
                           trhip_stats* stats, const trhip_env* env, float scale, uint32_t flags);
-bool film_fused(const trhip_ctx* ctx, const DeviceSensor& ds, uint32_t spp);
 // tu_whitted.hip
 int render_whitted_impl(trhip_ctx* ctx, const trhip_scene* scene, const DeviceSensor& ds, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
                         void* d_film, trhip_stats* stats);

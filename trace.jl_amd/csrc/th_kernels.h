@@ -3,7 +3,7 @@
 //   k_raygen          camera samples -> ray queue            (sampler/sampler.jl:135-139, camera/perspective.jl:85-114)
 //   k_trace<ANY,…>    BVH2 closest-hit / any-hit traversal    (accel/bvh.jl:212-299, bounds.jl:186-206, shapes/*.jl)
 //   k_shade_path      PathIntegrator vertex: interaction, BSDF, light sample -> shadow queue, sample_f + RR -> next queue
-//   k_film_gather     add_sample! + merge_film_tile! as a deterministic gather in the reference's summation order
+//   k_film_gather_*   add_sample! + merge_film_tile! as a deterministic gather in the reference's summation order
 //
 // Execution model: persistent grid-stride kernels (no host round trip per bounce: queue sizes live in HBM),
 // one ray per lane, 64-wide waves, per-lane traversal stack staged in LDS as stack[level][lane] (conflict-free: lane l
@@ -194,7 +194,10 @@ struct FilmSideTable {
     uint32_t cap;
 };
 TH_D uint32_t film_pack_word(const FilmSideTable& side, uint4 d, int px, int py);
-TH_D uint4 film_splat_desc(const DeviceSensor& se, int px, int py, uint64_t key) {  // the SplatDesc of one camera sample (k_film_descriptors' arithmetic)
+// The splat descriptor of one camera sample — everything add_sample! derives from camera_sample.film (film.jl:145-153), with the reference's Float32 operations:
+//   .x  int16 p0x | int16 p0y << 16 = ceil(dp - r), unclamped (film.jl:145)     .y  nx | ny << 8 = floor(dp + r) + 1 - p0 + 1 (film.jl:146: the extra column / row of A.9 included)
+//   .z  4 bits per column: clamp(ceil(|x - dpx| / rx * 16), 1, 16) - 1          .w  4 bits per row: clamp(floor(|y - dpy| / ry * 16), 1, 16) - 1
+TH_D uint4 film_splat_desc(const DeviceSensor& se, int px, int py, uint64_t key) {
     const float rx = se.filter_radius[0], ry = se.filter_radius[1];
     const float inv_rx = 1.0f / rx, inv_ry = 1.0f / ry;
     const float pfx = (float)px + ts_uniform(key, TS_DIM_FILM_X), pfy = (float)py + ts_uniform(key, TS_DIM_FILM_Y);  // camera_sample.film
@@ -792,24 +795,14 @@ template <int TH_ONE_COPY = 0> __global__ __launch_bounds__(kBlock) void k_fill_
 // (integrators/sampler.jl:24-31), inside a tile in Bounds2 iteration order (x fastest, bounds.jl:39-47), samples in order —
 // i.e. exactly the reference's (single-threaded) summation order, with no atomics and no race (the reference's
 // merge_film_tile! is unsynchronised).  out = xyz sums + filter_weight_sum.
-// camera_sample.film of every slot (p_raster + get_2d, sampler/sampler.jl:135-139): written once so that the gather does not
-// re-derive it from the sampler for each of the ~16 film pixels a sample reaches.
-// Where sample s of sample-pixel pix lives in the film pass's inputs.  The integrators write L sample-major ([s][pix]: what the
-// queues want); the gather walks ALL samples of a pixel before it moves to the next pixel (the reference's order), i.e. with a
-// stride of npix * 16 bytes (16 MB at 1024²) between consecutive loads — a new page for every one.  launch_film therefore
-// re-lays L (k_film_transpose) and writes p_film pixel-group-major: [group of 64 sample-pixels][s][lane]; consecutive samples
-// are then 1 KB apart and a wave's load is one contiguous chunk as before.  layout 0 = sample-major (option film_transpose 0).
-// film_index: defined with the camera-sample helpers above (k_raygen writes in that layout too)
-template <int TH_ONE_COPY = 0> __global__ __launch_bounds__(kBlock) void k_film_transpose(const float4* __restrict__ L, uint32_t npix, uint32_t spp, float4* __restrict__ Lt) {
-    const uint32_t groups = (npix + 63u) >> 6;
-    const uint64_t chunks = (uint64_t)groups * spp;
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint64_t c = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6; c < chunks; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
-        const uint32_t s = (uint32_t)(c / groups), g = (uint32_t)(c - (uint64_t)s * groups);  // consecutive waves read consecutive chunks
-        const uint32_t pix = g * 64u + lane;
-        if (pix < npix) Lt[film_index(1u, npix, spp, s, pix)] = L[(size_t)s * npix + pix];
-    }
-}
+// Two film passes (tu_path.hip, launch_film).  Packed, both filter radii in (0, 1]: a 30-bit splat descriptor in the record's .w lane and
+// k_film_gather_packed<2, 4>, further down.  Wide, anything else: k_film_positions and k_film_gather_block<1, 4> on sample-major records, here.
+// What else was built lost its measurement and is gone (docs/design/04-kernels.md "Removed film variants" has the figures; the code is in 42228bf):
+// a film pixel per thread (k_film_gather, 67 ms against 32 for 1 x 4 blocks), sample-major p_film / L re-laid pixel-group-major for the block gather
+// (k_film_transpose: no gain), the block gather from 16-byte descriptors (k_film_descriptors / k_film_gather_desc: 29.0 ms against 24.3) and the
+// LDS-staged gather (k_film_gather_tiled: 2.7x slower, 11 % lane use).
+// camera_sample.film of every slot (p_raster + get_2d, sampler/sampler.jl:135-139): written once so that the wide gather does not
+// re-derive it from the sampler for each of the film pixels a sample reaches.  Sample-major, like the records (film_index, layout 0).
 template <int TH_ONE_COPY = 0> __global__ __launch_bounds__(kBlock) void k_film_positions(const DeviceSensor* __restrict__ sep, uint64_t n, uint64_t seed, uint32_t sample_offset, float2* __restrict__ pfilm, uint32_t layout,
                                                            uint32_t spp) {
     const DeviceSensor& se = *sep;
@@ -819,77 +812,6 @@ template <int TH_ONE_COPY = 0> __global__ __launch_bounds__(kBlock) void k_film_
         pfilm[film_index(layout, (uint32_t)(se.sb_w * se.band_rows), spp, si.sample, si.pix)] = make_float2((float)si.px + ts_uniform(key, TS_DIM_FILM_X), (float)si.py + ts_uniform(key, TS_DIM_FILM_Y));
     }
 }
-template <int TH_ONE_COPY = 0> __global__ __launch_bounds__(kBlock) void k_film_gather(const DeviceSensor* __restrict__ sep, const float* __restrict__ table, const float4* __restrict__ L,
-                                                        const float2* __restrict__ pfilm, uint32_t spp, uint32_t layout, float4* __restrict__ out) {
-    const DeviceSensor& se = *sep;
-    const uint32_t npx = (uint32_t)(se.film_w * se.film_h);
-    const uint32_t npix = (uint32_t)(se.sb_w * se.band_rows);
-    const float rx = se.filter_radius[0], ry = se.filter_radius[1];
-    const float inv_rx = 1.0f / rx, inv_ry = 1.0f / ry;
-    for (uint32_t idx = blockIdx.x * kBlock + threadIdx.x; idx < npx; idx += gridDim.x * kBlock) {
-        const int fy = (int)(idx / (uint32_t)se.film_w), fx = (int)(idx - (uint32_t)fy * (uint32_t)se.film_w);
-        const float X = se.crop_min[0] + (float)fx, Y = se.crop_min[1] + (float)fy;
-        // sample-pixels that can reach (X, Y): sx in (X - 1.5 - r, X + r + 0.5]
-        int sx_lo = (int)__builtin_floorf(X - 1.5f - rx), sx_hi = (int)__builtin_ceilf(X + rx + 0.5f);
-        int sy_lo = (int)__builtin_floorf(Y - 1.5f - ry), sy_hi = (int)__builtin_ceilf(Y + ry + 0.5f);
-        sx_lo = max(sx_lo, se.sb_min[0]);
-        sy_lo = max(sy_lo, se.sb_min[1]);
-        sx_hi = min(sx_hi, se.sb_max[0]);
-        sy_hi = min(sy_hi, se.sb_max[1]);
-        f3 xyz = splat3(0.0f);
-        float wsum = 0.0f;
-        if (se.accumulate) {  // a later band of the frame: its tiles are added, in k order, onto the tiles of the bands before
-            const float4 prev = out[idx];
-            xyz = mk3(prev.x, prev.y, prev.z);
-            wsum = prev.w;
-        }
-        if (sx_lo <= sx_hi && sy_lo <= sy_hi) {
-            const int ty_lo = max((sy_lo - se.sb_min[1]) >> 4, se.band_ty0), ty_hi = min((sy_hi - se.sb_min[1]) >> 4, se.band_ty1);
-            const int tx_lo = (sx_lo - se.sb_min[0]) >> 4, tx_hi = (sx_hi - se.sb_min[0]) >> 4;
-            for (int ty = ty_lo; ty <= ty_hi; ++ty)
-                for (int tx = tx_lo; tx <= tx_hi; ++tx) {
-                    // tile sample bounds (integrators/sampler.jl:29-31) and FilmTile bounds (film.jl:120-125)
-                    const float tbx0 = (float)se.sb_min[0] + (float)tx * 16.0f, tby0 = (float)se.sb_min[1] + (float)ty * 16.0f;
-                    const float tbx1 = jmin(tbx0 + 15.0f, (float)se.sb_max[0]), tby1 = jmin(tby0 + 15.0f, (float)se.sb_max[1]);
-                    const float bx0 = jmax(__builtin_ceilf(tbx0 - 0.5f - rx), se.crop_min[0]), by0 = jmax(__builtin_ceilf(tby0 - 0.5f - ry), se.crop_min[1]);
-                    const float bx1 = jmin(__builtin_floorf(tbx1 - 0.5f + rx) + 1.0f, se.crop_max[0]), by1 = jmin(__builtin_floorf(tby1 - 0.5f + ry) + 1.0f, se.crop_max[1]);
-                    if (X < bx0 || X > bx1 || Y < by0 || Y > by1) continue;  // pixel not in this FilmTile: merge does not touch it
-                    f3 csum = splat3(0.0f);
-                    float fws = 0.0f;
-                    const int y0 = max(sy_lo, (int)tby0), y1 = min(sy_hi, (int)tby1);
-                    const int x0 = max(sx_lo, (int)tbx0), x1 = min(sx_hi, (int)tbx1);
-                    for (int sy = y0; sy <= y1; ++sy)
-                        for (int sx = x0; sx <= x1; ++sx) {
-                            const uint32_t pix = (uint32_t)(sy - se.band_y0) * (uint32_t)se.sb_w + (uint32_t)(sx - se.sb_min[0]);
-                            for (uint32_t s = 0; s < spp; ++s) {
-                                const float2 pf = pfilm[film_index(layout, npix, spp, s, pix)];  // camera_sample.film, from k_film_positions
-                                const float dpx = pf.x - 0.5f, dpy = pf.y - 0.5f;
-                                float p0x = __builtin_ceilf(dpx - rx), p0y = __builtin_ceilf(dpy - ry);
-                                float p1x = __builtin_floorf(dpx + rx) + 1.0f, p1y = __builtin_floorf(dpy + ry) + 1.0f;
-                                p0x = jmax(p0x, jmax(bx0, 1.0f));
-                                p0y = jmax(p0y, jmax(by0, 1.0f));
-                                p1x = jmin(p1x, bx1);
-                                p1y = jmin(p1y, by1);
-                                if (X < p0x || X > p1x || Y < p0y || Y > p1y) continue;
-                                const float ffx = fabs_((X - dpx) * inv_rx * 16.0f), ffy = fabs_((Y - dpy) * inv_ry * 16.0f);
-                                const int ox = (int)jclamp(__builtin_ceilf(ffx), 1.0f, 16.0f);   // ceil for x …
-                                const int oy = (int)jclamp(__builtin_floorf(ffy), 1.0f, 16.0f);  // … floor for y (A.9)
-                                const float w = table[(oy - 1) * 16 + (ox - 1)];
-                                const float4 l4 = L[film_index(layout, npix, spp, s, pix)];
-                                f3 l = mk3(l4.x, l4.y, l4.z);
-                                if (has_nan(l)) l = splat3(0.0f);  // integrators/sampler.jl:46
-                                csum = csum + l * 1.0f * w;
-                                fws += w;
-                            }
-                        }
-                    xyz = xyz + rgb_to_xyz(csum);
-                    wsum += fws;
-                }
-        }
-        out[idx] = make_float4(xyz.x, xyz.y, xyz.z, wsum);
-    }
-}
-
 // FilmTile bounds of sample tile (ty, tx) (integrators/sampler.jl:29-31 + film.jl:120-125).
 TH_D void film_tile_bounds(const DeviceSensor& se, int ty, int tx, float rx, float ry, float& bx0, float& by0, float& bx1, float& by1) {
     const float tbx0 = (float)se.sb_min[0] + (float)tx * 16.0f, tby0 = (float)se.sb_min[1] + (float)ty * 16.0f;
@@ -900,11 +822,11 @@ TH_D void film_tile_bounds(const DeviceSensor& se, int ty, int tx, float rx, flo
     by1 = jmin(__builtin_floorf(tby1 - 0.5f + ry) + 1.0f, se.crop_max[1]);
 }
 
-// k_film_gather for a BX x BY block of film pixels per thread.  k_film_gather is bound by re-reading every sample for each of
+// The gather for a BX x BY block of film pixels per thread.  A pixel per thread is bound by re-reading every sample for each of
 // the ~(2r+3)^2 film pixels in whose reach it lies; here a sample is loaded once per block and offered to all BX*BY pixels
 // (reach of the block: (BX + 2r + 2) x (BY + 2r + 2) sample pixels), and the filter index is computed once per row / column.
 // Per film pixel nothing changes: tiles in k order, sample pixels in Bounds2 order, samples in order, one csum per tile; a
-// tile or sample outside a pixel's own reach fails the same bounds tests as in k_film_gather and contributes nothing.
+// tile or sample outside a pixel's own reach fails that pixel's own bounds tests and contributes nothing.
 // SPP = MapSpp (a map frame): the records are laid out at max_spp and sample pixel pix offers its first counts[pix] samples only; the other records are never read.
 template <int BX, int BY, class SPP = uint32_t>
 __global__ __launch_bounds__(kBlock) void k_film_gather_block(const DeviceSensor* __restrict__ sep, const float* __restrict__ table, const float4* __restrict__ L,
@@ -925,7 +847,7 @@ __global__ __launch_bounds__(kBlock) void k_film_gather_block(const DeviceSensor
         float X[BX], Y[BY];
         for (int i = 0; i < BX; ++i) X[i] = se.crop_min[0] + (float)(fx0 + i);
         for (int j = 0; j < BY; ++j) Y[j] = se.crop_min[1] + (float)(fy0 + j);
-        // union of the pixels' reaches (k_film_gather: sx in (X - 1.5 - r, X + r + 0.5])
+        // union of the pixels' reaches (a pixel's: sx in (X - 1.5 - r, X + r + 0.5])
         int sx_lo = max((int)__builtin_floorf(X[0] - 1.5f - rx), se.sb_min[0]), sx_hi = min((int)__builtin_ceilf(X[BX - 1] + rx + 0.5f), se.sb_max[0]);
         int sy_lo = max((int)__builtin_floorf(Y[0] - 1.5f - ry), se.sb_min[1]), sy_hi = min((int)__builtin_ceilf(Y[BY - 1] + ry + 0.5f), se.sb_max[1]);
         f3 xyz[BY][BX];
@@ -1048,152 +970,7 @@ template <int TH_ONE_COPY = 0> __global__ __launch_bounds__(kBlock) void k_film_
     }
 }
 
-// ---- film gather from per-sample splat descriptors (film_block = 3, the default) ---------------------------------------------------
-// k_film_gather_block spends ~300 VALU instructions per (sample, thread): every thread that a sample can reach recomputes the sample's
-// pixel range (ceil / floor, film.jl:145-146) and, per pixel, the filter-table index (|x - dp| / r * 16, ceil for x, floor for y, clamp,
-// film.jl:149-153).  All of that depends on the sample alone, so k_film_descriptors computes it ONCE per sample — with the same Float32
-// operations — into 16 bytes: the first pixel column / row of the unclamped range (int16 each), the number of columns / rows (<= 8: filter
-// radius <= 3), and one 4-bit table index per column and per row.  The gather then reads {descriptor, radiance} and, per film pixel, does
-// two compares, two bit-field extracts, one LDS lookup and the three multiply-adds of add_sample! (film.jl:161-162) — in the same order
-// (tile k, sample pixel, sample): the film is bit-identical to k_film_gather's.
-struct SplatDesc {   // uint4
-    uint32_t origin;  // int16 p0x | int16 p0y << 16  = ceil(dp - r), unclamped (film.jl:145)
-    uint32_t count;   // nx | ny << 8               = floor(dp + r) + 1 - p0 + 1 (film.jl:146: the extra column / row of A.9 included)
-    uint32_t ox;      // 4 bits per column: clamp(ceil(|x - dpx| / rx * 16), 1, 16) - 1
-    uint32_t oy;      // 4 bits per row:    clamp(floor(|y - dpy| / ry * 16), 1, 16) - 1
-};
-template <int TH_ONE_COPY = 0> __global__ __launch_bounds__(kBlock) void k_film_descriptors(const DeviceSensor* __restrict__ sep, uint64_t n, uint64_t seed, uint32_t sample_offset, uint4* __restrict__ desc) {
-    const DeviceSensor& se = *sep;
-    const float rx = se.filter_radius[0], ry = se.filter_radius[1];
-    const float inv_rx = 1.0f / rx, inv_ry = 1.0f / ry;
-    for (uint64_t slot = (uint64_t)blockIdx.x * kBlock + threadIdx.x; slot < n; slot += (uint64_t)gridDim.x * kBlock) {
-        const SlotInfo si = slot_info(se, (uint32_t)slot);
-        const uint64_t key = ts_stream_key(seed, si.px, si.py, sample_offset + si.sample);
-        const float pfx = (float)si.px + ts_uniform(key, TS_DIM_FILM_X), pfy = (float)si.py + ts_uniform(key, TS_DIM_FILM_Y);  // camera_sample.film
-        const float dpx = pfx - 0.5f, dpy = pfy - 0.5f;
-        const float p0x = __builtin_ceilf(dpx - rx), p0y = __builtin_ceilf(dpy - ry);
-        const float p1x = __builtin_floorf(dpx + rx) + 1.0f, p1y = __builtin_floorf(dpy + ry) + 1.0f;
-        const int nx = (int)(p1x - p0x) + 1, ny = (int)(p1y - p0y) + 1;
-        uint32_t oxw = 0, oyw = 0;
-        for (int c = 0; c < 8; ++c) {
-            const float X = p0x + (float)c, Y = p0y + (float)c;
-            oxw |= (uint32_t)((int)jclamp(__builtin_ceilf(fabs_((X - dpx) * inv_rx * 16.0f)), 1.0f, 16.0f) - 1) << (4 * c);   // ceil for x …
-            oyw |= (uint32_t)((int)jclamp(__builtin_floorf(fabs_((Y - dpy) * inv_ry * 16.0f)), 1.0f, 16.0f) - 1) << (4 * c);  // … floor for y (A.9)
-        }
-        desc[slot] = make_uint4(((uint32_t)(int)p0x & 0xffffu) | ((uint32_t)(int)p0y << 16), (uint32_t)nx | ((uint32_t)ny << 8), oxw, oyw);
-    }
-}
-template <int BY>
-__global__ __launch_bounds__(kBlock) void k_film_gather_desc(const DeviceSensor* __restrict__ sep, const float* __restrict__ table, const float4* __restrict__ L,
-                                                             const uint4* __restrict__ desc, uint32_t spp, float4* __restrict__ out) {
-    const DeviceSensor& se = *sep;
-    __shared__ float s_table[256];
-    for (uint32_t t = threadIdx.x; t < 256u; t += kBlock) s_table[t] = table[t];
-    __syncthreads();
-    const uint32_t npix = (uint32_t)(se.sb_w * se.band_rows);
-    const float rx = se.filter_radius[0], ry = se.filter_radius[1];
-    const uint32_t nbx = (uint32_t)se.film_w, nby = ((uint32_t)se.film_h + BY - 1) / BY;
-    for (uint32_t bidx = blockIdx.x * kBlock + threadIdx.x; bidx < nbx * nby; bidx += gridDim.x * kBlock) {
-        const int fy0 = (int)(bidx / nbx) * BY, fx0 = (int)(bidx - (bidx / nbx) * nbx);
-        const float X = se.crop_min[0] + (float)fx0;
-        const int Xi = (int)X;
-        float Y[BY];
-        int Yi[BY];
-        for (int j = 0; j < BY; ++j) {
-            Y[j] = se.crop_min[1] + (float)(fy0 + j);
-            Yi[j] = (int)Y[j];
-        }
-        // union of the pixels' reaches (k_film_gather: sx in (X - 1.5 - r, X + r + 0.5])
-        const int sx_lo = max((int)__builtin_floorf(X - 1.5f - rx), se.sb_min[0]), sx_hi = min((int)__builtin_ceilf(X + rx + 0.5f), se.sb_max[0]);
-        const int sy_lo = max((int)__builtin_floorf(Y[0] - 1.5f - ry), se.sb_min[1]), sy_hi = min((int)__builtin_ceilf(Y[BY - 1] + ry + 0.5f), se.sb_max[1]);
-        f3 xyz[BY];
-        float wsum[BY];
-        for (int j = 0; j < BY; ++j) {
-            xyz[j] = splat3(0.0f);
-            wsum[j] = 0.0f;
-            if (se.accumulate && fy0 + j < se.film_h) {  // a later band: add onto the tiles of the bands before (k order)
-                const float4 prev = out[(size_t)(fy0 + j) * (size_t)se.film_w + (size_t)fx0];
-                xyz[j] = mk3(prev.x, prev.y, prev.z);
-                wsum[j] = prev.w;
-            }
-        }
-        if (sx_lo <= sx_hi && sy_lo <= sy_hi) {
-            const int ty_lo = max((sy_lo - se.sb_min[1]) >> 4, se.band_ty0), ty_hi = min((sy_hi - se.sb_min[1]) >> 4, se.band_ty1);
-            const int tx_lo = (sx_lo - se.sb_min[0]) >> 4, tx_hi = (sx_hi - se.sb_min[0]) >> 4;
-            for (int ty = ty_lo; ty <= ty_hi; ++ty)
-                for (int tx = tx_lo; tx <= tx_hi; ++tx) {
-                    float bx0, by0, bx1, by1;
-                    film_tile_bounds(se, ty, tx, rx, ry, bx0, by0, bx1, by1);
-                    const float tbx0 = (float)se.sb_min[0] + (float)tx * 16.0f, tby0 = (float)se.sb_min[1] + (float)ty * 16.0f;
-                    const float tbx1 = jmin(tbx0 + 15.0f, (float)se.sb_max[0]), tby1 = jmin(tby0 + 15.0f, (float)se.sb_max[1]);
-                    // merge_film_tile! touches the pixel (film.jl:182-193); add_sample! clamps its range to the tile's film bounds and to 1 (film.jl:147-148)
-                    const bool in_x = !(X < bx0 || X > bx1), ok_x = in_x && !(X < 1.0f);
-                    bool in_tile[BY], ok_y[BY];
-                    bool any_in = false;
-                    for (int j = 0; j < BY; ++j) {
-                        const bool in_y = !(Y[j] < by0 || Y[j] > by1);
-                        in_tile[j] = in_x && in_y;
-                        ok_y[j] = in_y && !(Y[j] < 1.0f);
-                        any_in = any_in || in_tile[j];
-                    }
-                    if (!any_in) continue;
-                    f3 csum[BY];
-                    float fws[BY];
-                    for (int j = 0; j < BY; ++j) {
-                        csum[j] = splat3(0.0f);
-                        fws[j] = 0.0f;
-                    }
-                    const int y0 = max(sy_lo, (int)tby0), y1 = min(sy_hi, (int)tby1);
-                    const int x0 = max(sx_lo, (int)tbx0), x1 = min(sx_hi, (int)tbx1);
-                    for (int sy = y0; sy <= y1; ++sy)
-                        for (int sx = x0; sx <= x1; ++sx) {
-                            const uint32_t pix = (uint32_t)(sy - se.band_y0) * (uint32_t)se.sb_w + (uint32_t)(sx - se.sb_min[0]);
-                            auto splat = [&](uint4 d, float4 l4) {
-                                const int cx = Xi - (int)(short)(d.x & 0xffffu);
-                                if (!(ok_x && (uint32_t)cx < (d.y & 0xffu))) return;
-                                f3 l = mk3(l4.x, l4.y, l4.z);
-                                if (has_nan(l)) l = splat3(0.0f);  // integrators/sampler.jl:46
-                                const uint32_t oxi = (d.z >> (4 * cx)) & 15u;
-                                const int p0y = (int)(short)(d.x >> 16);
-                                const uint32_t ny = (d.y >> 8) & 0xffu;
-                                for (int j = 0; j < BY; ++j) {
-                                    const int cy = Yi[j] - p0y;
-                                    if (ok_y[j] && (uint32_t)cy < ny) {
-                                        const float w = s_table[((d.w >> (4 * cy)) & 15u) * 16u + oxi];
-                                        csum[j] = csum[j] + l * w;   // contrib_sum += l * sample_weight (1) * w
-                                        fws[j] += w;
-                                    }
-                                }
-                            };
-                            constexpr uint32_t kU = 4;
-                            uint32_t s = 0;
-                            for (; s + kU <= spp; s += kU) {
-                                uint4 dv[kU];
-                                float4 lv[kU];
-#pragma unroll
-                                for (uint32_t u = 0; u < kU; ++u) {
-                                    const size_t at = (size_t)(s + u) * npix + pix;
-                                    dv[u] = desc[at];
-                                    lv[u] = L[at];
-                                }
-#pragma unroll
-                                for (uint32_t u = 0; u < kU; ++u) splat(dv[u], lv[u]);
-                            }
-                            for (; s < spp; ++s) splat(desc[(size_t)s * npix + pix], L[(size_t)s * npix + pix]);
-                        }
-                    for (int j = 0; j < BY; ++j)
-                        if (in_tile[j]) {
-                            xyz[j] = xyz[j] + rgb_to_xyz(csum[j]);
-                            wsum[j] += fws[j];
-                        }
-                }
-        }
-        for (int j = 0; j < BY; ++j)
-            if (fy0 + j < se.film_h) out[(size_t)(fy0 + j) * (size_t)se.film_w + (size_t)fx0] = make_float4(xyz[j].x, xyz[j].y, xyz[j].z, wsum[j]);
-    }
-}
-
-// ---- film gather from a 32-bit splat descriptor carried in the radiance record itself (film_block >= 4, the default for filter radii <= 1) --------------
+// ---- film gather from a 32-bit splat descriptor carried in the radiance record itself (the packed pass: both filter radii in (0, 1]) --------------------
 // Counters of round 2 (profiles/r2): k_film_gather_block<1,4> moves 139 GB per 1024^2 x 256 spp frame (2 x FETCH_SIZE, coalesced 16 B / lane loads) in 24 ms:
 // 5.8 TB/s — it is bound by HBM, by RE-READS: every sample (16 B radiance + 8 B film position) is fetched by each of the ~10 threads whose pixels it can
 // reach, at re-read distances no cache covers, for 6.5 GB of distinct data.  Two levers, both taken here:
@@ -1206,7 +983,9 @@ __global__ __launch_bounds__(kBlock) void k_film_gather_desc(const DeviceSensor*
 //     large blocks slower before — ~300 VALU instructions per (sample, thread) recomputing ceil / floor ranges and table indices for every pixel — is gone:
 //     decode, two unsigned compares and a bit-field extract per column / row, one LDS lookup and the multiply-adds of add_sample! per pixel.
 // Per film pixel nothing changes: tiles in k order, sample pixels in Bounds2 order, samples in order, one csum per tile (film.jl:134-193); the arithmetic of
-// the descriptor is k_film_descriptors' (bit-identical to the reference's per-pixel computation: tests/test_gpu_parity.py, tools/soak_film.py).
+// the descriptor is film_splat_desc's (bit-identical to the reference's per-pixel computation: tests/test_gpu_parity.py, tools/soak_film.py).
+// Block shapes measured at 1024^2 x 256 spp: 2 x 4 17.1 ms, 1 x 4 19.0, 4 x 4 24.2, 2 x 2 25.9, 4 x 2 30.8, 8 x 4 40.4, 1 x 8 17.1, 1 x 2 22.5, 1 x 1 33.7, against 25.0 for
+// the wide pass's k_film_gather_block<1, 4>: only <2, 4> is instantiated (the others were options of 42228bf).
 // A sample whose range is 4 wide (or otherwise outside the encoding) keeps its full 16-byte descriptor in a side table: .w = kFilmPackSide | index.  The table
 // holds total / 16 + 65536 entries (the rate is ~2.4e-4 at 1024^2); should it ever run full the word is kFilmPackOverflow and the gather recomputes that
 // sample's descriptor from the sampler — in a cold copy of the loop, so that the hash and the descriptor arithmetic are not inlined into the unrolled hot one.
@@ -1260,9 +1039,9 @@ __global__ __launch_bounds__(kBlock) void k_film_gather_packed(const DeviceSenso
     const size_t sstride = layout ? (size_t)64 : (size_t)npix;  // records between consecutive samples of one sample pixel (film_index)
     const float rx = se.filter_radius[0], ry = se.filter_radius[1];
     const uint32_t nbx = ((uint32_t)se.film_w + BX - 1) / BX, nby = ((uint32_t)se.film_h + BY - 1) / BY;
-    // option "film_swizzle" (A/B, off): workgroup ids are dealt to the 8 XCDs round-robin; with it XCD x gets the x-th contiguous eighth of the grid, so that vertically
-    // adjacent strips share an L2.  Measured (profiles/r4): no fewer bytes leave L2 — a strip re-reads its neighbour's 3 halo rows ~4 row passes (hundreds of MB of
-    // streaming per XCD) after the neighbour did, far beyond what the 4 MB L2 holds.
+    // xcd_bands is 0 in every launch (its option, "film_swizzle", is gone with 42228bf's other film variants): workgroup ids are dealt to the 8 XCDs round-robin; with it
+    // XCD x got the x-th contiguous eighth of the grid, so that vertically adjacent strips share an L2.  Measured (profiles/r4): no fewer bytes leave L2 — a strip re-reads
+    // its neighbour's 3 halo rows ~4 row passes (hundreds of MB of streaming per XCD) after the neighbour did, far beyond what the 4 MB L2 holds.
     const uint32_t vblock = (xcd_bands && gridDim.x % 8u == 0u) ? (blockIdx.x % 8u) * (gridDim.x / 8u) + blockIdx.x / 8u : blockIdx.x;
     for (uint32_t bidx = vblock * kBlock + threadIdx.x; bidx < nbx * nby; bidx += gridDim.x * kBlock) {
         const int fy0 = (int)(bidx / nbx) * BY, fx0 = (int)(bidx - (bidx / nbx) * nbx) * BX;
@@ -1463,139 +1242,6 @@ __global__ __launch_bounds__(kBlock) void k_film_gather_packed(const DeviceSenso
         for (int j = 0; j < BY; ++j)
             for (int i = 0; i < BX; ++i)
                 if (fx0 + i < se.film_w && fy0 + j < se.film_h) out[(size_t)(fy0 + j) * (size_t)se.film_w + (size_t)(fx0 + i)] = make_float4(xyz[j][i].x, xyz[j][i].y, xyz[j][i].z, wsum[j][i]);
-    }
-}
-
-// k_film_gather with the samples staged through LDS: one block = a 16x16 film tile; for every sample row (ascending) the
-// block stages `cols` sample columns x `ns` samples {p_film, L} once (instead of each of the ~16 film pixels a sample
-// reaches re-reading them from HBM/MALL), then the film pixels in reach accumulate from LDS.  The summation order per film
-// pixel is unchanged: one accumulator per sample tile (at most 2x2 reach a pixel), inside a tile rows ascending, columns
-// ascending, samples ascending; tiles merged in k order (film.jl:182-193).  LDS layout: five planes [s][col], so the lanes
-// of a wave (different columns, same s) read consecutive banks and equal columns broadcast.
-template <int TH_ONE_COPY = 0> __global__ __launch_bounds__(kBlock) void k_film_gather_tiled(const DeviceSensor* __restrict__ sep, const float* __restrict__ table, const float4* __restrict__ L,
-                                                              const float2* __restrict__ pfilm, uint32_t spp, uint32_t layout, uint32_t cols, uint32_t ns_stage, float4* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) float s_planes[];
-    __shared__ float s_table[256];
-    const DeviceSensor& se = *sep;
-    const uint32_t npix = (uint32_t)(se.sb_w * se.sb_h);
-    const float rx = se.filter_radius[0], ry = se.filter_radius[1];
-    const float inv_rx = 1.0f / rx, inv_ry = 1.0f / ry;
-    const int tid = (int)threadIdx.x, ltx = tid & 15, lty = tid >> 4;
-    s_table[tid] = table[tid];  // Film.filter_table (16 x 16), kBlock == 256
-    const int fx = (int)blockIdx.x * 16 + ltx, fy = (int)blockIdx.y * 16 + lty;
-    const bool in_film = fx < se.film_w && fy < se.film_h;
-    const float X = se.crop_min[0] + (float)fx, Y = se.crop_min[1] + (float)fy;
-    // this pixel's reach (same arithmetic as k_film_gather)
-    int sx_lo = max((int)__builtin_floorf(X - 1.5f - rx), se.sb_min[0]), sx_hi = min((int)__builtin_ceilf(X + rx + 0.5f), se.sb_max[0]);
-    int sy_lo = max((int)__builtin_floorf(Y - 1.5f - ry), se.sb_min[1]), sy_hi = min((int)__builtin_ceilf(Y + ry + 0.5f), se.sb_max[1]);
-    const int ty_lo = (sy_lo - se.sb_min[1]) >> 4, tx_lo = (sx_lo - se.sb_min[0]) >> 4;
-    // block-wide reach
-    const float Xb0 = se.crop_min[0] + (float)(blockIdx.x * 16), Yb0 = se.crop_min[1] + (float)(blockIdx.y * 16);
-    const float Xb1 = jmin(Xb0 + 15.0f, se.crop_max[0]), Yb1 = jmin(Yb0 + 15.0f, se.crop_max[1]);
-    const int SX0 = max((int)__builtin_floorf(Xb0 - 1.5f - rx), se.sb_min[0]), SX1 = min((int)__builtin_ceilf(Xb1 + rx + 0.5f), se.sb_max[0]);
-    const int SY0 = max((int)__builtin_floorf(Yb0 - 1.5f - ry), se.sb_min[1]), SY1 = min((int)__builtin_ceilf(Yb1 + ry + 0.5f), se.sb_max[1]);
-    const int NC = SX1 - SX0 + 1;
-    float* p_fx = s_planes;
-    float* p_fy = p_fx + (size_t)cols * ns_stage;
-    float* p_r = p_fy + (size_t)cols * ns_stage;
-    float* p_g = p_r + (size_t)cols * ns_stage;
-    float* p_b = p_g + (size_t)cols * ns_stage;
-    // accumulators of the (up to) 2 x 2 sample tiles that reach this pixel: [tile row][tile column]
-    f3 c00 = splat3(0.0f), c01 = c00, c10 = c00, c11 = c00;
-    float w00 = 0.0f, w01 = 0.0f, w10 = 0.0f, w11 = 0.0f;
-    for (int sy = SY0; sy <= SY1; ++sy) {
-        for (int c0 = 0; c0 < NC; c0 += (int)cols) {
-            const int ncol = min((int)cols, NC - c0);
-            for (uint32_t s0 = 0; s0 < spp; s0 += ns_stage) {
-                const uint32_t nsn = min(ns_stage, spp - s0);
-                // ---- stage ----
-                for (uint32_t e = (uint32_t)tid; e < (uint32_t)ncol * nsn; e += kBlock) {
-                    const uint32_t c = e % (uint32_t)ncol, sl = e / (uint32_t)ncol;
-                    const uint32_t pix = (uint32_t)(sy - se.sb_min[1]) * (uint32_t)se.sb_w + (uint32_t)(SX0 + c0 + (int)c - se.sb_min[0]);
-                    const size_t idx = film_index(layout, npix, spp, s0 + sl, pix);
-                    const float2 pf = pfilm[idx];
-                    const float4 l4 = L[idx];
-                    f3 l = mk3(l4.x, l4.y, l4.z);
-                    if (has_nan(l)) l = splat3(0.0f);  // integrators/sampler.jl:46
-                    const uint32_t a = sl * cols + c;
-                    p_fx[a] = pf.x;
-                    p_fy[a] = pf.y;
-                    p_r[a] = l.x;
-                    p_g[a] = l.y;
-                    p_b[a] = l.z;
-                }
-                __syncthreads();
-                // ---- accumulate ----
-                if (in_film && sy >= sy_lo && sy <= sy_hi) {
-                    const int xa = max(sx_lo, SX0 + c0), xb = min(sx_hi, SX0 + c0 + ncol - 1);
-                    const int tyi = ((sy - se.sb_min[1]) >> 4) - ty_lo;
-                    for (int sx = xa; sx <= xb; ++sx) {
-                        const int txi = ((sx - se.sb_min[0]) >> 4) - tx_lo;
-                        float bx0, by0, bx1, by1;
-                        film_tile_bounds(se, tyi + ty_lo, txi + tx_lo, rx, ry, bx0, by0, bx1, by1);
-                        if (X < bx0 || X > bx1 || Y < by0 || Y > by1) continue;  // pixel not in this FilmTile
-                        const bool r1 = tyi != 0, q1 = txi != 0;
-                        f3 csum = r1 ? (q1 ? c11 : c10) : (q1 ? c01 : c00);
-                        float fws = r1 ? (q1 ? w11 : w10) : (q1 ? w01 : w00);
-                        const uint32_t c = (uint32_t)(sx - SX0 - c0);
-                        const float lim_x0 = jmax(bx0, 1.0f), lim_y0 = jmax(by0, 1.0f);
-#pragma unroll 4
-                        for (uint32_t sl = 0; sl < nsn; ++sl) {  // branch-free body: the four unrolled iterations' LDS reads overlap
-                            const uint32_t a = sl * cols + c;
-                            const float dpx = p_fx[a] - 0.5f, dpy = p_fy[a] - 0.5f;
-                            const f3 lrgb = mk3(p_r[a], p_g[a], p_b[a]);
-                            const float p0x = jmax(__builtin_ceilf(dpx - rx), lim_x0), p0y = jmax(__builtin_ceilf(dpy - ry), lim_y0);
-                            const float p1x = jmin(__builtin_floorf(dpx + rx) + 1.0f, bx1), p1y = jmin(__builtin_floorf(dpy + ry) + 1.0f, by1);
-                            const bool reach = !(X < p0x || X > p1x || Y < p0y || Y > p1y);
-                            const float ffx = fabs_((X - dpx) * inv_rx * 16.0f), ffy = fabs_((Y - dpy) * inv_ry * 16.0f);
-                            const int ox = (int)jclamp(__builtin_ceilf(ffx), 1.0f, 16.0f);
-                            const int oy = (int)jclamp(__builtin_floorf(ffy), 1.0f, 16.0f);
-                            const float w = s_table[(oy - 1) * 16 + (ox - 1)];
-                            const f3 cnew = csum + lrgb * 1.0f * w;
-                            const float wnew = fws + w;
-                            csum = reach ? cnew : csum;
-                            fws = reach ? wnew : fws;
-                        }
-                        if (r1) {
-                            if (q1) {
-                                c11 = csum;
-                                w11 = fws;
-                            } else {
-                                c10 = csum;
-                                w10 = fws;
-                            }
-                        } else {
-                            if (q1) {
-                                c01 = csum;
-                                w01 = fws;
-                            } else {
-                                c00 = csum;
-                                w00 = fws;
-                            }
-                        }
-                    }
-                }
-                __syncthreads();
-            }
-        }
-    }
-    if (in_film) {
-        // merge_film_tile! in k order: tile rows ascending, tile columns ascending; a tile whose FilmTile does not contain the
-        // pixel never touched it (its accumulator is still zero and is skipped, as the reference's merge loop skips the pixel)
-        f3 xyz = splat3(0.0f);
-        float wsum = 0.0f;
-        const int ty_hi = (sy_hi - se.sb_min[1]) >> 4, tx_hi = (sx_hi - se.sb_min[0]) >> 4;
-        if (sx_lo <= sx_hi && sy_lo <= sy_hi)
-            for (int ty = ty_lo; ty <= ty_hi; ++ty)
-                for (int tx = tx_lo; tx <= tx_hi; ++tx) {
-                    float bx0, by0, bx1, by1;
-                    film_tile_bounds(se, ty, tx, rx, ry, bx0, by0, bx1, by1);
-                    if (X < bx0 || X > bx1 || Y < by0 || Y > by1) continue;
-                    const bool r1 = ty != ty_lo, q1 = tx != tx_lo;
-                    xyz = xyz + rgb_to_xyz(r1 ? (q1 ? c11 : c10) : (q1 ? c01 : c00));
-                    wsum += r1 ? (q1 ? w11 : w10) : (q1 ? w01 : w00);
-                }
-        out[(size_t)fy * se.film_w + fx] = make_float4(xyz.x, xyz.y, xyz.z, wsum);
     }
 }
 

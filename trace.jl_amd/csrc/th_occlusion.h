@@ -46,7 +46,7 @@ inline int occlusion_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip
     if (int rc = ensure(ctx, ctx->ao_tmax, Pphys * sizeof(float))) return rc;
     ctx->last = LastRecords{};  // (until this frame's radiance is complete)
     if (int rc = ensure(ctx, ctx->Lbuf, total_slots * sizeof(float4))) return rc;
-    if (int rc = ensure_film_samples(ctx, ds, total_slots)) return rc;
+    if (int rc = ensure_film_samples(ctx, film_packed(ds), total_slots)) return rc;
     void* d_film;
     if (int rc = stage_output(ctx, out, out_is_device, film_bytes, &d_film)) return rc;
     hipStream_t st = ctx->stream;

@@ -24,7 +24,6 @@ struct Options {
                            // the tree Trace.jl builds, hence its tie-breaks), -1 = automatic: builder 3 from 64 Ki primitives on, builder 0 below and
                            // for the scenes builder 3 hands back.  Measured (r3): building the tree 18 ms (1 M triangles) / 53 ms (10 M) on the device
                            // against ~0.17 s / ~1.5 s on the host, commit 0.39 -> 0.26 s and 3.67 -> 2.37 s; the LBVH builds a 25-35 % costlier tree
-    bool film_transpose = false;     // film pass on pixel-group-major copies of p_film / L (option "film_transpose"; launch_film)
     bool occluder_pretest = true;    // any-hit rays test the scene's largest triangles before the walk (option "occluder_pretest")
     int stream2_priority = -1;       // shadow-ray stream: 1 highest priority, -1 lowest, 0 the default level (option "stream2_priority", read when the streams are created)
     bool leaf_kernel = true;         // one-leaf scenes run k_trace_leaf instead of k_trace2 (option "leaf_kernel", for A/B)
@@ -32,20 +31,12 @@ struct Options {
                                      // (th_trace2.h, slab_test2); 0 = the reference's loose test alone (its exact visit set)
     int band_tile_rows = 0;          // DIAGNOSTIC / tests: render frames in bands of this many tile rows (0 = one band unless the samples do not fit in HBM)
     uint32_t tiny_scene_prims = 16;  // scenes of at most this many primitives get a single-leaf BVH (th_bvh.h); 0 = always build the hierarchy
-    int film_block = 5;  // film gather: >= 4 (filter radius <= 1; wider filters run 2): from a 32-bit splat descriptor in the radiance record's .w lane, a thread owning
-                         // 4: 1 x 4, 5 (default): 2 x 4, 6: 4 x 4, 7: 2 x 2, 8: 4 x 2, 9: 8 x 4, 10: 1 x 8, 11: 1 x 16, 12: 1 x 2, 13: 1 x 1 film pixels (th_kernels.h,
-                         // k_film_gather_packed; measured at 1024^2 x 256 spp: 19.0 / 17.1 / 24.2 / 25.9 / 30.8 / 40.4 / 17.1 / - / 22.5 / 33.7 ms against 25.0 for 2);
-                         // 0 = one film pixel per thread, 1 = 2 x 2 pixels per thread, 2 = TH_FILM_BX x TH_FILM_BY = 1 x 4, all three recomputing a
-                         // sample's pixel range and table indices per thread; 3 = 1 x 4 from per-sample splat descriptors (k_film_descriptors): measured SLOWER
-                         // (1024^2, 256 spp: 29.0 ms against 24.3 ms: the 16-byte descriptor doubles the gather's loads and the arithmetic it saves was hidden)
     bool film_relayout = true;  // packed film pass: gather from a pixel-group-major copy of the radiance records (k_film_pack_transpose) instead of the integrators' sample-major order
     int any_on_accelerator = -1;  // hybrid mode: any-hit rays without a zero direction component walk the library's tree (TraceOut::zero_mode): 1 always, 0 never, -1 where the
                                   // integrator asks for it (TraceOut::any_acc_hint: SPPM).  Option "any_on_accelerator"
     bool wide4 = true;  // hybrid mode: the accelerator is also laid out four children wide and the certified walk runs on that (th_trace3c4.h); option "wide4", read at commit and at launch
     bool leaf_queue = false;  // hybrid mode: the certified walk queues the leaves it reaches and tests them 64 at a time with whichever lanes (th_trace3d.h, option "leaf_queue")
     int node_layout = 0;  // children-in-parent nodes: 0 depth-first, 1 the two interior children of a node in one aligned 128-byte line (option "node_layout", read at commit; tu_scene.hip)
-    bool film_swizzle = false;  // packed film gather: XCD x owns the x-th contiguous eighth of the workgroups (option "film_swizzle"; measured: no effect, th_kernels.h)
-    bool film_tiled = false;  // LDS-staged film gather (k_film_gather_tiled): bit-identical, measured 2.7x SLOWER than k_film_gather (11 % lane use), kept as an option
     bool overlap = true;   // shadow rays of depth d on a second stream beside the closest-hit rays of depth d+1 (option "overlap").  On again since round 5: with the four-wide
                            // certified walk no longer saturating VALU issue the shadow kernels fill its gaps and tails — 256 spp, off / on: S-mesh 325.5 / 314.5 ms, S-blob 234.8 / 222.3,
                            // S-cornell 160.4 / 157.1, 10.5 M triangles 376.4 / 367.7.  (Rounds 2-4 measured it neutral — S-cornell 158.2 / 157.9, S-mesh 399 / 393 — and kept it off.)
@@ -111,7 +102,6 @@ inline const OptionRow kOptionRows[] = {
     {"sppm_batch", OptionRule::Clamp, at<&Options::sppm_batch>(), 0, kOptionNoMax},
     {"bvh_builder", OptionRule::Clamp, at<&Options::bvh_builder>(), -1, 4, nullptr, 1u << 1, "bvh_builder = 1 (the linear BVH)"},
     {"hybrid", OptionRule::Flag, at<&Options::hybrid>()},
-    {"film_transpose", OptionRule::Flag, at<&Options::film_transpose>()},
     {"band_tile_rows", OptionRule::Clamp, at<&Options::band_tile_rows>(), 0, kOptionNoMax},
     {"compose_spheres", OptionRule::Tri, at<&Options::compose_spheres>()},
     {"occluder_pretest", OptionRule::Flag, at<&Options::occluder_pretest>()},
@@ -123,14 +113,11 @@ inline const OptionRow kOptionRows[] = {
     {"leaf_kernel", OptionRule::Flag, at<&Options::leaf_kernel>()},
     {"slab_margin_log2", OptionRule::Clamp, at<&Options::slab_margin_log2>(), 0, 20},
     {"tiny_scene_prims", OptionRule::Clamp, at<&Options::tiny_scene_prims>(), 0, 255},
-    {"film_block", OptionRule::Clamp, at<&Options::film_block>(), 0, 13},
     {"film_relayout", OptionRule::Flag, at<&Options::film_relayout>()},
     {"any_on_accelerator", OptionRule::Tri, at<&Options::any_on_accelerator>()},
     {"leaf_queue", OptionRule::Flag, at<&Options::leaf_queue>(), 0, 0, nullptr, 1u << 1, "leaf_queue"},
     {"wide4", OptionRule::Flag, at<&Options::wide4>()},
     {"node_layout", OptionRule::Range, at<&Options::node_layout>(), 0, 1, "node_layout: 0 (depth-first) or 1 (sibling pairs per 128-byte line)"},
-    {"film_swizzle", OptionRule::Flag, at<&Options::film_swizzle>()},
-    {"film_tiled", OptionRule::Flag, at<&Options::film_tiled>()},
     {"denoise_lds", OptionRule::Mask3, at<&Options::denoise_lds>()},
     {"temporal_patch", OptionRule::Flag, at<&Options::temporal_patch>()},
     {"denoise_var_lds", OptionRule::Mask3, at<&Options::denoise_var_lds>()},

@@ -32,34 +32,21 @@ void derive_sensor(const trhip_sensor* sn, DeviceSensor& d) {
     d.accumulate = 0;
 }
 
-// Film accumulation: positions, then the LDS-tiled gather (falls back to the per-pixel gather when a 16x16 film tile is reached
-// by more than two sample tiles per axis, i.e. very wide filters).
-#ifndef TH_FILM_BX
-#define TH_FILM_BX 1  // film_block = 2; measured at 1024^2, 256 spp, 4 samples in flight per thread: 1x1 67 ms, 2x2 40, 1x4 32, 1x6 47, 1x8 42, 2x4 39
-#define TH_FILM_BY 4
-#endif
-// film_block = 3: the gather reads one 16-byte splat descriptor per sample (k_film_descriptors) instead of recomputing the sample's pixel range
-// and table indices in every thread it reaches; needs a filter radius <= 3 (<= 8 columns / rows per sample)
-bool film_uses_desc(const trhip_ctx* ctx, const DeviceSensor& ds) {
-    return ctx->opt.film_block == 3 && !ctx->opt.film_tiled && !ctx->opt.film_transpose && std::fmax(ds.filter_radius[0], ds.filter_radius[1]) <= 3.0f && ds.film_w < 32000 && ds.film_h < 32000;
-}
-// film_block >= 4: the gather reads a 32-bit descriptor from the .w lane of the radiance records (k_film_pack_w / k_film_gather_packed); needs a filter radius <= 1
-// (<= 4 columns / rows per sample) — every scene of the reference uses LanczosSincFilter(Point2f(1f0), 3f0)
-bool film_uses_packed(const trhip_ctx* ctx, const DeviceSensor& ds) {
-    return ctx->opt.film_block >= 4 && !ctx->opt.film_tiled && !ctx->opt.film_transpose && std::fmax(ds.filter_radius[0], ds.filter_radius[1]) <= 1.0f && ds.filter_radius[0] > 0.0f && ds.filter_radius[1] > 0.0f;
-}
-// the per-sample buffer the film pass needs next to the radiance: nothing (packed), descriptors (16 B) or film positions (8 B)
-int ensure_film_samples(trhip_ctx* ctx, const DeviceSensor& ds, uint64_t total_slots) {
-    if (film_uses_packed(ctx, ds)) return 0;
-    if (film_uses_desc(ctx, ds)) return ensure(ctx, ctx->fdesc, total_slots * sizeof(uint4));
-    return ensure(ctx, ctx->pfilm, total_slots * sizeof(float2));
-}
-// can k_raygen write the radiance records in the film pass's layout, descriptors included (th_kernels.h, k_raygen's Lf)?  Whole sample passes of one band, 32-bit indices.
-bool film_fused(const trhip_ctx* ctx, const DeviceSensor& ds, uint32_t spp) {
-    const uint64_t npix_b = (uint64_t)ds.sb_w * ds.band_rows;
-    return ctx->opt.film_fused && ctx->opt.film_relayout && film_uses_packed(ctx, ds) && ((npix_b + 63u) / 64u) * 64u * spp < (1ull << 32);
-}
-FilmSideTable film_side_table(trhip_ctx* ctx, hipStream_t st, uint64_t total_slots, bool* ok) {
+// ---- the film pass (th_kernels.h "film") ----
+// Two passes, and the filter alone chooses.  Packed, both radii in (0, 1] — every scene of the reference uses LanczosSincFilter(Point2f(1f0), 3f0) —: a sample reaches <= 4
+// columns / rows, its 30-bit splat descriptor rides in the .w lane of its radiance record, and a thread gathers 2 x 4 film pixels.  Wide, anything else: film positions
+// beside sample-major records and the 1 x 4 block gather.
+bool film_packed(const DeviceSensor& ds) { return std::fmax(ds.filter_radius[0], ds.filter_radius[1]) <= 1.0f && ds.filter_radius[0] > 0.0f && ds.filter_radius[1] > 0.0f; }
+// what the film pass reads per camera sample: the 16-byte radiance record, and the wide pass its film position (8 B)
+static double film_sample_bytes(bool packed) { return packed ? 16.0 : 24.0; }
+int ensure_film_samples(trhip_ctx* ctx, bool packed, uint64_t total_slots) { return packed ? 0 : ensure(ctx, ctx->pfilm, total_slots * sizeof(float2)); }
+// pixel-group-major records (th_kernels.h, film_index layout 1) of one band: whole groups of 64 sample pixels
+static uint64_t film_padded_slots(const DeviceSensor& ds, uint32_t spp) { return (((uint64_t)ds.sb_w * ds.band_rows + 63u) / 64u) * 64u * spp; }
+// can k_raygen write the radiance records in the packed pass's layout, descriptors included (th_kernels.h, k_raygen's Lf)?  Whole sample passes of one band, 32-bit indices.
+// A map frame asks this alone: it is fused or wide, whatever the two options say.
+static bool film_fusable(const DeviceSensor& ds, uint32_t spp) { return film_packed(ds) && film_padded_slots(ds, spp) < (1ull << 32); }
+static bool film_fused(const trhip_ctx* ctx, const DeviceSensor& ds, uint32_t spp) { return ctx->opt.film_fused && ctx->opt.film_relayout && film_fusable(ds, spp); }
+static FilmSideTable film_side_table(trhip_ctx* ctx, hipStream_t st, uint64_t total_slots, bool* ok) {
     // side table for the descriptors that do not fit 30 bits (one sample in ~4000 at 1024^2): entry 0 of film_side is the counter, the descriptors follow
     const uint32_t side_cap = (uint32_t)std::min<uint64_t>(total_slots / 16 + 65536, 0x7ffffff0ull);
     *ok = ensure(ctx, ctx->film_side, ((size_t)side_cap + 1) * sizeof(uint4)) == 0;
@@ -67,116 +54,49 @@ FilmSideTable film_side_table(trhip_ctx* ctx, hipStream_t st, uint64_t total_slo
     (void)hipMemsetAsync(ctx->film_side.p, 0, sizeof(uint4), st);
     return FilmSideTable{(uint4*)ctx->film_side.p + 1, (uint32_t*)ctx->film_side.p, side_cap};
 }
+// `fused`: k_raygen wrote the records re-laid and with their descriptors (its side table is ctx->film_side, reset before the frame's first launch).  `map`: a map frame
+// (trhip_render_path_map) — `spp` is its max_spp, which lays the records out; the gather stops at counts[pix], and only the drawn samples have a film position.
 void launch_film(trhip_ctx* ctx, hipStream_t st, const DeviceSensor& ds, const DeviceSensor* dsp, const float4* L, uint64_t total_slots, uint32_t spp, uint64_t seed, uint32_t sample_offset,
-                 float4* d_film, bool fused) {
-    if (film_uses_packed(ctx, ds)) {
+                 float4* d_film, bool fused, const MapFrame* map) {
+    const float* tb = (const float*)ctx->table.p;
+    const bool packed = fused || (!map && film_packed(ds));
+    uint32_t layout = 0;  // of L: sample-major, or 1 = pixel-group-major
+    if (fused) {
+        layout = 1;
+    } else if (packed) {
         // the descriptors go into the records' .w lanes — on the way into a pixel-group-major copy when there is room for one (option "film_relayout", default on)
+        bool ok = false;
+        const FilmSideTable side = film_side_table(ctx, st, total_slots, &ok);
+        if (!ok) return;
         const uint32_t npix_b = (uint32_t)(ds.sb_w * ds.band_rows);
-        const uint64_t padded = (uint64_t)((npix_b + 63u) / 64u) * 64u * spp;
-        uint32_t layout = 0;
-        FilmSideTable side{ctx->film_side.p ? (uint4*)ctx->film_side.p + 1 : nullptr, (uint32_t*)ctx->film_side.p, 0};
-        if (fused) {
-            layout = 1;  // k_raygen wrote the records re-laid and with their descriptors (its side table is ctx->film_side, reset before the frame's first launch)
-        } else {
-            bool ok = false;
-            side = film_side_table(ctx, st, total_slots, &ok);
-            if (!ok) return;
-        }
-        if (fused) {
-        } else if (ctx->opt.film_relayout && total_slots == (uint64_t)npix_b * spp && ensure(ctx, ctx->film_Lt, padded * sizeof(float4)) == 0) {
+        const uint64_t padded = film_padded_slots(ds, spp);
+        if (ctx->opt.film_relayout && total_slots == (uint64_t)npix_b * spp && ensure(ctx, ctx->film_Lt, padded * sizeof(float4)) == 0) {
             layout = 1;
             hipLaunchKernelGGL(k_film_pack_transpose, dim3(grid_for(ctx, padded, 8)), dim3(kBlock), 0, st, dsp, npix_b, spp, seed, sample_offset, L, (float4*)ctx->film_Lt.p, side);
             L = (const float4*)ctx->film_Lt.p;
         } else {
             hipLaunchKernelGGL(k_film_pack_w, dim3(grid_for(ctx, total_slots, 8)), dim3(kBlock), 0, st, dsp, total_slots, seed, sample_offset, const_cast<float4*>(L), side);
         }
-        const float* tb = (const float*)ctx->table.p;
-        auto threads = [&](int bx, int by) { return (uint64_t)((ds.film_w + bx - 1) / bx) * (uint64_t)((ds.film_h + by - 1) / by); };
-#define TH_FILM_PACKED(BXV, BYV) hipLaunchKernelGGL((k_film_gather_packed<BXV, BYV>), dim3(grid_for(ctx, threads(BXV, BYV), 8)), dim3(kBlock), 0, st, dsp, tb, L, spp, seed, sample_offset, layout, (const uint4*)side.desc, d_film, ctx->opt.film_swizzle ? 1u : 0u)
-        switch (ctx->opt.film_block) {
-        case 4: TH_FILM_PACKED(1, 4); break;
-        case 7: TH_FILM_PACKED(2, 2); break;
-        case 8: TH_FILM_PACKED(4, 2); break;
-        case 9: TH_FILM_PACKED(8, 4); break;
-        case 10: TH_FILM_PACKED(1, 8); break;
-        case 11: TH_FILM_PACKED(1, 16); break;
-        case 12: TH_FILM_PACKED(1, 2); break;
-        case 13: TH_FILM_PACKED(1, 1); break;
-        case 6: TH_FILM_PACKED(4, 4); break;
-        default: TH_FILM_PACKED(2, 4); break;  // 5
+    } else if (map) {
+        hipLaunchKernelGGL(k_film_positions_map, dim3(grid_for(ctx, map->total, 8)), dim3(kBlock), 0, st, dsp, map->jobs, map->total, seed, sample_offset, (float2*)ctx->pfilm.p);
+    } else {  // (layout 0: k_film_positions still takes a layout, and spp to index the other one)
+        hipLaunchKernelGGL(k_film_positions, dim3(grid_for(ctx, total_slots, 8)), dim3(kBlock), 0, st, dsp, total_slots, seed, sample_offset, (float2*)ctx->pfilm.p, 0u, spp);
+    }
+    const uint4* side_desc = ctx->film_side.p ? (const uint4*)ctx->film_side.p + 1 : nullptr;
+    auto gather = [&](auto spp_arg) {  // the frame's spp, or a map frame's MapSpp
+        using SPP = decltype(spp_arg);
+        if (packed) {  // (xcd_bands 0: the kernel's workgroup swizzle lost its option)
+            const uint64_t threads = (uint64_t)((ds.film_w + 1) / 2) * (uint64_t)((ds.film_h + 3) / 4);
+            hipLaunchKernelGGL((k_film_gather_packed<2, 4, SPP>), dim3(grid_for(ctx, threads, 8)), dim3(kBlock), 0, st, dsp, tb, L, spp_arg, seed, sample_offset, layout, side_desc, d_film, 0u);
+        } else {  // (layout 0: the block gather reads sample-major records and positions alone)
+            const uint64_t threads = (uint64_t)ds.film_w * (uint64_t)((ds.film_h + 3) / 4);
+            hipLaunchKernelGGL((k_film_gather_block<1, 4, SPP>), dim3(grid_for(ctx, threads, 8)), dim3(kBlock), 0, st, dsp, tb, L, (const float2*)ctx->pfilm.p, spp_arg, 0u, d_film);
         }
-#undef TH_FILM_PACKED
-        return;
-    }
-    if (film_uses_desc(ctx, ds) && ctx->fdesc.bytes >= total_slots * sizeof(uint4)) {
-        hipLaunchKernelGGL(k_film_descriptors, dim3(grid_for(ctx, total_slots, 8)), dim3(kBlock), 0, st, dsp, total_slots, seed, sample_offset, (uint4*)ctx->fdesc.p);
-        const uint64_t nthreads = (uint64_t)ds.film_w * ((ds.film_h + 3) / 4);
-        hipLaunchKernelGGL((k_film_gather_desc<4>), dim3(grid_for(ctx, nthreads, 8)), dim3(kBlock), 0, st, dsp, (const float*)ctx->table.p, L, (const uint4*)ctx->fdesc.p, spp, d_film);
-        return;
-    }
-    // pixel-group-major inputs for the gather (th_kernels.h, film_index): p_film is written that way, L is re-laid into a second buffer
-    // (the frame's radiance, 16 B per sample, once more); without room for it the gather reads the sample-major arrays as before
-    const uint32_t npix = (uint32_t)(ds.sb_w * ds.band_rows);
-    const uint64_t padded = (uint64_t)((npix + 63u) / 64u) * 64u * spp;
-    uint32_t layout = 0;
-    const bool whole = ds.band_rows == ds.sb_h;
-    if (whole && ctx->opt.film_transpose && spp > 1 && total_slots == (uint64_t)npix * spp && ensure(ctx, ctx->pfilm, padded * sizeof(float2)) == 0 && ensure(ctx, ctx->film_Lt, padded * sizeof(float4)) == 0) {
-        layout = 1;
-        hipLaunchKernelGGL(k_film_transpose, dim3(grid_for(ctx, padded, 8)), dim3(kBlock), 0, st, L, npix, spp, (float4*)ctx->film_Lt.p);
-        L = (const float4*)ctx->film_Lt.p;
-    }
-    hipLaunchKernelGGL(k_film_positions, dim3(grid_for(ctx, total_slots, 8)), dim3(kBlock), 0, st, dsp, total_slots, seed, sample_offset, (float2*)ctx->pfilm.p, layout, spp);
-    const float rmax = std::fmax(ds.filter_radius[0], ds.filter_radius[1]);
-    if (whole && ctx->opt.film_tiled && rmax <= 6.0f) {  // reach of a pixel = 2r + 3 sample pixels <= 16: at most 2 x 2 sample tiles
-        const uint32_t budget = 24 * 1024 / 20;  // staged {p_film, L} elements in 24 KiB of LDS: ~6 blocks per CU
-        const uint32_t nc_max = 16 + 2 * (uint32_t)std::ceil(rmax) + 4;
-        uint32_t cols, ns;
-        if (spp <= budget) {
-            ns = spp;
-            cols = std::max(1u, std::min(nc_max, budget / spp));
-        } else {
-            cols = 1;
-            ns = budget;
-        }
-        const dim3 grid((ds.film_w + 15) / 16, (ds.film_h + 15) / 16);
-        hipLaunchKernelGGL(k_film_gather_tiled, grid, dim3(kBlock), (size_t)cols * ns * 20 + 16, st, dsp, (const float*)ctx->table.p, L, (const float2*)ctx->pfilm.p, spp, layout, cols, ns, d_film);
-    } else {
-        const uint64_t npx = (uint64_t)ds.film_w * ds.film_h;
-        const int fblock = ctx->opt.film_block >= 4 ? 2 : ctx->opt.film_block;  // a filter too wide for the packed descriptor: the 1 x 4 block gather
-        if (fblock == 1)
-            hipLaunchKernelGGL((k_film_gather_block<2, 2>), dim3(grid_for(ctx, (npx + 3) / 4, 8)), dim3(kBlock), 0, st, dsp, (const float*)ctx->table.p, L, (const float2*)ctx->pfilm.p, spp, layout, d_film);
-        else if (fblock == 2)
-            hipLaunchKernelGGL((k_film_gather_block<TH_FILM_BX, TH_FILM_BY>), dim3(grid_for(ctx, (npx + TH_FILM_BX * TH_FILM_BY - 1) / (TH_FILM_BX * TH_FILM_BY), 8)), dim3(kBlock), 0, st, dsp, (const float*)ctx->table.p, L, (const float2*)ctx->pfilm.p, spp, layout, d_film);
-        else
-            hipLaunchKernelGGL(k_film_gather, dim3(grid_for(ctx, npx, 8)), dim3(kBlock), 0, st, dsp, (const float*)ctx->table.p, L, (const float2*)ctx->pfilm.p, spp, layout, d_film);
-    }
-}
-
-// ---- map frames (trhip_render_path_map): a per-pixel sample count instead of one spp ----
-// The records keep the dense max_spp layouts; the frame's camera samples are the job list (th_adaptive.h, k_map_expand) and the gather stops at counts[pix].
-struct MapFrame {
-    const uint32_t* counts;  // device: one per sample pixel
-    const uint32_t* jobs;    // device: `total` dense sample-major slots
-    uint64_t total;          // Σ counts
-};
-// Map frames take one film pass per case, whatever the film options say: a filter radius in (0, 1] goes through the fused pixel-group-major records with packed
-// descriptors and the 2 x 4 gather, anything wider through sample-major records, film positions and the 1 x 4 block gather.
-static bool map_uses_packed(const DeviceSensor& ds, uint32_t max_spp) {
-    const uint64_t npix = (uint64_t)ds.sb_w * ds.band_rows;
-    return std::fmax(ds.filter_radius[0], ds.filter_radius[1]) <= 1.0f && ds.filter_radius[0] > 0.0f && ds.filter_radius[1] > 0.0f && ((npix + 63u) / 64u) * 64u * max_spp < (1ull << 32);
-}
-static void launch_film_map(trhip_ctx* ctx, hipStream_t st, const DeviceSensor& ds, const DeviceSensor* dsp, const float4* L, const MapFrame& map, uint32_t max_spp, uint64_t seed,
-                            uint32_t sample_offset, float4* d_film, bool packed) {
-    const float* tb = (const float*)ctx->table.p;
-    if (packed) {  // k_raygen (its MapJobs form) wrote the drawn samples' records re-laid and with their descriptors
-        const uint64_t threads = (uint64_t)((ds.film_w + 1) / 2) * (uint64_t)((ds.film_h + 3) / 4);
-        hipLaunchKernelGGL((k_film_gather_packed<2, 4, MapSpp>), dim3(grid_for(ctx, threads, 8)), dim3(kBlock), 0, st, dsp, tb, L, MapSpp{map.counts, max_spp}, seed, sample_offset, 1u,
-                           (const uint4*)ctx->film_side.p + 1, d_film, 0u);
-        return;
-    }
-    hipLaunchKernelGGL(k_film_positions_map, dim3(grid_for(ctx, map.total, 8)), dim3(kBlock), 0, st, dsp, map.jobs, map.total, seed, sample_offset, (float2*)ctx->pfilm.p);
-    const uint64_t blocks = (uint64_t)ds.film_w * (uint64_t)((ds.film_h + 3) / 4);
-    hipLaunchKernelGGL((k_film_gather_block<1, 4, MapSpp>), dim3(grid_for(ctx, blocks, 8)), dim3(kBlock), 0, st, dsp, tb, L, (const float2*)ctx->pfilm.p, MapSpp{map.counts, max_spp}, 0u, d_film);
+    };
+    if (map)
+        gather(MapSpp{map->counts, spp});
+    else
+        gather(spp);
 }
 
 // ---- the frame scaffold's out-of-line part (th_host.h) ----
@@ -286,7 +206,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
         if (int rc = ensure(ctx, pp.overflow[k], slab_bytes)) return rc;
     ctx->last = LastRecords{};
     if (int rc = ensure(ctx, ctx->Lbuf, total_slots * sizeof(float4))) return rc;
-    if (int rc = ensure_film_samples(ctx, ds, total_slots)) return rc;
+    if (int rc = ensure_film_samples(ctx, film_packed(ds), total_slots)) return rc;
     if (int rc = ensure(ctx, ctx->st_terms, terms_bytes)) return rc;
     for (int k = 0; k < 2; ++k)
         if (int rc = ensure(ctx, ctx->st_tags[k], Pphys * sizeof(uint32_t))) return rc;
@@ -447,7 +367,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         if (int rc = upload(ctx, ctx->table, sensor->filter_table, 256 * sizeof(float))) return rc;
         ctx->last = LastRecords{};
         if (int rc = ensure(ctx, ctx->Lbuf, total_slots * sizeof(float4))) return rc;
-        if (int rc = ensure_film_samples(ctx, ds, total_slots)) return rc;
+        if (int rc = ensure_film_samples(ctx, film_packed(ds), total_slots)) return rc;
         if (int rc = ensure(ctx, ctx->counters, sizeof(Counters))) return rc;
         const size_t fb = (size_t)ds.film_w * ds.film_h * sizeof(float4);
         void* df;
@@ -461,21 +381,24 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         const int rc = render_stream_impl(ctx, scene, sensor, ds, spp, max_depth, seed, sample_offset, out, out_is_device, stats, &declined);
         if (!declined) return rc;
     }
-    // A map frame (`spp` is its max_spp) has no bands: its records, dense at max_spp, and the film pass's per-sample buffer must fit beside the queues.
-    const bool map_packed = map && map_uses_packed(ds, spp);
+    // the radiance records: sample-major, or — when k_raygen can initialise them for the film pass — pixel-group-major, padded to whole groups of 64 pixels.
+    // A map frame is fused or wide: one film pass per case, whatever the options "film_fused" / "film_relayout" say.
+    const bool fused = map ? film_fusable(ds, spp) : film_fused(ctx, ds, spp);
+    const bool packed = map ? fused : film_packed(ds);
+    // A map frame (`spp` is its max_spp) has no bands: its records, dense at max_spp, with the poison byte, and the film pass's per-sample buffer must fit beside the queues.
     if (map) {
         bool fits = false;
         double free_gb = 0.0;
-        const double need = (double)total_slots * (map_packed ? 17.0 : 25.0) + (double)npix * 8.0 + (double)map->total * 4.0;
+        const double need = (double)total_slots * (film_sample_bytes(packed) + 1.0) + (double)npix * 8.0 + (double)map->total * 4.0;
         if (int rc = fits_in_hbm(ctx, 2.0 * need, ctx->Lbuf.bytes + ctx->pfilm.bytes + held_in_pipes(ctx), &fits, &free_gb)) return rc;  // half of what is free, as render_impl plans its bands
         if (!fits) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "the per-sample buffers of a map frame (%.2f GB at max_spp %u) do not fit in half of free HBM (%.2f GB): there are no bands here", need * 1e-9, spp, free_gb);
     }
     // A path-env frame (docs/design/26-path-env.md) has no bands either: the path's records, their fold, the escape records (16 + 16 + 32 B per slot), the poison byte and
-    // what the film pass keeps per sample must fit the same way.
+    // what an unfused film pass reads per sample (counted as buffers of its own) must fit the same way.
     if (envf_in) {
         bool fits = false;
         double free_gb = 0.0;
-        const double film_own = film_uses_packed(ctx, ds) ? (film_fused(ctx, ds, spp) ? 0.0 : 16.0) : film_uses_desc(ctx, ds) ? 16.0 : 24.0;
+        const double film_own = fused ? 0.0 : film_sample_bytes(packed);
         const double need = (double)total_slots * (65.0 + film_own);
         const size_t held = ctx->Lbuf.bytes + ctx->pfilm.bytes + ctx->env_base.bytes + ctx->env_rec.bytes + held_in_pipes(ctx);
         if (int rc = fits_in_hbm(ctx, 2.0 * need, held, &fits, &free_gb)) return rc;
@@ -527,9 +450,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         for (int k = 0; k < 2; ++k)
             if (int rc = ensure(ctx, pp.overflow[k], slab_bytes)) return rc;
     }
-    // the radiance records: sample-major, or — when k_raygen can initialise them for the film pass (film_fused) — pixel-group-major, padded to whole groups of 64 pixels
-    const bool fused = map ? map_packed : film_fused(ctx, ds, spp);
-    const uint64_t l_slots = fused ? ((npix + 63u) / 64u) * 64u * (uint64_t)spp : total_slots;
+    const uint64_t l_slots = fused ? film_padded_slots(ds, spp) : total_slots;
     ctx->last = LastRecords{};
     if (int rc = ensure(ctx, ctx->poison, l_slots)) return rc;
     if (int rc = ensure(ctx, ctx->Lbuf, l_slots * sizeof(float4))) return rc;
@@ -541,12 +462,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         envf.base = (float4*)ctx->env_base.p;
         envf.rec = (float4*)ctx->env_rec.p;
     }
-    if (map) {
-        if (!map_packed)
-            if (int rc = ensure(ctx, ctx->pfilm, total_slots * sizeof(float2))) return rc;
-    } else if (int rc = ensure_film_samples(ctx, ds, total_slots)) {
-        return rc;
-    }
+    if (int rc = ensure_film_samples(ctx, packed, total_slots)) return rc;
     const size_t film_bytes = (size_t)ds.film_w * ds.film_h * sizeof(float4);
     void* d_film;
     if (int rc = stage_output(ctx, out, out_is_device, film_bytes, &d_film)) return rc;
@@ -651,10 +567,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         launch_escape_fold(ctx, st, envf, l_slots, (float4*)ctx->Lbuf.p);
         L = (float4*)ctx->Lbuf.p;
     }
-    if (map)
-        launch_film_map(ctx, st, ds, dsp, L, *map, spp, seed, sample_offset, (float4*)d_film, map_packed);
-    else
-        launch_film(ctx, st, ds, dsp, L, total_slots, spp, seed, sample_offset, (float4*)d_film, fused);
+    launch_film(ctx, st, ds, dsp, L, total_slots, spp, seed, sample_offset, (float4*)d_film, fused, map);
     tm.end(4, st);
     HIP_TRY(ctx, ev.end(st));
     HIP_TRY(ctx, hipGetLastError());
@@ -730,7 +643,7 @@ int render_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* se
             const size_t held = ctx->Lbuf.bytes + ctx->pfilm.bytes + held_in_pipes(ctx);
             // half of what is free for the per-sample buffers, the rest for the wavefront queues (164 B per path in flight); 32-bit slot indices
             const double budget = std::min(0.5 * (double)(free_b + held), 4.0e9 * 24.0);
-            rows_per_band = plan_rows_per_band(ds, spp, budget, film_uses_packed(ctx, ds) ? 17.0 : film_uses_desc(ctx, ds) ? 33.0 : 25.0);  // radiance (+ descriptor / film position) + poison byte
+            rows_per_band = plan_rows_per_band(ds, spp, budget, film_sample_bytes(film_packed(ds)) + 1.0);  // radiance (+ film position) + poison byte
         }
     }
     if (rows_per_band >= ds.tiles_y) return render_impl_band(ctx, scene, sensor, integrator, spp, max_depth, seed, sample_offset, out, out_is_device, stats, nullptr);
@@ -904,7 +817,7 @@ int trhip_film_accumulate(trhip_ctx* ctx, const trhip_sensor* sn, uint32_t spp, 
     if (int rc = ensure(ctx, ctx->Lbuf, n * sizeof(float4))) return rc;
     const size_t film_bytes = (size_t)ds.film_w * ds.film_h * sizeof(float4);
     if (int rc = ensure(ctx, ctx->film, film_bytes)) return rc;
-    if (int rc = ensure_film_samples(ctx, ds, n)) return rc;
+    if (int rc = ensure_film_samples(ctx, film_packed(ds), n)) return rc;
     if (n) hipLaunchKernelGGL(k_import_L, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)ctx->scratch[0].p, n, (float4*)ctx->Lbuf.p);
     launch_film(ctx, ctx->stream, ds, (const DeviceSensor*)ctx->sensor.p, (const float4*)ctx->Lbuf.p, n, spp, seed, sample_offset, (float4*)ctx->film.p, false);
     HIP_TRY(ctx, hipGetLastError());

@@ -37,7 +37,7 @@ int relight_impl(trhip_ctx* ctx, const trhip_env* env, const trhip_path_env_para
     const LastRecords last = ctx->last;
     if (int rc = upload(ctx, ctx->sensor, &k.ds, sizeof k.ds)) return rc;
     if (int rc = upload(ctx, ctx->table, k.filter_table, sizeof k.filter_table)) return rc;
-    if (int rc = ensure_film_samples(ctx, k.ds, k.total_slots)) return rc;
+    if (int rc = ensure_film_samples(ctx, film_packed(k.ds), k.total_slots)) return rc;
     const size_t film_bytes = (size_t)k.ds.film_w * k.ds.film_h * sizeof(float4);
     void* d_film;
     if (int rc = stage_output(ctx, out, out_is_device, film_bytes, &d_film)) return rc;
