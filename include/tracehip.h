@@ -498,6 +498,39 @@ int trhip_last_escapes(trhip_ctx* ctx, float* out8, uint64_t n_floats);
 int trhip_path_env_relight(trhip_ctx* ctx, const trhip_env* env, const trhip_path_env_params* params, float* out_xyzw);
 int trhip_path_env_relight_device(trhip_ctx* ctx, const trhip_env* env, const trhip_path_env_params* params, void* d_out_xyzw);
 
+/* ---- importance sampling of the environment map (since ABI 3001, added without a version change: nothing existing moved) ---------
+ * docs/design/27-sky-importance.md holds the specification.  trhip_env_make_sampler builds, once and on the host in Float64, a
+ * piecewise-constant distribution over the map's n x n cells (the channel sum of the interpolated map integrated over each cell, times
+ * the solid angle per unit area of the octahedral square at the cell's centre) and keeps its tables, (n + 1)^2 floats, with the handle;
+ * it is idempotent, and trhip_env_free frees the tables.  TRHIP_ERR_INVALID, in this order: a null argument; an env of another context;
+ * a world_to_env that is not orthonormal (max |R R^T - I| > 1e-5: sampling needs R^-1 = R^T); a map whose weights are all zero.
+ * trhip_env_sample maps `count` points u = (u0, u1) of [0, 1)^2 (count * 2 floats) to unit directions (count * 3 floats), distributed
+ * like the table; trhip_env_pdf returns the density of `count` directions with respect to solid angle (0 where the lookup has no
+ * answer).  Both run on the device and are specified bit for bit; their refusals are trhip_env_eval's, plus an env without a sampler.
+ *
+ * trhip_render_sky_is is trhip_render_sky with one substitution per hit: with probability `mix` the occlusion ray's direction is drawn
+ * from the map's distribution instead of the cosine lobe, and the contribution is that of the one-sample mixture estimator,
+ *   c = (E(wi) * scale) * g,   g = pc / ((1 - mix) pc + mix pe),   pc = cos / pi,   pe = trhip_env_pdf(wi),
+ * unbiased wherever cos > 0 and never larger than E * scale / (1 - mix).  Everything else — camera samples, walks, the miss term, the
+ * flags, the film pass, statistics, trhip_last_sample_radiance — is trhip_render_sky's.  TRHIP_ERR_INVALID: trhip_render_sky's refusals
+ * in its order, with `mix` outside (0, 1) or not finite after `reserved` (still before any handle is looked at); then an env without a
+ * sampler, and a scale for which (largest texel) * scale / (1 - mix) is not finite.  trhip_sky_is_default_params needs no context. */
+int trhip_env_make_sampler(trhip_ctx* ctx, trhip_env* env);
+int trhip_env_sample(trhip_ctx* ctx, const trhip_env* env, const float* u2, uint64_t count, float* out_dir3);
+int trhip_env_pdf(trhip_ctx* ctx, const trhip_env* env, const float* dirs3, uint64_t count, float* out_pdf);
+typedef struct {
+    float max_distance;       /* reach of the occlusion rays: > 0 or +Inf */
+    float scale;              /* multiplies every lookup: finite, >= 0 */
+    float mix;                /* probability of drawing the direction from the map: in (0, 1) */
+    uint32_t flags;           /* TRHIP_SKY_ALBEDO | TRHIP_SKY_HIDE_BACKGROUND */
+    uint32_t reserved[4];     /* 0 */
+} trhip_sky_is_params;        /* 32 bytes */
+int trhip_sky_is_default_params(trhip_sky_is_params* out); /* {+Inf, 1, 0.5, 0, {0, 0, 0, 0}} */
+int trhip_render_sky_is(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset,
+                        const trhip_env* env, const trhip_sky_is_params* params, float* out_xyzw, trhip_stats* stats);
+int trhip_render_sky_is_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset,
+                               const trhip_env* env, const trhip_sky_is_params* params, void* d_out_xyzw, trhip_stats* stats);
+
 /* ---- edge-avoiding denoiser for path / Whitted films (since ABI 3001, added without a version change: nothing existing moved) ----
  * An à-trous wavelet filter after Dammertz et al. 2010 ("Edge-Avoiding À-Trous Wavelet Transform for fast Global Illumination
  * Filtering") on the film state of a path or Whitted render, guided by the three planes of trhip_render_aov for the same sensor,

@@ -171,6 +171,17 @@ SKY_HIDE_BACKGROUND = 2  # TRHIP_SKY_HIDE_BACKGROUND
 ENV_MAX_N = 4096  # the largest map trhip_env_create takes
 
 
+class SkyIsParams(C.Structure):
+    """trhip_sky_is_params (32 bytes)"""
+    _fields_ = [
+        ("max_distance", C.c_float),
+        ("scale", C.c_float),
+        ("mix", C.c_float),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
 class PathEnvParams(C.Structure):
     """trhip_path_env_params (16 bytes)"""
     _fields_ = [
@@ -421,6 +432,12 @@ SIGNATURES = {
     "trhip_sky_default_params": (C.c_int, [C.POINTER(SkyParams)]),
     "trhip_render_sky": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, C.POINTER(SkyParams), _F, C.POINTER(Stats)]),
     "trhip_render_sky_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, C.POINTER(SkyParams), _VP, C.POINTER(Stats)]),
+    "trhip_env_make_sampler": (C.c_int, [_VP, _VP]),
+    "trhip_env_sample": (C.c_int, [_VP, _VP, _F, C.c_uint64, _F]),
+    "trhip_env_pdf": (C.c_int, [_VP, _VP, _F, C.c_uint64, _F]),
+    "trhip_sky_is_default_params": (C.c_int, [C.POINTER(SkyIsParams)]),
+    "trhip_render_sky_is": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, C.POINTER(SkyIsParams), _F, C.POINTER(Stats)]),
+    "trhip_render_sky_is_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _VP, C.POINTER(SkyIsParams), _VP, C.POINTER(Stats)]),
     "trhip_path_env_default_params": (C.c_int, [C.POINTER(PathEnvParams)]),
     "trhip_render_path_env": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(PathEnvParams), _F, C.POINTER(Stats)]),
     "trhip_render_path_env_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(PathEnvParams), _VP, C.POINTER(Stats)]),

@@ -1490,6 +1490,7 @@ class Environment:
             raise TraceHipError("Environment: every entry of world_to_env must be finite")
         self.texels, self.world_to_env = t, r
         self._handles = {}  # id(context) -> (context, trhip_env*)
+        self._samplers = set()  # id(context) of the handles that have their sampling tables
 
     @property
     def n(self) -> int:
@@ -1548,11 +1549,43 @@ class Environment:
         ctx.check(_ffi.lib().trhip_env_eval(ctx._h, self._handle(ctx), _ffi.fptr(d), d.size // 3, _ffi.fptr(out)))
         return out
 
+    def _sampler_handle(self, ctx: _ffi.Context):
+        """This map's trhip_env on `ctx` with its sampling tables (trhip_env_make_sampler; docs/design/27-sky-importance.md), made on first use per context."""
+        h = self._handle(ctx)
+        if id(ctx) not in self._samplers:
+            ctx.check(_ffi.lib().trhip_env_make_sampler(ctx._h, h))
+            self._samplers.add(id(ctx))
+        return h
+
+    def sample(self, u, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
+        """A unit direction for every point of `u` (..., 2) in [0, 1)^2, distributed like the map's radiance times solid angle: the device's deterministic sampler
+        (trhip_env_sample).  The map's matrix must be orthonormal and the map not black."""
+        p = _ffi.f32(u)
+        if p.ndim < 1 or p.shape[-1] != 2:
+            raise TraceHipError(f"Environment.sample: points must be (..., 2), not {p.shape}")
+        if not ((p >= 0) & (p < 1)).all():
+            raise TraceHipError("Environment.sample: every coordinate must lie in [0, 1)")
+        ctx = ctx or _ffi.default_context()
+        out = np.empty(p.shape[:-1] + (3,), dtype=np.float32)
+        ctx.check(_ffi.lib().trhip_env_sample(ctx._h, self._sampler_handle(ctx), _ffi.fptr(p), p.size // 2, _ffi.fptr(out)))
+        return out
+
+    def pdf(self, dirs, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
+        """The density, with respect to solid angle, with which sample() returns every direction of `dirs` (..., 3) (trhip_env_pdf)."""
+        d = _ffi.f32(dirs)
+        if d.ndim < 1 or d.shape[-1] != 3:
+            raise TraceHipError(f"Environment.pdf: directions must be (..., 3), not {d.shape}")
+        ctx = ctx or _ffi.default_context()
+        out = np.empty(d.shape[:-1], dtype=np.float32)
+        ctx.check(_ffi.lib().trhip_env_pdf(ctx._h, self._sampler_handle(ctx), _ffi.fptr(d), d.size // 3, _ffi.fptr(out)))
+        return out
+
     def close(self):
         for ctx, h in self._handles.values():
             if ctx._h:  # (a context that was shut down took its device memory with it)
                 _ffi.lib().trhip_env_free(h)
         self._handles = {}
+        self._samplers = set()
 
     def __del__(self):
         try:
@@ -1565,13 +1598,19 @@ class SkyIntegrator(_SamplerIntegrator):
     """A sky-lit clay or albedo render (trhip_render_sky; docs/design/25-sky.md): AmbientOcclusionIntegrator's frame in which the occlusion ray that escapes brings
     back `environment`'s radiance from its direction, times `scale` (times the base colour with ``albedo``), and a camera ray that misses shows the environment (or 0
     with ``hide_background``).  No lights, no BSDF; one ray per camera sample, quality comes from the sampler's samples_per_pixel.  The film has the path frame's
-    weights, so it goes through Denoiser.denoise with AOVIntegrator's planes, as an AO film does."""
+    weights, so it goes through Denoiser.denoise with AOVIntegrator's planes, as an AO film does.
+
+    ``importance`` (docs/design/27-sky-importance.md): None is that frame.  A float in (0, 1) — True is 0.5 — draws that share of the occlusion rays from the map's own
+    distribution and weights every ray as the one-sample mixture estimator does (trhip_render_sky_is): unbiased as before, far less noise under a small bright sun."""
 
     def __init__(self, camera: PerspectiveCamera, sampler: SeededSampler, environment: Environment, max_distance: float = math.inf, albedo: bool = False, scale: float = 1.0,
-                 hide_background: bool = False):
+                 hide_background: bool = False, importance=None):
         super().__init__(camera, sampler, 1)
         if not isinstance(environment, Environment):
             raise TraceHipError(f"SkyIntegrator: environment must be an Environment, not {type(environment).__name__}")
+        if importance is not None and importance is not True:
+            if isinstance(importance, bool) or not isinstance(importance, (int, float, np.floating)) or not 0.0 < float(importance) < 1.0:
+                raise TraceHipError(f"SkyIntegrator: importance must be None, True or a float in (0, 1), not {importance}")
         max_distance, scale = float(max_distance), float(scale)
         if not max_distance > 0.0:
             raise TraceHipError(f"SkyIntegrator: max_distance must be > 0 or inf, not {max_distance}")
@@ -1583,12 +1622,24 @@ class SkyIntegrator(_SamplerIntegrator):
             raise TraceHipError(f"trhip_sky_default_params failed ({rc})")
         p.max_distance, p.scale, p.flags = max_distance, scale, (_ffi.SKY_ALBEDO if albedo else 0) | (_ffi.SKY_HIDE_BACKGROUND if hide_background else 0)
         self.environment, self.params = environment, p
+        self.is_params = None  # trhip_sky_is_params with `importance`: the frame is then trhip_render_sky_is
+        if importance is not None:
+            q = _ffi.SkyIsParams()
+            rc = _ffi.lib().trhip_sky_is_default_params(C.byref(q))
+            if rc:
+                raise TraceHipError(f"trhip_sky_is_default_params failed ({rc})")
+            q.max_distance, q.scale, q.flags = p.max_distance, p.scale, p.flags
+            if importance is not True:
+                q.mix = float(importance)
+            self.is_params = q
 
     def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None) -> np.ndarray:
         """Render into camera.film (and return xyzw, H x W x 4).  With ``device_out`` (a device pointer to H * W * 4 floats) the film accumulators are written there
         instead, nothing is copied to the host and None is returned."""
         flat = scene.flatten(ctx)
         ctx = flat.ctx
+        if self.is_params is not None:
+            return self._render_is(flat, device_out)
         sn, st, smp, L, env = self.camera.sensor(), _ffi.Stats(), self.sampler, _ffi.lib(), self.environment._handle(flat.ctx)
         if device_out is not None:
             ctx.check(L.trhip_render_sky_device(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, env, C.byref(self.params), C.c_void_p(device_out), C.byref(st)))
@@ -1597,6 +1648,22 @@ class SkyIntegrator(_SamplerIntegrator):
         h, w = self.camera.film.size
         out = np.empty((h, w, 4), dtype=np.float32)
         ctx.check(L.trhip_render_sky(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, env, C.byref(self.params), _ffi.fptr(out), C.byref(st)))
+        self.stats = st
+        self.camera.film.set_xyzw(out)
+        return out
+
+    def _render_is(self, flat, device_out):
+        """render() with `importance`: trhip_render_sky_is, the sampling tables made on first use."""
+        ctx = flat.ctx
+        sn, st, smp, L, env = self.camera.sensor(), _ffi.Stats(), self.sampler, _ffi.lib(), self.environment._sampler_handle(ctx)
+        if device_out is not None:
+            ctx.check(L.trhip_render_sky_is_device(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, env, C.byref(self.is_params), C.c_void_p(device_out),
+                                                   C.byref(st)))
+            self.stats = st
+            return None
+        h, w = self.camera.film.size
+        out = np.empty((h, w, 4), dtype=np.float32)
+        ctx.check(L.trhip_render_sky_is(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, env, C.byref(self.is_params), _ffi.fptr(out), C.byref(st)))
         self.stats = st
         self.camera.film.set_xyzw(out)
         return out

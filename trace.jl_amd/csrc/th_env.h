@@ -68,6 +68,7 @@ struct trhip_env {
     float R[9] = {};
     float max_texel = 0.0f;  // the largest channel of any texel: a frame refuses a scale that takes it to +Inf (tu_sky.hip)
     DevBuf tex;              // (n + 2)^2 float4
+    DevBuf sampler;          // (n + 1)^2 floats once trhip_env_make_sampler has run: the marginal, then the conditionals (th_env_sample.h)
     DeviceEnv dev() const {
         DeviceEnv d{(const float4*)tex.p, n, {}};
         std::memcpy(d.R, R, sizeof R);

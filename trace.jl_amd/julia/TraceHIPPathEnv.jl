@@ -93,3 +93,6 @@ function relight!(i::PathEnvIntegrator, environment::Environment; scale = i.scal
     write_film!(film, out, h, w)
     Trace.save(film)
 end
+
+# importance sampling of the map and the importance-sampled sky frame (trhip_render_sky_is): env_sample, env_pdf, SkyISIntegrator (tests/golden/julia_shim_sky_is_calls.json)
+include("TraceHIPSkyIS.jl")
