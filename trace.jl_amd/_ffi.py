@@ -521,6 +521,29 @@ def f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+_POINTER_OF = {np.dtype(np.float32): _F, np.dtype(np.uint32): _U32, np.dtype(np.uint8): C.POINTER(C.c_uint8)}
+
+
+def optr(a):
+    """An optional host array for a call: None stays None (NULL); a Float32, UInt32 or UInt8 array gives the pointer of its element type, any other (the 16-byte
+    records of an id plane) a void *."""
+    return None if a is None else a.ctypes.data_as(_POINTER_OF.get(a.dtype, _VP))
+
+
+def dptr(p):
+    """An optional device address for a call: None or 0 stays None (NULL)."""
+    return _VP(p) if p else None
+
+
+def default_params(struct_type, entry_name: str):
+    """A parameter block filled by its trhip_*_default_params entry (host arithmetic: no context, no GPU)."""
+    p = struct_type()
+    rc = getattr(lib(), entry_name)(C.byref(p))
+    if rc:
+        raise TraceHipError(f"{entry_name} failed ({rc})")
+    return p
+
+
 def build_bvh_host(prim_bounds, max_node_primitives: int = 1, builder: int = 2):
     """BVHAccel construction alone, on the host (trhip_build_bvh_host; no GPU needed): builder 2 = the reference's own construction node for
     node (accel/bvh.jl:87-206), 0 = the library's binned SAH.  prim_bounds: (n, 6) world bounds.  Returns (bounds (m, 6), a, flags, order, max_depth)
@@ -544,7 +567,7 @@ def detmath(fn: int, x, y=None):
     x = f32(np.atleast_1d(x))
     out = np.empty_like(x)
     yy = f32(np.atleast_1d(y)) if y is not None else None
-    rc = lib().trhip_detmath_f32(fn, fptr(x), fptr(yy) if yy is not None else None, x.size, fptr(out))
+    rc = lib().trhip_detmath_f32(fn, fptr(x), optr(yy), x.size, fptr(out))
     if rc:
         raise TraceHipError("trhip_detmath_f32 failed")
     return out
@@ -558,7 +581,7 @@ class Context:
         x = f32(np.atleast_1d(x))
         out = np.empty_like(x)
         yy = f32(np.atleast_1d(y)) if y is not None else None
-        self.check(lib().trhip_detmath_f32_device(self._h, fn, fptr(x), fptr(yy) if yy is not None else None, x.size, fptr(out)))
+        self.check(lib().trhip_detmath_f32_device(self._h, fn, fptr(x), optr(yy), x.size, fptr(out)))
         return out
 
     def __init__(self, device: int = 0):

@@ -858,15 +858,14 @@ class FlatScene:
         L = _ffi.lib()
         nrm, tan, uv = mesh.normals, getattr(mesh, "tangents", None), getattr(mesh, "uv", None)
         if tan is None and uv is None:
-            ctx.check(L.trhip_scene_add_triangles(self._h, _ffi.fptr(mesh.vertices), mesh.vertices.shape[0], _ffi.u32ptr(idx), idx.shape[0],
-                                                  _ffi.fptr(nrm) if nrm is not None else None, _ffi.u32ptr(mats), flip, None))
+            ctx.check(L.trhip_scene_add_triangles(self._h, _ffi.fptr(mesh.vertices), mesh.vertices.shape[0], _ffi.u32ptr(idx), idx.shape[0], _ffi.optr(nrm), _ffi.u32ptr(mats), flip,
+                                                  None))
             return
         if uv is not None:
             uv = uv[:3 * mesh.n_triangles].reshape(-1, 3, 2)
             uv = np.ascontiguousarray(uv if ks is None else uv[ks], dtype=np.float32)
-        ctx.check(L.trhip_scene_add_triangles_ex(self._h, _ffi.fptr(mesh.vertices), mesh.vertices.shape[0], _ffi.u32ptr(idx), idx.shape[0],
-                                                 _ffi.fptr(nrm) if nrm is not None else None, _ffi.fptr(tan) if tan is not None else None,
-                                                 _ffi.fptr(uv) if uv is not None else None, _ffi.u32ptr(mats), flip, None))
+        ctx.check(L.trhip_scene_add_triangles_ex(self._h, _ffi.fptr(mesh.vertices), mesh.vertices.shape[0], _ffi.u32ptr(idx), idx.shape[0], _ffi.optr(nrm), _ffi.optr(tan),
+                                                 _ffi.optr(uv), _ffi.u32ptr(mats), flip, None))
 
     def bvh(self):
         L = _ffi.lib()
@@ -998,39 +997,36 @@ class FlatScene:
 # ---- integrators -------------------------------------------------------------------------------------------------------------------
 class _SamplerIntegrator:
     _entry = None
-    _entry_device = None
 
     def __init__(self, camera: PerspectiveCamera, sampler: SeededSampler, max_depth: int):
         self.camera, self.sampler, self.max_depth = camera, sampler, int(max_depth)
         self.stats: Optional[_ffi.Stats] = None
 
+    def _render_film(self, flat: "FlatScene", entry: str, args, device_out: Optional[int]):
+        """One film frame of the flattened scene through `entry`(ctx, scene, sensor, *args, out, stats) — `entry`_device with ``device_out``, a device pointer the film
+        accumulators are then written to, nothing copied to the host and None returned; without it the film goes into camera.film and is returned."""
+        ctx, sn, st, film = flat.ctx, self.camera.sensor(), _ffi.Stats(), self.camera.film
+        if device_out is not None:
+            entry, out, target = entry + "_device", None, C.c_void_p(device_out)
+        else:
+            out = np.empty(film.size + (4,), dtype=np.float32)
+            target = _ffi.fptr(out)
+        ctx.check(getattr(_ffi.lib(), entry)(ctx._h, flat._h, C.byref(sn), *args, target, C.byref(st)))
+        self.stats = st
+        if out is not None:
+            film.set_xyzw(out)
+        return out
+
     def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None) -> np.ndarray:
         """Render into camera.film (and return xyzw, H x W x 4).  With ``device_out`` (a device pointer) the film
         accumulators are written there instead and nothing is copied to the host."""
-        flat = scene.flatten(ctx)
-        ctx = flat.ctx
-        sn = self.camera.sensor()
-        st = _ffi.Stats()
-        film = self.camera.film
-        h, w = film.size
         smp = self.sampler
-        L = _ffi.lib()
-        if device_out is not None:
-            ctx.check(getattr(L, self._entry_device)(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, self.max_depth, smp.seed, smp.sample_offset, C.c_void_p(device_out), C.byref(st)))
-            self.stats = st
-            return None
-        out = np.empty((h, w, 4), dtype=np.float32)
-        ctx.check(getattr(L, self._entry)(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, self.max_depth, smp.seed, smp.sample_offset, _ffi.fptr(out), C.byref(st)))
-        self.stats = st
-        film.set_xyzw(out)
-        return out
+        return self._render_film(scene.flatten(ctx), self._entry, (smp.samples_per_pixel, self.max_depth, smp.seed, smp.sample_offset), device_out)
 
     def sample_radiance(self, scene: Scene) -> np.ndarray:
         """Per-sample radiance of the last render: (spp, sb_h, sb_w, 3)."""
         flat = scene.flatten()
-        sb = self.camera.film.get_sample_bounds()
-        sbw = int(sb.p_max[0] - sb.p_min[0]) + 1
-        sbh = int(sb.p_max[1] - sb.p_min[1]) + 1
+        sbh, sbw, _, _ = sample_bounds_shape(self.camera.film)
         out = np.empty((self.sampler.samples_per_pixel, sbh, sbw, 3), dtype=np.float32)
         flat.ctx.check(_ffi.lib().trhip_last_sample_radiance(flat.ctx._h, _ffi.fptr(out), out.size))
         return out
@@ -1045,13 +1041,11 @@ class _SamplerIntegrator:
 
 class WhittedIntegrator(_SamplerIntegrator):  # integrators/sampler.jl:3-7
     _entry = "trhip_render_whitted"
-    _entry_device = "trhip_render_whitted_device"
 
 
 class PathIntegrator(_SamplerIntegrator):
     """Not in the reference; defined in DESIGN.md from integrators/sppm.jl:208-266, 503-554."""
     _entry = "trhip_render_path"
-    _entry_device = "trhip_render_path_device"
 
     def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None, sample_map: Optional["SampleMap"] = None,
                environment: Optional["Environment"] = None, env_scale: float = 1.0, hide_background: bool = False) -> np.ndarray:
@@ -1059,49 +1053,25 @@ class PathIntegrator(_SamplerIntegrator):
         sample_offset on, and ``sampler.samples_per_pixel`` is not read.  With ``environment`` a path-env frame (trhip_render_path_env; docs/design/26-path-env.md): a path
         that leaves the scene brings back beta * E(dir) * env_scale — not at depth 1 with ``hide_background`` — and escapes() / relight() work on the frame afterwards.
         Without either it is trhip_render_path, the same call and the same bits."""
+        smp = self.sampler
         if environment is not None:
             if sample_map is not None:
                 raise TraceHipError("PathIntegrator.render: sample_map and environment cannot be combined (map frames have no environment term)")
             prm = path_env_params(environment, env_scale, hide_background, "PathIntegrator.render")
             flat = scene.flatten(ctx)
-            ctx = flat.ctx
-            sn, st, smp, L, env = self.camera.sensor(), _ffi.Stats(), self.sampler, _ffi.lib(), environment._handle(flat.ctx)
-            if device_out is not None:
-                ctx.check(L.trhip_render_path_env_device(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, self.max_depth, smp.seed, smp.sample_offset, env, C.byref(prm),
-                                                         C.c_void_p(device_out), C.byref(st)))
-                self.stats = st
-                return None
-            h, w = self.camera.film.size
-            out = np.empty((h, w, 4), dtype=np.float32)
-            ctx.check(L.trhip_render_path_env(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, self.max_depth, smp.seed, smp.sample_offset, env, C.byref(prm), _ffi.fptr(out), C.byref(st)))
-            self.stats = st
-            self.camera.film.set_xyzw(out)
-            return out
+            args = (smp.samples_per_pixel, self.max_depth, smp.seed, smp.sample_offset, environment._handle(flat.ctx), C.byref(prm))
+            return self._render_film(flat, "trhip_render_path_env", args, device_out)
         if sample_map is None:
             return super().render(scene, ctx, device_out)
         flat = scene.flatten(ctx)
-        ctx = flat.ctx
-        sn = self.camera.sensor()
-        st = _ffi.Stats()
-        film = self.camera.film
-        h, w = film.size
-        smp = self.sampler
-        counts = sample_map.for_film(film)
-        L = _ffi.lib()
-        if device_out is not None:
-            d_counts = _ffi.DeviceBuffer(counts.nbytes).from_host(counts)
-            try:
-                ctx.check(L.trhip_render_path_map_device(ctx._h, flat._h, C.byref(sn), C.c_void_p(d_counts.ptr), sample_map.max_spp, self.max_depth, smp.seed, smp.sample_offset,
-                                                         C.c_void_p(device_out), C.byref(st)))
-            finally:
+        counts = sample_map.for_film(self.camera.film)
+        d_counts = _ffi.DeviceBuffer(counts.nbytes).from_host(counts) if device_out is not None else None  # a device frame reads its counts on the device
+        try:
+            args = (_ffi.u32ptr(counts) if d_counts is None else C.c_void_p(d_counts.ptr), sample_map.max_spp, self.max_depth, smp.seed, smp.sample_offset)
+            return self._render_film(flat, "trhip_render_path_map", args, device_out)
+        finally:
+            if d_counts is not None:
                 d_counts.free()
-            self.stats = st
-            return None
-        out = np.empty((h, w, 4), dtype=np.float32)
-        ctx.check(L.trhip_render_path_map(ctx._h, flat._h, C.byref(sn), _ffi.u32ptr(counts), sample_map.max_spp, self.max_depth, smp.seed, smp.sample_offset, _ffi.fptr(out), C.byref(st)))
-        self.stats = st
-        film.set_xyzw(out)
-        return out
 
     def escapes(self, scene: Scene):
         """(beta, depth, dir) of the last render(environment=...) on the scene's context (trhip_last_escapes): beta and dir (spp, sb_h, sb_w, 3), depth (spp, sb_h, sb_w)
@@ -1136,10 +1106,7 @@ def path_env_params(environment, env_scale, hide_background, who: str) -> "_ffi.
     scale = float(env_scale)
     if not (scale >= 0.0 and math.isfinite(scale)):
         raise TraceHipError(f"{who}: env_scale must be finite and >= 0, not {env_scale}")
-    p = _ffi.PathEnvParams()
-    rc = _ffi.lib().trhip_path_env_default_params(C.byref(p))
-    if rc:
-        raise TraceHipError(f"trhip_path_env_default_params failed ({rc})")
+    p = _ffi.default_params(_ffi.PathEnvParams, "trhip_path_env_default_params")
     p.scale, p.flags = scale, _ffi.PATH_ENV_HIDE_BACKGROUND if hide_background else 0
     return p
 
@@ -1230,10 +1197,7 @@ class AdaptivePathIntegrator:
         if sampler.samples_per_pixel < 2:
             raise TraceHipError("AdaptivePathIntegrator: the pilot frame needs at least 2 samples per pixel (a variance)")
         self.camera, self.sampler, self.max_depth = camera, sampler, int(max_depth)
-        p = _ffi.SampleMapParams()
-        rc = _ffi.lib().trhip_sample_map_default_params(C.byref(p))
-        if rc:
-            raise TraceHipError(f"trhip_sample_map_default_params failed ({rc})")
+        p = _ffi.default_params(_ffi.SampleMapParams, "trhip_sample_map_default_params")
         p.pilot = sampler.samples_per_pixel
         if tau is not None:
             p.tau = tau
@@ -1348,8 +1312,7 @@ class AOVIntegrator:
         self.stats: Optional[_ffi.Stats] = None
 
     def _sample_shape(self):
-        sb = self.camera.film.get_sample_bounds()
-        return int(sb.p_max[1] - sb.p_min[1]) + 1, int(sb.p_max[0] - sb.p_min[0]) + 1
+        return sample_bounds_shape(self.camera.film)[:2]
 
     def _call(self, scene, ctx, planes, samples, device, ids=None):
         """One frame through trhip_render_aov(_device), or, with an id plane asked for, through trhip_render_aov_ids(_device)."""
@@ -1426,29 +1389,15 @@ class AmbientOcclusionIntegrator(_SamplerIntegrator):
             raise TraceHipError(f"AmbientOcclusionIntegrator: max_distance must be > 0 or inf, not {max_distance}")
         if not (background >= 0.0 and math.isfinite(background)):
             raise TraceHipError(f"AmbientOcclusionIntegrator: background must be finite and >= 0, not {background}")
-        p = _ffi.AoParams()
-        rc = _ffi.lib().trhip_ao_default_params(C.byref(p))
-        if rc:
-            raise TraceHipError(f"trhip_ao_default_params failed ({rc})")
+        p = _ffi.default_params(_ffi.AoParams, "trhip_ao_default_params")
         p.max_distance, p.background, p.flags = max_distance, background, _ffi.AO_ALBEDO if albedo else 0
         self.params = p
 
     def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None) -> np.ndarray:
         """Render into camera.film (and return xyzw, H x W x 4).  With ``device_out`` (a device pointer to H * W * 4 floats) the film accumulators are written there
         instead, nothing is copied to the host and None is returned."""
-        flat = scene.flatten(ctx)
-        ctx = flat.ctx
-        sn, st, smp, L = self.camera.sensor(), _ffi.Stats(), self.sampler, _ffi.lib()
-        if device_out is not None:
-            ctx.check(L.trhip_render_ao_device(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, C.byref(self.params), C.c_void_p(device_out), C.byref(st)))
-            self.stats = st
-            return None
-        h, w = self.camera.film.size
-        out = np.empty((h, w, 4), dtype=np.float32)
-        ctx.check(L.trhip_render_ao(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, C.byref(self.params), _ffi.fptr(out), C.byref(st)))
-        self.stats = st
-        self.camera.film.set_xyzw(out)
-        return out
+        smp = self.sampler
+        return self._render_film(scene.flatten(ctx), "trhip_render_ao", (smp.samples_per_pixel, smp.seed, smp.sample_offset, C.byref(self.params)), device_out)
 
 
 # ---- environment map and sky-lit frames (include/tracehip.h, trhip_env, trhip_render_sky) ----------------------------------------------------
@@ -1616,18 +1565,12 @@ class SkyIntegrator(_SamplerIntegrator):
             raise TraceHipError(f"SkyIntegrator: max_distance must be > 0 or inf, not {max_distance}")
         if not (scale >= 0.0 and math.isfinite(scale)):
             raise TraceHipError(f"SkyIntegrator: scale must be finite and >= 0, not {scale}")
-        p = _ffi.SkyParams()
-        rc = _ffi.lib().trhip_sky_default_params(C.byref(p))
-        if rc:
-            raise TraceHipError(f"trhip_sky_default_params failed ({rc})")
+        p = _ffi.default_params(_ffi.SkyParams, "trhip_sky_default_params")
         p.max_distance, p.scale, p.flags = max_distance, scale, (_ffi.SKY_ALBEDO if albedo else 0) | (_ffi.SKY_HIDE_BACKGROUND if hide_background else 0)
         self.environment, self.params = environment, p
         self.is_params = None  # trhip_sky_is_params with `importance`: the frame is then trhip_render_sky_is
         if importance is not None:
-            q = _ffi.SkyIsParams()
-            rc = _ffi.lib().trhip_sky_is_default_params(C.byref(q))
-            if rc:
-                raise TraceHipError(f"trhip_sky_is_default_params failed ({rc})")
+            q = _ffi.default_params(_ffi.SkyIsParams, "trhip_sky_is_default_params")
             q.max_distance, q.scale, q.flags = p.max_distance, p.scale, p.flags
             if importance is not True:
                 q.mix = float(importance)
@@ -1636,37 +1579,68 @@ class SkyIntegrator(_SamplerIntegrator):
     def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None) -> np.ndarray:
         """Render into camera.film (and return xyzw, H x W x 4).  With ``device_out`` (a device pointer to H * W * 4 floats) the film accumulators are written there
         instead, nothing is copied to the host and None is returned."""
-        flat = scene.flatten(ctx)
-        ctx = flat.ctx
+        flat, smp = scene.flatten(ctx), self.sampler
         if self.is_params is not None:
             return self._render_is(flat, device_out)
-        sn, st, smp, L, env = self.camera.sensor(), _ffi.Stats(), self.sampler, _ffi.lib(), self.environment._handle(flat.ctx)
-        if device_out is not None:
-            ctx.check(L.trhip_render_sky_device(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, env, C.byref(self.params), C.c_void_p(device_out), C.byref(st)))
-            self.stats = st
-            return None
-        h, w = self.camera.film.size
-        out = np.empty((h, w, 4), dtype=np.float32)
-        ctx.check(L.trhip_render_sky(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, env, C.byref(self.params), _ffi.fptr(out), C.byref(st)))
-        self.stats = st
-        self.camera.film.set_xyzw(out)
-        return out
+        args = (smp.samples_per_pixel, smp.seed, smp.sample_offset, self.environment._handle(flat.ctx), C.byref(self.params))
+        return self._render_film(flat, "trhip_render_sky", args, device_out)
 
     def _render_is(self, flat, device_out):
         """render() with `importance`: trhip_render_sky_is, the sampling tables made on first use."""
-        ctx = flat.ctx
-        sn, st, smp, L, env = self.camera.sensor(), _ffi.Stats(), self.sampler, _ffi.lib(), self.environment._sampler_handle(ctx)
-        if device_out is not None:
-            ctx.check(L.trhip_render_sky_is_device(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, env, C.byref(self.is_params), C.c_void_p(device_out),
-                                                   C.byref(st)))
-            self.stats = st
-            return None
-        h, w = self.camera.film.size
-        out = np.empty((h, w, 4), dtype=np.float32)
-        ctx.check(L.trhip_render_sky_is(ctx._h, flat._h, C.byref(sn), smp.samples_per_pixel, smp.seed, smp.sample_offset, env, C.byref(self.is_params), _ffi.fptr(out), C.byref(st)))
-        self.stats = st
-        self.camera.film.set_xyzw(out)
-        return out
+        smp = self.sampler
+        args = (smp.samples_per_pixel, smp.seed, smp.sample_offset, self.environment._sampler_handle(flat.ctx), C.byref(self.is_params))
+        return self._render_film(flat, "trhip_render_sky_is", args, device_out)
+
+
+# ---- the inputs of the image-space passes: one check per kind, `who` the method named in the refusal -----------------------------------------
+def _film_and_planes(who: str, xyzw, planes):
+    """The (H, W, 4) film and the (H, W, 3, 4) planes of one frame, as contiguous Float32 arrays."""
+    xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
+    if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
+        raise TraceHipError(f"{who}: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
+    return xyzw, planes
+
+
+def _low_and_high(who: str, lo_xyzw, lo_planes, hi_planes):
+    """The low-resolution film and planes and the full-size planes of an upscaling pass, as contiguous Float32 arrays."""
+    lo_xyzw, lo_planes, hi_planes = _ffi.f32(lo_xyzw), _ffi.f32(lo_planes), _ffi.f32(hi_planes)
+    if lo_xyzw.ndim != 3 or lo_xyzw.shape[2] != 4 or lo_planes.shape != lo_xyzw.shape[:2] + (3, 4) or hi_planes.ndim != 4 or hi_planes.shape[2:] != (3, 4):
+        raise TraceHipError(f"{who}: lo_xyzw must be (h, w, 4), lo_planes (h, w, 3, 4) and hi_planes (H, W, 3, 4), not {lo_xyzw.shape}, {lo_planes.shape} and {hi_planes.shape}")
+    return lo_xyzw, lo_planes, hi_planes
+
+
+def _history_like(who: str, history, planes, planes_name: str = "planes"):
+    """An optional history, shaped like the planes it is validated against."""
+    if history is None:
+        return None
+    history = _ffi.f32(history)
+    if history.shape != planes.shape:
+        raise TraceHipError(f"{who}: history must be {planes.shape} like {planes_name}, not {history.shape}")
+    return history
+
+
+def _id_plane(who: str, ids, h: int, w: int, per: str = "pixel"):
+    """An id plane: h * w 16-byte records (_ffi.AOV_ID_DTYPE), contiguous."""
+    ids = np.ascontiguousarray(ids)
+    if ids.nbytes != h * w * 16:
+        raise TraceHipError(f"{who}: ids must hold one 16-byte record per {per}, not {ids.nbytes} bytes for {h} x {w}")
+    return ids
+
+
+def _body_tables(ids, body_of_prim, bodies):
+    """(table, matrices) of a motion-aware pass: uint32 per ordered-primitive slot and (n_bodies, 12) Float32, each None when not given — and both None without an id
+    plane, since every pixel is static then."""
+    table = None if body_of_prim is None or ids is None else np.ascontiguousarray(body_of_prim, dtype=np.uint32).reshape(-1)
+    mats = None if bodies is None or ids is None else _ffi.f32(bodies).reshape(-1, 12)
+    return table, mats
+
+
+def _pixel_map(who: str, pixel_map):
+    """(ax, bx, ay, by) of Upscaler.pixel_map as four floats; `who` is the class named in the refusal."""
+    m = [float(v) for v in pixel_map]
+    if len(m) != 4:
+        raise TraceHipError(f"{who}: pixel_map must be (ax, bx, ay, by), not {pixel_map!r}")
+    return m
 
 
 # ---- edge-avoiding denoiser (include/tracehip.h, trhip_denoise) ----------------------------------------------------------------------------
@@ -1682,20 +1656,14 @@ class Denoiser:
     def __init__(self, iterations: Optional[int] = None, demodulate: bool = True, sigma_colour: Optional[float] = None, sigma_normal: Optional[float] = None,
                  sigma_plane: Optional[float] = None, albedo_floor: Optional[float] = None, min_coverage: Optional[float] = None, variance_sigma: Optional[float] = None,
                  var_eps: Optional[float] = None):
-        p = _ffi.DenoiseParams()
-        rc = _ffi.lib().trhip_denoise_default_params(C.byref(p))
-        if rc:
-            raise TraceHipError(f"trhip_denoise_default_params failed ({rc})")
+        p = _ffi.default_params(_ffi.DenoiseParams, "trhip_denoise_default_params")
         for name, value in (("iterations", iterations), ("sigma_colour", sigma_colour), ("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane), ("albedo_floor", albedo_floor),
                             ("min_coverage", min_coverage)):
             if value is not None:
                 setattr(p, name, value)
         p.flags = _ffi.DENOISE_DEMODULATE if demodulate else 0
         self.params = p
-        vp = _ffi.DenoiseVarParams()
-        rc = _ffi.lib().trhip_denoise_var_default_params(C.byref(vp))
-        if rc:
-            raise TraceHipError(f"trhip_denoise_var_default_params failed ({rc})")
+        vp = _ffi.default_params(_ffi.DenoiseVarParams, "trhip_denoise_var_default_params")
         self.variance_sigma = float(vp.base.sigma_colour if variance_sigma is None else variance_sigma)
         self.var_eps = float(vp.var_eps if var_eps is None else var_eps)
         self.stats: Optional[_ffi.Stats] = None
@@ -1726,14 +1694,12 @@ class Denoiser:
         ctx = ctx or _ffi.default_context()
         st, vp = _ffi.Stats(), self._var_params()
         ctx.check(_ffi.lib().trhip_denoise_var_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), C.c_void_p(d_variance), int(width), int(height), C.byref(vp), C.c_void_p(d_out),
-                                                      C.c_void_p(d_out_variance) if d_out_variance else None, C.byref(st)))
+                                                      _ffi.dptr(d_out_variance), C.byref(st)))
         self.stats = st
 
     def denoise(self, xyzw: np.ndarray, planes: np.ndarray, ctx: Optional[_ffi.Context] = None) -> np.ndarray:
         """xyzw: (H, W, 4) as PathIntegrator.render returns it; planes: (H, W, 3, 4) as AOVIntegrator.render(...).planes.  Returns the denoised (H, W, 4)."""
-        xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
-        if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
-            raise TraceHipError(f"denoise: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
+        xyzw, planes = _film_and_planes("denoise", xyzw, planes)
         ctx = ctx or _ffi.default_context()
         h, w = xyzw.shape[:2]
         out, st = np.empty_like(xyzw), _ffi.Stats()
@@ -1794,10 +1760,7 @@ class Upscaler:
 
     def __init__(self, radius: Optional[int] = None, demodulate: Optional[bool] = None, coverage: Optional[bool] = None, sigma_normal: Optional[float] = None, sigma_plane: Optional[float] = None,
                  albedo_floor: Optional[float] = None, min_coverage: Optional[float] = None):
-        p = _ffi.UpscaleParams()
-        rc = _ffi.lib().trhip_upscale_default_params(C.byref(p))
-        if rc:
-            raise TraceHipError(f"trhip_upscale_default_params failed ({rc})")
+        p = _ffi.default_params(_ffi.UpscaleParams, "trhip_upscale_default_params")
         if radius is not None:
             if int(radius) != radius or not 0 <= radius < 2 ** 32:
                 raise TraceHipError(f"Upscaler: radius must be 1 or 2, not {radius!r}")
@@ -1852,18 +1815,13 @@ class Upscaler:
 
     def _params_for(self, pixel_map) -> _ffi.UpscaleParams:
         p = _ffi.UpscaleParams.from_buffer_copy(self.params)
-        m = [float(v) for v in pixel_map]
-        if len(m) != 4:
-            raise TraceHipError(f"Upscaler: pixel_map must be (ax, bx, ay, by), not {pixel_map!r}")
-        p.lo_from_hi[:] = m
+        p.lo_from_hi[:] = _pixel_map("Upscaler", pixel_map)
         return p
 
     def upscale(self, lo_xyzw: np.ndarray, lo_planes: np.ndarray, hi_planes: np.ndarray, pixel_map, ctx: Optional[_ffi.Context] = None):
         """lo_xyzw (h, w, 4) and lo_planes (h, w, 3, 4) of the low-resolution camera, hi_planes (H, W, 3, 4) of the full-size one, pixel_map as `pixel_map` returns it.
         Returns (xyzw (H, W, 4), mask (H, W) uint8)."""
-        lo_xyzw, lo_planes, hi_planes = _ffi.f32(lo_xyzw), _ffi.f32(lo_planes), _ffi.f32(hi_planes)
-        if lo_xyzw.ndim != 3 or lo_xyzw.shape[2] != 4 or lo_planes.shape != lo_xyzw.shape[:2] + (3, 4) or hi_planes.ndim != 4 or hi_planes.shape[2:] != (3, 4):
-            raise TraceHipError(f"upscale: lo_xyzw must be (h, w, 4), lo_planes (h, w, 3, 4) and hi_planes (H, W, 3, 4), not {lo_xyzw.shape}, {lo_planes.shape} and {hi_planes.shape}")
+        lo_xyzw, lo_planes, hi_planes = _low_and_high("upscale", lo_xyzw, lo_planes, hi_planes)
         p = self._params_for(pixel_map)
         ctx = ctx or _ffi.default_context()
         (lh, lw), (h, w) = lo_xyzw.shape[:2], hi_planes.shape[:2]
@@ -1880,7 +1838,7 @@ class Upscaler:
         ctx = ctx or _ffi.default_context()
         st = _ffi.Stats()
         ctx.check(_ffi.lib().trhip_upscale_device(ctx._h, C.c_void_p(d_lo_xyzw), C.c_void_p(d_lo_planes), int(lo_width), int(lo_height), C.c_void_p(d_hi_planes), int(width), int(height),
-                                                  C.byref(p), C.c_void_p(d_out), C.c_void_p(d_out_mask) if d_out_mask else None, C.byref(st)))
+                                                  C.byref(p), C.c_void_p(d_out), _ffi.dptr(d_out_mask), C.byref(st)))
         self.stats = st
 
     def render(self, scene: Scene, camera: PerspectiveCamera, sampler: SeededSampler, max_depth: int, factor=2, guide_spp: Optional[int] = None,
@@ -1927,10 +1885,7 @@ class Display:
     def __init__(self, curve=None, transfer=None, auto_exposure: Optional[bool] = None, flip_rows: Optional[bool] = None, exposure: Optional[float] = None, key: Optional[float] = None,
                  percentile: Optional[float] = None, adapt_rate: Optional[float] = None, min_exposure: Optional[float] = None, max_exposure: Optional[float] = None,
                  white: Optional[float] = None):
-        p = _ffi.DisplayParams()
-        rc = _ffi.lib().trhip_display_default_params(C.byref(p))
-        if rc:
-            raise TraceHipError(f"trhip_display_default_params failed ({rc})")
+        p = _ffi.default_params(_ffi.DisplayParams, "trhip_display_default_params")
         for name, value, names in (("curve", curve, _ffi.DISPLAY_CURVES), ("transfer", transfer, _ffi.DISPLAY_TRANSFERS)):
             if value is not None:
                 number = names.get(value.lower()) if isinstance(value, str) else value
@@ -1977,7 +1932,7 @@ class Display:
         hist = np.empty(256, np.uint32) if want_histogram else None
         new_state = _ffi.DisplayState.from_buffer_copy(state) if state is not None else None
         ctx.check(_ffi.lib().trhip_display(ctx._h, _ffi.fptr(xyzw), w, h, float(scale), C.byref(self.params), C.byref(new_state) if new_state is not None else None,
-                                           out.ctypes.data_as(C.POINTER(C.c_uint8)), _ffi.u32ptr(hist) if hist is not None else None, C.byref(st)))
+                                           out.ctypes.data_as(C.POINTER(C.c_uint8)), _ffi.optr(hist), C.byref(st)))
         self.stats = st
         if want_histogram:
             return out, new_state, hist
@@ -1989,8 +1944,8 @@ class Display:
         copied to the host."""
         ctx = ctx or _ffi.default_context()
         st = _ffi.Stats()
-        ctx.check(_ffi.lib().trhip_display_device(ctx._h, C.c_void_p(d_xyzw), int(width), int(height), float(scale), C.byref(self.params), C.c_void_p(d_state) if d_state else None,
-                                                  C.c_void_p(d_out_rgba), C.c_void_p(d_histogram) if d_histogram else None, C.byref(st)))
+        ctx.check(_ffi.lib().trhip_display_device(ctx._h, C.c_void_p(d_xyzw), int(width), int(height), float(scale), C.byref(self.params), _ffi.dptr(d_state),
+                                                  C.c_void_p(d_out_rgba), _ffi.dptr(d_histogram), C.byref(st)))
         self.stats = st
 
     def save(self, film: "Film", ctx: Optional[_ffi.Context] = None) -> str:
@@ -2049,10 +2004,7 @@ class TemporalAccumulator:
         if not moments and (spatial_below is not None or albedo_floor is not None):
             raise TraceHipError("TemporalAccumulator: spatial_below and albedo_floor belong to moments=True")
         if moments:
-            mp = _ffi.TemporalMomentsParams()
-            rc = _ffi.lib().trhip_temporal_moments_default_params(C.byref(mp))
-            if rc:
-                raise TraceHipError(f"trhip_temporal_moments_default_params failed ({rc})")
+            mp = _ffi.default_params(_ffi.TemporalMomentsParams, "trhip_temporal_moments_default_params")
             if spatial_below is not None:
                 mp.spatial_below = spatial_below
             if albedo_floor is not None:
@@ -2060,15 +2012,9 @@ class TemporalAccumulator:
             mp.flags = _ffi.DENOISE_DEMODULATE if demodulate else 0
             self.moments_params, p = mp, mp.base  # a view, as below
         elif clip_gamma is None and clip_radius is None:
-            p = _ffi.TemporalParams()
-            rc = _ffi.lib().trhip_temporal_default_params(C.byref(p))
-            if rc:
-                raise TraceHipError(f"trhip_temporal_default_params failed ({rc})")
+            p = _ffi.default_params(_ffi.TemporalParams, "trhip_temporal_default_params")
         else:
-            cp = _ffi.TemporalClipParams()
-            rc = _ffi.lib().trhip_temporal_clip_default_params(C.byref(cp))
-            if rc:
-                raise TraceHipError(f"trhip_temporal_clip_default_params failed ({rc})")
+            cp = _ffi.default_params(_ffi.TemporalClipParams, "trhip_temporal_clip_default_params")
             if clip_gamma is not None:
                 cp.clip_gamma = clip_gamma
             if clip_radius is not None:
@@ -2077,10 +2023,7 @@ class TemporalAccumulator:
                 cp.clip_radius = int(clip_radius)
             self.clip_params, p = cp, cp.base  # p is a view of cp.base: the fields set below land in the block that is passed
             if carry_bodies:
-                cm = _ffi.TemporalClipMotionParams()
-                rc = _ffi.lib().trhip_temporal_clip_motion_default_params(C.byref(cm))
-                if rc:
-                    raise TraceHipError(f"trhip_temporal_clip_motion_default_params failed ({rc})")
+                cm = _ffi.default_params(_ffi.TemporalClipMotionParams, "trhip_temporal_clip_motion_default_params")
                 if clip_max_history is not None:
                     cm.clip_max_history = clip_max_history
                 self.clip_motion_params = cm  # gamma, radius and the base are taken from clip_params / params when a call is made
@@ -2114,68 +2057,12 @@ class TemporalAccumulator:
         cm.clip_gamma, cm.clip_radius = self.clip_params.clip_gamma, self.clip_params.clip_radius
         return cm
 
-    def accumulate(self, xyzw: np.ndarray, planes: np.ndarray, history: Optional[np.ndarray], prev_camera, ctx: Optional[_ffi.Context] = None):
-        """xyzw: (H, W, 4) as PathIntegrator.render returns it; planes: (H, W, 3, 4) as AOVIntegrator.render(...).planes; history: the second result of the previous
-        frame's call, or None.  Returns (xyzw, history) of this frame; the xyzw goes into Denoiser.denoise with the same planes."""
-        if self.clip_motion_params is not None:  # no id plane: every pixel is static
-            return self._accumulate_clip_motion("accumulate", xyzw, planes, history, None, None, None, prev_camera, ctx)
-        xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
-        if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
-            raise TraceHipError(f"accumulate: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
-        if history is not None:
-            history = _ffi.f32(history)
-            if history.shape != planes.shape:
-                raise TraceHipError(f"accumulate: history must be {planes.shape} like planes, not {history.shape}")
-        ctx = ctx or _ffi.default_context()
-        h, w = xyzw.shape[:2]
-        out, out_history, st = np.empty_like(xyzw), np.empty_like(planes), _ffi.Stats()
-        clipped = self.clip_params is not None
-        p = self._clip_params_for(prev_camera) if clipped else self._params_for(prev_camera)
-        entry = _ffi.lib().trhip_temporal_clip if clipped else _ffi.lib().trhip_temporal
-        ctx.check(entry(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(planes), _ffi.fptr(history) if history is not None else None, w, h, C.byref(p), _ffi.fptr(out), _ffi.fptr(out_history), C.byref(st)))
-        self.stats = st
-        return out, out_history
-
     def _moments_params_for(self, prev_camera) -> _ffi.TemporalMomentsParams:
         if self.moments_params is None:
             raise TraceHipError("TemporalAccumulator: accumulate_moments needs TemporalAccumulator(moments=True)")
         mp = _ffi.TemporalMomentsParams.from_buffer_copy(self.moments_params)
         mp.base = self._params_for(prev_camera)
         return mp
-
-    def accumulate_moments(self, xyzw: np.ndarray, planes: np.ndarray, history: Optional[np.ndarray], moments: Optional[np.ndarray], prev_camera,
-                           ctx: Optional[_ffi.Context] = None):
-        """`accumulate` with the moments: `moments` is (H, W, 2), the third result of the previous frame's call, None exactly when `history` is.  Returns (xyzw, history,
-        moments, variance (H, W)) of this frame; the variance goes into Denoiser.denoise_variance with the returned xyzw and the same planes."""
-        mp = self._moments_params_for(prev_camera)
-        xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
-        if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
-            raise TraceHipError(f"accumulate_moments: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
-        if (history is None) != (moments is None):
-            raise TraceHipError("accumulate_moments: moments must be None exactly when history is")
-        if history is not None:
-            history, moments = _ffi.f32(history), _ffi.f32(moments)
-            if history.shape != planes.shape or moments.shape != xyzw.shape[:2] + (2,):
-                raise TraceHipError(f"accumulate_moments: history must be {planes.shape} and moments {xyzw.shape[:2] + (2,)}, not {history.shape} and {moments.shape}")
-        ctx = ctx or _ffi.default_context()
-        h, w = xyzw.shape[:2]
-        out, out_history, out_moments, out_var, st = np.empty_like(xyzw), np.empty_like(planes), np.empty((h, w, 2), np.float32), np.empty((h, w), np.float32), _ffi.Stats()
-        ctx.check(_ffi.lib().trhip_temporal_moments(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(planes), _ffi.fptr(history) if history is not None else None,
-                                                    _ffi.fptr(moments) if moments is not None else None, w, h, C.byref(mp), _ffi.fptr(out), _ffi.fptr(out_history), _ffi.fptr(out_moments),
-                                                    _ffi.fptr(out_var), C.byref(st)))
-        self.stats = st
-        return out, out_history, out_moments, out_var
-
-    def accumulate_moments_device(self, d_xyzw: int, d_planes: int, d_history: Optional[int], d_moments: Optional[int], width: int, height: int, prev_camera, d_out: int,
-                                  d_out_history: int, d_out_moments: int, d_out_variance: int, ctx: Optional[_ffi.Context] = None) -> None:
-        """The same on device pointers (d_out may equal d_xyzw; d_history and d_moments may both be None); nothing is copied to the host."""
-        mp = self._moments_params_for(prev_camera)
-        ctx = ctx or _ffi.default_context()
-        st = _ffi.Stats()
-        ctx.check(_ffi.lib().trhip_temporal_moments_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), C.c_void_p(d_history) if d_history else None,
-                                                           C.c_void_p(d_moments) if d_moments else None, int(width), int(height), C.byref(mp), C.c_void_p(d_out), C.c_void_p(d_out_history),
-                                                           C.c_void_p(d_out_moments), C.c_void_p(d_out_variance), C.byref(st)))
-        self.stats = st
 
     def _motion_params_for(self, prev_camera, n_prims: int, n_bodies: int) -> _ffi.TemporalMotionParams:
         if self.clip_params is not None or self.moments_params is not None:
@@ -2187,146 +2074,145 @@ class TemporalAccumulator:
         mp.n_prims, mp.n_bodies = int(n_prims), int(n_bodies)
         return mp
 
+    def _split_params_for(self, prev_camera, n_prims: int, n_bodies: int) -> _ffi.TemporalMotionParams:
+        if self.clip_params is not None or self.moments_params is not None:
+            raise TraceHipError("TemporalAccumulator: accumulate_split needs a plain accumulator (trhip_temporal_split neither clips nor carries moments)")
+        return self._motion_params_for(prev_camera, n_prims, n_bodies)
+
     @staticmethod
     def prev_from_cur(motion) -> np.ndarray:
         """The (3, 4) Float32 matrix trhip_temporal_motion wants for a body that `motion` (a Transformation) carried from the previous frame's pose to this one: the first
         three rows of its inv_m, each entry rounded to Float32 once."""
         return np.ascontiguousarray(np.asarray(motion.inv_m, np.float64)[:3, :4], dtype=np.float32)
 
+    # The calls.  Five entries serve the colour passes, their argument lists extensions of one another: trhip_temporal and trhip_temporal_clip take (film, planes, history);
+    # trhip_temporal_motion and trhip_temporal_clip_motion the id plane, the body table and the body matrices after them; trhip_temporal_split those and the direct film
+    # after the film.  Each public method names its entry; _accumulate / _accumulate_device make the call.
+    def _accumulate_entry(self) -> str:
+        """What accumulate / accumulate_device call: with carry_bodies trhip_temporal_clip_motion (no id plane: every pixel static), with clipping trhip_temporal_clip."""
+        if self.clip_motion_params is not None:
+            return "trhip_temporal_clip_motion"
+        return "trhip_temporal_clip" if self.clip_params is not None else "trhip_temporal"
+
+    def _motion_entry(self) -> str:
+        """What accumulate_motion / accumulate_motion_device call."""
+        return "trhip_temporal_clip_motion" if self.clip_motion_params is not None else "trhip_temporal_motion"
+
+    def _block_for(self, entry: str, prev_camera, n_prims: int, n_bodies: int):
+        """The parameter block `entry` takes (and the refusal of an accumulator of the wrong kind)."""
+        if entry == "trhip_temporal":
+            return self._params_for(prev_camera)
+        if entry == "trhip_temporal_clip":
+            return self._clip_params_for(prev_camera)
+        if entry == "trhip_temporal_clip_motion":
+            return self._clip_motion_params_for(prev_camera, n_prims, n_bodies)
+        if entry == "trhip_temporal_split":
+            return self._split_params_for(prev_camera, n_prims, n_bodies)
+        return self._motion_params_for(prev_camera, n_prims, n_bodies)
+
+    def _accumulate(self, who: str, entry: str, xyzw, direct, planes, history, ids, body_of_prim, bodies, prev_camera, ctx):
+        """The host call of accumulate, accumulate_motion and accumulate_split (`who`, for the refusals) through `entry`: (xyzw, history) of this frame."""
+        xyzw, planes = _film_and_planes(who, xyzw, planes)
+        if direct is not None:
+            direct = _ffi.f32(direct)
+            if direct.shape != xyzw.shape:
+                raise TraceHipError(f"{who}: direct must be {xyzw.shape} like xyzw, not {direct.shape}")
+        history = _history_like(who, history, planes)
+        h, w = xyzw.shape[:2]
+        if ids is not None or entry == "trhip_temporal_motion":  # the one entry whose id plane is not optional
+            ids = _id_plane(who, ids, h, w)
+        table, mats = _body_tables(ids, body_of_prim, bodies)
+        p = self._block_for(entry, prev_camera, 0 if table is None else table.size, 0 if mats is None else mats.shape[0])
+        ctx = ctx or _ffi.default_context()
+        out, out_history, st = np.empty_like(xyzw), np.empty_like(planes), _ffi.Stats()
+        args = [_ffi.fptr(xyzw)] + ([_ffi.optr(direct)] if entry == "trhip_temporal_split" else []) + [_ffi.fptr(planes), _ffi.optr(history)]
+        if entry not in ("trhip_temporal", "trhip_temporal_clip"):
+            args += [_ffi.optr(ids), _ffi.optr(table), _ffi.optr(mats)]
+        ctx.check(getattr(_ffi.lib(), entry)(ctx._h, *args, w, h, C.byref(p), _ffi.fptr(out), _ffi.fptr(out_history), C.byref(st)))
+        self.stats = st
+        return out, out_history
+
+    def _accumulate_device(self, entry: str, d_xyzw, d_direct, d_planes, d_history, d_ids, d_body_of_prim, n_prims, d_bodies, n_bodies, width, height, prev_camera, d_out,
+                           d_out_history, ctx) -> None:
+        """The same through `entry`_device, on device pointers; a table that is not given counts no entries."""
+        p = self._block_for(entry, prev_camera, n_prims if d_body_of_prim else 0, n_bodies if d_bodies else 0)
+        ctx = ctx or _ffi.default_context()
+        st = _ffi.Stats()
+        args = [C.c_void_p(d_xyzw)] + ([_ffi.dptr(d_direct)] if entry == "trhip_temporal_split" else []) + [C.c_void_p(d_planes), _ffi.dptr(d_history)]
+        if entry not in ("trhip_temporal", "trhip_temporal_clip"):
+            args += [_ffi.dptr(d_ids), _ffi.dptr(d_body_of_prim), _ffi.dptr(d_bodies)]
+        ctx.check(getattr(_ffi.lib(), entry + "_device")(ctx._h, *args, int(width), int(height), C.byref(p), C.c_void_p(d_out), C.c_void_p(d_out_history), C.byref(st)))
+        self.stats = st
+
+    def accumulate(self, xyzw: np.ndarray, planes: np.ndarray, history: Optional[np.ndarray], prev_camera, ctx: Optional[_ffi.Context] = None):
+        """xyzw: (H, W, 4) as PathIntegrator.render returns it; planes: (H, W, 3, 4) as AOVIntegrator.render(...).planes; history: the second result of the previous
+        frame's call, or None.  Returns (xyzw, history) of this frame; the xyzw goes into Denoiser.denoise with the same planes."""
+        return self._accumulate("accumulate", self._accumulate_entry(), xyzw, None, planes, history, None, None, None, prev_camera, ctx)
+
+    def accumulate_device(self, d_xyzw: int, d_planes: int, d_history: Optional[int], width: int, height: int, prev_camera, d_out: int, d_out_history: int,
+                          ctx: Optional[_ffi.Context] = None) -> None:
+        """The same on device pointers (d_out may equal d_xyzw, d_history may be None); nothing is copied to the host."""
+        self._accumulate_device(self._accumulate_entry(), d_xyzw, None, d_planes, d_history, None, None, 0, None, 0, width, height, prev_camera, d_out, d_out_history, ctx)
+
     def accumulate_motion(self, xyzw: np.ndarray, planes: np.ndarray, history: Optional[np.ndarray], ids: np.ndarray, body_of_prim: Optional[np.ndarray],
                           bodies: Optional[np.ndarray], prev_camera, ctx: Optional[_ffi.Context] = None):
         """`accumulate` for a scene with moving rigid bodies (trhip_temporal_motion; docs/design/20-motion.md).  ids: (H, W) of _ffi.AOV_ID_DTYPE, this frame's
         AOVIntegrator.ids; body_of_prim: uint32 per ordered-primitive slot (FlatScene.body_table) or None; bodies: (n_bodies, 3, 4) prev_from_cur matrices or None.
         Returns (xyzw, history) of this frame.  An accumulator built with carry_bodies=True makes the same call through trhip_temporal_clip_motion."""
-        if self.clip_motion_params is not None:
-            return self._accumulate_clip_motion("accumulate_motion", xyzw, planes, history, ids, body_of_prim, bodies, prev_camera, ctx)
-        xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
-        if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
-            raise TraceHipError(f"accumulate_motion: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
-        if history is not None:
-            history = _ffi.f32(history)
-            if history.shape != planes.shape:
-                raise TraceHipError(f"accumulate_motion: history must be {planes.shape} like planes, not {history.shape}")
-        ids = np.ascontiguousarray(ids)
-        h, w = xyzw.shape[:2]
-        if ids.nbytes != h * w * 16:
-            raise TraceHipError(f"accumulate_motion: ids must hold one 16-byte record per pixel, not {ids.nbytes} bytes for {h} x {w}")
-        table = None if body_of_prim is None else np.ascontiguousarray(body_of_prim, dtype=np.uint32).reshape(-1)
-        mats = None if bodies is None else _ffi.f32(bodies).reshape(-1, 12)
-        ctx = ctx or _ffi.default_context()
-        out, out_history, st = np.empty_like(xyzw), np.empty_like(planes), _ffi.Stats()
-        p = self._motion_params_for(prev_camera, 0 if table is None else table.size, 0 if mats is None else mats.shape[0])
-        ctx.check(_ffi.lib().trhip_temporal_motion(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(planes), _ffi.fptr(history) if history is not None else None, ids.ctypes.data_as(C.c_void_p),
-                                                   _ffi.u32ptr(table) if table is not None else None, _ffi.fptr(mats) if mats is not None else None, w, h, C.byref(p), _ffi.fptr(out),
-                                                   _ffi.fptr(out_history), C.byref(st)))
-        self.stats = st
-        return out, out_history
+        return self._accumulate("accumulate_motion", self._motion_entry(), xyzw, None, planes, history, ids, body_of_prim, bodies, prev_camera, ctx)
 
-    def _split_params_for(self, prev_camera, n_prims: int, n_bodies: int) -> _ffi.TemporalMotionParams:
-        if self.clip_params is not None or self.moments_params is not None:
-            raise TraceHipError("TemporalAccumulator: accumulate_split needs a plain accumulator (trhip_temporal_split neither clips nor carries moments)")
-        return self._motion_params_for(prev_camera, n_prims, n_bodies)
+    def accumulate_motion_device(self, d_xyzw: int, d_planes: int, d_history: Optional[int], d_ids: int, d_body_of_prim: Optional[int], n_prims: int, d_bodies: Optional[int],
+                                 n_bodies: int, width: int, height: int, prev_camera, d_out: int, d_out_history: int, ctx: Optional[_ffi.Context] = None) -> None:
+        """The same on device pointers (d_out may equal d_xyzw; d_history, d_body_of_prim and d_bodies may be None); nothing is copied to the host."""
+        self._accumulate_device(self._motion_entry(), d_xyzw, None, d_planes, d_history, d_ids, d_body_of_prim, n_prims, d_bodies, n_bodies, width, height, prev_camera, d_out,
+                                d_out_history, ctx)
 
     def accumulate_split(self, xyzw: np.ndarray, direct: Optional[np.ndarray], planes: np.ndarray, history: Optional[np.ndarray], ids: Optional[np.ndarray],
                          body_of_prim: Optional[np.ndarray], bodies: Optional[np.ndarray], prev_camera, ctx: Optional[_ffi.Context] = None):
         """`accumulate_motion` on xyzw.xyz - direct.xyz (a plain accumulator only; trhip_temporal_split, docs/design/23-direct-split.md): `direct` is the (H, W, 4) film of the
         frame's first-hit direct light, or None (then `accumulate_motion`'s result bit for bit).  ids may be None when there is no table: every pixel is static.  The returned
         film and history hold the indirect remainder; Film.add puts `direct` back after the filter."""
-        xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
-        if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
-            raise TraceHipError(f"accumulate_split: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
-        if direct is not None:
-            direct = _ffi.f32(direct)
-            if direct.shape != xyzw.shape:
-                raise TraceHipError(f"accumulate_split: direct must be {xyzw.shape} like xyzw, not {direct.shape}")
-        if history is not None:
-            history = _ffi.f32(history)
-            if history.shape != planes.shape:
-                raise TraceHipError(f"accumulate_split: history must be {planes.shape} like planes, not {history.shape}")
-        h, w = xyzw.shape[:2]
-        if ids is not None:
-            ids = np.ascontiguousarray(ids)
-            if ids.nbytes != h * w * 16:
-                raise TraceHipError(f"accumulate_split: ids must hold one 16-byte record per pixel, not {ids.nbytes} bytes for {h} x {w}")
-        table = None if body_of_prim is None or ids is None else np.ascontiguousarray(body_of_prim, dtype=np.uint32).reshape(-1)
-        mats = None if bodies is None or ids is None else _ffi.f32(bodies).reshape(-1, 12)
-        p = self._split_params_for(prev_camera, 0 if table is None else table.size, 0 if mats is None else mats.shape[0])
-        ctx = ctx or _ffi.default_context()
-        out, out_history, st = np.empty_like(xyzw), np.empty_like(planes), _ffi.Stats()
-        ctx.check(_ffi.lib().trhip_temporal_split(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(direct) if direct is not None else None, _ffi.fptr(planes),
-                                                  _ffi.fptr(history) if history is not None else None, ids.ctypes.data_as(C.c_void_p) if ids is not None else None,
-                                                  _ffi.u32ptr(table) if table is not None else None, _ffi.fptr(mats) if mats is not None else None, w, h, C.byref(p), _ffi.fptr(out),
-                                                  _ffi.fptr(out_history), C.byref(st)))
-        self.stats = st
-        return out, out_history
+        return self._accumulate("accumulate_split", "trhip_temporal_split", xyzw, direct, planes, history, ids, body_of_prim, bodies, prev_camera, ctx)
 
     def accumulate_split_device(self, d_xyzw: int, d_direct: Optional[int], d_planes: int, d_history: Optional[int], d_ids: Optional[int], d_body_of_prim: Optional[int], n_prims: int,
                                 d_bodies: Optional[int], n_bodies: int, width: int, height: int, prev_camera, d_out: int, d_out_history: int,
                                 ctx: Optional[_ffi.Context] = None) -> None:
         """The same on device pointers (d_out may equal d_xyzw; d_direct, d_history, d_body_of_prim, d_bodies and, without a table, d_ids may be None); nothing is copied to
         the host."""
-        st, p = _ffi.Stats(), self._split_params_for(prev_camera, n_prims if d_body_of_prim and d_ids else 0, n_bodies if d_bodies and d_ids else 0)
-        ctx = ctx or _ffi.default_context()
-        ctx.check(_ffi.lib().trhip_temporal_split_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_direct) if d_direct else None, C.c_void_p(d_planes),
-                                                         C.c_void_p(d_history) if d_history else None, C.c_void_p(d_ids) if d_ids else None,
-                                                         C.c_void_p(d_body_of_prim) if d_body_of_prim else None, C.c_void_p(d_bodies) if d_bodies else None, int(width), int(height),
-                                                         C.byref(p), C.c_void_p(d_out), C.c_void_p(d_out_history), C.byref(st)))
-        self.stats = st
+        if not d_ids:  # every pixel is static: the tables count no entries
+            n_prims = n_bodies = 0
+        self._accumulate_device("trhip_temporal_split", d_xyzw, d_direct, d_planes, d_history, d_ids, d_body_of_prim, n_prims, d_bodies, n_bodies, width, height, prev_camera, d_out,
+                                d_out_history, ctx)
 
-    def _accumulate_clip_motion(self, who, xyzw, planes, history, ids, body_of_prim, bodies, prev_camera, ctx):
-        """The host call of an accumulator built with carry_bodies=True (trhip_temporal_clip_motion); ids None: every pixel is static."""
-        xyzw, planes = _ffi.f32(xyzw), _ffi.f32(planes)
-        if xyzw.ndim != 3 or xyzw.shape[2] != 4 or planes.shape != xyzw.shape[:2] + (3, 4):
-            raise TraceHipError(f"{who}: xyzw must be (H, W, 4) and planes (H, W, 3, 4), not {xyzw.shape} and {planes.shape}")
+    def accumulate_moments(self, xyzw: np.ndarray, planes: np.ndarray, history: Optional[np.ndarray], moments: Optional[np.ndarray], prev_camera,
+                           ctx: Optional[_ffi.Context] = None):
+        """`accumulate` with the moments: `moments` is (H, W, 2), the third result of the previous frame's call, None exactly when `history` is.  Returns (xyzw, history,
+        moments, variance (H, W)) of this frame; the variance goes into Denoiser.denoise_variance with the returned xyzw and the same planes."""
+        mp = self._moments_params_for(prev_camera)
+        xyzw, planes = _film_and_planes("accumulate_moments", xyzw, planes)
+        if (history is None) != (moments is None):
+            raise TraceHipError("accumulate_moments: moments must be None exactly when history is")
         if history is not None:
-            history = _ffi.f32(history)
-            if history.shape != planes.shape:
-                raise TraceHipError(f"{who}: history must be {planes.shape} like planes, not {history.shape}")
+            history, moments = _ffi.f32(history), _ffi.f32(moments)
+            if history.shape != planes.shape or moments.shape != xyzw.shape[:2] + (2,):
+                raise TraceHipError(f"accumulate_moments: history must be {planes.shape} and moments {xyzw.shape[:2] + (2,)}, not {history.shape} and {moments.shape}")
+        ctx = ctx or _ffi.default_context()
         h, w = xyzw.shape[:2]
-        if ids is not None:
-            ids = np.ascontiguousarray(ids)
-            if ids.nbytes != h * w * 16:
-                raise TraceHipError(f"{who}: ids must hold one 16-byte record per pixel, not {ids.nbytes} bytes for {h} x {w}")
-        table = None if body_of_prim is None or ids is None else np.ascontiguousarray(body_of_prim, dtype=np.uint32).reshape(-1)
-        mats = None if bodies is None or ids is None else _ffi.f32(bodies).reshape(-1, 12)
-        ctx = ctx or _ffi.default_context()
-        out, out_history, st = np.empty_like(xyzw), np.empty_like(planes), _ffi.Stats()
-        p = self._clip_motion_params_for(prev_camera, 0 if table is None else table.size, 0 if mats is None else mats.shape[0])
-        ctx.check(_ffi.lib().trhip_temporal_clip_motion(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(planes), _ffi.fptr(history) if history is not None else None,
-                                                        ids.ctypes.data_as(C.c_void_p) if ids is not None else None, _ffi.u32ptr(table) if table is not None else None,
-                                                        _ffi.fptr(mats) if mats is not None else None, w, h, C.byref(p), _ffi.fptr(out), _ffi.fptr(out_history), C.byref(st)))
+        out, out_history, out_moments, out_var, st = np.empty_like(xyzw), np.empty_like(planes), np.empty((h, w, 2), np.float32), np.empty((h, w), np.float32), _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_temporal_moments(ctx._h, _ffi.fptr(xyzw), _ffi.fptr(planes), _ffi.optr(history), _ffi.optr(moments), w, h, C.byref(mp), _ffi.fptr(out),
+                                                    _ffi.fptr(out_history), _ffi.fptr(out_moments), _ffi.fptr(out_var), C.byref(st)))
         self.stats = st
-        return out, out_history
+        return out, out_history, out_moments, out_var
 
-    def accumulate_motion_device(self, d_xyzw: int, d_planes: int, d_history: Optional[int], d_ids: int, d_body_of_prim: Optional[int], n_prims: int, d_bodies: Optional[int],
-                                 n_bodies: int, width: int, height: int, prev_camera, d_out: int, d_out_history: int, ctx: Optional[_ffi.Context] = None) -> None:
-        """The same on device pointers (d_out may equal d_xyzw; d_history, d_body_of_prim and d_bodies may be None); nothing is copied to the host."""
+    def accumulate_moments_device(self, d_xyzw: int, d_planes: int, d_history: Optional[int], d_moments: Optional[int], width: int, height: int, prev_camera, d_out: int,
+                                  d_out_history: int, d_out_moments: int, d_out_variance: int, ctx: Optional[_ffi.Context] = None) -> None:
+        """The same on device pointers (d_out may equal d_xyzw; d_history and d_moments may both be None); nothing is copied to the host."""
+        mp = self._moments_params_for(prev_camera)
         ctx = ctx or _ffi.default_context()
-        if self.clip_motion_params is not None:
-            st, p = _ffi.Stats(), self._clip_motion_params_for(prev_camera, n_prims if d_body_of_prim else 0, n_bodies if d_bodies else 0)
-            ctx.check(_ffi.lib().trhip_temporal_clip_motion_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), C.c_void_p(d_history) if d_history else None,
-                                                                   C.c_void_p(d_ids) if d_ids else None, C.c_void_p(d_body_of_prim) if d_body_of_prim else None,
-                                                                   C.c_void_p(d_bodies) if d_bodies else None, int(width), int(height), C.byref(p), C.c_void_p(d_out),
-                                                                   C.c_void_p(d_out_history), C.byref(st)))
-            self.stats = st
-            return
-        st, p = _ffi.Stats(), self._motion_params_for(prev_camera, n_prims if d_body_of_prim else 0, n_bodies if d_bodies else 0)
-        ctx.check(_ffi.lib().trhip_temporal_motion_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), C.c_void_p(d_history) if d_history else None, C.c_void_p(d_ids),
-                                                          C.c_void_p(d_body_of_prim) if d_body_of_prim else None, C.c_void_p(d_bodies) if d_bodies else None, int(width), int(height),
-                                                          C.byref(p), C.c_void_p(d_out), C.c_void_p(d_out_history), C.byref(st)))
-        self.stats = st
-
-    def accumulate_device(self, d_xyzw: int, d_planes: int, d_history: Optional[int], width: int, height: int, prev_camera, d_out: int, d_out_history: int,
-                          ctx: Optional[_ffi.Context] = None) -> None:
-        """The same on device pointers (d_out may equal d_xyzw, d_history may be None); nothing is copied to the host."""
-        if self.clip_motion_params is not None:  # no id plane: every pixel is static
-            return self.accumulate_motion_device(d_xyzw, d_planes, d_history, None, None, 0, None, 0, width, height, prev_camera, d_out, d_out_history, ctx)
-        ctx = ctx or _ffi.default_context()
-        st, clipped = _ffi.Stats(), self.clip_params is not None
-        p = self._clip_params_for(prev_camera) if clipped else self._params_for(prev_camera)
-        entry = _ffi.lib().trhip_temporal_clip_device if clipped else _ffi.lib().trhip_temporal_device
-        ctx.check(entry(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), C.c_void_p(d_history) if d_history else None, int(width), int(height), C.byref(p), C.c_void_p(d_out),
-                        C.c_void_p(d_out_history), C.byref(st)))
+        st = _ffi.Stats()
+        ctx.check(_ffi.lib().trhip_temporal_moments_device(ctx._h, C.c_void_p(d_xyzw), C.c_void_p(d_planes), _ffi.dptr(d_history), _ffi.dptr(d_moments), int(width), int(height),
+                                                           C.byref(mp), C.c_void_p(d_out), C.c_void_p(d_out_history), C.c_void_p(d_out_moments), C.c_void_p(d_out_variance),
+                                                           C.byref(st)))
         self.stats = st
 
 
@@ -2349,10 +2235,7 @@ class TemporalUpsampler:
                  confidence_sharpness: Optional[float] = None, min_coverage: Optional[float] = None, jitter: Optional[str] = "grid", carry_bodies: bool = False):
         if jitter not in ("grid", "halton", None):
             raise TraceHipError(f"TemporalUpsampler: jitter must be 'grid', 'halton' or None, not {jitter!r}")
-        p = _ffi.TemporalUpsampleParams()
-        rc = _ffi.lib().trhip_temporal_upsample_default_params(C.byref(p))
-        if rc:
-            raise TraceHipError(f"trhip_temporal_upsample_default_params failed ({rc})")
+        p = _ffi.default_params(_ffi.TemporalUpsampleParams, "trhip_temporal_upsample_default_params")
         if radius is not None:
             if int(radius) != radius or not 0 <= radius < 2 ** 32:
                 raise TraceHipError(f"TemporalUpsampler: radius must be 1 or 2, not {radius!r}")
@@ -2390,10 +2273,7 @@ class TemporalUpsampler:
     def _params_for(self, pixel_map, prev_camera) -> _ffi.TemporalUpsampleParams:
         """`pixel_map`: Upscaler.pixel_map of this frame's cameras; `prev_camera`: the previous frame's FULL-SIZE PerspectiveCamera, its world_to_pixel() matrix, or None."""
         p = _ffi.TemporalUpsampleParams.from_buffer_copy(self.params)
-        m = [float(v) for v in pixel_map]
-        if len(m) != 4:
-            raise TraceHipError(f"TemporalUpsampler: pixel_map must be (ax, bx, ay, by), not {pixel_map!r}")
-        p.lo_from_hi[:] = m
+        p.lo_from_hi[:] = _pixel_map("TemporalUpsampler", pixel_map)
         if prev_camera is not None:
             w2p = prev_camera.world_to_pixel() if hasattr(prev_camera, "world_to_pixel") else _ffi.f32(prev_camera)
             if w2p.size != 12:
@@ -2412,50 +2292,56 @@ class TemporalUpsampler:
         mp.n_prims, mp.n_bodies = int(n_prims), int(n_bodies)
         return mp
 
+    # The calls.  trhip_temporal_upsample_motion takes trhip_temporal_upsample's arguments with the id plane, the body table and the body matrices after the history.
+    def _accumulate(self, who: str, motion: bool, lo_xyzw, lo_planes, hi_planes, history, ids, body_of_prim, bodies, pixel_map, prev_camera, ctx):
+        """The host call of accumulate (trhip_temporal_upsample) and, with `motion`, of accumulate_motion (trhip_temporal_upsample_motion); `who` for the refusals."""
+        lo_xyzw, lo_planes, hi_planes = _low_and_high(who, lo_xyzw, lo_planes, hi_planes)
+        history = _history_like(who, history, hi_planes, "hi_planes")
+        (lh, lw), (h, w) = lo_xyzw.shape[:2], hi_planes.shape[:2]
+        if ids is not None:
+            ids = _id_plane(who, ids, h, w, "FULL-SIZE pixel")
+        table, mats = _body_tables(ids, body_of_prim, bodies)
+        if motion:
+            entry, p = "trhip_temporal_upsample_motion", self._motion_params_for(pixel_map, prev_camera, 0 if table is None else table.size, 0 if mats is None else mats.shape[0])
+            tables = [_ffi.optr(ids), _ffi.optr(table), _ffi.optr(mats)]
+        else:
+            entry, p, tables = "trhip_temporal_upsample", self._params_for(pixel_map, prev_camera), []
+        ctx = ctx or _ffi.default_context()
+        out, out_history, mask, st = np.empty((h, w, 4), np.float32), np.empty((h, w, 3, 4), np.float32), np.empty((h, w), np.uint8), _ffi.Stats()
+        ctx.check(getattr(_ffi.lib(), entry)(ctx._h, _ffi.fptr(lo_xyzw), _ffi.fptr(lo_planes), lw, lh, _ffi.fptr(hi_planes), _ffi.optr(history), *tables, w, h, C.byref(p),
+                                             _ffi.fptr(out), _ffi.fptr(out_history), mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st)))
+        self.stats = st
+        return out, out_history, mask
+
+    def _accumulate_device(self, motion: bool, d_lo_xyzw, d_lo_planes, lo_width, lo_height, d_hi_planes, d_history, d_ids, d_body_of_prim, n_prims, d_bodies, n_bodies, width, height,
+                           pixel_map, prev_camera, d_out, d_out_history, d_out_mask, ctx) -> None:
+        """The same on device pointers; a table that is not given, or any table without an id plane, counts no entries."""
+        if motion:
+            entry, p = "trhip_temporal_upsample_motion_device", self._motion_params_for(pixel_map, prev_camera, n_prims if d_body_of_prim and d_ids else 0,
+                                                                                        n_bodies if d_bodies and d_ids else 0)
+            tables = [_ffi.dptr(d_ids), _ffi.dptr(d_body_of_prim), _ffi.dptr(d_bodies)]
+        else:
+            entry, p, tables = "trhip_temporal_upsample_device", self._params_for(pixel_map, prev_camera), []
+        ctx = ctx or _ffi.default_context()
+        st = _ffi.Stats()
+        ctx.check(getattr(_ffi.lib(), entry)(ctx._h, C.c_void_p(d_lo_xyzw), C.c_void_p(d_lo_planes), int(lo_width), int(lo_height), C.c_void_p(d_hi_planes), _ffi.dptr(d_history),
+                                             *tables, int(width), int(height), C.byref(p), C.c_void_p(d_out), C.c_void_p(d_out_history), _ffi.dptr(d_out_mask), C.byref(st)))
+        self.stats = st
+
     def accumulate_motion(self, lo_xyzw: np.ndarray, lo_planes: np.ndarray, hi_planes: np.ndarray, history: Optional[np.ndarray], ids: Optional[np.ndarray],
                           body_of_prim: Optional[np.ndarray], bodies: Optional[np.ndarray], pixel_map, prev_camera, ctx: Optional[_ffi.Context] = None):
         """`accumulate` for a scene with moving rigid bodies (trhip_temporal_upsample_motion; docs/design/22-upsample-motion.md).  ids: (H, W) of _ffi.AOV_ID_DTYPE, the
         FULL-SIZE frame's AOVIntegrator.ids, or None (every pixel static); body_of_prim: uint32 per ordered-primitive slot (FlatScene.body_table) or None; bodies:
         (n_bodies, 3, 4) prev_from_cur matrices or None.  Returns (xyzw, history, mask) of this frame."""
         self._require_carry_bodies()
-        lo_xyzw, lo_planes, hi_planes = _ffi.f32(lo_xyzw), _ffi.f32(lo_planes), _ffi.f32(hi_planes)
-        if lo_xyzw.ndim != 3 or lo_xyzw.shape[2] != 4 or lo_planes.shape != lo_xyzw.shape[:2] + (3, 4) or hi_planes.ndim != 4 or hi_planes.shape[2:] != (3, 4):
-            raise TraceHipError(f"accumulate_motion: lo_xyzw must be (h, w, 4), lo_planes (h, w, 3, 4) and hi_planes (H, W, 3, 4), not {lo_xyzw.shape}, {lo_planes.shape} and "
-                                f"{hi_planes.shape}")
-        if history is not None:
-            history = _ffi.f32(history)
-            if history.shape != hi_planes.shape:
-                raise TraceHipError(f"accumulate_motion: history must be {hi_planes.shape} like hi_planes, not {history.shape}")
-        (lh, lw), (h, w) = lo_xyzw.shape[:2], hi_planes.shape[:2]
-        if ids is not None:
-            ids = np.ascontiguousarray(ids)
-            if ids.nbytes != h * w * 16:
-                raise TraceHipError(f"accumulate_motion: ids must hold one 16-byte record per FULL-SIZE pixel, not {ids.nbytes} bytes for {h} x {w}")
-        table = None if body_of_prim is None or ids is None else np.ascontiguousarray(body_of_prim, dtype=np.uint32).reshape(-1)
-        mats = None if bodies is None or ids is None else _ffi.f32(bodies).reshape(-1, 12)
-        p = self._motion_params_for(pixel_map, prev_camera, 0 if table is None else table.size, 0 if mats is None else mats.shape[0])
-        ctx = ctx or _ffi.default_context()
-        out, out_history, mask, st = np.empty((h, w, 4), np.float32), np.empty((h, w, 3, 4), np.float32), np.empty((h, w), np.uint8), _ffi.Stats()
-        ctx.check(_ffi.lib().trhip_temporal_upsample_motion(ctx._h, _ffi.fptr(lo_xyzw), _ffi.fptr(lo_planes), lw, lh, _ffi.fptr(hi_planes),
-                                                            _ffi.fptr(history) if history is not None else None, ids.ctypes.data_as(C.c_void_p) if ids is not None else None,
-                                                            _ffi.u32ptr(table) if table is not None else None, _ffi.fptr(mats) if mats is not None else None, w, h, C.byref(p),
-                                                            _ffi.fptr(out), _ffi.fptr(out_history), mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st)))
-        self.stats = st
-        return out, out_history, mask
+        return self._accumulate("accumulate_motion", True, lo_xyzw, lo_planes, hi_planes, history, ids, body_of_prim, bodies, pixel_map, prev_camera, ctx)
 
     def accumulate_motion_device(self, d_lo_xyzw: int, d_lo_planes: int, lo_width: int, lo_height: int, d_hi_planes: int, d_history: Optional[int], d_ids: Optional[int],
                                  d_body_of_prim: Optional[int], n_prims: int, d_bodies: Optional[int], n_bodies: int, width: int, height: int, pixel_map, prev_camera,
                                  d_out: int, d_out_history: int, d_out_mask: Optional[int] = None, ctx: Optional[_ffi.Context] = None) -> None:
         """The same on device pointers (d_history, d_ids, d_body_of_prim, d_bodies and d_out_mask may be None); nothing is copied to the host."""
-        p = self._motion_params_for(pixel_map, prev_camera, n_prims if d_body_of_prim and d_ids else 0, n_bodies if d_bodies and d_ids else 0)
-        ctx = ctx or _ffi.default_context()
-        st = _ffi.Stats()
-        ctx.check(_ffi.lib().trhip_temporal_upsample_motion_device(ctx._h, C.c_void_p(d_lo_xyzw), C.c_void_p(d_lo_planes), int(lo_width), int(lo_height), C.c_void_p(d_hi_planes),
-                                                                   C.c_void_p(d_history) if d_history else None, C.c_void_p(d_ids) if d_ids else None,
-                                                                   C.c_void_p(d_body_of_prim) if d_body_of_prim else None, C.c_void_p(d_bodies) if d_bodies else None, int(width),
-                                                                   int(height), C.byref(p), C.c_void_p(d_out), C.c_void_p(d_out_history),
-                                                                   C.c_void_p(d_out_mask) if d_out_mask else None, C.byref(st)))
-        self.stats = st
+        self._accumulate_device(True, d_lo_xyzw, d_lo_planes, lo_width, lo_height, d_hi_planes, d_history, d_ids, d_body_of_prim, n_prims, d_bodies, n_bodies, width, height, pixel_map,
+                                prev_camera, d_out, d_out_history, d_out_mask, ctx)
 
     def accumulate(self, lo_xyzw: np.ndarray, lo_planes: np.ndarray, hi_planes: np.ndarray, history: Optional[np.ndarray], pixel_map, prev_camera,
                    ctx: Optional[_ffi.Context] = None):
@@ -2463,35 +2349,14 @@ class TemporalUpsampler:
         previous frame's call, or None.  Returns (xyzw (H, W, 4), history (H, W, 3, 4), mask (H, W) uint8)."""
         if self.carry_bodies:  # no id plane: every pixel is static
             return self.accumulate_motion(lo_xyzw, lo_planes, hi_planes, history, None, None, None, pixel_map, prev_camera, ctx)
-        lo_xyzw, lo_planes, hi_planes = _ffi.f32(lo_xyzw), _ffi.f32(lo_planes), _ffi.f32(hi_planes)
-        if lo_xyzw.ndim != 3 or lo_xyzw.shape[2] != 4 or lo_planes.shape != lo_xyzw.shape[:2] + (3, 4) or hi_planes.ndim != 4 or hi_planes.shape[2:] != (3, 4):
-            raise TraceHipError(f"accumulate: lo_xyzw must be (h, w, 4), lo_planes (h, w, 3, 4) and hi_planes (H, W, 3, 4), not {lo_xyzw.shape}, {lo_planes.shape} and {hi_planes.shape}")
-        if history is not None:
-            history = _ffi.f32(history)
-            if history.shape != hi_planes.shape:
-                raise TraceHipError(f"accumulate: history must be {hi_planes.shape} like hi_planes, not {history.shape}")
-        p = self._params_for(pixel_map, prev_camera)
-        ctx = ctx or _ffi.default_context()
-        (lh, lw), (h, w) = lo_xyzw.shape[:2], hi_planes.shape[:2]
-        out, out_history, mask, st = np.empty((h, w, 4), np.float32), np.empty((h, w, 3, 4), np.float32), np.empty((h, w), np.uint8), _ffi.Stats()
-        ctx.check(_ffi.lib().trhip_temporal_upsample(ctx._h, _ffi.fptr(lo_xyzw), _ffi.fptr(lo_planes), lw, lh, _ffi.fptr(hi_planes), _ffi.fptr(history) if history is not None else None,
-                                                     w, h, C.byref(p), _ffi.fptr(out), _ffi.fptr(out_history), mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st)))
-        self.stats = st
-        return out, out_history, mask
+        return self._accumulate("accumulate", False, lo_xyzw, lo_planes, hi_planes, history, None, None, None, pixel_map, prev_camera, ctx)
 
     def accumulate_device(self, d_lo_xyzw: int, d_lo_planes: int, lo_width: int, lo_height: int, d_hi_planes: int, d_history: Optional[int], width: int, height: int, pixel_map,
                           prev_camera, d_out: int, d_out_history: int, d_out_mask: Optional[int] = None, ctx: Optional[_ffi.Context] = None) -> None:
         """The same on device pointers (d_history and d_out_mask may be None); nothing is copied to the host."""
-        if self.carry_bodies:  # no id plane: every pixel is static
-            return self.accumulate_motion_device(d_lo_xyzw, d_lo_planes, lo_width, lo_height, d_hi_planes, d_history, None, None, 0, None, 0, width, height, pixel_map,
-                                                 prev_camera, d_out, d_out_history, d_out_mask, ctx)
-        p = self._params_for(pixel_map, prev_camera)
-        ctx = ctx or _ffi.default_context()
-        st = _ffi.Stats()
-        ctx.check(_ffi.lib().trhip_temporal_upsample_device(ctx._h, C.c_void_p(d_lo_xyzw), C.c_void_p(d_lo_planes), int(lo_width), int(lo_height), C.c_void_p(d_hi_planes),
-                                                            C.c_void_p(d_history) if d_history else None, int(width), int(height), C.byref(p), C.c_void_p(d_out),
-                                                            C.c_void_p(d_out_history), C.c_void_p(d_out_mask) if d_out_mask else None, C.byref(st)))
-        self.stats = st
+        # (with carry_bodies no id plane: every pixel is static)
+        self._accumulate_device(self.carry_bodies, d_lo_xyzw, d_lo_planes, lo_width, lo_height, d_hi_planes, d_history, None, None, 0, None, 0, width, height, pixel_map, prev_camera,
+                                d_out, d_out_history, d_out_mask, ctx)
 
 
 class PreviewSession:
@@ -2741,8 +2606,6 @@ class PreviewSession:
         self.frame += 1
         return out
 
-
-# ---- SPPM and the DirectionalLight -------------------------------------------------------------------------------------------------
     def _upscale(self, hi_camera, lo_camera, sampler, d_lo, d_lo_planes, ctx) -> "_ffi.DeviceBuffer":
         """The session's filtered low-resolution frame onto the full-size planes of this frame (left on the device)."""
         (hh, hw), (lh, lw) = hi_camera.film.size, lo_camera.film.size
@@ -2803,6 +2666,7 @@ class PreviewSession:
         return d_out, (hh, hw), ctx
 
 
+# ---- SPPM and the DirectionalLight -------------------------------------------------------------------------------------------------
 def _to_Y(c) -> np.float32:  # spectrum.jl:64-66
     c = np.asarray(c, np.float32)
     return f32(f32(f32(0.212671) * c[0]) + f32(f32(0.715160) * c[1])) + f32(f32(0.072169) * c[2])
