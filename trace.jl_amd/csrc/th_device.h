@@ -523,14 +523,15 @@ struct LobeSample {
     f3 f;
     int sampled_type;  // -1 = nothing
 };
-// sample_f(bxdf, wo, u)
+// sample_f(bxdf, wo, u).  KIND >= 0: the caller knows the lobe's kind; only that case is compiled in (specular_bsdf_sample_f).
+template <int KIND = -1>
 TH_D LobeSample lobe_sample_f(const Lobe& l, f3 wo, f2 u) {
     LobeSample s;
     s.wi = splat3(0.0f);
     s.pdf = 0.0f;
     s.f = splat3(0.0f);
     s.sampled_type = -1;
-    switch (l.kind) {
+    switch (KIND >= 0 ? KIND : l.kind) {
     case LOBE_SPECULAR_R: {  // specular.jl:34-39
         s.wi = mk3(-wo.x, -wo.y, wo.z);
         s.pdf = 1.0f;
@@ -816,6 +817,29 @@ TH_D BsdfSample lambert_bsdf_sample_f(const Lobe& l, const Shading& s, f3 wo_w, 
     r.f = f;
     r.pdf = pdf;
     r.sampled_type = l.type;
+    return r;
+}
+// A BSDF that is exactly one perfectly specular lobe (MirrorMaterial; smooth GlassMaterial with multiple lobes; PRIM_SPEC, th_scene.h).  No flag set without
+// BSDF_SPECULAR matches it, so bsdf_f(…, BSDF_ALL & ~BSDF_SPECULAR) is zero and its light estimate adds nothing (bsdf_has_non_specular below is what shade_vertex asks);
+// bsdf_sample_f(…, BSDF_ALL) for that case, operation for operation: one matching lobe, a specular one — no lobe loops, no pdf sum, no second evaluation of f.
+TH_D bool bsdf_has_non_specular(const LobeSet& b) { return bsdf_num_components(b, BSDF_ALL & ~BSDF_SPECULAR) > 0; }
+TH_D BsdfSample specular_bsdf_sample_f(const Lobe& l, const Shading& s, f3 wo_w, f2 u) {
+    BsdfSample r;
+    r.wi = splat3(0.0f);
+    r.f = splat3(0.0f);
+    r.pdf = 0.0f;
+    r.sampled_type = BSDF_NONE;
+    const f2 ur{jmin(u.x * 1.0f - 0.0f, 1.0f), u.y};  // one matching lobe: component 1, remapped u (bsdf.jl:118-131)
+    const f3 wo = bsdf_to_local(s, wo_w);
+    if (wo.z == 0.0f) return r;
+    const LobeSample ls = l.kind == LOBE_SPECULAR_R   ? lobe_sample_f<LOBE_SPECULAR_R>(l, wo, ur)
+                          : l.kind == LOBE_SPECULAR_T ? lobe_sample_f<LOBE_SPECULAR_T>(l, wo, ur)
+                                                      : lobe_sample_f<LOBE_FRESNEL_SPECULAR>(l, wo, ur);
+    if (ls.pdf == 0.0f) return r;
+    r.wi = bsdf_to_world(s, ls.wi);
+    r.f = ls.f;
+    r.pdf = ls.pdf;
+    r.sampled_type = ls.sampled_type >= 0 ? ls.sampled_type : l.type;
     return r;
 }
 

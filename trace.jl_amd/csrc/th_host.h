@@ -135,6 +135,7 @@ struct SceneGeometry {
     std::vector<float> occ_boxes;
     DevBuf d_leaf_boxes;  // one-leaf scenes: the boxes of the leaf's triangles in slot order (th_leaf2.h)
     DevBuf d_nodes, d_prims, d_nrm, d_tan, d_shade, d_spheres, d_materials, d_base_colour, d_wnodes, d_w8nodes, d_w8tris;
+    DevBuf d_shade_cold;  // one ShadeCold (th_scene.h): the sphere, material and tangent pointers k_shade_path reads outside its matte path
     DevBuf d_acc_w4nodes;  // the accelerator four children wide (th_trace3c4.h)
     DevBuf d_acc_wnodes, d_acc_prims, d_slot_boxes, d_sphere_boxes, d_sphere_slots, d_sphere_cert;
 };

@@ -500,8 +500,23 @@ __global__ __launch_bounds__(kBlock) void k_trace_any(DeviceScene sc, SegQueue q
 // barycentrics ARE the accepted candidate's.
 // TAN = false: the scene has no mesh with vertex tangents (DeviceScene::tri_tan is null) — the hot shading kernels are instantiated both ways, because even the
 // never-taken branch costs the general code 5 % (S-mesh shading 59.7 -> 62.7 ms, measured)
-template <bool TRI_ONLY = false, bool TAN = true>
-TH_D bool rebuild_shading(const DeviceScene& sc, int prim, f3 o, f3 d, Shading& sh, uint32_t& material, const float4* bary = nullptr, f3* fast_r = nullptr) {
+// k_shade_path's view of the scene: what its matte path reads comes as kernel arguments, the rest through one pointer to a record written at commit (th_scene.h, ShadeCold),
+// loaded where the sphere, material and tangent code needs it — not 84 bytes of DeviceScene held in scalar registers across the whole loop.
+struct ShadeScene {
+    const float4* shade;
+    const LightRec* lights;
+    uint32_t n_lights;
+    const ShadeCold* cold;
+};
+TH_D const SphereRec* scene_spheres(const DeviceScene& sc) { return sc.spheres; }
+TH_D const MaterialRec* scene_materials(const DeviceScene& sc) { return sc.materials; }
+TH_D const float4* scene_tri_tan(const DeviceScene& sc) { return sc.tri_tan; }
+TH_D const SphereRec* scene_spheres(const ShadeScene& sc) { return sc.cold->spheres; }
+TH_D const MaterialRec* scene_materials(const ShadeScene& sc) { return sc.cold->materials; }
+TH_D const float4* scene_tri_tan(const ShadeScene& sc) { return sc.cold->tri_tan; }
+
+template <bool TRI_ONLY = false, bool TAN = true, class Scene>
+TH_D bool rebuild_shading(const Scene& sc, int prim, f3 o, f3 d, Shading& sh, uint32_t& material, const float4* bary = nullptr, f3* fast_r = nullptr) {
     // all six 16-byte loads are issued up front (independent of the sphere / normals flags) so that their latencies overlap.  (Fetching them
     // in k_shade_path while it classifies the entry — two dependent trips instead of three — was measured: 24 more live registers, 368
     // instead of 208 bytes of scratch, S-mesh shading 92 -> 163 ms; fetching only the ray and the throughput there: 92 -> 107 ms.)
@@ -513,7 +528,7 @@ TH_D bool rebuild_shading(const DeviceScene& sc, int prim, f3 o, f3 d, Shading& 
     material = meta & PRIM_MATERIAL_MASK;
     if (fast_r) *fast_r = mk3(na.w, nb.w, nc.w);  // PRIM_FAST: the single Lambert lobe's reflectance
     if (!TRI_ONLY && (meta & PRIM_SPHERE)) {
-        const SphereRec& s = sc.spheres[__float_as_uint(p0.x)];
+        const SphereRec& s = scene_spheres(sc)[__float_as_uint(p0.x)];
         SphereHit h;
         if (!sphere_intersect<true>(s, o, d, kInf, h)) return false;
         sh = shade_sphere(s, h, d);
@@ -528,7 +543,8 @@ TH_D bool rebuild_shading(const DeviceScene& sc, int prim, f3 o, f3 d, Shading& 
     const bool has_n = (meta & PRIM_HAS_NORMALS) != 0;
     const TriConstants tc{mk3(cn.x, cn.y, cn.z), mk3(cs.x, cs.y, cs.z)};
     // a mesh with vertex tangents (no scene of the reference has one): the three records are fetched inside shade_triangle, where the normals are no longer live
-    const float4* tan = (TAN && sc.tri_tan && (meta & PRIM_HAS_TANGENTS)) ? sc.tri_tan + 3 * (size_t)prim : nullptr;
+    const float4* tan_base = (TAN && (meta & PRIM_HAS_TANGENTS)) ? scene_tri_tan(sc) : nullptr;
+    const float4* tan = tan_base ? tan_base + 3 * (size_t)prim : nullptr;
     sh = shade_triangle(v0, v1, v2, has_n, mk3(na.x, na.y, na.z), mk3(nb.x, nb.y, nb.z), mk3(nc.x, nc.y, nc.z), (meta & PRIM_FLIP) != 0, tt.bary, d, &tc, tan);
     return true;
 }
@@ -566,6 +582,9 @@ template <int TH_ONE_COPY = 0> __global__ __launch_bounds__(kBlock) void k_shade
 #ifndef TH_SHADE_WAVES
 #define TH_SHADE_WAVES 4  // waves per SIMD the register allocator must leave room for: 128 VGPRs + 136 B scratch instead of 175 VGPRs at 2 waves; measured 37.0 -> 32.2 ms (S-cornell, 64 spp)
 #endif
+#ifndef TH_SHADE_SPEC
+#define TH_SHADE_SPEC 1  // 0 (variant builds, the A/B switch): PRIM_SPEC entries take the general code
+#endif
 // STREAM (streaming wavefront, th_trace2.h): the queue of a ROUND holds paths of mixed depths — `row` is the round, every entry
 // carries its depth tag (tags_in / tags_out), and what the path adds to its sample's radiance at depth d goes to the term slot
 // L[(d - 1) * term_stride + slot] (k_fold_terms adds the slots in depth order afterwards).  Entries whose ray was suspended
@@ -582,11 +601,15 @@ struct ShadeOut {  // what one vertex emits: a shadow ray and / or the continuat
     float4 so4, sd4, sc4, no4, nd4, nb4;
     uint32_t next_depth;
 };
-// One PathIntegrator vertex for queue entry i (a real hit).  FAST: the caller has established that the hit is a triangle whose
-// material is a single LambertianReflection lobe; the sphere path and the general BSDF code are then not even compiled in.
-template <bool STREAM, bool FAST, bool TAN = true, bool DIRL = false>
-TH_D void shade_vertex(const DeviceScene& sc, const PathQueue& qin, const float4* __restrict__ hits, float4* __restrict__ L, uint32_t i, int depth_fixed, int max_depth,
+// One PathIntegrator vertex for queue entry i (a real hit).  MODE says what the caller has established about the hit, from the flags set at upload:
+//   SHADE_FAST  a triangle whose material is a single LambertianReflection lobe: the sphere path and the general BSDF code are not even compiled in
+//   SHADE_SPEC  a primitive whose material is a single perfectly specular lobe (PRIM_SPEC): no light estimate — it is zero by construction —, one sampler case
+//   SHADE_GENERIC  anything
+enum : int { SHADE_GENERIC = 0, SHADE_FAST = 1, SHADE_SPEC = 2 };
+template <bool STREAM, int MODE, bool TAN = true, bool DIRL = false>
+TH_D void shade_vertex(const ShadeScene& sc, const PathQueue& qin, const float4* __restrict__ hits, float4* __restrict__ L, uint32_t i, int depth_fixed, int max_depth,
                        uint32_t hits_have_bary, const ShadeStream& ss, ShadeOut& out) {
+    constexpr bool FAST = MODE == SHADE_FAST, SPEC = MODE == SHADE_SPEC;
     const float4 h4 = hits[i];
     const int prim = __float_as_int(h4.y);
     const float4 o4 = qin.o[i], d4 = qin.d[i], b4 = qin.beta[i];
@@ -599,16 +622,16 @@ TH_D void shade_vertex(const DeviceScene& sc, const PathQueue& qin, const float4
     uint32_t material;
     f3 fast_r;
     if (!(rebuild_shading<FAST, TAN>(sc, prim, o, d, sh, material, hits_have_bary ? &h4 : nullptr, &fast_r) && material != PRIM_NO_MATERIAL)) return;
-    const LobeSet& bsdf = sc.materials[FAST ? 0u : material].set[1];  // compute_scattering!(si, ray, true); FAST never reads it
-    const bool lambert = FAST || bsdf_is_single_lambert(bsdf);  // specialised evaluation of the same arithmetic (th_device.h)
-    Lobe lam;  // the one lobe of a `lambert` vertex: FAST rebuilds it from the reflectance stored beside the normals
+    const LobeSet& bsdf = scene_materials(sc)[FAST ? 0u : material].set[1];  // compute_scattering!(si, ray, true); FAST never reads it (nor the pointer)
+    const bool lambert = FAST || (!SPEC && bsdf_is_single_lambert(bsdf));  // specialised evaluation of the same arithmetic (th_device.h)
+    Lobe lam;  // the one lobe of a `lambert` or SPEC vertex: FAST rebuilds it from the reflectance stored beside the normals
     if (FAST) {
         lam.kind = LOBE_LAMBERT_R;
         lam.type = BSDF_DIFFUSE | BSDF_REFLECTION;
         lam.r[0] = fast_r.x;
         lam.r[1] = fast_r.y;
         lam.r[2] = fast_r.z;
-    } else if (lambert) {
+    } else if (SPEC || lambert) {
         lam = bsdf.lobe[0];
     }
     // the sampler stream key of this camera sample rides in the queue (k_raygen): no slot -> pixel division, no re-hash
@@ -618,7 +641,8 @@ TH_D void shade_vertex(const DeviceScene& sc, const PathQueue& qin, const float4
     const uint32_t poison = ((isnan_(beta.x) || isinf_(beta.x)) ? 1u : 0u) | ((isnan_(beta.y) || isinf_(beta.y)) ? 2u : 0u) | ((isnan_(beta.z) || isinf_(beta.z)) ? 4u : 0u);
     // ---- uniform_sample_one_light ----
     bool direct_added = false;
-    if (sc.n_lights > 0) {
+    // (a BSDF without a non-specular lobe: bsdf_f below is zero whatever the light — nothing to estimate, and the counter-based sampler has nothing to skip)
+    if (!SPEC && sc.n_lights > 0 && (lambert || bsdf_has_non_specular(bsdf))) {
         const int nl = (int)sc.n_lights;
         int ln = (int)__builtin_ceilf(ts_uniform(key, ts_vertex_dim(v, TS_V_LIGHT_PICK)) * (float)nl);
         if (ln > nl) ln = nl;
@@ -660,7 +684,7 @@ TH_D void shade_vertex(const DeviceScene& sc, const PathQueue& qin, const float4
     // ---- continue the path ----
     if (depth < max_depth) {
         const f2 u{ts_uniform(key, ts_vertex_dim(v, TS_V_BSDF_U0)), ts_uniform(key, ts_vertex_dim(v, TS_V_BSDF_U1))};
-        const BsdfSample bs = lambert ? lambert_bsdf_sample_f(lam, sh, wo, u) : bsdf_sample_f(bsdf, sh, wo, u, BSDF_ALL);
+        const BsdfSample bs = SPEC ? specular_bsdf_sample_f(lam, sh, wo, u) : lambert ? lambert_bsdf_sample_f(lam, sh, wo, u) : bsdf_sample_f(bsdf, sh, wo, u, BSDF_ALL);
         if (!(bs.pdf == 0.0f || is_black(bs.f))) {
             beta = beta * (bs.f * fabs_(dot(bs.wi, sh.ns)) / bs.pdf);
             const float by = to_Y(beta);
@@ -689,20 +713,22 @@ TH_D void shade_vertex(const DeviceScene& sc, const PathQueue& qin, const float4
 // multi-lobe materials) run several times as many instructions.  Mixed in one wave they serialise (S-cornell: 108 ms against
 // 58 ms for the same box without its two spheres), so every wave shades its FAST entries at once and parks the indices of the
 // others in an LDS ring; whenever 64 are parked they are shaded together by the general code, with all lanes busy.
+// A batch whose 64 entries are all PRIM_SPEC (one perfectly specular lobe: the mirror and the glass sphere of the reference's scenes, i.e. every parked entry there) takes
+// the specular code instead: no light estimate, one sampler case.  A parked vertex cost 2.3 matte ones before that, 39 % of the class on S-mesh (profiles/r25/shade_specular.txt).
 // (Two launches instead — the FAST entries, then the others from an index list in HBM, each with a register allocation of its
 // own — were measured: S-mesh frame 405 -> 415 ms, S-cornell 162 -> 173 ms; the list traffic and the second launch's tail cost
 // more than the 144 bytes of scratch the FAST code gets rid of.)
 // (Round 5 built the two-launch form again — the matte entries alone, restructured to 88 VGPRs without scratch at 5 waves per SIMD, then the rest from index lists: 2 ms per
 // 64 spp SLOWER on S-mesh and S-cornell at 4, 5 and 6 waves alike; the matte path is bound neither by occupancy nor by scratch: profiles/r5/r5_shade_split_experiment.txt.)
 template <bool STREAM, bool TAN = true, bool DIRL = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE_WAVES))) void k_shade_path(DeviceScene sc, const DeviceSensor* __restrict__ sep, PathQueue qin, PathQueue qout, ShadowQueue sq, uint32_t cap,
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE_WAVES))) void k_shade_path(ShadeScene sc, const DeviceSensor* __restrict__ sep, PathQueue qin, PathQueue qout, ShadowQueue sq, uint32_t cap,
                                                        const float4* __restrict__ hits, float4* __restrict__ L, Counters* ctr, int row, int depth_fixed, int max_depth, uint32_t hits_have_bary,
                                                        ShadeStream ss) {
     __shared__ SegView sv;
     __shared__ uint32_t s_ring[kBlock / 64][128];
     const SegQueue qv{ctr->n_queue[row], cap, 0u};
     seg_load(qv, sv);
-    const uint32_t total = sv.prefix[kSeg];  // multiple of kSegGran: whole waves stay in the loop, so ballots see every lane
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)sv.prefix[kSeg]);  // multiple of kSegGran: whole waves stay in the loop, so ballots see every lane
     const uint32_t lane = lane_id(), wv = threadIdx.x >> 6;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     // every wave-iteration of a wave feeds the same output segment (the grid is a multiple of kSeg waves): at most cap entries each
@@ -725,49 +751,63 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TH_SHADE
             if (STREAM) ss.tags_out[ni] = e.next_depth;
         }
     };
-    uint32_t seg_in = 0;
-    for (uint32_t flat = blockIdx.x * kBlock + threadIdx.x; flat < total; flat += gridDim.x * kBlock) {
-        uint32_t lb;
-        seg_locate_from(sv, flat & ~63u, seg_in, lb);
-        const uint32_t local = lb + (flat & 63u);
-        const uint32_t i = seg_in * cap + local;
-        int cls = 0;  // 0: nothing to shade (padding, miss, suspended ray), 1: FAST, 2: general
-        if (local < sv.count[seg_in]) {
-            const int prim = __float_as_int(hits[i].y);
-            if (prim >= 0) {
-                cls = (__float_as_uint(sc.shade[8 * (size_t)prim].w) & PRIM_FAST) ? 1 : 2;  // flag set at upload: no material fetch to classify
-            }
-        }
-        ShadeOut e;
-        e.want_shadow = e.want_next = false;
-        e.next_depth = 0;
-        if (cls == 1) shade_vertex<STREAM, true, TAN, DIRL>(sc, qin, hits, L, i, depth_fixed, max_depth, hits_have_bary, ss, e);
-        emit(e);
-        // park the others
-        const unsigned long long m2 = __ballot(cls == 2);
-        if (m2) {
-            if (cls == 2) s_ring[wv][(ring_head + ring_cnt + (uint32_t)__popcll(m2 & lt_mask)) & 127u] = i;
-            ring_cnt += (uint32_t)__popcll(m2);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            if (ring_cnt >= 64u) {
-                const uint32_t j = s_ring[wv][(ring_head + lane) & 127u];
-                ShadeOut g;
-                g.want_shadow = g.want_next = false;
-                g.next_depth = 0;
-                shade_vertex<STREAM, false, TAN, DIRL>(sc, qin, hits, L, j, depth_fixed, max_depth, hits_have_bary, ss, g);
-                emit(g);
-                ring_head = (ring_head + 64u) & 127u;
-                ring_cnt -= 64u;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            }
-        }
-    }
-    if (ring_cnt) {  // the last, partial batch
+    // One batch of parked entries: the specular code when every entry of the batch is PRIM_SPEC (in the scenes of the reference every parked entry is), else the general code
+    uint32_t ring_gen = 0;  // wave-uniform: the parked entries that are not PRIM_SPEC
+    auto shade_parked = [&](bool active, bool all_spec) {
+        const uint32_t j = s_ring[wv][(ring_head + lane) & 127u];
         ShadeOut g;
         g.want_shadow = g.want_next = false;
         g.next_depth = 0;
-        if (lane < ring_cnt) shade_vertex<STREAM, false, TAN, DIRL>(sc, qin, hits, L, s_ring[wv][(ring_head + lane) & 127u], depth_fixed, max_depth, hits_have_bary, ss, g);
+        if (TH_SHADE_SPEC && all_spec) {
+            if (active) shade_vertex<STREAM, SHADE_SPEC, TAN, DIRL>(sc, qin, hits, L, j, depth_fixed, max_depth, hits_have_bary, ss, g);
+        } else {
+            if (active) shade_vertex<STREAM, SHADE_GENERIC, TAN, DIRL>(sc, qin, hits, L, j, depth_fixed, max_depth, hits_have_bary, ss, g);
+        }
         emit(g);
+    };
+    // One loop serves the queue and the last, partial batch: the general and the specular code stand once in the kernel.  A wave's 64 lanes leave together (`total` is a
+    // multiple of 64), and the exit is taken from lane 0's index so that the compiler knows it too: a scalar branch, and counters that stay in scalar registers.
+    uint32_t seg_in = 0;
+    for (uint32_t flat = blockIdx.x * kBlock + threadIdx.x;; flat += gridDim.x * kBlock) {
+        const bool more = (uint32_t)__builtin_amdgcn_readfirstlane((int)flat) < total;
+        uint32_t gen_rest = 0;
+        if (more) {
+            uint32_t lb;
+            seg_locate_from(sv, flat & ~63u, seg_in, lb);
+            const uint32_t local = lb + (flat & 63u);
+            const uint32_t i = seg_in * cap + local;
+            int cls = 0;  // 0: nothing to shade (padding, miss, suspended ray), 1: FAST, 2: general, 3: specular
+            if (local < sv.count[seg_in]) {
+                const int prim = __float_as_int(hits[i].y);
+                if (prim >= 0) {
+                    const uint32_t meta = __float_as_uint(sc.shade[8 * (size_t)prim].w);  // flags set at upload: no material fetch to classify
+                    cls = (meta & PRIM_FAST) ? 1 : (TH_SHADE_SPEC && (meta & PRIM_SPEC)) ? 3 : 2;
+                }
+            }
+            ShadeOut e;
+            e.want_shadow = e.want_next = false;
+            e.next_depth = 0;
+            if (cls == 1) shade_vertex<STREAM, SHADE_FAST, TAN, DIRL>(sc, qin, hits, L, i, depth_fixed, max_depth, hits_have_bary, ss, e);
+            emit(e);
+            // park the others
+            const unsigned long long m2 = __ballot(cls >= 2);
+            if (m2) {
+                const uint32_t rank = (uint32_t)__popcll(m2 & lt_mask), room = 64u - ring_cnt;  // (ring_cnt < 64 here) the first `room` of them complete the next batch
+                if (cls >= 2) s_ring[wv][(ring_head + ring_cnt + rank) & 127u] = i;
+                ring_gen += (uint32_t)__popcll(__ballot(cls == 2 && rank < room));
+                gen_rest = (uint32_t)__popcll(__ballot(cls == 2 && rank >= room));
+                ring_cnt += (uint32_t)__popcll(m2);
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            }
+        }
+        if (ring_cnt >= 64u || (!more && ring_cnt)) {  // a full batch; behind the queue's end, what is left
+            shade_parked(lane < ring_cnt, ring_gen == 0u);
+            ring_head = (ring_head + 64u) & 127u;
+            ring_cnt -= ring_cnt < 64u ? ring_cnt : 64u;
+            ring_gen = gen_rest;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        }
+        if (!more) break;
     }
 }
 // STREAM: per-sample radiance = its per-depth terms added in depth order, which is the order the classic wavefront (and the

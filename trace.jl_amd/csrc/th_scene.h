@@ -27,6 +27,8 @@ enum : uint32_t {
                                   // reflectance rides in the .w lanes of the three normal records (upload_scene), the shading kernel
                                   // classifies and shades it without touching the material table   // is_degenerate(triangle) (triangle_mesh.jl:65-68), evaluated once at scene commit
     PRIM_HAS_TANGENTS = 1u << 29, // the mesh has vertex tangents: slot k's three are in DeviceScene::tri_tan (triangle_mesh.jl:172-176)
+    PRIM_SPEC = 1u << 30,         // triangle or sphere whose material (with multiple lobes) is ONE perfectly specular lobe (SpecularReflection, SpecularTransmission or
+                                  // FresnelSpecular): no light estimate, one sampler case (th_device.h, specular_bsdf_sample_f); never together with PRIM_FAST
     PRIM_MATERIAL_MASK = 0x00ffffffu,
     PRIM_NO_MATERIAL = 0x00ffffffu
 };
@@ -83,6 +85,14 @@ struct DeviceScene {
     const MaterialRec* materials;
     const LightRec* lights;
     uint32_t n_nodes, n_prims, n_spheres, n_materials, n_lights;
+};
+
+// What k_shade_path reads of the scene outside its matte path, behind one pointer (th_kernels.h, ShadeScene): written once at commit, the same for every frame and
+// every relit view of the geometry.
+struct ShadeCold {
+    const SphereRec* spheres;
+    const MaterialRec* materials;
+    const float4* tri_tan;
 };
 
 struct DeviceSensor {

@@ -33,6 +33,8 @@ void derive_sensor(const trhip_sensor* sn, DeviceSensor& d) {
 }
 
 // ---- the film pass (th_kernels.h "film") ----
+// k_shade_path's scene arguments: the shading lines and this handle's lights by value, the geometry's cold record (written at commit) by pointer
+static ShadeScene shade_scene(const trhip_scene* s) { return ShadeScene{s->dev.shade, s->dev.lights, s->dev.n_lights, (const ShadeCold*)s->g->d_shade_cold.p}; }
 // Two passes, and the filter alone chooses.  Packed, both radii in (0, 1] — every scene of the reference uses LanczosSincFilter(Point2f(1f0), 3f0) —: a sample reaches <= 4
 // columns / rows, its 30-bit splat descriptor rides in the .w lane of its radiance record, and a thread gathers 2 x 4 film pixels.  Wide, anything else: film positions
 // beside sample-major records and the 1 x 4 block gather.
@@ -273,13 +275,13 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
         const ShadeStream sst{tags[cur], tags[cur ^ 1], (uint32_t)total_slots};
         if (has_directional_light(scene)) {
             if (scene->dev.tri_tan)
-                hipLaunchKernelGGL((k_shade_path<true, true, true>), dim3(g_shade), dim3(kBlock), 0, ps, scene->dev, dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, terms, ctr, r, 0, max_depth, 1u, sst);
+                hipLaunchKernelGGL((k_shade_path<true, true, true>), dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, terms, ctr, r, 0, max_depth, 1u, sst);
             else
-                hipLaunchKernelGGL((k_shade_path<true, false, true>), dim3(g_shade), dim3(kBlock), 0, ps, scene->dev, dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, terms, ctr, r, 0, max_depth, 1u, sst);
+                hipLaunchKernelGGL((k_shade_path<true, false, true>), dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, terms, ctr, r, 0, max_depth, 1u, sst);
         } else if (scene->dev.tri_tan) {
-            hipLaunchKernelGGL(k_shade_path<true>, dim3(g_shade), dim3(kBlock), 0, ps, scene->dev, dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, terms, ctr, r, 0, max_depth, 1u, sst);
+            hipLaunchKernelGGL(k_shade_path<true>, dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, terms, ctr, r, 0, max_depth, 1u, sst);
         } else {
-            hipLaunchKernelGGL((k_shade_path<true, false>), dim3(g_shade), dim3(kBlock), 0, ps, scene->dev, dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, terms, ctr, r, 0, max_depth, 1u, sst);
+            hipLaunchKernelGGL((k_shade_path<true, false>), dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, terms, ctr, r, 0, max_depth, 1u, sst);
         }
         tm.end(2, ps);
         if (ps2 != ps) {
@@ -533,13 +535,13 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
             const ShadeStream sst{nullptr, nullptr, 0u, two ? (uint8_t*)ctx->poison.p : nullptr};
             if (has_directional_light(scene)) {
                 if (scene->dev.tri_tan)
-                    hipLaunchKernelGGL((k_shade_path<false, true, true>), dim3(g_shade), dim3(kBlock), 0, ps, scene->dev, dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, L, ctr, depth - 1, depth, max_depth, bary_mode, sst);
+                    hipLaunchKernelGGL((k_shade_path<false, true, true>), dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, L, ctr, depth - 1, depth, max_depth, bary_mode, sst);
                 else
-                    hipLaunchKernelGGL((k_shade_path<false, false, true>), dim3(g_shade), dim3(kBlock), 0, ps, scene->dev, dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, L, ctr, depth - 1, depth, max_depth, bary_mode, sst);
+                    hipLaunchKernelGGL((k_shade_path<false, false, true>), dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, L, ctr, depth - 1, depth, max_depth, bary_mode, sst);
             } else if (scene->dev.tri_tan) {
-                hipLaunchKernelGGL(k_shade_path<false>, dim3(g_shade), dim3(kBlock), 0, ps, scene->dev, dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, L, ctr, depth - 1, depth, max_depth, bary_mode, sst);
+                hipLaunchKernelGGL(k_shade_path<false>, dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, L, ctr, depth - 1, depth, max_depth, bary_mode, sst);
             } else {
-                hipLaunchKernelGGL((k_shade_path<false, false>), dim3(g_shade), dim3(kBlock), 0, ps, scene->dev, dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, L, ctr, depth - 1, depth, max_depth, bary_mode, sst);
+                hipLaunchKernelGGL((k_shade_path<false, false>), dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, L, ctr, depth - 1, depth, max_depth, bary_mode, sst);
             }
             tm.end(2, ps);
             if (two) {

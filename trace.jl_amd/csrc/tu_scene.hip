@@ -237,6 +237,12 @@ bool has_sphere_subtree(const trhip_scene* s, uint32_t root) {
                 if (s->g->prims[s->g->bvh.order[k]].kind == 1) return true;
     return false;
 }
+// PRIM_SPEC (th_scene.h): the material's BSDF with multiple lobes is exactly one perfectly specular lobe — not an empty one (a black mirror), not rough or two-lobe glass
+bool single_specular(const trhip_scene* s, uint32_t mat) {
+    if (mat == PRIM_NO_MATERIAL || mat >= s->g->materials.size()) return false;
+    const LobeSet& b = s->g->materials[mat].set[1];
+    return b.n == 1 && (b.lobe[0].kind == LOBE_SPECULAR_R || b.lobe[0].kind == LOBE_SPECULAR_T || b.lobe[0].kind == LOBE_FRESNEL_SPECULAR);
+}
 }  // namespace
 
 int upload_scene(trhip_scene* s) {
@@ -255,7 +261,7 @@ int upload_scene(trhip_scene* s) {
         for (size_t k = k0; k < k1; ++k) {
             const HostPrim& p = s->g->prims[s->g->bvh.order[k]];
             if (p.kind == 1) {
-                prims[3 * k] = make_float4(__builtin_bit_cast(float, p.sphere_id), 0, 0, __builtin_bit_cast(float, p.meta));
+                prims[3 * k] = make_float4(__builtin_bit_cast(float, p.sphere_id), 0, 0, __builtin_bit_cast(float, p.meta | (single_specular(s, p.meta & PRIM_MATERIAL_MASK) ? PRIM_SPEC : 0u)));
                 prims[3 * k + 1] = prims[3 * k + 2] = make_float4(0, 0, 0, 0);
                 nrm[3 * k] = nrm[3 * k + 1] = nrm[3 * k + 2] = make_float4(0, 0, 0, 0);
             } else {
@@ -265,6 +271,7 @@ int upload_scene(trhip_scene* s) {
                 const uint32_t mat = p.meta & PRIM_MATERIAL_MASK;
                 const bool fast = mat != PRIM_NO_MATERIAL && mat < s->g->materials.size() && s->g->materials[mat].set[1].n == 1 && s->g->materials[mat].set[1].lobe[0].kind == LOBE_LAMBERT_R;
                 if (fast) prims[3 * k].w = __builtin_bit_cast(float, p.meta | PRIM_FAST);
+                if (single_specular(s, mat)) prims[3 * k].w = __builtin_bit_cast(float, p.meta | PRIM_SPEC);
                 for (int j = 0; j < 3; ++j) nrm[3 * k + j] = make_float4(p.n[3 * j], p.n[3 * j + 1], p.n[3 * j + 2], fast ? s->g->materials[mat].set[1].lobe[0].r[j] : 0.0f);
             }
         }
@@ -334,6 +341,10 @@ int upload_scene(trhip_scene* s) {
     s->dev.n_spheres = (uint32_t)s->g->spheres.size();
     s->dev.n_materials = (uint32_t)s->g->materials.size();
     s->dev.n_lights = 0;
+    {  // the path shading kernel's cold fields (th_kernels.h, ShadeScene): geometry alone, so every relit view shares the record
+        const ShadeCold cold{s->dev.spheres, s->dev.materials, s->dev.tri_tan};
+        if (int rc = upload(ctx, s->g->d_shade_cold, &cold, sizeof cold)) return rc;
+    }
     // ---- children-in-parent nodes for k_trace2 (th_trace2.h) ----
     bool has_empty_leaf = false;
     s->wide_ok = false;
