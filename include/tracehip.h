@@ -531,6 +531,37 @@ int trhip_render_sky_is(trhip_ctx* ctx, const trhip_scene* scene, const trhip_se
 int trhip_render_sky_is_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, uint64_t seed, uint32_t sample_offset,
                                const trhip_env* env, const trhip_sky_is_params* params, void* d_out_xyzw, trhip_stats* stats);
 
+/* ---- next-event estimation of the environment map in path frames (since ABI 3001, added without a version change: nothing existing moved)
+ * trhip_render_path_env with two changes (docs/design/28-path-nee.md holds the specification, step by step):
+ *  1. at every vertex whose BSDF has a non-specular lobe — the last one, at max_depth, included — one shadow ray estimates the map's direct
+ *     light with the one-sample mixture of BSDF sampling and map sampling: with probability `mix` the direction wi is trhip_env_sample's
+ *     (from the vertex's TS_V_LIGHT_U0 / U1 numbers), otherwise the non-specular lobes' sample (from TS_V_SCATTER_U0 / U1), and where
+ *     the ray reaches nothing the sample gains
+ *       beta * ((f(wo, wi) |wi . n|) * (E(wi) * scale) / ((1 - mix) pdf_bsdf(wi) + mix trhip_env_pdf(wi)))
+ *     after the vertex's point-light term.  The path itself — its rays, its throughput, its Russian roulette — is trhip_render_path's
+ *     in every bit: the continuation keeps TS_V_BSDF_U0 / U1 to itself;
+ *  2. an escape that follows such a vertex no longer counts (its light is already estimated): an escape at depth d contributes as in
+ *     trhip_render_path_env if and only if d == 1 (without TRHIP_PATH_ENV_HIDE_BACKGROUND) or vertex d - 1 had specular lobes only.
+ * With scale == 0 the frame is trhip_render_path, and in a scene without a non-specular material trhip_render_path_env, bit for bit.
+ * trhip_last_escapes works after the frame: a suppressed escape still leaves its record, with the 8th float 1 in place of 0.
+ * trhip_path_env_relight refuses it (TRHIP_ERR_INVALID): the base radiance contains the map.  Options, bands and statistics as
+ * trhip_render_path_env; shadow_rays counts the point-light rays and the NEE rays.
+ * Refusals, in this order: the parameter block (NULL; scale; unknown flag bits; reserved; mix not finite or outside (0, 1)), before any
+ * handle is looked at; trhip_render_path_env's in its order; an env without a sampler (trhip_env_make_sampler); TRHIP_ERR_UNSUPPORTED
+ * for a scene with a material whose lobe set mixes specular and non-specular lobes (trhip_scene_add_material builds none), and for a
+ * frame whose per-sample buffers and NEE shadow queues do not fit in half of free HBM.  trhip_path_nee_default_params needs no context. */
+typedef struct {
+    float scale;              /* multiplies every lookup: finite, >= 0 */
+    float mix;                /* probability of drawing the direction from the map: in (0, 1) */
+    uint32_t flags;           /* TRHIP_PATH_ENV_HIDE_BACKGROUND */
+    uint32_t reserved[5];     /* 0 */
+} trhip_path_nee_params;      /* 32 bytes */
+int trhip_path_nee_default_params(trhip_path_nee_params* out); /* {1, 0.5, 0, {0, 0, 0, 0, 0}} */
+int trhip_render_path_env_nee(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
+                              const trhip_env* env, const trhip_path_nee_params* params, float* out_xyzw, trhip_stats* stats);
+int trhip_render_path_env_nee_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
+                                     const trhip_env* env, const trhip_path_nee_params* params, void* d_out_xyzw, trhip_stats* stats);
+
 /* ---- edge-avoiding denoiser for path / Whitted films (since ABI 3001, added without a version change: nothing existing moved) ----
  * An à-trous wavelet filter after Dammertz et al. 2010 ("Edge-Avoiding À-Trous Wavelet Transform for fast Global Illumination
  * Filtering") on the film state of a path or Whitted render, guided by the three planes of trhip_render_aov for the same sensor,

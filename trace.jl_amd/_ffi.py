@@ -194,6 +194,16 @@ class PathEnvParams(C.Structure):
 PATH_ENV_HIDE_BACKGROUND = 1  # TRHIP_PATH_ENV_HIDE_BACKGROUND
 
 
+class PathNeeParams(C.Structure):
+    """trhip_path_nee_params (32 bytes)"""
+    _fields_ = [
+        ("scale", C.c_float),
+        ("mix", C.c_float),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 5),
+    ]
+
+
 class TemporalParams(C.Structure):
     """trhip_temporal_params (72 bytes)"""
     _fields_ = [
@@ -442,6 +452,9 @@ SIGNATURES = {
     "trhip_render_path_env": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(PathEnvParams), _F, C.POINTER(Stats)]),
     "trhip_render_path_env_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(PathEnvParams), _VP, C.POINTER(Stats)]),
     "trhip_last_escapes": (C.c_int, [_VP, _F, C.c_uint64]),
+    "trhip_path_nee_default_params": (C.c_int, [C.POINTER(PathNeeParams)]),
+    "trhip_render_path_env_nee": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(PathNeeParams), _F, C.POINTER(Stats)]),
+    "trhip_render_path_env_nee_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(PathNeeParams), _VP, C.POINTER(Stats)]),
     "trhip_path_env_relight": (C.c_int, [_VP, _VP, C.POINTER(PathEnvParams), _F]),
     "trhip_path_env_relight_device": (C.c_int, [_VP, _VP, C.POINTER(PathEnvParams), _VP]),
     "trhip_render_aov_ids": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _F, _VP, _VP, C.POINTER(Stats)]),

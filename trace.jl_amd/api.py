@@ -1048,12 +1048,23 @@ class PathIntegrator(_SamplerIntegrator):
     _entry = "trhip_render_path"
 
     def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None, sample_map: Optional["SampleMap"] = None,
-               environment: Optional["Environment"] = None, env_scale: float = 1.0, hide_background: bool = False) -> np.ndarray:
+               environment: Optional["Environment"] = None, env_scale: float = 1.0, hide_background: bool = False, env_importance=None) -> np.ndarray:
         """_SamplerIntegrator.render; with ``sample_map`` a map frame (trhip_render_path_map): sample pixel p draws ``sample_map.counts[p]`` samples from the sampler's
         sample_offset on, and ``sampler.samples_per_pixel`` is not read.  With ``environment`` a path-env frame (trhip_render_path_env; docs/design/26-path-env.md): a path
         that leaves the scene brings back beta * E(dir) * env_scale — not at depth 1 with ``hide_background`` — and escapes() / relight() work on the frame afterwards.
-        Without either it is trhip_render_path, the same call and the same bits."""
+        With ``env_importance`` as well — a mix in (0, 1), or True for 0.5 — the frame estimates the map's direct light at every non-specular vertex with one shadow ray,
+        drawn from the map with that probability and from the BSDF otherwise (trhip_render_path_env_nee; docs/design/28-path-nee.md): far less noise under a small bright
+        sun; escapes() and suppressed() work afterwards, relight() does not.  Without any of them it is trhip_render_path, the same call and the same bits."""
         smp = self.sampler
+        if env_importance is not None:
+            if sample_map is not None:
+                raise TraceHipError("PathIntegrator.render: sample_map and env_importance cannot be combined (map frames have no environment term)")
+            if environment is None:
+                raise TraceHipError("PathIntegrator.render: env_importance needs an environment")
+            prm = path_nee_params(environment, env_scale, hide_background, env_importance, "PathIntegrator.render")
+            flat = scene.flatten(ctx)
+            args = (smp.samples_per_pixel, self.max_depth, smp.seed, smp.sample_offset, environment._sampler_handle(flat.ctx), C.byref(prm))
+            return self._render_film(flat, "trhip_render_path_env_nee", args, device_out)
         if environment is not None:
             if sample_map is not None:
                 raise TraceHipError("PathIntegrator.render: sample_map and environment cannot be combined (map frames have no environment term)")
@@ -1082,6 +1093,15 @@ class PathIntegrator(_SamplerIntegrator):
         flat.ctx.check(_ffi.lib().trhip_last_escapes(flat.ctx._h, _ffi.fptr(rec), rec.size))
         return rec[..., 0:3].copy(), rec[..., 3].astype(np.int32), rec[..., 4:7].copy()
 
+    def suppressed(self, scene: Scene) -> np.ndarray:
+        """Which escapes of the last render(environment=..., env_importance=...) do not count, because next-event estimation at the vertex before has already accounted for
+        their light (the 8th float of trhip_last_escapes): (spp, sb_h, sb_w) bool, shaped like escapes()'s depth; all False after a frame without env_importance."""
+        flat = scene.flatten()
+        sbh, sbw, _, _ = sample_bounds_shape(self.camera.film)
+        rec = np.empty((self.sampler.samples_per_pixel, sbh, sbw, 8), dtype=np.float32)
+        flat.ctx.check(_ffi.lib().trhip_last_escapes(flat.ctx._h, _ffi.fptr(rec), rec.size))
+        return rec[..., 7] != 0
+
     def relight(self, scene: Scene, environment: "Environment", env_scale: float = 1.0, hide_background: bool = False, device_out: Optional[int] = None) -> np.ndarray:
         """The film of the last render(environment=...) under another environment and / or other parameters, without tracing a ray (trhip_path_env_relight): film and
         sample_radiance equal a fresh render with these arguments bit for bit.  Valid only while that frame is the context's last; the counterpart of Scene.with_lights
@@ -1108,6 +1128,22 @@ def path_env_params(environment, env_scale, hide_background, who: str) -> "_ffi.
         raise TraceHipError(f"{who}: env_scale must be finite and >= 0, not {env_scale}")
     p = _ffi.default_params(_ffi.PathEnvParams, "trhip_path_env_default_params")
     p.scale, p.flags = scale, _ffi.PATH_ENV_HIDE_BACKGROUND if hide_background else 0
+    return p
+
+
+def path_nee_params(environment, env_scale, hide_background, env_importance, who: str) -> "_ffi.PathNeeParams":
+    """trhip_path_nee_params from the Python arguments: path_env_params' checks, and env_importance — True (0.5) or a mix in (0, 1)."""
+    e = path_env_params(environment, env_scale, hide_background, who)
+    if env_importance is True:
+        mix = 0.5
+    elif isinstance(env_importance, bool) or not isinstance(env_importance, (int, float, np.floating)):
+        raise TraceHipError(f"{who}: env_importance must be None, True or a mix in (0, 1), not {env_importance!r}")
+    else:
+        mix = float(env_importance)
+    if not (0.0 < mix < 1.0) or not (0.0 < float(np.float32(mix)) < 1.0):
+        raise TraceHipError(f"{who}: env_importance must lie in (0, 1), not {env_importance}")
+    p = _ffi.default_params(_ffi.PathNeeParams, "trhip_path_nee_default_params")
+    p.scale, p.flags, p.mix = e.scale, e.flags, mix
     return p
 
 

@@ -43,6 +43,7 @@ struct LastRecords {
     uint32_t layout = 0, npix = 1, spp = 1;  // how they are laid out (th_kernels.h, film_index)
     uint32_t kind = 0;  // whose they are: 1 a one-band path frame or trhip_film_accumulate's records (trhip_last_sample_stats reads them), 2 a map frame (exported through map_counts), 0 anything else
     uint32_t path_env = 0;  // 1: a path-env frame's (tu_path_env.hip): Lbuf holds the folded records, env_base and env_rec what they were folded from (ctx->env_keep says how)
+                            // 2: a path-env frame with next-event estimation (tu_path_nee.hip): the same records for trhip_last_escapes, but no relight — the base holds the map's light
 };
 // What trhip_path_env_relight needs of the path-env frame before it to run the film pass "exactly as the frame ran it" (valid while ctx->last.path_env).
 struct PathEnvKeep {
@@ -99,7 +100,10 @@ struct trhip_ctx {
     DevBuf map_counts, map_offsets, map_jobs, map_tmp, map_word, map_mv, map_out;
     DevBuf env_base, env_rec;  // a path-env frame (th_path_env.h): the path's own radiance records (16 B per slot) and the escape records (32 B per slot); Lbuf holds their fold
     PathEnvKeep env_keep;
-    DevBuf cb_rc;      // one word: a host callback's return code, max-reduced over the ranks of a job (tu_sppm.hip)
+    // a path-env frame with next-event estimation (th_path_nee.h): per pipe the NEE shadow queues of odd / even depths (3 float4 arrays each) and their NeeCounters; one
+    // byte per slot: "the vertex before was non-specular"
+    DevBuf nee_sq[kMaxPipes][2][3], nee_ctr[kMaxPipes], nee_note;
+    DevBuf cb_rc;     // one word: a host callback's return code, max-reduced over the ranks of a job (tu_sppm.hip)
     DevBuf ov8[2], fb_list[2], fb_counts[2];  // k_trace8: global stack levels, fallback lists + their counters / work cursors ([closest | any])
     Comm comm;  // multi-GPU job this context belongs to (trhip_comm_init); n_ranks == 1 without one; trhip_shutdown destroys its communicator before the context goes
 };
@@ -480,6 +484,25 @@ void launch_escape_fold(trhip_ctx* ctx, hipStream_t st, const PathEnvFrame& f, u
 // tu_path.hip: trhip_render_path's frame — its refusals in its order, the classic wavefront without bands — with the environment frame
 int render_path_env_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out, bool out_is_device,
                           trhip_stats* stats, const trhip_env* env, float scale, uint32_t flags);
+// tu_path_nee.hip: next-event estimation of the environment map in a path-env frame (th_path_nee.h; docs/design/28-path-nee.md).  PathNeeFrame is handed to the loop beside
+// the PathEnvFrame: the mixture, and — filled by path_nee_buffers once the loop knows its pipes and queue size — where the notes, the NEE shadow queues and their counters are.
+struct PathNeeFrame {
+    float mix, om;               // om = 1 - mix, computed once in Float32
+    uint8_t* note;               // l_slots bytes: the vertex before was non-specular
+    ShadowQueue sq[kMaxPipes][2];  // by pipe and by parity of the depth, as the loop's own shadow queues
+    void* ctr[kMaxPipes];        // NeeCounters, zeroed per batch
+};
+int path_nee_check(trhip_ctx* ctx, const trhip_scene* scene, const trhip_env* env);  // an env without a sampler; a material that mixes specular and non-specular lobes
+// the budget (the path-env frame's per-sample bytes `sample_bytes`, the note byte and the queues must fit in half of free HBM) and the buffers
+int path_nee_buffers(trhip_ctx* ctx, PathNeeFrame& f, int n_pipes, uint64_t queue_entries, uint64_t total_slots, uint64_t l_slots, double sample_bytes, uint32_t spp);
+void path_nee_begin_batch(trhip_ctx* ctx, hipStream_t st, const PathNeeFrame& f, int pipe);
+void launch_path_nee(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, const uint32_t* counts, uint32_t cap, const PathQueue& q, const float4* hits, int depth, uint32_t hits_have_bary,
+                     const PathEnvFrame& ef, const PathNeeFrame& f, int pipe);
+// the any-hit launch over the NEE shadow rays of `depth`: open rays add their contribution to L
+void launch_nee_shadow(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, uint32_t cap, int depth, float4* L, const PathNeeFrame& f, int pipe, Counters* ctr, void* overflow_slab);
+void launch_escape_fold_nee(trhip_ctx* ctx, hipStream_t st, const PathEnvFrame& f, uint64_t l_slots, float4* out);
+int render_path_env_nee_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out,
+                              bool out_is_device, trhip_stats* stats, const trhip_env* env, float scale, uint32_t flags, float mix);
 // tu_whitted.hip
 int render_whitted_impl(trhip_ctx* ctx, const trhip_scene* scene, const DeviceSensor& ds, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
                         void* d_film, trhip_stats* stats);

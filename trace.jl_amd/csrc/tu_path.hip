@@ -335,7 +335,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
 // One band of a frame (band == nullptr: the whole frame, the normal case).  A band is a range of whole tile rows; its DeviceSensor carries
 // the range and whether the film gather starts from zero or adds onto the bands before (th_scene.h).
 int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, int integrator, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out,
-                     bool out_is_device, trhip_stats* stats, const DeviceSensor* band, const MapFrame* map = nullptr, const PathEnvFrame* envf_in = nullptr) {
+                     bool out_is_device, trhip_stats* stats, const DeviceSensor* band, const MapFrame* map = nullptr, const PathEnvFrame* envf_in = nullptr, const PathNeeFrame* nee_in = nullptr) {
     HostClock hclk;
     if (!ctx || !scene || !sensor || !out) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
     if (!scene->committed) return fail(ctx, TRHIP_ERR_INVALID, "scene not committed");
@@ -364,6 +364,8 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     if (total_slots >= (1ull << 32)) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "more than 2^32 camera samples in one band of a frame");
     if (envf_in)  // a path-env frame: the environment's refusals come after the path frame's
         if (int rc = path_env_check(ctx, envf_in->env, envf_in->scale)) return rc;
+    if (nee_in)  // … with next-event estimation (docs/design/28-path-nee.md): the sampler and the materials after those
+        if (int rc = path_nee_check(ctx, scene, envf_in->env)) return rc;
     if (integrator == 0) {
         if (int rc = upload(ctx, ctx->sensor, &ds, sizeof ds)) return rc;
         if (int rc = upload(ctx, ctx->table, sensor->filter_table, 256 * sizeof(float))) return rc;
@@ -414,7 +416,8 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         const size_t held = ctx->Lbuf.bytes + ctx->pfilm.bytes + held_in_pipes(ctx);  // reused below, so it counts as available
         const double avail = 0.85 * (double)(free_b + held) - (double)total_slots * (sizeof(float4) + sizeof(float2)) - 2.5e9 -
                              (envf_in ? (double)total_slots * 3.0 * sizeof(float4) : 0.0);  // (a path-env frame: the base records and the escape records beside Lbuf)
-        batch_paths = avail > 0 ? (uint64_t)(avail / 212.0) : npix;  // per path in flight: 2 x 3 queue float4 + 2 x 3 shadow float4 + 1 hit float4 + counters
+        // per path in flight: 2 x 3 queue float4 + 2 x 3 shadow float4 + 1 hit float4 + counters; with next-event estimation 2 x 3 NEE shadow float4 more
+        batch_paths = avail > 0 ? (uint64_t)(avail / (nee_in ? 308.0 : 212.0)) : npix;
     }
     uint64_t spp_batch = std::max<uint64_t>(1, batch_paths / npix);
     spp_batch = std::min<uint64_t>(spp_batch, spp);
@@ -464,6 +467,11 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         envf.base = (float4*)ctx->env_base.p;
         envf.rec = (float4*)ctx->env_rec.p;
     }
+    PathNeeFrame nee{};
+    if (nee_in) {  // the note bytes and, per pipe, the NEE shadow queues: refused where they do not fit beside the path-env frame's buffers
+        nee = *nee_in;
+        if (int rc = path_nee_buffers(ctx, nee, NP, Pphys, total_slots, l_slots, 65.0 + (fused ? 0.0 : film_sample_bytes(packed)), spp)) return rc;
+    }
     if (int rc = ensure_film_samples(ctx, packed, total_slots)) return rc;
     const size_t film_bytes = (size_t)ds.film_w * ds.film_h * sizeof(float4);
     void* d_film;
@@ -488,6 +496,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     }
     HIP_TRY(ctx, hipMemsetAsync(ctx->poison.p, 0, l_slots, st));
     if (envf_in) HIP_TRY(ctx, hipMemsetAsync(envf.rec, 0, l_slots * 2 * sizeof(float4), st));  // depth 0: no escape
+    if (nee_in) HIP_TRY(ctx, hipMemsetAsync(nee.note, 0, l_slots, st));  // depth 1 has no vertex before it
     HIP_TRY(ctx, hipEventRecord(ev_start.e, st));
     const int g_shade = ctx->num_cu * 8;
     const uint32_t bary_mode = (ctx->opt.traversal >= 2 && scene->wide_ok) ? 1u : 0u;  // k_trace2 hands the barycentrics to the shading kernel
@@ -497,7 +506,8 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         HIP_TRY(ctx, hipMemsetAsync(ctx->pipes[pi].counters.p, 0, sizeof(Counters), ctx->pipes[pi].st));
     }
     for (uint64_t j0 = 0; j0 < total_jobs; j0 += P) {  // (whole sample passes: j0 = s0 * npix)
-        Pipe& pp = ctx->pipes[n_batches % NP];
+        const int pipe = (int)(n_batches % NP);
+        Pipe& pp = ctx->pipes[pipe];
         n_batches++;
         const uint64_t nb = std::min<uint64_t>(P, total_jobs - j0);
         // Within a batch, shadow rays of depth d (any-hit + accumulate) and closest-hit rays of depth d+1 are independent: two streams.
@@ -515,6 +525,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         hipEvent_t ev_anys[2] = {pp.ev_any, pp.ev_any2};
         float4* hits = (float4*)pp.hits.p;
         HIP_TRY(ctx, hipMemsetAsync(ctr, 0, offsetof(Counters, closest_total), ps));  // queue sizes + work cursors of this batch
+        if (nee_in) path_nee_begin_batch(ctx, ps, nee, pipe);
         tm.begin(0, ps);
         if (map)
             hipLaunchKernelGGL((k_raygen<0, MapJobs>), dim3(grid_for(ctx, nb, 8)), dim3(kBlock), 0, ps, dsp, MapJobs{map->jobs, (uint32_t)j0}, (uint32_t)nb, seed, sample_offset, pq[0], cap, ctr, fused ? L : nullptr, spp, fside);
@@ -531,7 +542,11 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
             if (two && depth > 2) HIP_TRY(ctx, hipStreamWaitEvent(ps, ev_anys[depth & 1], 0));  // shade(d) refills the queue the shadow rays of depth d - 2 read
             tm.begin(2, ps);
             // every ray of this depth has its final answer: the entries that missed leave their record (one writer per slot; never L, which the shadow rays of depth - 1 may still add to)
-            if (envf_in) launch_path_escape(ctx, ps, ctr->n_queue[depth - 1], cap, pq[cur], hits, depth, envf.rec);
+            // (with next-event estimation k_path_nee stands in k_path_escape's place: the records with their marks, the notes, and the NEE shadow rays of this depth)
+            if (nee_in)
+                launch_path_nee(ctx, ps, scene, ctr->n_queue[depth - 1], cap, pq[cur], hits, depth, bary_mode, envf, nee, pipe);
+            else if (envf_in)
+                launch_path_escape(ctx, ps, ctr->n_queue[depth - 1], cap, pq[cur], hits, depth, envf.rec);
             const ShadeStream sst{nullptr, nullptr, 0u, two ? (uint8_t*)ctx->poison.p : nullptr};
             if (has_directional_light(scene)) {
                 if (scene->dev.tri_tan)
@@ -550,6 +565,8 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
             }
             tm.begin(3, ps2);
             launch_trace(ctx, ps2, scene, true, SegQueue{ctr->n_shadow[depth - 1], cap, 0u}, sq.o, sq.d, nullptr, TraceOut{nullptr, L, sq.c, nullptr}, ctr->work_shadow[depth - 1], ctr, pp.overflow[1].p);
+            // the NEE rays of the same depth directly after: the two terms of one depth reach L[slot] in model order, and no launch holds two writers of one slot
+            if (nee_in) launch_nee_shadow(ctx, ps2, scene, cap, depth, L, nee, pipe, ctr, pp.overflow[1].p);
             tm.end(3, ps2);
             if (two) HIP_TRY(ctx, hipEventRecord(ev_anys[depth & 1], ps2));
             cur ^= 1;
@@ -566,7 +583,10 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     tm.begin(4, st);
     if (ctx->opt.overlap) hipLaunchKernelGGL(k_apply_poison, dim3(grid_for(ctx, l_slots, 8)), dim3(kBlock), 0, st, L, (const uint8_t*)ctx->poison.p, l_slots);
     if (envf_in) {  // out = base, + beta * (E(dir) * scale) where a record contributes; the film pass and trhip_last_sample_radiance read out
-        launch_escape_fold(ctx, st, envf, l_slots, (float4*)ctx->Lbuf.p);
+        if (nee_in)
+            launch_escape_fold_nee(ctx, st, envf, l_slots, (float4*)ctx->Lbuf.p);
+        else
+            launch_escape_fold(ctx, st, envf, l_slots, (float4*)ctx->Lbuf.p);
         L = (float4*)ctx->Lbuf.p;
     }
     launch_film(ctx, st, ds, dsp, L, total_slots, spp, seed, sample_offset, (float4*)d_film, fused, map);
@@ -576,7 +596,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     hclk.tick("enqueue");
     HIP_TRY(ctx, hipStreamSynchronize(st));
     hclk.tick("stream sync");
-    ctx->last = LastRecords{total_slots, fused ? 1u : 0u, (uint32_t)npix, spp, map ? 2u : band ? 0u : 1u, envf_in ? 1u : 0u};
+    ctx->last = LastRecords{total_slots, fused ? 1u : 0u, (uint32_t)npix, spp, map ? 2u : band ? 0u : 1u, nee_in ? 2u : envf_in ? 1u : 0u};
     if (envf_in) {  // what trhip_path_env_relight repeats the film pass with
         PathEnvKeep& k = ctx->env_keep;
         k.ds = ds;
@@ -701,6 +721,15 @@ int render_map_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor
     return render_impl_band(ctx, scene, sensor, 1, max_spp, max_depth, seed, sample_offset, out, on_device, stats, nullptr, &map);
 }
 }  // namespace
+
+int render_path_env_nee_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out,
+                              bool out_is_device, trhip_stats* stats, const trhip_env* env, float scale, uint32_t flags, float mix) {
+    const PathEnvFrame f{env, scale, flags, nullptr, nullptr};
+    PathNeeFrame n{};
+    n.mix = mix;
+    n.om = 1.0f - mix;  // once, in Float32: the kernel's (1 - mix)
+    return render_impl_band(ctx, scene, sensor, 1, spp, max_depth, seed, sample_offset, out, out_is_device, stats, nullptr, nullptr, &f, &n);
+}
 
 int render_path_env_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out, bool out_is_device,
                           trhip_stats* stats, const trhip_env* env, float scale, uint32_t flags) {

@@ -31,6 +31,8 @@ int relight_impl(trhip_ctx* ctx, const trhip_env* env, const trhip_path_env_para
     if (int rc = check_params(ctx, prm, "trhip_path_env_relight")) return rc;
     if (!ctx || !out) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
     if (!ctx->last.path_env) return fail(ctx, TRHIP_ERR_INVALID, "trhip_path_env_relight: the context's last frame is not a path-env frame");
+    if (ctx->last.path_env == 2)  // (tu_path_nee.hip: the base records hold the map's direct light, which no fold can exchange)
+        return fail(ctx, TRHIP_ERR_INVALID, "trhip_path_env_relight: the context's last frame was rendered with next-event estimation (trhip_render_path_env_nee): its base radiance contains the map");
     if (int rc = path_env_check(ctx, env, prm->scale)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const PathEnvKeep k = ctx->env_keep;

@@ -110,3 +110,6 @@ function (i::SkyISIntegrator)(scene::Trace.Scene)
     write_film!(film, out, h, w)
     Trace.save(film)
 end
+
+# next-event estimation of the environment map in path frames (trhip_render_path_env_nee): PathNEEIntegrator (tests/golden/julia_shim_path_nee_calls.json)
+include("TraceHIPPathNEE.jl")
