@@ -47,7 +47,10 @@ enum {
     TS_V_SCATTER_U1 = 4,
     TS_V_BSDF_U0 = 5,
     TS_V_BSDF_U1 = 6,
-    TS_V_RR = 7
+    TS_V_RR = 7,
+    /* an emit frame's next-event estimate at vertex v (tracehip.h, trhip_render_path_emit) draws TS_DIM_EMIT_BASE + 3 v + {0, 1, 2} = pick, u0, u1:
+     * above every vertex dimension (the last vertex, v = 62, ends at 5 + 8 * 63 - 1 = 508), so no existing frame consumes them */
+    TS_DIM_EMIT_BASE = 517
 };
 
 TS_HD uint64_t ts_mix64(uint64_t z) {

@@ -562,6 +562,51 @@ int trhip_render_path_env_nee(trhip_ctx* ctx, const trhip_scene* scene, const tr
 int trhip_render_path_env_nee_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
                                      const trhip_env* env, const trhip_path_nee_params* params, void* d_out_xyzw, trhip_stats* stats);
 
+/* ---- area lights in path frames: emissive triangles (since ABI 3001, added without a version change: nothing existing moved)
+ * docs/design/29-path-emit.md holds the specification, step by step.
+ *
+ * An emitter set is made from a committed scene: every triangle whose material id is listed emits that material's radiance Le, on both sides.  Emitters are ordered by
+ * canonical primitive slot, ascending.  The set belongs to the scene's committed geometry (trhip_scene_geometry_id) and serves every relit view of it.  Its sampling table
+ * is built once on the host in Float64: weight_j = area_j * (Le.r + Le.g + Le.b), a cdf of n + 1 Float32 values; pick(xi) is the largest j with cdf[j] <= xi, the point
+ * s = sqrt(u0), b0 = 1 - s, b1 = u1 s, b2 = (1 - b0) - b1, y = (b0 p0 + b1 p1) + b2 p2, and the area density P_j / A_j with P_j = cdf[j + 1] - cdf[j].
+ * trhip_emitters_create refuses, in this order: null arguments or n_materials == 0; a radiance component that is not finite or is negative (before any handle is looked
+ * at); a scene that is not committed or belongs to another context; an unknown or repeated material id; a listed material carried by a sphere (TRHIP_ERR_UNSUPPORTED); no
+ * triangle with positive weight; more than 2^20 emissive triangles (TRHIP_ERR_UNSUPPORTED).
+ * trhip_emitters_sample runs pick and point on the device for `count` triples (xi, u0, u1): the emitter's index, the point and the area density. */
+typedef struct trhip_emitters trhip_emitters;
+int trhip_emitters_create(trhip_ctx* ctx, const trhip_scene* scene, const uint32_t* material_ids, const float* radiance_rgb3, uint32_t n_materials, trhip_emitters** out);
+void trhip_emitters_free(trhip_emitters* em);
+int trhip_emitters_size(const trhip_emitters* em, uint32_t* n_triangles);
+int trhip_emitters_sample(trhip_ctx* ctx, const trhip_emitters* em, const float* u3, uint64_t count, uint32_t* out_index, float* out_point3, float* out_pdf_area);
+
+/* trhip_render_path_emit: trhip_render_path in which the emitters shine.  At a hit at depth d (vertex v = d - 1):
+ *  1. where the hit triangle's material emits, and d == 1 or vertex d - 1 had specular lobes only or TRHIP_PATH_EMIT_HITS_ONLY is set, the sample's emitted sum gains
+ *     beta * (Le * scale);
+ *  2. the path continues exactly as in trhip_render_path — its rays, its throughput, its point-light term, its Russian roulette — in every bit;
+ *  3. without HITS_ONLY, at every vertex whose BSDF has a non-specular lobe — the last one, at max_depth, included — one shadow ray estimates the emitters' direct light:
+ *     (xi, u0, u1) = ts_uniform(key, TS_DIM_EMIT_BASE + 3 v + {0, 1, 2}), j = pick(xi), y = point_j(u0, u1), wi = (y - p) / dist, and where nothing lies within
+ *     dist * 0.999 the sample gains  beta * ((f(wo, wi) |wi . n|) * (Le_j * scale) / ((P_j / A_j) dist^2 / |n_j . wi|))  after the vertex's point-light term.
+ * Per sample the radiance is L + Lh (the emitted sum, added to in depth order), then the NaN rule and the film pass.  With scale == 0 the frame is trhip_render_path bit
+ * for bit wherever the throughput stays finite; with HITS_ONLY it is plain path tracing, the unbiased reference estimator.
+ * trhip_last_emitted: 4 floats per camera sample — Lh.rgb and the number of counted hits —, indexed like trhip_last_sample_radiance; valid only after an emit frame.
+ * Options and statistics as trhip_render_path_env (no bands, no streaming); shadow_rays counts the point-light rays and the emitter rays.
+ * Refusals, in this order: the parameter block (NULL; scale not finite or negative; unknown flag bits; reserved), before any handle is looked at; trhip_render_path's in
+ * its order; null emitters or emitters of another context; emitters of another geometry than the scene's; TRHIP_ERR_UNSUPPORTED for a scene with a material whose lobe set
+ * mixes specular and non-specular lobes, and for a frame whose per-sample buffers and shadow queues do not fit in half of free HBM.
+ * trhip_path_emit_default_params needs no context. */
+#define TRHIP_PATH_EMIT_HITS_ONLY 1u /* no next-event estimation; every hit on an emitter counts */
+typedef struct {
+    float scale;              /* multiplies every Le: finite, >= 0 */
+    uint32_t flags;           /* TRHIP_PATH_EMIT_HITS_ONLY */
+    uint32_t reserved[6];     /* 0 */
+} trhip_path_emit_params;     /* 32 bytes */
+int trhip_path_emit_default_params(trhip_path_emit_params* out); /* {1, 0, {0, 0, 0, 0, 0, 0}} */
+int trhip_render_path_emit(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
+                           const trhip_emitters* emitters, const trhip_path_emit_params* params, float* out_xyzw, trhip_stats* stats);
+int trhip_render_path_emit_device(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
+                                  const trhip_emitters* emitters, const trhip_path_emit_params* params, void* d_out_xyzw, trhip_stats* stats);
+int trhip_last_emitted(trhip_ctx* ctx, float* out4, uint64_t n_floats);
+
 /* ---- edge-avoiding denoiser for path / Whitted films (since ABI 3001, added without a version change: nothing existing moved) ----
  * An à-trous wavelet filter after Dammertz et al. 2010 ("Edge-Avoiding À-Trous Wavelet Transform for fast Global Illumination
  * Filtering") on the film state of a path or Whitted render, guided by the three planes of trhip_render_aov for the same sensor,

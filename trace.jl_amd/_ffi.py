@@ -204,6 +204,18 @@ class PathNeeParams(C.Structure):
     ]
 
 
+class PathEmitParams(C.Structure):
+    """trhip_path_emit_params (32 bytes)"""
+    _fields_ = [
+        ("scale", C.c_float),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 6),
+    ]
+
+
+PATH_EMIT_HITS_ONLY = 1  # TRHIP_PATH_EMIT_HITS_ONLY
+
+
 class TemporalParams(C.Structure):
     """trhip_temporal_params (72 bytes)"""
     _fields_ = [
@@ -455,6 +467,14 @@ SIGNATURES = {
     "trhip_path_nee_default_params": (C.c_int, [C.POINTER(PathNeeParams)]),
     "trhip_render_path_env_nee": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(PathNeeParams), _F, C.POINTER(Stats)]),
     "trhip_render_path_env_nee_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(PathNeeParams), _VP, C.POINTER(Stats)]),
+    "trhip_emitters_create": (C.c_int, [_VP, _VP, C.POINTER(C.c_uint32), _F, C.c_uint32, C.POINTER(_VP)]),
+    "trhip_emitters_free": (None, [_VP]),
+    "trhip_emitters_size": (C.c_int, [_VP, C.POINTER(C.c_uint32)]),
+    "trhip_emitters_sample": (C.c_int, [_VP, _VP, _F, C.c_uint64, C.POINTER(C.c_uint32), _F, _F]),
+    "trhip_path_emit_default_params": (C.c_int, [C.POINTER(PathEmitParams)]),
+    "trhip_render_path_emit": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(PathEmitParams), _F, C.POINTER(Stats)]),
+    "trhip_render_path_emit_device": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, _VP, C.POINTER(PathEmitParams), _VP, C.POINTER(Stats)]),
+    "trhip_last_emitted": (C.c_int, [_VP, _F, C.c_uint64]),
     "trhip_path_env_relight": (C.c_int, [_VP, _VP, C.POINTER(PathEnvParams), _F]),
     "trhip_path_env_relight_device": (C.c_int, [_VP, _VP, C.POINTER(PathEnvParams), _VP]),
     "trhip_render_aov_ids": (C.c_int, [_VP, _VP, C.POINTER(Sensor), C.c_uint32, C.c_uint64, C.c_uint32, _F, _VP, _VP, C.POINTER(Stats)]),

@@ -183,7 +183,7 @@ def _tex_f(t) -> float:
     return float(f32(v))
 
 
-@dataclass
+@dataclass(unsafe_hash=True)  # (hashable, by its fields as == compares them: Emitters takes {material: radiance})
 class MatteMaterial:  # materials/material.jl:1-31
     Kd: ConstantTexture
     sigma: ConstantTexture
@@ -192,7 +192,7 @@ class MatteMaterial:  # materials/material.jl:1-31
         return 0, _tex_rgb(self.Kd) + [_tex_f(self.sigma)]
 
 
-@dataclass
+@dataclass(unsafe_hash=True)  # (hashable, by its fields as == compares them: Emitters takes {material: radiance})
 class MirrorMaterial:  # :34-46
     Kr: ConstantTexture
 
@@ -200,7 +200,7 @@ class MirrorMaterial:  # :34-46
         return 1, _tex_rgb(self.Kr)
 
 
-@dataclass
+@dataclass(unsafe_hash=True)  # (hashable, by its fields as == compares them: Emitters takes {material: radiance})
 class GlassMaterial:  # :49-116
     Kr: ConstantTexture
     Kt: ConstantTexture
@@ -213,7 +213,7 @@ class GlassMaterial:  # :49-116
         return 2, _tex_rgb(self.Kr) + _tex_rgb(self.Kt) + [_tex_f(self.u_roughness), _tex_f(self.v_roughness), _tex_f(self.index), 1.0 if self.remap_roughness else 0.0]
 
 
-@dataclass
+@dataclass(unsafe_hash=True)  # (hashable, by its fields as == compares them: Emitters takes {material: radiance})
 class PlasticMaterial:  # :119-151
     Kd: ConstantTexture
     Ks: ConstantTexture
@@ -771,6 +771,7 @@ class FlatScene:
         self._h = C.c_void_p()
         ctx.check(L.trhip_scene_new(ctx._h, C.byref(self._h)))
         mat_ids = {}
+        self.materials = []  # the material objects in id order (kept: Emitters resolves a material object to its id through material_id_of)
 
         def material_id(m):
             if m is None:
@@ -781,6 +782,7 @@ class FlatScene:
                 out = C.c_uint32()
                 ctx.check(L.trhip_scene_add_material(self._h, kind, _ffi.fptr(p), p.size, C.byref(out)))
                 mat_ids[id(m)] = out.value
+                self.materials.append(m)
             return mat_ids[id(m)]
 
         prims = splice_nested(scene.aggregate.primitives)
@@ -833,6 +835,7 @@ class FlatScene:
         self._h = C.c_void_p()
         self.n_prims = base.n_prims
         self.top_counts = base.top_counts
+        self.materials = base.materials
         self.ctx.check(L.trhip_scene_relight(base._h, C.byref(self._h)))
         self._add_lights(scene)
         self.ctx.check(L.trhip_scene_commit(self._h, scene.aggregate.max_node_primitives))
@@ -899,6 +902,13 @@ class FlatScene:
         if order.size != per_prim.size:
             raise TraceHipError(f"FlatScene.body_table: the scene holds {order.size} primitives, its top-level entries {per_prim.size}")
         return np.ascontiguousarray(per_prim[order], dtype=np.uint32)
+
+    def material_id_of(self, material) -> int:
+        """The id this flat scene gave `material` (the object itself, not an equal one) when it was flattened."""
+        for k, m in enumerate(self.materials):
+            if m is material:
+                return k
+        raise TraceHipError(f"the scene has no primitive with this {type(material).__name__} object")
 
     @property
     def geometry_id(self) -> int:
@@ -1048,14 +1058,25 @@ class PathIntegrator(_SamplerIntegrator):
     _entry = "trhip_render_path"
 
     def render(self, scene: Scene, ctx: Optional[_ffi.Context] = None, device_out: Optional[int] = None, sample_map: Optional["SampleMap"] = None,
-               environment: Optional["Environment"] = None, env_scale: float = 1.0, hide_background: bool = False, env_importance=None) -> np.ndarray:
+               environment: Optional["Environment"] = None, env_scale: float = 1.0, hide_background: bool = False,
+               emitters: Optional["Emitters"] = None, emit_scale: float = 1.0, emit_hits_only: bool = False, env_importance=None) -> np.ndarray:
         """_SamplerIntegrator.render; with ``sample_map`` a map frame (trhip_render_path_map): sample pixel p draws ``sample_map.counts[p]`` samples from the sampler's
         sample_offset on, and ``sampler.samples_per_pixel`` is not read.  With ``environment`` a path-env frame (trhip_render_path_env; docs/design/26-path-env.md): a path
         that leaves the scene brings back beta * E(dir) * env_scale — not at depth 1 with ``hide_background`` — and escapes() / relight() work on the frame afterwards.
         With ``env_importance`` as well — a mix in (0, 1), or True for 0.5 — the frame estimates the map's direct light at every non-specular vertex with one shadow ray,
         drawn from the map with that probability and from the BSDF otherwise (trhip_render_path_env_nee; docs/design/28-path-nee.md): far less noise under a small bright
-        sun; escapes() and suppressed() work afterwards, relight() does not.  Without any of them it is trhip_render_path, the same call and the same bits."""
+        sun; escapes() and suppressed() work afterwards, relight() does not.  With ``emitters`` an emit frame (trhip_render_path_emit; docs/design/29-path-emit.md): the
+        triangles of the set's materials shine with their radiance times ``emit_scale``, every non-specular vertex casts one shadow ray towards them, and emitted() works
+        afterwards; ``emit_hits_only`` casts none and counts every hit on an emitter instead — plain path tracing, the reference estimator.  Without any of them it is
+        trhip_render_path, the same call and the same bits."""
         smp = self.sampler
+        if emitters is not None:
+            if sample_map is not None or environment is not None or env_importance is not None:
+                raise TraceHipError("PathIntegrator.render: emitters cannot be combined with sample_map or environment")
+            prm = path_emit_params(emitters, emit_scale, emit_hits_only, "PathIntegrator.render")
+            flat = scene.flatten(ctx)
+            args = (smp.samples_per_pixel, self.max_depth, smp.seed, smp.sample_offset, emitters._handle_for(flat), C.byref(prm))
+            return self._render_film(flat, "trhip_render_path_emit", args, device_out)
         if env_importance is not None:
             if sample_map is not None:
                 raise TraceHipError("PathIntegrator.render: sample_map and env_importance cannot be combined (map frames have no environment term)")
@@ -1093,6 +1114,15 @@ class PathIntegrator(_SamplerIntegrator):
         flat.ctx.check(_ffi.lib().trhip_last_escapes(flat.ctx._h, _ffi.fptr(rec), rec.size))
         return rec[..., 0:3].copy(), rec[..., 3].astype(np.int32), rec[..., 4:7].copy()
 
+    def emitted(self, scene: Scene):
+        """(Lh, hits) of the last render(emitters=...) on the scene's context (trhip_last_emitted): the emitted light every camera sample collected, (spp, sb_h, sb_w, 3),
+        and the number of hits on an emitter that counted, (spp, sb_h, sb_w) int32; shaped like sample_radiance."""
+        flat = scene.flatten()
+        sbh, sbw, _, _ = sample_bounds_shape(self.camera.film)
+        rec = np.empty((self.sampler.samples_per_pixel, sbh, sbw, 4), dtype=np.float32)
+        flat.ctx.check(_ffi.lib().trhip_last_emitted(flat.ctx._h, _ffi.fptr(rec), rec.size))
+        return rec[..., 0:3].copy(), rec[..., 3].astype(np.int32)
+
     def suppressed(self, scene: Scene) -> np.ndarray:
         """Which escapes of the last render(environment=..., env_importance=...) do not count, because next-event estimation at the vertex before has already accounted for
         their light (the 8th float of trhip_last_escapes): (spp, sb_h, sb_w) bool, shaped like escapes()'s depth; all False after a frame without env_importance."""
@@ -1128,6 +1158,18 @@ def path_env_params(environment, env_scale, hide_background, who: str) -> "_ffi.
         raise TraceHipError(f"{who}: env_scale must be finite and >= 0, not {env_scale}")
     p = _ffi.default_params(_ffi.PathEnvParams, "trhip_path_env_default_params")
     p.scale, p.flags = scale, _ffi.PATH_ENV_HIDE_BACKGROUND if hide_background else 0
+    return p
+
+
+def path_emit_params(emitters, emit_scale, emit_hits_only, who: str) -> "_ffi.PathEmitParams":
+    """trhip_path_emit_params from the Python arguments, with the checks that need no library call answered here."""
+    if not isinstance(emitters, Emitters):
+        raise TraceHipError(f"{who}: emitters must be an Emitters, not {type(emitters).__name__}")
+    scale = float(emit_scale)
+    if not (scale >= 0.0 and math.isfinite(scale)):
+        raise TraceHipError(f"{who}: emit_scale must be finite and >= 0, not {emit_scale}")
+    p = _ffi.default_params(_ffi.PathEmitParams, "trhip_path_emit_default_params")
+    p.scale, p.flags = scale, _ffi.PATH_EMIT_HITS_ONLY if emit_hits_only else 0
     return p
 
 
@@ -1571,6 +1613,66 @@ class Environment:
                 _ffi.lib().trhip_env_free(h)
         self._handles = {}
         self._samplers = set()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Emitters:
+    """The area lights of a scene (trhip_emitters; docs/design/29-path-emit.md): every triangle that carries one of the given material objects emits that material's
+    radiance, on both sides.  ``radiance`` is {material object: RGBSpectrum}, each finite, >= 0.  The set is made from the scene's committed geometry — `scene` is flattened
+    on `ctx` if it is not yet — and serves every relit view of it (Scene.with_lights); PathIntegrator.render(scene, emitters=...) renders with it."""
+
+    def __init__(self, scene: Scene, radiance, ctx: Optional[_ffi.Context] = None):
+        if not isinstance(radiance, dict) or not radiance:
+            raise TraceHipError("Emitters: radiance must be a non-empty {material: RGBSpectrum}")
+        mats, le = list(radiance.keys()), []
+        for m in mats:
+            v = radiance[m]
+            c = np.asarray(v.c if isinstance(v, RGBSpectrum) else v, dtype=np.float32).reshape(-1)
+            if c.shape != (3,) or not np.isfinite(c).all() or (c < 0).any():
+                raise TraceHipError("Emitters: every radiance must be an RGBSpectrum with finite components >= 0")
+            le.append(c)
+        flat = scene.flatten(ctx)
+        ids = np.array([flat.material_id_of(m) for m in mats], dtype=np.uint32)
+        le = np.ascontiguousarray(np.stack(le), dtype=np.float32)
+        self.ctx, self.geometry_id = flat.ctx, flat.geometry_id
+        self._h = C.c_void_p()
+        self.ctx.check(_ffi.lib().trhip_emitters_create(self.ctx._h, flat._h, _ffi.u32ptr(ids), _ffi.fptr(le), ids.size, C.byref(self._h)))
+        n = C.c_uint32()
+        self.ctx.check(_ffi.lib().trhip_emitters_size(self._h, C.byref(n)))
+        self.n_triangles = int(n.value)
+
+    def _handle_for(self, flat: "FlatScene"):
+        if not self._h:
+            raise TraceHipError("Emitters: closed")
+        if flat.ctx is not self.ctx:
+            raise TraceHipError("Emitters: made on another context than the scene's")
+        return self._h
+
+    def sample(self, u, ctx: Optional[_ffi.Context] = None):
+        """(index, point, pdf_area) for every triple (xi, u0, u1) of `u` (..., 3) in [0, 1)^3: the emitter the device's sampler picks, the point on it and the density
+        with respect to area (trhip_emitters_sample)."""
+        p = _ffi.f32(u)
+        if p.ndim < 1 or p.shape[-1] != 3:
+            raise TraceHipError(f"Emitters.sample: points must be (..., 3), not {p.shape}")
+        if not ((p >= 0) & (p < 1)).all():
+            raise TraceHipError("Emitters.sample: every coordinate must lie in [0, 1)")
+        if ctx is not None and ctx is not self.ctx:
+            raise TraceHipError("Emitters.sample: made on another context")
+        idx = np.empty(p.shape[:-1], dtype=np.uint32)
+        pts = np.empty(p.shape[:-1] + (3,), dtype=np.float32)
+        pdf = np.empty(p.shape[:-1], dtype=np.float32)
+        self.ctx.check(_ffi.lib().trhip_emitters_sample(self.ctx._h, self._h, _ffi.fptr(p), p.size // 3, _ffi.u32ptr(idx), _ffi.fptr(pts), _ffi.fptr(pdf)))
+        return idx, pts, pdf
+
+    def close(self):
+        if self._h and self.ctx._h:  # (a context that was shut down took its device memory with it)
+            _ffi.lib().trhip_emitters_free(self._h)
+        self._h = None
 
     def __del__(self):
         try:

@@ -44,6 +44,7 @@ struct LastRecords {
     uint32_t kind = 0;  // whose they are: 1 a one-band path frame or trhip_film_accumulate's records (trhip_last_sample_stats reads them), 2 a map frame (exported through map_counts), 0 anything else
     uint32_t path_env = 0;  // 1: a path-env frame's (tu_path_env.hip): Lbuf holds the folded records, env_base and env_rec what they were folded from (ctx->env_keep says how)
                             // 2: a path-env frame with next-event estimation (tu_path_nee.hip): the same records for trhip_last_escapes, but no relight — the base holds the map's light
+    uint32_t emit = 0;  // 1: an emit frame's (tu_path_emit.hip): Lbuf holds L + Lh, emit_lh the emitted sums (trhip_last_emitted)
 };
 // What trhip_path_env_relight needs of the path-env frame before it to run the film pass "exactly as the frame ran it" (valid while ctx->last.path_env).
 struct PathEnvKeep {
@@ -103,6 +104,9 @@ struct trhip_ctx {
     // a path-env frame with next-event estimation (th_path_nee.h): per pipe the NEE shadow queues of odd / even depths (3 float4 arrays each) and their NeeCounters; one
     // byte per slot: "the vertex before was non-specular"
     DevBuf nee_sq[kMaxPipes][2][3], nee_ctr[kMaxPipes], nee_note;
+    // an emit frame (th_path_emit.h) runs on the same queues, counters and note bytes (there: "the vertex before was specular") and on env_base for the path's own records;
+    // beside them the reach of every emitter ray, per pipe and parity (4 B per queue entry), and the per-sample emitted sums Lh (16 B per slot)
+    DevBuf emit_tmax[kMaxPipes][2], emit_lh;
     DevBuf cb_rc;     // one word: a host callback's return code, max-reduced over the ranks of a job (tu_sppm.hip)
     DevBuf ov8[2], fb_list[2], fb_counts[2];  // k_trace8: global stack levels, fallback lists + their counters / work cursors ([closest | any])
     Comm comm;  // multi-GPU job this context belongs to (trhip_comm_init); n_ranks == 1 without one; trhip_shutdown destroys its communicator before the context goes
@@ -493,6 +497,7 @@ struct PathNeeFrame {
     void* ctr[kMaxPipes];        // NeeCounters, zeroed per batch
 };
 int path_nee_check(trhip_ctx* ctx, const trhip_scene* scene, const trhip_env* env);  // an env without a sampler; a material that mixes specular and non-specular lobes
+int path_mixed_lobes_check(trhip_ctx* ctx, const trhip_scene* scene, const char* entry);  // … the second of the two on its own (an emit frame refuses the same materials)
 // the budget (the path-env frame's per-sample bytes `sample_bytes`, the note byte and the queues must fit in half of free HBM) and the buffers
 int path_nee_buffers(trhip_ctx* ctx, PathNeeFrame& f, int n_pipes, uint64_t queue_entries, uint64_t total_slots, uint64_t l_slots, double sample_bytes, uint32_t spp);
 void path_nee_begin_batch(trhip_ctx* ctx, hipStream_t st, const PathNeeFrame& f, int pipe);
@@ -503,6 +508,33 @@ void launch_nee_shadow(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene,
 void launch_escape_fold_nee(trhip_ctx* ctx, hipStream_t st, const PathEnvFrame& f, uint64_t l_slots, float4* out);
 int render_path_env_nee_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out,
                               bool out_is_device, trhip_stats* stats, const trhip_env* env, float scale, uint32_t flags, float mix);
+// tu_path_emit.hip: area lights in path frames (th_path_emit.h; docs/design/29-path-emit.md).  PathEmitFrame is handed to the loop the way a PathNeeFrame is: the emitter set
+// and the parameters, and — filled by path_emit_buffers once the loop knows its pipes and queue size — where the base records, the emitted sums, the notes, the emitter
+// shadow queues with their reaches and the counters are.
+struct trhip_emitters;
+struct PathEmitFrame {
+    const trhip_emitters* em;
+    float scale;
+    uint32_t flags;
+    float4* base;                // l_slots records: the shading kernels' and the shadow rays' target in Lbuf's place
+    float4* lh;                  // l_slots: {Lh.rgb, counted hits}
+    uint8_t* note;               // l_slots bytes: the vertex before was specular
+    ShadowQueue sq[kMaxPipes][2];  // by pipe and by parity of the depth
+    float* tmax[kMaxPipes][2];   // the reach of every queue entry
+    void* ctr[kMaxPipes];        // NeeCounters, zeroed per batch
+};
+int path_emit_check(trhip_ctx* ctx, const trhip_scene* scene, const trhip_emitters* em);  // null / another context's; another geometry's; a material that mixes lobes
+// the budget (per-sample buffers and queues must fit in half of free HBM; `film_bytes`: what an unfused film pass reads per sample) and the buffers
+int path_emit_buffers(trhip_ctx* ctx, PathEmitFrame& f, int n_pipes, uint64_t queue_entries, uint64_t total_slots, uint64_t l_slots, double film_bytes, uint32_t spp);
+void path_emit_begin_batch(trhip_ctx* ctx, hipStream_t st, const PathEmitFrame& f, int pipe);
+void launch_path_emit(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, const uint32_t* counts, uint32_t cap, const PathQueue& q, const float4* hits, int depth, uint32_t hits_have_bary,
+                      const PathEmitFrame& f, int pipe);
+// the any-hit launch over the emitter rays of `depth`, each with its reach: open rays add their contribution to L
+void launch_emit_shadow(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, uint32_t cap, int depth, float4* L, const PathEmitFrame& f, int pipe, Counters* ctr, void* overflow_slab);
+void launch_emit_fold(trhip_ctx* ctx, hipStream_t st, const PathEmitFrame& f, uint64_t l_slots, float4* out);
+// tu_path.hip: trhip_render_path's frame — its refusals in its order, the classic wavefront without bands — with the emit frame
+int render_path_emit_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out,
+                           bool out_is_device, trhip_stats* stats, const trhip_emitters* em, float scale, uint32_t flags);
 // tu_whitted.hip
 int render_whitted_impl(trhip_ctx* ctx, const trhip_scene* scene, const DeviceSensor& ds, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
                         void* d_film, trhip_stats* stats);

@@ -335,7 +335,8 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
 // One band of a frame (band == nullptr: the whole frame, the normal case).  A band is a range of whole tile rows; its DeviceSensor carries
 // the range and whether the film gather starts from zero or adds onto the bands before (th_scene.h).
 int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, int integrator, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out,
-                     bool out_is_device, trhip_stats* stats, const DeviceSensor* band, const MapFrame* map = nullptr, const PathEnvFrame* envf_in = nullptr, const PathNeeFrame* nee_in = nullptr) {
+                     bool out_is_device, trhip_stats* stats, const DeviceSensor* band, const MapFrame* map = nullptr, const PathEnvFrame* envf_in = nullptr, const PathNeeFrame* nee_in = nullptr,
+                     const PathEmitFrame* emit_in = nullptr) {
     HostClock hclk;
     if (!ctx || !scene || !sensor || !out) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
     if (!scene->committed) return fail(ctx, TRHIP_ERR_INVALID, "scene not committed");
@@ -366,6 +367,8 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         if (int rc = path_env_check(ctx, envf_in->env, envf_in->scale)) return rc;
     if (nee_in)  // … with next-event estimation (docs/design/28-path-nee.md): the sampler and the materials after those
         if (int rc = path_nee_check(ctx, scene, envf_in->env)) return rc;
+    if (emit_in)  // an emit frame (docs/design/29-path-emit.md): the emitter set's refusals and the materials come after the path frame's
+        if (int rc = path_emit_check(ctx, scene, emit_in->em)) return rc;
     if (integrator == 0) {
         if (int rc = upload(ctx, ctx->sensor, &ds, sizeof ds)) return rc;
         if (int rc = upload(ctx, ctx->table, sensor->filter_table, 256 * sizeof(float))) return rc;
@@ -380,7 +383,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         ctx->last = LastRecords{total_slots, 0u, (uint32_t)npix, spp, 0u};  // (render_whitted_impl has synchronised its stream)
         return copy_back(ctx, out, out_is_device, df, fb);
     }
-    if (!band && !map && !envf_in && (ctx->opt.streaming == 1 || (ctx->opt.streaming < 0 && total_slots <= 96ull * scene->g->prims.size())) && ctx->opt.traversal >= 2 && scene->wide_ok && scene->wide.root_cnt == 0 && scene->wide.root_ref != kRefNone && ctx->opt.batch_paths == 0 && ctx->opt.pipelines <= 1) {
+    if (!band && !map && !envf_in && !emit_in && (ctx->opt.streaming == 1 || (ctx->opt.streaming < 0 && total_slots <= 96ull * scene->g->prims.size())) && ctx->opt.traversal >= 2 && scene->wide_ok && scene->wide.root_cnt == 0 && scene->wide.root_ref != kRefNone && ctx->opt.batch_paths == 0 && ctx->opt.pipelines <= 1) {
         bool declined = false;
         const int rc = render_stream_impl(ctx, scene, sensor, ds, spp, max_depth, seed, sample_offset, out, out_is_device, stats, &declined);
         if (!declined) return rc;
@@ -415,9 +418,11 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
         const size_t held = ctx->Lbuf.bytes + ctx->pfilm.bytes + held_in_pipes(ctx);  // reused below, so it counts as available
         const double avail = 0.85 * (double)(free_b + held) - (double)total_slots * (sizeof(float4) + sizeof(float2)) - 2.5e9 -
-                             (envf_in ? (double)total_slots * 3.0 * sizeof(float4) : 0.0);  // (a path-env frame: the base records and the escape records beside Lbuf)
-        // per path in flight: 2 x 3 queue float4 + 2 x 3 shadow float4 + 1 hit float4 + counters; with next-event estimation 2 x 3 NEE shadow float4 more
-        batch_paths = avail > 0 ? (uint64_t)(avail / (nee_in ? 308.0 : 212.0)) : npix;
+                             (envf_in ? (double)total_slots * 3.0 * sizeof(float4) : 0.0) -  // (a path-env frame: the base records and the escape records beside Lbuf)
+                             (emit_in ? (double)total_slots * 2.0 * sizeof(float4) : 0.0);    // (an emit frame: the base records and the emitted sums)
+        // per path in flight: 2 x 3 queue float4 + 2 x 3 shadow float4 + 1 hit float4 + counters; with next-event estimation 2 x 3 NEE shadow float4 more, and an emit
+        // frame's two reaches
+        batch_paths = avail > 0 ? (uint64_t)(avail / (emit_in ? 316.0 : nee_in ? 308.0 : 212.0)) : npix;
     }
     uint64_t spp_batch = std::max<uint64_t>(1, batch_paths / npix);
     spp_batch = std::min<uint64_t>(spp_batch, spp);
@@ -472,13 +477,18 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         nee = *nee_in;
         if (int rc = path_nee_buffers(ctx, nee, NP, Pphys, total_slots, l_slots, 65.0 + (fused ? 0.0 : film_sample_bytes(packed)), spp)) return rc;
     }
+    PathEmitFrame emit{};
+    if (emit_in) {  // the base records, the emitted sums, the note bytes and, per pipe, the emitter shadow queues with their reaches: refused where they do not fit
+        emit = *emit_in;
+        if (int rc = path_emit_buffers(ctx, emit, NP, Pphys, total_slots, l_slots, fused ? 0.0 : film_sample_bytes(packed), spp)) return rc;
+    }
     if (int rc = ensure_film_samples(ctx, packed, total_slots)) return rc;
     const size_t film_bytes = (size_t)ds.film_w * ds.film_h * sizeof(float4);
     void* d_film;
     if (int rc = stage_output(ctx, out, out_is_device, film_bytes, &d_film)) return rc;
     hipStream_t st = ctx->stream;
     const DeviceSensor* dsp = (const DeviceSensor*)ctx->sensor.p;
-    float4* L = envf_in ? envf.base : (float4*)ctx->Lbuf.p;  // a path-env frame: the paths add into the base records, Lbuf receives their fold with the escapes
+    float4* L = emit_in ? emit.base : envf_in ? envf.base : (float4*)ctx->Lbuf.p;  // a path-env frame: the paths add into the base records, Lbuf receives their fold with the escapes
 
     hclk.tick("setup (budget, buffers)");
     Timer tm(ctx, ctx->opt.timing && stats);
@@ -497,6 +507,10 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     HIP_TRY(ctx, hipMemsetAsync(ctx->poison.p, 0, l_slots, st));
     if (envf_in) HIP_TRY(ctx, hipMemsetAsync(envf.rec, 0, l_slots * 2 * sizeof(float4), st));  // depth 0: no escape
     if (nee_in) HIP_TRY(ctx, hipMemsetAsync(nee.note, 0, l_slots, st));  // depth 1 has no vertex before it
+    if (emit_in) {
+        HIP_TRY(ctx, hipMemsetAsync(emit.note, 0, l_slots, st));                   // (depth 1 counts whatever the note says)
+        HIP_TRY(ctx, hipMemsetAsync(emit.lh, 0, l_slots * sizeof(float4), st));  // Lh starts at +0
+    }
     HIP_TRY(ctx, hipEventRecord(ev_start.e, st));
     const int g_shade = ctx->num_cu * 8;
     const uint32_t bary_mode = (ctx->opt.traversal >= 2 && scene->wide_ok) ? 1u : 0u;  // k_trace2 hands the barycentrics to the shading kernel
@@ -526,6 +540,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         float4* hits = (float4*)pp.hits.p;
         HIP_TRY(ctx, hipMemsetAsync(ctr, 0, offsetof(Counters, closest_total), ps));  // queue sizes + work cursors of this batch
         if (nee_in) path_nee_begin_batch(ctx, ps, nee, pipe);
+        if (emit_in) path_emit_begin_batch(ctx, ps, emit, pipe);
         tm.begin(0, ps);
         if (map)
             hipLaunchKernelGGL((k_raygen<0, MapJobs>), dim3(grid_for(ctx, nb, 8)), dim3(kBlock), 0, ps, dsp, MapJobs{map->jobs, (uint32_t)j0}, (uint32_t)nb, seed, sample_offset, pq[0], cap, ctr, fused ? L : nullptr, spp, fside);
@@ -543,7 +558,10 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
             tm.begin(2, ps);
             // every ray of this depth has its final answer: the entries that missed leave their record (one writer per slot; never L, which the shadow rays of depth - 1 may still add to)
             // (with next-event estimation k_path_nee stands in k_path_escape's place: the records with their marks, the notes, and the NEE shadow rays of this depth)
-            if (nee_in)
+            // (an emit frame's k_path_emit stands in the same slot: the emitted terms, the notes, and the emitter shadow rays of this depth)
+            if (emit_in)
+                launch_path_emit(ctx, ps, scene, ctr->n_queue[depth - 1], cap, pq[cur], hits, depth, bary_mode, emit, pipe);
+            else if (nee_in)
                 launch_path_nee(ctx, ps, scene, ctr->n_queue[depth - 1], cap, pq[cur], hits, depth, bary_mode, envf, nee, pipe);
             else if (envf_in)
                 launch_path_escape(ctx, ps, ctr->n_queue[depth - 1], cap, pq[cur], hits, depth, envf.rec);
@@ -567,6 +585,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
             launch_trace(ctx, ps2, scene, true, SegQueue{ctr->n_shadow[depth - 1], cap, 0u}, sq.o, sq.d, nullptr, TraceOut{nullptr, L, sq.c, nullptr}, ctr->work_shadow[depth - 1], ctr, pp.overflow[1].p);
             // the NEE rays of the same depth directly after: the two terms of one depth reach L[slot] in model order, and no launch holds two writers of one slot
             if (nee_in) launch_nee_shadow(ctx, ps2, scene, cap, depth, L, nee, pipe, ctr, pp.overflow[1].p);
+            if (emit_in && !(emit.flags & TRHIP_PATH_EMIT_HITS_ONLY)) launch_emit_shadow(ctx, ps2, scene, cap, depth, L, emit, pipe, ctr, pp.overflow[1].p);  // (the same argument)
             tm.end(3, ps2);
             if (two) HIP_TRY(ctx, hipEventRecord(ev_anys[depth & 1], ps2));
             cur ^= 1;
@@ -589,6 +608,10 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
             launch_escape_fold(ctx, st, envf, l_slots, (float4*)ctx->Lbuf.p);
         L = (float4*)ctx->Lbuf.p;
     }
+    if (emit_in) {  // out = base + Lh; the film pass and trhip_last_sample_radiance read out
+        launch_emit_fold(ctx, st, emit, l_slots, (float4*)ctx->Lbuf.p);
+        L = (float4*)ctx->Lbuf.p;
+    }
     launch_film(ctx, st, ds, dsp, L, total_slots, spp, seed, sample_offset, (float4*)d_film, fused, map);
     tm.end(4, st);
     HIP_TRY(ctx, ev.end(st));
@@ -596,7 +619,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     hclk.tick("enqueue");
     HIP_TRY(ctx, hipStreamSynchronize(st));
     hclk.tick("stream sync");
-    ctx->last = LastRecords{total_slots, fused ? 1u : 0u, (uint32_t)npix, spp, map ? 2u : band ? 0u : 1u, nee_in ? 2u : envf_in ? 1u : 0u};
+    ctx->last = LastRecords{total_slots, fused ? 1u : 0u, (uint32_t)npix, spp, map ? 2u : band ? 0u : 1u, nee_in ? 2u : envf_in ? 1u : 0u, emit_in ? 1u : 0u};
     if (envf_in) {  // what trhip_path_env_relight repeats the film pass with
         PathEnvKeep& k = ctx->env_keep;
         k.ds = ds;
@@ -729,6 +752,13 @@ int render_path_env_nee_frame(trhip_ctx* ctx, const trhip_scene* scene, const tr
     n.mix = mix;
     n.om = 1.0f - mix;  // once, in Float32: the kernel's (1 - mix)
     return render_impl_band(ctx, scene, sensor, 1, spp, max_depth, seed, sample_offset, out, out_is_device, stats, nullptr, nullptr, &f, &n);
+}
+
+int render_path_emit_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out,
+                           bool out_is_device, trhip_stats* stats, const trhip_emitters* em, float scale, uint32_t flags) {
+    PathEmitFrame f{};
+    f.em = em, f.scale = scale, f.flags = flags;
+    return render_impl_band(ctx, scene, sensor, 1, spp, max_depth, seed, sample_offset, out, out_is_device, stats, nullptr, nullptr, nullptr, nullptr, &f);
 }
 
 int render_path_env_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out, bool out_is_device,

@@ -26,9 +26,8 @@ int render_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* se
 
 }  // namespace
 
-int path_nee_check(trhip_ctx* ctx, const trhip_scene* scene, const trhip_env* env) {
-    if (!env->sampler.p) return fail(ctx, TRHIP_ERR_INVALID, "trhip_render_path_env_nee: the environment has no sampler (trhip_env_make_sampler)");
-    // A lobe set with specular AND non-specular lobes: the vertex would be "non-specular", its escapes suppressed, and the specular lobe's share of the map lost.
+int path_mixed_lobes_check(trhip_ctx* ctx, const trhip_scene* scene, const char* entry) {
+    // A lobe set with specular AND non-specular lobes: the vertex would be "non-specular", what follows it suppressed, and the specular lobe's share of the light lost.
     // trhip_scene_add_material builds no such set; checked over the materials, on the host.
     constexpr int NS = BSDF_ALL & ~BSDF_SPECULAR;
     const std::vector<MaterialRec>& mats = scene->g->materials;
@@ -37,9 +36,13 @@ int path_nee_check(trhip_ctx* ctx, const trhip_scene* scene, const trhip_env* en
         int n_ns = 0;
         for (int k = 0; k < b.n; ++k) n_ns += (b.lobe[k].type & NS) == b.lobe[k].type ? 1 : 0;
         if (n_ns != 0 && n_ns != b.n)
-            return fail(ctx, TRHIP_ERR_UNSUPPORTED, "trhip_render_path_env_nee: material %zu mixes specular and non-specular lobes: next-event estimation would be biased", m);
+            return fail(ctx, TRHIP_ERR_UNSUPPORTED, "%s: material %zu mixes specular and non-specular lobes: next-event estimation would be biased", entry, m);
     }
     return 0;
+}
+int path_nee_check(trhip_ctx* ctx, const trhip_scene* scene, const trhip_env* env) {
+    if (!env->sampler.p) return fail(ctx, TRHIP_ERR_INVALID, "trhip_render_path_env_nee: the environment has no sampler (trhip_env_make_sampler)");
+    return path_mixed_lobes_check(ctx, scene, "trhip_render_path_env_nee");
 }
 
 int path_nee_buffers(trhip_ctx* ctx, PathNeeFrame& f, int n_pipes, uint64_t queue_entries, uint64_t total_slots, uint64_t l_slots, double sample_bytes, uint32_t spp) {

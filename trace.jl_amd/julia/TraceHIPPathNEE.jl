@@ -80,3 +80,5 @@ end
 
 # which escapes of this process's last PathNEEIntegrator frame do not count (the 8th float of trhip_last_escapes), for the n_samples the frame drew
 suppressed_escapes(n_samples::Integer) = last_escapes(n_samples)[8, :] .!= 0f0
+
+include("TraceHIPPathEmit.jl")
