@@ -42,17 +42,36 @@ struct LastRecords {
     uint64_t count = 0;  // float4 entries valid in Lbuf
     uint32_t layout = 0, npix = 1, spp = 1;  // how they are laid out (th_kernels.h, film_index)
     uint32_t kind = 0;  // whose they are: 1 a one-band path frame or trhip_film_accumulate's records (trhip_last_sample_stats reads them), 2 a map frame (exported through map_counts), 0 anything else
-    uint32_t path_env = 0;  // 1: a path-env frame's (tu_path_env.hip): Lbuf holds the folded records, env_base and env_rec what they were folded from (ctx->env_keep says how)
-                            // 2: a path-env frame with next-event estimation (tu_path_nee.hip): the same records for trhip_last_escapes, but no relight — the base holds the map's light
-    uint32_t emit = 0;  // 1: an emit frame's (tu_path_emit.hip): Lbuf holds L + Lh, emit_lh the emitted sums (trhip_last_emitted)
+    enum Term : uint32_t { kNoTerm, kEnv, kEnvNee, kEmit } term = kNoTerm;  // which term's records are retained beside Lbuf's (docs/design/30-path-terms.md); the term writes it.
+    // kEnv (tu_path_env.hip): Lbuf holds the folded records, env_base and env_rec what they were folded from (ctx->env_keep says how).  kEnvNee (tu_path_nee.hip): the same
+    // records for trhip_last_escapes, but no relight — the base holds the map's light.  kEmit (tu_path_emit.hip): Lbuf holds L + Lh, emit_lh the emitted sums (trhip_last_emitted)
+    bool env_records() const { return term == kEnv || term == kEnvNee; }
+    void drop_env_records() {  // another render or an image pass between a path-env frame and its relight: the relight and trhip_last_escapes are refused after it
+        if (env_records()) term = kNoTerm;
+    }
 };
-// What trhip_path_env_relight needs of the path-env frame before it to run the film pass "exactly as the frame ran it" (valid while ctx->last.path_env).
+// What trhip_path_env_relight needs of the path-env frame before it to run the film pass "exactly as the frame ran it" (valid while ctx->last.env_records()).
 struct PathEnvKeep {
     DeviceSensor ds{};
     float filter_table[256] = {};
     uint32_t spp = 0, sample_offset = 0;
     uint64_t seed = 0, total_slots = 0, l_slots = 0;
     bool fused = false;
+};
+struct trhip_ctx;
+struct trhip_scene;
+// The extra shadow-ray lane of a path term (the NEE rays, the emitter rays; docs/design/30-path-terms.md): per pipe and parity of the depth a shadow queue (3 float4 arrays)
+// with, for a term that asks for it, the reach of every entry (4 B); per pipe the NeeCounters (th_path_nee.h), zeroed per batch; one note byte per slot, whose meaning is the
+// term's.  In tu_path_nee.hip.
+struct ShadowLane {
+    DevBuf sq[kMaxPipes][2][3], reach[kMaxPipes][2], ctr[kMaxPipes], note;
+    size_t held(bool with_reach) const;  // what a frame reuses of it, for fits_in_hbm: the notes, the queues and, with_reach, the reaches
+    int grow(trhip_ctx* ctx, int n_pipes, uint64_t queue_entries, uint64_t l_slots, bool with_reach);
+    ShadowQueue queue(int pipe, int depth) const { return ShadowQueue{(float4*)sq[pipe][depth & 1][0].p, (float4*)sq[pipe][depth & 1][1].p, (float4*)sq[pipe][depth & 1][2].p}; }
+    uint32_t* emitted(int pipe, int depth) const;  // NeeCounters::n of that depth: where the term's kernel counts the rays it appends
+    int begin_batch(trhip_ctx* ctx, hipStream_t st, int pipe);
+    // the any-hit launch over the lane's rays of `depth` (with_reach: each up to its reach): open rays add their contribution to L
+    void launch_any(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, uint32_t cap, int depth, float4* L, int pipe, bool with_reach, Counters* ctr, void* overflow_slab);
 };
 
 struct Timer;
@@ -99,14 +118,12 @@ struct trhip_ctx {
     // adaptive sampling (th_adaptive.h): the last map frame's counts (kept for trhip_last_sample_radiance), their exclusive sum, the job list, hipcub's workspace, the
     // word k_map_reduce / k_sample_map sum into; the host entry points' copies of (m, v) and of the counts they return
     DevBuf map_counts, map_offsets, map_jobs, map_tmp, map_word, map_mv, map_out;
-    DevBuf env_base, env_rec;  // a path-env frame (th_path_env.h): the path's own radiance records (16 B per slot) and the escape records (32 B per slot); Lbuf holds their fold
+    // the path terms (docs/design/30-path-terms.md).  env_base: the path's own radiance records of a frame with a term (16 B per slot); Lbuf holds the term's fold.  env_rec: the
+    // escape records of a path-env frame, with or without next-event estimation (32 B per slot).  emit_lh: an emit frame's per-sample emitted sums Lh (16 B per slot).
+    // lane: the NEE rays' or the emitter rays' queues, counters and note bytes ("the vertex before was non-specular"; in an emit frame "… was specular")
+    DevBuf env_base, env_rec, emit_lh;
     PathEnvKeep env_keep;
-    // a path-env frame with next-event estimation (th_path_nee.h): per pipe the NEE shadow queues of odd / even depths (3 float4 arrays each) and their NeeCounters; one
-    // byte per slot: "the vertex before was non-specular"
-    DevBuf nee_sq[kMaxPipes][2][3], nee_ctr[kMaxPipes], nee_note;
-    // an emit frame (th_path_emit.h) runs on the same queues, counters and note bytes (there: "the vertex before was specular") and on env_base for the path's own records;
-    // beside them the reach of every emitter ray, per pipe and parity (4 B per queue entry), and the per-sample emitted sums Lh (16 B per slot)
-    DevBuf emit_tmax[kMaxPipes][2], emit_lh;
+    ShadowLane lane;
     DevBuf cb_rc;     // one word: a host callback's return code, max-reduced over the ranks of a job (tu_sppm.hip)
     DevBuf ov8[2], fb_list[2], fb_counts[2];  // k_trace8: global stack levels, fallback lists + their counters / work cursors ([closest | any])
     Comm comm;  // multi-GPU job this context belongs to (trhip_comm_init); n_ranks == 1 without one; trhip_shutdown destroys its communicator before the context goes
@@ -472,69 +489,78 @@ void stats_accumulate(trhip_stats& sum, const trhip_stats& band);  // a banded f
 // tu_adaptive.hip: a map frame's job list from ctx->map_counts (npix counts, already on the device).  sum_on_device: Σ counts and "some count lies above max_spp" come from
 // the device (8 bytes read back) into *total and *above; otherwise the caller has both.  Nothing is built when *above or *total == 0.
 int map_job_list(trhip_ctx* ctx, uint32_t npix, uint32_t max_spp, bool sum_on_device, uint64_t* total, bool* above);
-// tu_path_env.hip: the two kernels of a path-env frame (th_path_env.h), launched from the classic wavefront's loop (tu_path.hip, render_impl_band), and the frame's entry points.
-// PathEnvFrame is what the loop is handed, the way it is handed a MapFrame: where the path's own records and the escape records go, and what they are folded with.
+// A path term: what a frame adds to trhip_render_path's frame (docs/design/30-path-terms.md: the hooks, their order within a depth, how to add a term).  The classic
+// wavefront's loop (tu_path.hip, render_impl_band) is handed one, the way it is handed a MapFrame, and asks it at these places, in this order.
+struct PathTermShape {  // what the loop has planned by the time it asks for the buffers
+    int n_pipes;
+    uint64_t queue_entries, total_slots, l_slots;
+    double film_bytes;  // what an unfused film pass reads per sample: buffers of its own beside the term's
+    uint32_t spp;
+};
+struct PathTerm {
+    float4* base = nullptr;  // l_slots records, set by buffers(): the shading kernels' and the shadow rays' target in Lbuf's place; Lbuf receives the fold
+    virtual ~PathTerm() = default;
+    virtual int check(trhip_ctx* ctx, const trhip_scene* scene) = 0;  // the term's refusals, after the path frame's own
+    virtual int early_budget(trhip_ctx*, uint64_t /*total_slots*/, double /*film_bytes*/, uint32_t /*spp*/) { return 0; }  // a refusal before batch planning, before any pipe is grown
+    virtual double slot_bytes() const = 0;             // batch planning: bytes per sample slot beside Lbuf …
+    virtual double path_bytes() const { return 0.0; }  // … and per path in flight beside the loop's own 212
+    virtual int buffers(trhip_ctx* ctx, const PathTermShape& s) = 0;  // the late budget refusal, then the buffers
+    virtual int clear(trhip_ctx* ctx, hipStream_t st, uint64_t l_slots) = 0;  // at the frame's start, after the loop's own clears
+    virtual int begin_batch(trhip_ctx*, hipStream_t, int /*pipe*/) { return 0; }  // on the pipe's main stream, before raygen
+    // after the closest-hit trace of `depth`, before its shade launch: every ray of the depth has its final answer
+    virtual void after_closest(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, const uint32_t* counts, uint32_t cap, const PathQueue& q, const float4* hits, int depth,
+                               uint32_t hits_have_bary, int pipe) = 0;
+    // directly after the point-light any-hit trace of `depth`, on its stream, with its Counters and its overflow slab
+    virtual void after_any(trhip_ctx*, hipStream_t, const trhip_scene*, uint32_t /*cap*/, int /*depth*/, int /*pipe*/, Counters*, void* /*overflow_slab*/) {}
+    virtual void fold(trhip_ctx* ctx, hipStream_t st, uint64_t l_slots, float4* out) = 0;  // out = base and what the term adds; the film pass and trhip_last_sample_radiance read out
+    virtual void retain(trhip_ctx* ctx, const PathEnvKeep& film_pass) = 0;  // after the frame's stream has been synchronised: ctx->last.term, and what a later call needs
+};
+// tu_path.hip: trhip_render_path's frame — its refusals in its order, the classic wavefront without bands — as a map frame and / or with a term
+int render_path_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out, bool out_is_device,
+                      trhip_stats* stats, const MapFrame* map, PathTerm* term);
+// the parameter block of a term's entry point (scale, flags, reserved): checked before any handle is looked at, and none of it needs a device
+template <class Params>
+int path_params_check(trhip_ctx* ctx, const Params* prm, uint32_t known_flags, const char* entry) {
+    if (!prm) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
+    if (!(prm->scale >= 0.0f) || std::isinf(prm->scale)) return fail(ctx, TRHIP_ERR_INVALID, "%s: scale must be finite and >= 0", entry);
+    if (prm->flags & ~known_flags) return fail(ctx, TRHIP_ERR_INVALID, "%s: unknown flag bits 0x%x", entry, prm->flags & ~known_flags);
+    for (uint32_t r : prm->reserved)
+        if (r != 0) return fail(ctx, TRHIP_ERR_INVALID, "%s: reserved must be 0", entry);
+    return 0;
+}
+// the tail of trhip_last_sample_radiance, trhip_last_escapes and trhip_last_emitted: `launch(dst)` exports ctx->last's records to scratch, which is brought to the caller
+template <class Launch>
+int read_back_records(trhip_ctx* ctx, float* out, uint64_t n_floats, Launch&& launch) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure(ctx, ctx->scratch[0], n_floats * sizeof(float))) return rc;
+    if (ctx->last.count) launch(ctx->scratch[0].p, dim3((unsigned)((ctx->last.count + 255) / 256)));
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(out, ctx->scratch[0].p, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+// tu_path_env.hip: the environment term (th_path_env.h; docs/design/26-path-env.md).  The term with next-event estimation (tu_path_nee.hip) is this one plus the lane: it
+// keeps the checks, the clears, the records and the keep, and replaces the per-depth kernel and the fold.
 struct trhip_env;
-struct PathEnvFrame {
+struct EnvTerm : PathTerm {
     const trhip_env* env;
     float scale;
     uint32_t flags;
-    float4* base;  // l_slots records: the shading kernels' and the shadow rays' target in Lbuf's place
-    float4* rec;   // 2 * l_slots: {beta.xyz, depth}, {dir.xyz, 0}
+    float4* rec = nullptr;  // 2 * l_slots: {beta.xyz, depth}, {dir.xyz, 0}
+    EnvTerm(const trhip_env* e, float s, uint32_t f) : env(e), scale(s), flags(f) {}
+    int check(trhip_ctx* ctx, const trhip_scene* scene) override;  // null, another context's, a scale that takes the largest texel to +Inf
+    int early_budget(trhip_ctx* ctx, uint64_t total_slots, double film_bytes, uint32_t spp) override;
+    double slot_bytes() const override { return 3.0 * sizeof(float4); }  // the base records and the escape records beside Lbuf
+    int buffers(trhip_ctx* ctx, const PathTermShape& s) override;
+    int clear(trhip_ctx* ctx, hipStream_t st, uint64_t l_slots) override;
+    void after_closest(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, const uint32_t* counts, uint32_t cap, const PathQueue& q, const float4* hits, int depth, uint32_t hits_have_bary,
+                       int pipe) override;
+    void fold(trhip_ctx* ctx, hipStream_t st, uint64_t l_slots, float4* out) override;
+    void retain(trhip_ctx* ctx, const PathEnvKeep& film_pass) override;
+    virtual LastRecords::Term kind() const { return LastRecords::kEnv; }
 };
-int path_env_check(trhip_ctx* ctx, const trhip_env* env, float scale);  // null, another context's, a scale that takes the largest texel to +Inf
-void launch_path_escape(trhip_ctx* ctx, hipStream_t st, const uint32_t* counts, uint32_t cap, const PathQueue& q, const float4* hits, int depth, float4* rec);
-void launch_escape_fold(trhip_ctx* ctx, hipStream_t st, const PathEnvFrame& f, uint64_t l_slots, float4* out);
-// tu_path.hip: trhip_render_path's frame — its refusals in its order, the classic wavefront without bands — with the environment frame
-int render_path_env_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out, bool out_is_device,
-                          trhip_stats* stats, const trhip_env* env, float scale, uint32_t flags);
-// tu_path_nee.hip: next-event estimation of the environment map in a path-env frame (th_path_nee.h; docs/design/28-path-nee.md).  PathNeeFrame is handed to the loop beside
-// the PathEnvFrame: the mixture, and — filled by path_nee_buffers once the loop knows its pipes and queue size — where the notes, the NEE shadow queues and their counters are.
-struct PathNeeFrame {
-    float mix, om;               // om = 1 - mix, computed once in Float32
-    uint8_t* note;               // l_slots bytes: the vertex before was non-specular
-    ShadowQueue sq[kMaxPipes][2];  // by pipe and by parity of the depth, as the loop's own shadow queues
-    void* ctr[kMaxPipes];        // NeeCounters, zeroed per batch
-};
-int path_nee_check(trhip_ctx* ctx, const trhip_scene* scene, const trhip_env* env);  // an env without a sampler; a material that mixes specular and non-specular lobes
-int path_mixed_lobes_check(trhip_ctx* ctx, const trhip_scene* scene, const char* entry);  // … the second of the two on its own (an emit frame refuses the same materials)
-// the budget (the path-env frame's per-sample bytes `sample_bytes`, the note byte and the queues must fit in half of free HBM) and the buffers
-int path_nee_buffers(trhip_ctx* ctx, PathNeeFrame& f, int n_pipes, uint64_t queue_entries, uint64_t total_slots, uint64_t l_slots, double sample_bytes, uint32_t spp);
-void path_nee_begin_batch(trhip_ctx* ctx, hipStream_t st, const PathNeeFrame& f, int pipe);
-void launch_path_nee(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, const uint32_t* counts, uint32_t cap, const PathQueue& q, const float4* hits, int depth, uint32_t hits_have_bary,
-                     const PathEnvFrame& ef, const PathNeeFrame& f, int pipe);
-// the any-hit launch over the NEE shadow rays of `depth`: open rays add their contribution to L
-void launch_nee_shadow(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, uint32_t cap, int depth, float4* L, const PathNeeFrame& f, int pipe, Counters* ctr, void* overflow_slab);
-void launch_escape_fold_nee(trhip_ctx* ctx, hipStream_t st, const PathEnvFrame& f, uint64_t l_slots, float4* out);
-int render_path_env_nee_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out,
-                              bool out_is_device, trhip_stats* stats, const trhip_env* env, float scale, uint32_t flags, float mix);
-// tu_path_emit.hip: area lights in path frames (th_path_emit.h; docs/design/29-path-emit.md).  PathEmitFrame is handed to the loop the way a PathNeeFrame is: the emitter set
-// and the parameters, and — filled by path_emit_buffers once the loop knows its pipes and queue size — where the base records, the emitted sums, the notes, the emitter
-// shadow queues with their reaches and the counters are.
-struct trhip_emitters;
-struct PathEmitFrame {
-    const trhip_emitters* em;
-    float scale;
-    uint32_t flags;
-    float4* base;                // l_slots records: the shading kernels' and the shadow rays' target in Lbuf's place
-    float4* lh;                  // l_slots: {Lh.rgb, counted hits}
-    uint8_t* note;               // l_slots bytes: the vertex before was specular
-    ShadowQueue sq[kMaxPipes][2];  // by pipe and by parity of the depth
-    float* tmax[kMaxPipes][2];   // the reach of every queue entry
-    void* ctr[kMaxPipes];        // NeeCounters, zeroed per batch
-};
-int path_emit_check(trhip_ctx* ctx, const trhip_scene* scene, const trhip_emitters* em);  // null / another context's; another geometry's; a material that mixes lobes
-// the budget (per-sample buffers and queues must fit in half of free HBM; `film_bytes`: what an unfused film pass reads per sample) and the buffers
-int path_emit_buffers(trhip_ctx* ctx, PathEmitFrame& f, int n_pipes, uint64_t queue_entries, uint64_t total_slots, uint64_t l_slots, double film_bytes, uint32_t spp);
-void path_emit_begin_batch(trhip_ctx* ctx, hipStream_t st, const PathEmitFrame& f, int pipe);
-void launch_path_emit(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, const uint32_t* counts, uint32_t cap, const PathQueue& q, const float4* hits, int depth, uint32_t hits_have_bary,
-                      const PathEmitFrame& f, int pipe);
-// the any-hit launch over the emitter rays of `depth`, each with its reach: open rays add their contribution to L
-void launch_emit_shadow(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, uint32_t cap, int depth, float4* L, const PathEmitFrame& f, int pipe, Counters* ctr, void* overflow_slab);
-void launch_emit_fold(trhip_ctx* ctx, hipStream_t st, const PathEmitFrame& f, uint64_t l_slots, float4* out);
-// tu_path.hip: trhip_render_path's frame — its refusals in its order, the classic wavefront without bands — with the emit frame
-int render_path_emit_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out,
-                           bool out_is_device, trhip_stats* stats, const trhip_emitters* em, float scale, uint32_t flags);
+// tu_path_nee.hip: a material that mixes specular and non-specular lobes (the NEE term and the emit term refuse it)
+int path_mixed_lobes_check(trhip_ctx* ctx, const trhip_scene* scene, const char* entry);
 // tu_whitted.hip
 int render_whitted_impl(trhip_ctx* ctx, const trhip_scene* scene, const DeviceSensor& ds, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset,
                         void* d_film, trhip_stats* stats);

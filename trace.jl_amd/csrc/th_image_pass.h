@@ -170,7 +170,7 @@ struct PassWindow {
     FrameEvents ev;
     hipStream_t st;
     PassWindow(trhip_ctx* ctx, const trhip_stats* stats) : tm(ctx, ctx->opt.timing && stats), st(ctx->stream) {
-        ctx->last.path_env = 0;  // an image pass between a path-env frame and its relight: the relight is refused (include/tracehip.h, trhip_path_env_relight)
+        ctx->last.drop_env_records();  // an image pass between a path-env frame and its relight: the relight is refused (include/tracehip.h, trhip_path_env_relight)
     }
     hipError_t open() { return ev.begin(st); }
     void begin(int cls) { tm.begin(cls, st); }

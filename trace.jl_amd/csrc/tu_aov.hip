@@ -21,7 +21,7 @@ int render_aov_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor
         return fail(ctx, TRHIP_ERR_INVALID, with_ids ? "trhip_render_aov_ids: all three output pointers are null" : "trhip_render_aov: both output pointers are null");
     CameraPass cp;
     if (int rc = camera_pass_size(ctx, scene, sensor, spp, cp)) return rc;
-    ctx->last.path_env = 0;  // another render between a path-env frame and its relight: the relight is refused (include/tracehip.h, trhip_path_env_relight)
+    ctx->last.drop_env_records();  // another render between a path-env frame and its relight: the relight is refused (include/tracehip.h, trhip_path_env_relight)
     const DeviceSensor& ds = cp.ds;
     const uint64_t total_slots = cp.total_slots;
     const size_t rec_bytes = (size_t)total_slots * sizeof(trhip_aov_sample);

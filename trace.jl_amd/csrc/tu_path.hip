@@ -156,6 +156,39 @@ void stats_accumulate(trhip_stats& sum, const trhip_stats& band) {
 }
 
 namespace {
+// The queues, hit records, counters and overflow slabs of one pipe for `entries` physical queue entries (second_sq: the other parity's shadow queue of the two-stream mode).
+int ensure_pipe_buffers(trhip_ctx* ctx, Pipe& pp, uint64_t entries, bool second_sq) {
+    for (auto& a : pp.q)
+        for (auto& b : a)
+            if (int rc = ensure(ctx, b, entries * sizeof(float4))) return rc;
+    for (auto& b : pp.sq)
+        if (int rc = ensure(ctx, b, entries * sizeof(float4))) return rc;
+    if (second_sq)
+        for (auto& b : pp.sq2)
+            if (int rc = ensure(ctx, b, entries * sizeof(float4))) return rc;
+    if (int rc = ensure(ctx, pp.hits, entries * sizeof(float4))) return rc;
+    if (int rc = ensure(ctx, pp.counters, sizeof(Counters))) return rc;
+    const size_t slab_bytes = (size_t)trace_grid(ctx) * kBlock * (size_t)kStackSlabLevels * sizeof(uint2);
+    for (auto& b : pp.overflow)
+        if (int rc = ensure(ctx, b, slab_bytes)) return rc;
+    return 0;
+}
+// The shade launch of both wavefronts: the scene picks the kernel's form (vertex tangents, a DirectionalLight).
+template <bool STREAM>
+void launch_shade_path(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, const DeviceSensor* dsp, const PathQueue& in, const PathQueue& out, const ShadowQueue& sq, uint32_t cap,
+                       const float4* hits, float4* L, Counters* ctr, int slot, int depth, int max_depth, uint32_t bary_mode, const ShadeStream& sst) {
+    const dim3 grid(ctx->num_cu * 8), block(kBlock);
+    if (has_directional_light(scene)) {
+        if (scene->dev.tri_tan)
+            hipLaunchKernelGGL((k_shade_path<STREAM, true, true>), grid, block, 0, st, shade_scene(scene), dsp, in, out, sq, cap, hits, L, ctr, slot, depth, max_depth, bary_mode, sst);
+        else
+            hipLaunchKernelGGL((k_shade_path<STREAM, false, true>), grid, block, 0, st, shade_scene(scene), dsp, in, out, sq, cap, hits, L, ctr, slot, depth, max_depth, bary_mode, sst);
+    } else if (scene->dev.tri_tan) {
+        hipLaunchKernelGGL(k_shade_path<STREAM>, grid, block, 0, st, shade_scene(scene), dsp, in, out, sq, cap, hits, L, ctr, slot, depth, max_depth, bary_mode, sst);
+    } else {
+        hipLaunchKernelGGL((k_shade_path<STREAM, false>), grid, block, 0, st, shade_scene(scene), dsp, in, out, sq, cap, hits, L, ctr, slot, depth, max_depth, bary_mode, sst);
+    }
+}
 // PathIntegrator as a STREAMING wavefront (th_trace2.h "streaming wavefront"): rounds instead of depths.  A round
 // traces every queued ray with a fetch budget, resumes the rays suspended in the round before, shades what finished (entries
 // carry their own depth), and traces the shadow rays the same way.  max_depth + 16 budgeted rounds, then max_depth rounds
@@ -196,16 +229,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
     if (int rc = ensure_pipe(ctx, 0, false)) return rc;
     if (int rc = upload(ctx, ctx->sensor, &ds, sizeof ds)) return rc;
     if (int rc = upload(ctx, ctx->table, sensor->filter_table, 256 * sizeof(float))) return rc;
-    for (int k = 0; k < 2; ++k)
-        for (int j = 0; j < 3; ++j)
-            if (int rc = ensure(ctx, pp.q[k][j], Pphys * sizeof(float4))) return rc;
-    for (int j = 0; j < 3; ++j)
-        if (int rc = ensure(ctx, pp.sq[j], Pphys * sizeof(float4))) return rc;
-    if (int rc = ensure(ctx, pp.hits, Pphys * sizeof(float4))) return rc;
-    if (int rc = ensure(ctx, pp.counters, sizeof(Counters))) return rc;
-    const size_t slab_bytes = (size_t)trace_grid(ctx) * kBlock * (size_t)kStackSlabLevels * sizeof(uint2);
-    for (int k = 0; k < 2; ++k)
-        if (int rc = ensure(ctx, pp.overflow[k], slab_bytes)) return rc;
+    if (int rc = ensure_pipe_buffers(ctx, pp, Pphys, false)) return rc;
     ctx->last = LastRecords{};
     if (int rc = ensure(ctx, ctx->Lbuf, total_slots * sizeof(float4))) return rc;
     if (int rc = ensure_film_samples(ctx, film_packed(ds), total_slots)) return rc;
@@ -254,7 +278,6 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
     hipLaunchKernelGGL(k_raygen, dim3(grid_for(ctx, P, 8)), dim3(kBlock), 0, ps, dsp, 0u, (uint32_t)P, seed, sample_offset, pq[0], cap, ctr);
     hipLaunchKernelGGL(k_fill_u32, dim3(grid_for(ctx, Pphys, 8)), dim3(kBlock), 0, ps, tags[0], Pphys, 1u);
     tm.end(0, ps);
-    const int g_shade = ctx->num_cu * 8;
     int cur = 0;
     for (int r = 0; r < R; ++r) {
         const uint32_t budget_min = r < R_b ? ctx->opt.stream_budget_min : 0u;  // the last max_depth rounds run every ray to its end
@@ -273,16 +296,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
         if (ps2 != ps && r > 0) HIP_TRY(ctx, hipStreamWaitEvent(ps, pp.ev_any, 0));  // shade(r) reuses the shadow queue
         tm.begin(2, ps);
         const ShadeStream sst{tags[cur], tags[cur ^ 1], (uint32_t)total_slots};
-        if (has_directional_light(scene)) {
-            if (scene->dev.tri_tan)
-                hipLaunchKernelGGL((k_shade_path<true, true, true>), dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, terms, ctr, r, 0, max_depth, 1u, sst);
-            else
-                hipLaunchKernelGGL((k_shade_path<true, false, true>), dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, terms, ctr, r, 0, max_depth, 1u, sst);
-        } else if (scene->dev.tri_tan) {
-            hipLaunchKernelGGL(k_shade_path<true>, dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, terms, ctr, r, 0, max_depth, 1u, sst);
-        } else {
-            hipLaunchKernelGGL((k_shade_path<true, false>), dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, terms, ctr, r, 0, max_depth, 1u, sst);
-        }
+        launch_shade_path<true>(ctx, ps, scene, dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, terms, ctr, r, 0, max_depth, 1u, sst);
         tm.end(2, ps);
         if (ps2 != ps) {
             HIP_TRY(ctx, hipEventRecord(pp.ev_shade, ps));
@@ -335,8 +349,7 @@ int render_stream_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sen
 // One band of a frame (band == nullptr: the whole frame, the normal case).  A band is a range of whole tile rows; its DeviceSensor carries
 // the range and whether the film gather starts from zero or adds onto the bands before (th_scene.h).
 int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, int integrator, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out,
-                     bool out_is_device, trhip_stats* stats, const DeviceSensor* band, const MapFrame* map = nullptr, const PathEnvFrame* envf_in = nullptr, const PathNeeFrame* nee_in = nullptr,
-                     const PathEmitFrame* emit_in = nullptr) {
+                     bool out_is_device, trhip_stats* stats, const DeviceSensor* band, const MapFrame* map = nullptr, PathTerm* term = nullptr) {
     HostClock hclk;
     if (!ctx || !scene || !sensor || !out) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
     if (!scene->committed) return fail(ctx, TRHIP_ERR_INVALID, "scene not committed");
@@ -363,12 +376,8 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     const uint64_t npix = (uint64_t)ds.sb_w * ds.band_rows;
     const uint64_t total_slots = npix * spp;
     if (total_slots >= (1ull << 32)) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "more than 2^32 camera samples in one band of a frame");
-    if (envf_in)  // a path-env frame: the environment's refusals come after the path frame's
-        if (int rc = path_env_check(ctx, envf_in->env, envf_in->scale)) return rc;
-    if (nee_in)  // … with next-event estimation (docs/design/28-path-nee.md): the sampler and the materials after those
-        if (int rc = path_nee_check(ctx, scene, envf_in->env)) return rc;
-    if (emit_in)  // an emit frame (docs/design/29-path-emit.md): the emitter set's refusals and the materials come after the path frame's
-        if (int rc = path_emit_check(ctx, scene, emit_in->em)) return rc;
+    if (term)  // a term's refusals come after the path frame's
+        if (int rc = term->check(ctx, scene)) return rc;
     if (integrator == 0) {
         if (int rc = upload(ctx, ctx->sensor, &ds, sizeof ds)) return rc;
         if (int rc = upload(ctx, ctx->table, sensor->filter_table, 256 * sizeof(float))) return rc;
@@ -383,7 +392,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         ctx->last = LastRecords{total_slots, 0u, (uint32_t)npix, spp, 0u};  // (render_whitted_impl has synchronised its stream)
         return copy_back(ctx, out, out_is_device, df, fb);
     }
-    if (!band && !map && !envf_in && !emit_in && (ctx->opt.streaming == 1 || (ctx->opt.streaming < 0 && total_slots <= 96ull * scene->g->prims.size())) && ctx->opt.traversal >= 2 && scene->wide_ok && scene->wide.root_cnt == 0 && scene->wide.root_ref != kRefNone && ctx->opt.batch_paths == 0 && ctx->opt.pipelines <= 1) {
+    if (!band && !map && !term && (ctx->opt.streaming == 1 || (ctx->opt.streaming < 0 && total_slots <= 96ull * scene->g->prims.size())) && ctx->opt.traversal >= 2 && scene->wide_ok && scene->wide.root_cnt == 0 && scene->wide.root_ref != kRefNone && ctx->opt.batch_paths == 0 && ctx->opt.pipelines <= 1) {
         bool declined = false;
         const int rc = render_stream_impl(ctx, scene, sensor, ds, spp, max_depth, seed, sample_offset, out, out_is_device, stats, &declined);
         if (!declined) return rc;
@@ -400,29 +409,19 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         if (int rc = fits_in_hbm(ctx, 2.0 * need, ctx->Lbuf.bytes + ctx->pfilm.bytes + held_in_pipes(ctx), &fits, &free_gb)) return rc;  // half of what is free, as render_impl plans its bands
         if (!fits) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "the per-sample buffers of a map frame (%.2f GB at max_spp %u) do not fit in half of free HBM (%.2f GB): there are no bands here", need * 1e-9, spp, free_gb);
     }
-    // A path-env frame (docs/design/26-path-env.md) has no bands either: the path's records, their fold, the escape records (16 + 16 + 32 B per slot), the poison byte and
-    // what an unfused film pass reads per sample (counted as buffers of its own) must fit the same way.
-    if (envf_in) {
-        bool fits = false;
-        double free_gb = 0.0;
-        const double film_own = fused ? 0.0 : film_sample_bytes(packed);
-        const double need = (double)total_slots * (65.0 + film_own);
-        const size_t held = ctx->Lbuf.bytes + ctx->pfilm.bytes + ctx->env_base.bytes + ctx->env_rec.bytes + held_in_pipes(ctx);
-        if (int rc = fits_in_hbm(ctx, 2.0 * need, held, &fits, &free_gb)) return rc;
-        if (!fits) return fail(ctx, TRHIP_ERR_UNSUPPORTED, "the per-sample buffers of a path-env frame (%.2f GB at %u spp) do not fit in half of free HBM (%.2f GB): there are no bands here", need * 1e-9, spp, free_gb);
-    }
+    // A frame with a term has no bands either: what the term's per-sample buffers need is the term's to refuse (film_own: an unfused film pass's buffer of its own)
+    const double film_own = fused ? 0.0 : film_sample_bytes(packed);
+    if (term)
+        if (int rc = term->early_budget(ctx, total_slots, film_own, spp)) return rc;
     // wavefront batch = whole sample passes (a map frame: ranges of its job list); per path in flight: 2 x 3 queue float4 + 3 shadow float4 + 1 hit float4 = 160 B
     uint64_t batch_paths = ctx->opt.batch_paths;
     if (batch_paths == 0) {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
         const size_t held = ctx->Lbuf.bytes + ctx->pfilm.bytes + held_in_pipes(ctx);  // reused below, so it counts as available
-        const double avail = 0.85 * (double)(free_b + held) - (double)total_slots * (sizeof(float4) + sizeof(float2)) - 2.5e9 -
-                             (envf_in ? (double)total_slots * 3.0 * sizeof(float4) : 0.0) -  // (a path-env frame: the base records and the escape records beside Lbuf)
-                             (emit_in ? (double)total_slots * 2.0 * sizeof(float4) : 0.0);    // (an emit frame: the base records and the emitted sums)
-        // per path in flight: 2 x 3 queue float4 + 2 x 3 shadow float4 + 1 hit float4 + counters; with next-event estimation 2 x 3 NEE shadow float4 more, and an emit
-        // frame's two reaches
-        batch_paths = avail > 0 ? (uint64_t)(avail / (emit_in ? 316.0 : nee_in ? 308.0 : 212.0)) : npix;
+        const double avail = 0.85 * (double)(free_b + held) - (double)total_slots * (sizeof(float4) + sizeof(float2)) - 2.5e9 - (term ? (double)total_slots * term->slot_bytes() : 0.0);
+        // per path in flight: 2 x 3 queue float4 + 2 x 3 shadow float4 + 1 hit float4 + counters, and what the term's lane holds
+        batch_paths = avail > 0 ? (uint64_t)(avail / (212.0 + (term ? term->path_bytes() : 0.0))) : npix;
     }
     uint64_t spp_batch = std::max<uint64_t>(1, batch_paths / npix);
     spp_batch = std::min<uint64_t>(spp_batch, spp);
@@ -443,52 +442,23 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     const uint64_t Pphys = (uint64_t)cap * kSeg;
     if (int rc = upload(ctx, ctx->sensor, &ds, sizeof ds)) return rc;
     if (int rc = upload(ctx, ctx->table, sensor->filter_table, 256 * sizeof(float))) return rc;
-    const size_t slab_bytes = (size_t)trace_grid(ctx) * kBlock * (size_t)kStackSlabLevels * sizeof(uint2);
     for (int pi = 0; pi < NP; ++pi) {
-        Pipe& pp = ctx->pipes[pi];
         if (int rc = ensure_pipe(ctx, pi, true)) return rc;
-        for (int k = 0; k < 2; ++k)
-            for (int j = 0; j < 3; ++j)
-                if (int rc = ensure(ctx, pp.q[k][j], Pphys * sizeof(float4))) return rc;
-        for (int j = 0; j < 3; ++j)
-            if (int rc = ensure(ctx, pp.sq[j], Pphys * sizeof(float4))) return rc;
-        if (ctx->opt.overlap)
-            for (int j = 0; j < 3; ++j)
-                if (int rc = ensure(ctx, pp.sq2[j], Pphys * sizeof(float4))) return rc;
-        if (int rc = ensure(ctx, pp.hits, Pphys * sizeof(float4))) return rc;
-        if (int rc = ensure(ctx, pp.counters, sizeof(Counters))) return rc;
-        for (int k = 0; k < 2; ++k)
-            if (int rc = ensure(ctx, pp.overflow[k], slab_bytes)) return rc;
+        if (int rc = ensure_pipe_buffers(ctx, ctx->pipes[pi], Pphys, ctx->opt.overlap)) return rc;
     }
     const uint64_t l_slots = fused ? film_padded_slots(ds, spp) : total_slots;
     ctx->last = LastRecords{};
     if (int rc = ensure(ctx, ctx->poison, l_slots)) return rc;
     if (int rc = ensure(ctx, ctx->Lbuf, l_slots * sizeof(float4))) return rc;
-    PathEnvFrame envf{};
-    if (envf_in) {
-        if (int rc = ensure(ctx, ctx->env_base, l_slots * sizeof(float4))) return rc;
-        if (int rc = ensure(ctx, ctx->env_rec, l_slots * 2 * sizeof(float4))) return rc;
-        envf = *envf_in;
-        envf.base = (float4*)ctx->env_base.p;
-        envf.rec = (float4*)ctx->env_rec.p;
-    }
-    PathNeeFrame nee{};
-    if (nee_in) {  // the note bytes and, per pipe, the NEE shadow queues: refused where they do not fit beside the path-env frame's buffers
-        nee = *nee_in;
-        if (int rc = path_nee_buffers(ctx, nee, NP, Pphys, total_slots, l_slots, 65.0 + (fused ? 0.0 : film_sample_bytes(packed)), spp)) return rc;
-    }
-    PathEmitFrame emit{};
-    if (emit_in) {  // the base records, the emitted sums, the note bytes and, per pipe, the emitter shadow queues with their reaches: refused where they do not fit
-        emit = *emit_in;
-        if (int rc = path_emit_buffers(ctx, emit, NP, Pphys, total_slots, l_slots, fused ? 0.0 : film_sample_bytes(packed), spp)) return rc;
-    }
+    if (term)  // its buffers, refused where they do not fit beside the frame's
+        if (int rc = term->buffers(ctx, PathTermShape{NP, Pphys, total_slots, l_slots, film_own, spp})) return rc;
     if (int rc = ensure_film_samples(ctx, packed, total_slots)) return rc;
     const size_t film_bytes = (size_t)ds.film_w * ds.film_h * sizeof(float4);
     void* d_film;
     if (int rc = stage_output(ctx, out, out_is_device, film_bytes, &d_film)) return rc;
     hipStream_t st = ctx->stream;
     const DeviceSensor* dsp = (const DeviceSensor*)ctx->sensor.p;
-    float4* L = emit_in ? emit.base : envf_in ? envf.base : (float4*)ctx->Lbuf.p;  // a path-env frame: the paths add into the base records, Lbuf receives their fold with the escapes
+    float4* L = term ? term->base : (float4*)ctx->Lbuf.p;  // with a term the paths add into its base records, and Lbuf receives the term's fold
 
     hclk.tick("setup (budget, buffers)");
     Timer tm(ctx, ctx->opt.timing && stats);
@@ -505,14 +475,9 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         HIP_TRY(ctx, hipMemsetAsync(L, 0, total_slots * sizeof(float4), st));
     }
     HIP_TRY(ctx, hipMemsetAsync(ctx->poison.p, 0, l_slots, st));
-    if (envf_in) HIP_TRY(ctx, hipMemsetAsync(envf.rec, 0, l_slots * 2 * sizeof(float4), st));  // depth 0: no escape
-    if (nee_in) HIP_TRY(ctx, hipMemsetAsync(nee.note, 0, l_slots, st));  // depth 1 has no vertex before it
-    if (emit_in) {
-        HIP_TRY(ctx, hipMemsetAsync(emit.note, 0, l_slots, st));                   // (depth 1 counts whatever the note says)
-        HIP_TRY(ctx, hipMemsetAsync(emit.lh, 0, l_slots * sizeof(float4), st));  // Lh starts at +0
-    }
+    if (term)
+        if (int rc = term->clear(ctx, st, l_slots)) return rc;
     HIP_TRY(ctx, hipEventRecord(ev_start.e, st));
-    const int g_shade = ctx->num_cu * 8;
     const uint32_t bary_mode = (ctx->opt.traversal >= 2 && scene->wide_ok) ? 1u : 0u;  // k_trace2 hands the barycentrics to the shading kernel
     uint32_t n_batches = 0;
     for (int pi = 0; pi < NP; ++pi) {
@@ -539,8 +504,8 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
         hipEvent_t ev_anys[2] = {pp.ev_any, pp.ev_any2};
         float4* hits = (float4*)pp.hits.p;
         HIP_TRY(ctx, hipMemsetAsync(ctr, 0, offsetof(Counters, closest_total), ps));  // queue sizes + work cursors of this batch
-        if (nee_in) path_nee_begin_batch(ctx, ps, nee, pipe);
-        if (emit_in) path_emit_begin_batch(ctx, ps, emit, pipe);
+        if (term)
+            if (int rc = term->begin_batch(ctx, ps, pipe)) return rc;
         tm.begin(0, ps);
         if (map)
             hipLaunchKernelGGL((k_raygen<0, MapJobs>), dim3(grid_for(ctx, nb, 8)), dim3(kBlock), 0, ps, dsp, MapJobs{map->jobs, (uint32_t)j0}, (uint32_t)nb, seed, sample_offset, pq[0], cap, ctr, fused ? L : nullptr, spp, fside);
@@ -556,26 +521,10 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
             tm.end(1, ps);
             if (two && depth > 2) HIP_TRY(ctx, hipStreamWaitEvent(ps, ev_anys[depth & 1], 0));  // shade(d) refills the queue the shadow rays of depth d - 2 read
             tm.begin(2, ps);
-            // every ray of this depth has its final answer: the entries that missed leave their record (one writer per slot; never L, which the shadow rays of depth - 1 may still add to)
-            // (with next-event estimation k_path_nee stands in k_path_escape's place: the records with their marks, the notes, and the NEE shadow rays of this depth)
-            // (an emit frame's k_path_emit stands in the same slot: the emitted terms, the notes, and the emitter shadow rays of this depth)
-            if (emit_in)
-                launch_path_emit(ctx, ps, scene, ctr->n_queue[depth - 1], cap, pq[cur], hits, depth, bary_mode, emit, pipe);
-            else if (nee_in)
-                launch_path_nee(ctx, ps, scene, ctr->n_queue[depth - 1], cap, pq[cur], hits, depth, bary_mode, envf, nee, pipe);
-            else if (envf_in)
-                launch_path_escape(ctx, ps, ctr->n_queue[depth - 1], cap, pq[cur], hits, depth, envf.rec);
+            // every ray of this depth has its final answer: the term's kernel reads it (one writer per slot; never L, which the shadow rays of depth - 1 may still add to)
+            if (term) term->after_closest(ctx, ps, scene, ctr->n_queue[depth - 1], cap, pq[cur], hits, depth, bary_mode, pipe);
             const ShadeStream sst{nullptr, nullptr, 0u, two ? (uint8_t*)ctx->poison.p : nullptr};
-            if (has_directional_light(scene)) {
-                if (scene->dev.tri_tan)
-                    hipLaunchKernelGGL((k_shade_path<false, true, true>), dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, L, ctr, depth - 1, depth, max_depth, bary_mode, sst);
-                else
-                    hipLaunchKernelGGL((k_shade_path<false, false, true>), dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, L, ctr, depth - 1, depth, max_depth, bary_mode, sst);
-            } else if (scene->dev.tri_tan) {
-                hipLaunchKernelGGL(k_shade_path<false>, dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, L, ctr, depth - 1, depth, max_depth, bary_mode, sst);
-            } else {
-                hipLaunchKernelGGL((k_shade_path<false, false>), dim3(g_shade), dim3(kBlock), 0, ps, shade_scene(scene), dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, L, ctr, depth - 1, depth, max_depth, bary_mode, sst);
-            }
+            launch_shade_path<false>(ctx, ps, scene, dsp, pq[cur], pq[cur ^ 1], sq, cap, hits, L, ctr, depth - 1, depth, max_depth, bary_mode, sst);
             tm.end(2, ps);
             if (two) {
                 HIP_TRY(ctx, hipEventRecord(pp.ev_shade, ps));
@@ -583,9 +532,7 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
             }
             tm.begin(3, ps2);
             launch_trace(ctx, ps2, scene, true, SegQueue{ctr->n_shadow[depth - 1], cap, 0u}, sq.o, sq.d, nullptr, TraceOut{nullptr, L, sq.c, nullptr}, ctr->work_shadow[depth - 1], ctr, pp.overflow[1].p);
-            // the NEE rays of the same depth directly after: the two terms of one depth reach L[slot] in model order, and no launch holds two writers of one slot
-            if (nee_in) launch_nee_shadow(ctx, ps2, scene, cap, depth, L, nee, pipe, ctr, pp.overflow[1].p);
-            if (emit_in && !(emit.flags & TRHIP_PATH_EMIT_HITS_ONLY)) launch_emit_shadow(ctx, ps2, scene, cap, depth, L, emit, pipe, ctr, pp.overflow[1].p);  // (the same argument)
+            if (term) term->after_any(ctx, ps2, scene, cap, depth, pipe, ctr, pp.overflow[1].p);  // the term's rays of the same depth directly after, inside the same time class
             tm.end(3, ps2);
             if (two) HIP_TRY(ctx, hipEventRecord(ev_anys[depth & 1], ps2));
             cur ^= 1;
@@ -601,16 +548,9 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     }
     tm.begin(4, st);
     if (ctx->opt.overlap) hipLaunchKernelGGL(k_apply_poison, dim3(grid_for(ctx, l_slots, 8)), dim3(kBlock), 0, st, L, (const uint8_t*)ctx->poison.p, l_slots);
-    if (envf_in) {  // out = base, + beta * (E(dir) * scale) where a record contributes; the film pass and trhip_last_sample_radiance read out
-        if (nee_in)
-            launch_escape_fold_nee(ctx, st, envf, l_slots, (float4*)ctx->Lbuf.p);
-        else
-            launch_escape_fold(ctx, st, envf, l_slots, (float4*)ctx->Lbuf.p);
+    if (term) {  // (k_apply_poison above ran on the term's base records)
         L = (float4*)ctx->Lbuf.p;
-    }
-    if (emit_in) {  // out = base + Lh; the film pass and trhip_last_sample_radiance read out
-        launch_emit_fold(ctx, st, emit, l_slots, (float4*)ctx->Lbuf.p);
-        L = (float4*)ctx->Lbuf.p;
+        term->fold(ctx, st, l_slots, L);
     }
     launch_film(ctx, st, ds, dsp, L, total_slots, spp, seed, sample_offset, (float4*)d_film, fused, map);
     tm.end(4, st);
@@ -619,12 +559,13 @@ int render_impl_band(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     hclk.tick("enqueue");
     HIP_TRY(ctx, hipStreamSynchronize(st));
     hclk.tick("stream sync");
-    ctx->last = LastRecords{total_slots, fused ? 1u : 0u, (uint32_t)npix, spp, map ? 2u : band ? 0u : 1u, nee_in ? 2u : envf_in ? 1u : 0u, emit_in ? 1u : 0u};
-    if (envf_in) {  // what trhip_path_env_relight repeats the film pass with
-        PathEnvKeep& k = ctx->env_keep;
+    ctx->last = LastRecords{total_slots, fused ? 1u : 0u, (uint32_t)npix, spp, map ? 2u : band ? 0u : 1u};
+    if (term) {  // what the term leaves behind: its mark in ctx->last, and how the film pass ran where a later call repeats it
+        PathEnvKeep k;
         k.ds = ds;
         std::memcpy(k.filter_table, sensor->filter_table, sizeof k.filter_table);
         k.spp = spp, k.sample_offset = sample_offset, k.seed = seed, k.total_slots = total_slots, k.l_slots = l_slots, k.fused = fused;
+        term->retain(ctx, k);
     }
     if (int rc = copy_back(ctx, out, out_is_device, d_film, film_bytes)) return rc;
     if (stats) {
@@ -741,30 +682,13 @@ int render_map_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor
     if (total == 0) return fail(ctx, TRHIP_ERR_INVALID, "the sample map draws no sample");
     const MapFrame map{(const uint32_t*)ctx->map_counts.p, (const uint32_t*)ctx->map_jobs.p, total};
     ctx->last = LastRecords{};  // (until this frame's radiance is complete: map_counts already belongs to it)
-    return render_impl_band(ctx, scene, sensor, 1, max_spp, max_depth, seed, sample_offset, out, on_device, stats, nullptr, &map);
+    return render_path_frame(ctx, scene, sensor, max_spp, max_depth, seed, sample_offset, out, on_device, stats, &map, nullptr);
 }
 }  // namespace
 
-int render_path_env_nee_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out,
-                              bool out_is_device, trhip_stats* stats, const trhip_env* env, float scale, uint32_t flags, float mix) {
-    const PathEnvFrame f{env, scale, flags, nullptr, nullptr};
-    PathNeeFrame n{};
-    n.mix = mix;
-    n.om = 1.0f - mix;  // once, in Float32: the kernel's (1 - mix)
-    return render_impl_band(ctx, scene, sensor, 1, spp, max_depth, seed, sample_offset, out, out_is_device, stats, nullptr, nullptr, &f, &n);
-}
-
-int render_path_emit_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out,
-                           bool out_is_device, trhip_stats* stats, const trhip_emitters* em, float scale, uint32_t flags) {
-    PathEmitFrame f{};
-    f.em = em, f.scale = scale, f.flags = flags;
-    return render_impl_band(ctx, scene, sensor, 1, spp, max_depth, seed, sample_offset, out, out_is_device, stats, nullptr, nullptr, nullptr, nullptr, &f);
-}
-
-int render_path_env_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out, bool out_is_device,
-                          trhip_stats* stats, const trhip_env* env, float scale, uint32_t flags) {
-    const PathEnvFrame f{env, scale, flags, nullptr, nullptr};
-    return render_impl_band(ctx, scene, sensor, 1, spp, max_depth, seed, sample_offset, out, out_is_device, stats, nullptr, nullptr, &f);
+int render_path_frame(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, void* out, bool out_is_device,
+                      trhip_stats* stats, const MapFrame* map, PathTerm* term) {
+    return render_impl_band(ctx, scene, sensor, 1, spp, max_depth, seed, sample_offset, out, out_is_device, stats, nullptr, map, term);
 }
 
 extern "C" {
@@ -812,17 +736,12 @@ int trhip_last_sample_radiance(trhip_ctx* ctx, float* out, uint64_t n_floats) {
     if (!ctx || !out) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
     const LastRecords& last = ctx->last;
     if (n_floats != last.count * 3) return fail(ctx, TRHIP_ERR_INVALID, "expected %llu floats", (unsigned long long)(last.count * 3));
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = ensure(ctx, ctx->scratch[0], n_floats * sizeof(float))) return rc;
-    const uint64_t n = last.count;
-    if (n && last.kind == 2)  // a map frame: the records that were drawn, +0 elsewhere
-        hipLaunchKernelGGL(k_export_L_map, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)ctx->Lbuf.p, n, (float*)ctx->scratch[0].p, last.layout, last.npix,
-                           last.spp, (const uint32_t*)ctx->map_counts.p);
-    else if (n)
-        hipLaunchKernelGGL(k_export_L, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)ctx->Lbuf.p, n, (float*)ctx->scratch[0].p, last.layout, last.npix, last.spp);
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(out, ctx->scratch[0].p, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    return read_back_records(ctx, out, n_floats, [&](void* dst, dim3 grid) {
+        if (last.kind == 2)  // a map frame: the records that were drawn, +0 elsewhere
+            hipLaunchKernelGGL(k_export_L_map, grid, dim3(256), 0, ctx->stream, (const float4*)ctx->Lbuf.p, last.count, (float*)dst, last.layout, last.npix, last.spp, (const uint32_t*)ctx->map_counts.p);
+        else
+            hipLaunchKernelGGL(k_export_L, grid, dim3(256), 0, ctx->stream, (const float4*)ctx->Lbuf.p, last.count, (float*)dst, last.layout, last.npix, last.spp);
+    });
 }
 int trhip_film_to_rgb(trhip_ctx* ctx, const float* xyzw, uint32_t w, uint32_t h, float scale, float* out) {
     if (!ctx || !xyzw || !out) return fail(ctx, TRHIP_ERR_INVALID, "null argument");

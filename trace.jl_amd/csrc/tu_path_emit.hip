@@ -1,9 +1,8 @@
 // tu_path_emit.hip — area lights in path frames (trhip_emitters_*, trhip_render_path_emit, trhip_last_emitted; docs/design/29-path-emit.md).  The frame is tu_path.hip's
-// classic wavefront, handed a PathEmitFrame; this unit holds the kernels it launches for it (th_path_emit.h) — in a unit of their own, so that every other unit instantiates
-// what it instantiated before —, the emitter set with its table, built here on the host in Float64 in the order the specification gives, the parameter checks, the buffers
-// and the launches.
+// classic wavefront, handed the emit term (th_host.h, PathTerm); this unit holds the kernels the term launches (th_path_emit.h) — in a unit of their own, so that every other
+// unit instantiates what it instantiated before —, the emitter set with its table, built here on the host in Float64 in the order the specification gives, and the term.
 #include "th_path_emit.h"
-#include "th_path_nee.h"  // NeeCounters: the emitter shadow queues' counters have their shape
+#include "th_path_nee.h"  // NeeCounters: the lane's counters (th_host.h, ShadowLane)
 
 #include <cmath>
 
@@ -17,84 +16,75 @@ constexpr uint32_t kPathEmitFlags = TRHIP_PATH_EMIT_HITS_ONLY;
 constexpr uint32_t kMaxEmitters = 1u << 20;
 constexpr double kEmitQueueBytes = 2.0 * (3.0 * sizeof(float4) + sizeof(float));  // per queue entry: two parities of three float4 arrays and a reach
 
+struct EmitTerm : PathTerm {
+    const trhip_emitters* em;
+    float scale;
+    uint32_t flags;
+    float4* lh = nullptr;  // l_slots: {Lh.rgb, counted hits}
+    EmitTerm(const trhip_emitters* e, float s, uint32_t f) : em(e), scale(s), flags(f) {}
+    int check(trhip_ctx* ctx, const trhip_scene* scene) override {  // null / another context's; another geometry's; a material that mixes lobes
+        if (!em) return fail(ctx, TRHIP_ERR_INVALID, "trhip_render_path_emit: null emitters");
+        if (em->ctx != ctx) return fail(ctx, TRHIP_ERR_INVALID, "trhip_render_path_emit: the emitters belong to another context");
+        if (em->geometry_id != scene->g->id || em->n_materials != scene->g->materials.size())
+            return fail(ctx, TRHIP_ERR_INVALID, "trhip_render_path_emit: the emitters were made from another committed geometry (%llu) than the scene's (%llu)", (unsigned long long)em->geometry_id,
+                        (unsigned long long)scene->g->id);
+        return path_mixed_lobes_check(ctx, scene, "trhip_render_path_emit");
+    }
+    double slot_bytes() const override { return 2.0 * sizeof(float4); }  // the base records and the emitted sums beside Lbuf
+    double path_bytes() const override { return kEmitQueueBytes; }
+    // the per-sample buffers and the queues must fit in half of free HBM
+    int buffers(trhip_ctx* ctx, const PathTermShape& s) override {
+        const size_t held = ctx->Lbuf.bytes + ctx->pfilm.bytes + ctx->env_base.bytes + ctx->emit_lh.bytes + ctx->lane.held(true) + held_in_pipes(ctx);
+        // per slot: the base records, their fold and the emitted sums (16 B each), the poison byte and the note byte; what an unfused film pass reads per sample
+        const double need = (double)s.total_slots * (50.0 + s.film_bytes) + (double)s.n_pipes * ((double)s.queue_entries * kEmitQueueBytes + (double)sizeof(NeeCounters));
+        bool fits = false;
+        double free_gb = 0.0;
+        if (int rc = fits_in_hbm(ctx, 2.0 * need, held, &fits, &free_gb)) return rc;
+        if (!fits)
+            return fail(ctx, TRHIP_ERR_UNSUPPORTED, "the per-sample buffers and the shadow queues of an emit frame (%.2f GB at %u spp) do not fit in half of free HBM (%.2f GB): there are no bands here",
+                        need * 1e-9, s.spp, free_gb);
+        if (int rc = ensure(ctx, ctx->env_base, s.l_slots * sizeof(float4))) return rc;
+        if (int rc = ensure(ctx, ctx->emit_lh, s.l_slots * sizeof(float4))) return rc;
+        base = (float4*)ctx->env_base.p, lh = (float4*)ctx->emit_lh.p;
+        return ctx->lane.grow(ctx, s.n_pipes, s.queue_entries, s.l_slots, true);
+    }
+    int clear(trhip_ctx* ctx, hipStream_t st, uint64_t l_slots) override {
+        HIP_TRY(ctx, hipMemsetAsync(ctx->lane.note.p, 0, l_slots, st));  // (depth 1 counts whatever the note says)
+        HIP_TRY(ctx, hipMemsetAsync(lh, 0, l_slots * sizeof(float4), st));  // Lh starts at +0
+        return 0;
+    }
+    int begin_batch(trhip_ctx* ctx, hipStream_t st, int pipe) override { return ctx->lane.begin_batch(ctx, st, pipe); }
+    // the emitted terms, the notes, and the emitter shadow rays of this depth
+    void after_closest(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, const uint32_t* counts, uint32_t cap, const PathQueue& q, const float4* hits, int depth, uint32_t hits_have_bary,
+                       int pipe) override {
+        const ShadowLane& lane = ctx->lane;
+        const size_t cdf_bytes = (size_t)(em->n + 1u) * sizeof(float);
+        const dim3 grid(grid_for(ctx, (uint64_t)cap * kSeg, 8));  // the queue holds at most kSeg * cap entries; the kernel's grid-stride loop covers whatever the counts say
+        if (cdf_bytes <= kEmitCdfLdsBytes)
+            hipLaunchKernelGGL(k_path_emit<true>, grid, dim3(kBlock), cdf_bytes, st, scene->dev, counts, cap, q, hits, (uint32_t)depth, hits_have_bary, lh, (uint8_t*)lane.note.p, em->dev(), scale,
+                               flags, lane.queue(pipe, depth), (float*)lane.reach[pipe][depth & 1].p, lane.emitted(pipe, depth));
+        else
+            hipLaunchKernelGGL(k_path_emit<false>, grid, dim3(kBlock), 0, st, scene->dev, counts, cap, q, hits, (uint32_t)depth, hits_have_bary, lh, (uint8_t*)lane.note.p, em->dev(), scale, flags,
+                               lane.queue(pipe, depth), (float*)lane.reach[pipe][depth & 1].p, lane.emitted(pipe, depth));
+    }
+    // the emitter rays directly after the point-light rays, each with its reach (the NEE term's argument holds: model order, one writer of a slot per launch)
+    void after_any(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, uint32_t cap, int depth, int pipe, Counters* ctr, void* overflow_slab) override {
+        if (!(flags & TRHIP_PATH_EMIT_HITS_ONLY)) ctx->lane.launch_any(ctx, st, scene, cap, depth, base, pipe, true, ctr, overflow_slab);
+    }
+    void fold(trhip_ctx* ctx, hipStream_t st, uint64_t l_slots, float4* out) override {  // out = base + Lh
+        hipLaunchKernelGGL(k_emit_fold, dim3(grid_for(ctx, l_slots, 8)), dim3(kBlock), 0, st, (const float4*)base, (const float4*)lh, l_slots, out);
+    }
+    void retain(trhip_ctx* ctx, const PathEnvKeep&) override { ctx->last.term = LastRecords::kEmit; }
+};
+
 int render_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_sensor* sensor, uint32_t spp, int max_depth, uint64_t seed, uint32_t sample_offset, const trhip_emitters* em,
                 const trhip_path_emit_params* prm, void* out, bool out_is_device, trhip_stats* stats) {
-    // the parameter block: checked before any handle is looked at, and none of it needs a device
-    if (!prm) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
-    if (!(prm->scale >= 0.0f) || std::isinf(prm->scale)) return fail(ctx, TRHIP_ERR_INVALID, "trhip_render_path_emit: scale must be finite and >= 0");
-    if (prm->flags & ~kPathEmitFlags) return fail(ctx, TRHIP_ERR_INVALID, "trhip_render_path_emit: unknown flag bits 0x%x", prm->flags & ~kPathEmitFlags);
-    for (int k = 0; k < 6; ++k)
-        if (prm->reserved[k] != 0) return fail(ctx, TRHIP_ERR_INVALID, "trhip_render_path_emit: reserved must be 0");
-    return render_path_emit_frame(ctx, scene, sensor, spp, max_depth, seed, sample_offset, out, out_is_device, stats, em, prm->scale, prm->flags);
+    if (int rc = path_params_check(ctx, prm, kPathEmitFlags, "trhip_render_path_emit")) return rc;
+    EmitTerm term(em, prm->scale, prm->flags);
+    return render_path_frame(ctx, scene, sensor, spp, max_depth, seed, sample_offset, out, out_is_device, stats, nullptr, &term);
 }
 
 }  // namespace
-
-int path_emit_check(trhip_ctx* ctx, const trhip_scene* scene, const trhip_emitters* em) {
-    if (!em) return fail(ctx, TRHIP_ERR_INVALID, "trhip_render_path_emit: null emitters");
-    if (em->ctx != ctx) return fail(ctx, TRHIP_ERR_INVALID, "trhip_render_path_emit: the emitters belong to another context");
-    if (em->geometry_id != scene->g->id || em->n_materials != scene->g->materials.size())
-        return fail(ctx, TRHIP_ERR_INVALID, "trhip_render_path_emit: the emitters were made from another committed geometry (%llu) than the scene's (%llu)", (unsigned long long)em->geometry_id,
-                    (unsigned long long)scene->g->id);
-    return path_mixed_lobes_check(ctx, scene, "trhip_render_path_emit");
-}
-
-int path_emit_buffers(trhip_ctx* ctx, PathEmitFrame& f, int n_pipes, uint64_t queue_entries, uint64_t total_slots, uint64_t l_slots, double film_bytes, uint32_t spp) {
-    size_t held = ctx->Lbuf.bytes + ctx->pfilm.bytes + ctx->env_base.bytes + ctx->emit_lh.bytes + ctx->nee_note.bytes + held_in_pipes(ctx);
-    for (auto& a : ctx->nee_sq)
-        for (auto& b : a)
-            for (auto& c : b) held += c.bytes;
-    for (auto& a : ctx->emit_tmax)
-        for (auto& b : a) held += b.bytes;
-    // per slot: the base records, their fold and the emitted sums (16 B each), the poison byte and the note byte; what an unfused film pass reads per sample
-    const double need = (double)total_slots * (50.0 + film_bytes) + (double)n_pipes * ((double)queue_entries * kEmitQueueBytes + (double)sizeof(NeeCounters));
-    bool fits = false;
-    double free_gb = 0.0;
-    if (int rc = fits_in_hbm(ctx, 2.0 * need, held, &fits, &free_gb)) return rc;
-    if (!fits)
-        return fail(ctx, TRHIP_ERR_UNSUPPORTED, "the per-sample buffers and the shadow queues of an emit frame (%.2f GB at %u spp) do not fit in half of free HBM (%.2f GB): there are no bands here",
-                    need * 1e-9, spp, free_gb);
-    if (int rc = ensure(ctx, ctx->env_base, l_slots * sizeof(float4))) return rc;
-    if (int rc = ensure(ctx, ctx->emit_lh, l_slots * sizeof(float4))) return rc;
-    if (int rc = ensure(ctx, ctx->nee_note, l_slots)) return rc;
-    f.base = (float4*)ctx->env_base.p;
-    f.lh = (float4*)ctx->emit_lh.p;
-    f.note = (uint8_t*)ctx->nee_note.p;
-    for (int pi = 0; pi < n_pipes; ++pi) {
-        for (int k = 0; k < 2; ++k) {
-            for (int j = 0; j < 3; ++j)
-                if (int rc = ensure(ctx, ctx->nee_sq[pi][k][j], queue_entries * sizeof(float4))) return rc;
-            if (int rc = ensure(ctx, ctx->emit_tmax[pi][k], queue_entries * sizeof(float))) return rc;
-            f.sq[pi][k] = ShadowQueue{(float4*)ctx->nee_sq[pi][k][0].p, (float4*)ctx->nee_sq[pi][k][1].p, (float4*)ctx->nee_sq[pi][k][2].p};
-            f.tmax[pi][k] = (float*)ctx->emit_tmax[pi][k].p;
-        }
-        if (int rc = ensure(ctx, ctx->nee_ctr[pi], sizeof(NeeCounters))) return rc;
-        f.ctr[pi] = ctx->nee_ctr[pi].p;
-    }
-    return 0;
-}
-void path_emit_begin_batch(trhip_ctx*, hipStream_t st, const PathEmitFrame& f, int pipe) { (void)hipMemsetAsync(f.ctr[pipe], 0, sizeof(NeeCounters), st); }
-void launch_path_emit(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, const uint32_t* counts, uint32_t cap, const PathQueue& q, const float4* hits, int depth, uint32_t hits_have_bary,
-                      const PathEmitFrame& f, int pipe) {
-    const trhip_emitters* em = f.em;
-    const size_t cdf_bytes = (size_t)(em->n + 1u) * sizeof(float);
-    NeeCounters* nc = (NeeCounters*)f.ctr[pipe];
-    const dim3 grid(grid_for(ctx, (uint64_t)cap * kSeg, 8));  // the queue holds at most kSeg * cap entries; the kernel's grid-stride loop covers whatever the counts say
-    if (cdf_bytes <= kEmitCdfLdsBytes)
-        hipLaunchKernelGGL(k_path_emit<true>, grid, dim3(kBlock), cdf_bytes, st, scene->dev, counts, cap, q, hits, (uint32_t)depth, hits_have_bary, f.lh, f.note, em->dev(), f.scale, f.flags,
-                           f.sq[pipe][depth & 1], f.tmax[pipe][depth & 1], nc->n[depth - 1]);
-    else
-        hipLaunchKernelGGL(k_path_emit<false>, grid, dim3(kBlock), 0, st, scene->dev, counts, cap, q, hits, (uint32_t)depth, hits_have_bary, f.lh, f.note, em->dev(), f.scale, f.flags,
-                           f.sq[pipe][depth & 1], f.tmax[pipe][depth & 1], nc->n[depth - 1]);
-}
-void launch_emit_shadow(trhip_ctx* ctx, hipStream_t st, const trhip_scene* scene, uint32_t cap, int depth, float4* L, const PathEmitFrame& f, int pipe, Counters* ctr, void* overflow_slab) {
-    NeeCounters* nc = (NeeCounters*)f.ctr[pipe];
-    const ShadowQueue& sq = f.sq[pipe][depth & 1];
-    launch_trace(ctx, st, scene, true, SegQueue{nc->n[depth - 1], cap, 0u}, sq.o, sq.d, f.tmax[pipe][depth & 1], TraceOut{nullptr, L, sq.c, nullptr}, nc->work[depth - 1], ctr, overflow_slab);
-}
-void launch_emit_fold(trhip_ctx* ctx, hipStream_t st, const PathEmitFrame& f, uint64_t l_slots, float4* out) {
-    hipLaunchKernelGGL(k_emit_fold, dim3(grid_for(ctx, l_slots, 8)), dim3(kBlock), 0, st, (const float4*)f.base, (const float4*)f.lh, l_slots, out);
-}
 
 extern "C" {
 
@@ -218,16 +208,11 @@ int trhip_render_path_emit_device(trhip_ctx* ctx, const trhip_scene* sc, const t
 int trhip_last_emitted(trhip_ctx* ctx, float* out4, uint64_t n_floats) {
     if (!ctx || !out4) return fail(ctx, TRHIP_ERR_INVALID, "null argument");
     const LastRecords& last = ctx->last;
-    if (!last.emit) return fail(ctx, TRHIP_ERR_INVALID, "trhip_last_emitted: the context's last frame is not an emit frame");
+    if (last.term != LastRecords::kEmit) return fail(ctx, TRHIP_ERR_INVALID, "trhip_last_emitted: the context's last frame is not an emit frame");
     if (n_floats != last.count * 4) return fail(ctx, TRHIP_ERR_INVALID, "expected %llu floats", (unsigned long long)(last.count * 4));
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = ensure(ctx, ctx->scratch[0], n_floats * sizeof(float))) return rc;
-    const uint64_t n = last.count;
-    if (n) hipLaunchKernelGGL(k_export_emitted, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)ctx->emit_lh.p, n, (float4*)ctx->scratch[0].p, last.layout, last.npix, last.spp);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(out4, ctx->scratch[0].p, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    return read_back_records(ctx, out4, n_floats, [&](void* dst, dim3 grid) {
+        hipLaunchKernelGGL(k_export_emitted, grid, dim3(256), 0, ctx->stream, (const float4*)ctx->emit_lh.p, last.count, (float4*)dst, last.layout, last.npix, last.spp);
+    });
 }
 
 }  // extern "C"

@@ -30,7 +30,7 @@ int render_sppm_impl(trhip_ctx* ctx, const trhip_scene* scene, const trhip_senso
     if (!scene->committed) return fail(ctx, TRHIP_ERR_INVALID, "scene not committed");
     if (n_iterations == 0 || max_depth < 1 || max_depth > kMaxDepth) return fail(ctx, TRHIP_ERR_INVALID, "n_iterations must be >= 1 and max_depth in 1..%d", kMaxDepth);
     if (!(initial_radius > 0.0f)) return fail(ctx, TRHIP_ERR_INVALID, "initial_search_radius must be positive");
-    ctx->last.path_env = 0;  // another render between a path-env frame and its relight: the relight is refused (include/tracehip.h, trhip_path_env_relight)
+    ctx->last.drop_env_records();  // another render between a path-env frame and its relight: the relight is refused (include/tracehip.h, trhip_path_env_relight)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DeviceSensor ds;
     derive_sensor(sensor, ds);
